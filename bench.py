@@ -24,6 +24,33 @@ sys.path.insert(0, ROOT)
 # pusher.h:61 [-2, 2]; every other gym-MuJoCo task here [-1, 1]): the reference benchmark draws
 # `action_space.sample()` (benchmark/test_envpool.py), i.e. uniform in these bounds
 ACTION_HI = {"Humanoid": 0.4, "HumanoidStandup": 0.4, "Pusher": 2.0}
+# --dump-outputs: size cap of the written arrays
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pool, ptrs, k, dev):
+    """Copy the batch `ptrs` / `k` of a recv_device (the pool's stream already synchronised) to the host and write
+    one DIR/<key>.npy per state key: rows sorted by info:env_id, integer / bool keys as float64, float keys in their
+    own precision; when the batch is larger than DUMP_LIMIT_BYTES, the same seeded sample of rows for every key."""
+    import torch
+
+    from envpool_amd.torch_interop import _DevArray
+
+    host = {name: torch.as_tensor(_DevArray(ptr, (k, *shape), dtype), device=dev).cpu().numpy()
+            for (name, dtype, shape), ptr in zip(pool.state_keys, ptrs)}
+    rows = np.argsort(host["info:env_id"].reshape(k), kind="stable")
+    arrays = {name: a.astype(a.dtype if a.dtype in (np.float32, np.float64) else np.float64, copy=False)
+              for name, a in host.items()}
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrays)  # (room for the .npy headers)
+    if k * row_bytes > budget:
+        keep = max(1, budget // row_bytes)
+        rows = rows[np.sort(np.random.default_rng(0).choice(k, size=keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name.replace(":", ".") + ".npy"), np.ascontiguousarray(a[rows]))
+    return {"dir": out_dir, "keys": len(arrays), "rows": int(len(rows)), "of_rows": int(k),
+            "bytes": int(len(rows) * row_bytes)}
 
 
 def cpu_baseline(task="HalfCheetah", target_s=12.0, action_hi=1.0):
@@ -104,9 +131,15 @@ def main():
                          "batches of the SAME kernel) would pollute the per-kernel means (tools/profile_bench.sh)")
     ap.add_argument("--action-scale", type=float, default=None,
                     help="actions are uniform in [-s, s]; default: the task's action-space bound")
-    ap.add_argument("--min-time", type=float, default=5.0,
+    ap.add_argument("--min-time", type=float, default=0.0,
                     help="the timed region repeats the K-step block until it lasts at least this many "
-                         "seconds (same repeat count on every rank); 0 = exactly K steps")
+                         "seconds (same repeat count on every rank); 0 (default) = exactly K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step returned (every state key, rows in "
+                         "env-id order) as DIR/<key>.npy in float64 (float32 keys stay float32), at most "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all: beyond that a fixed, seeded sample of the env rows; "
+                         "rank 0 only; needs --min-time 0 so that the step count, and with it every input, is the "
+                         "same from run to run")
     ap.add_argument("--param", action="append", default=[], metavar="KEY=VALUE",
                     help="extra pool parameter (A/B switches such as sort_by_cost=0)")
     ap.add_argument("--no-bind", action="store_true",
@@ -123,6 +156,8 @@ def main():
                     help="also all-gather the obs batch over RCCL every step (optional "
                          "exchange of SURVEY §8e; off by default: the path needs no collective)")
     args = ap.parse_args()
+    if args.dump_outputs and args.min_time > 0:
+        raise SystemExit("--dump-outputs needs --min-time 0: a timed calibration would make the step count vary")
 
     import torch
     import torch.distributed as dist
@@ -218,6 +253,7 @@ def main():
                                     device=dev)
             with torch.cuda.stream(pool_stream):  # ordered after the step kernel
                 dist.all_gather_into_tensor(gathered, local)
+        return ptrs, k
 
     pool.send_device(None)  # reset all (first step of every env is a reset anyway)
     pool.recv_device()
@@ -251,7 +287,7 @@ def main():
     pool.set_timing(2)
     t0 = time.perf_counter()
     for i in range(timed_steps):
-        step(i)
+        last = step(i)
     kernel_ms, launches = pool.kernel_time_ms()  # records the closing event, waits for the stream
     pool.synchronize()
     torch.cuda.synchronize()
@@ -266,6 +302,9 @@ def main():
         per_rank_s = [float(x.item()) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (the pool's stream is synchronised; the next send would reuse the block)
+        dumped = dump_outputs(args.dump_outputs, pool, *last, dev)
 
     reset_ms = None
     numpy_api = None
@@ -497,6 +536,8 @@ def main():
         # every rank's own rate over its own wall time; `value` = all env-steps / the SLOWEST rank's time
         out["per_rank"] = [{"rank": r, "device": r % max(ngpu, 1), "timed_s": ts,
                             "env_steps_per_s": n * timed_steps / ts} for r, ts in enumerate(per_rank_s)]
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1:
             out["reset_step_ms"] = reset_ms
             out["numpy_api"] = numpy_api

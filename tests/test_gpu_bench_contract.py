@@ -33,7 +33,7 @@ def test_bench_line_schema():
         assert key in r, key
     assert r["peak"] > 0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     # value = env-steps of the timed window / its wall time; the window is whole K-step blocks and
-    # lasts at least --min-time (5 s by default, 1 s here) however small K is
+    # lasts at least --min-time (1 s here; by default exactly K steps) however small K is
     assert d["timed_steps"] % 6 == 0 and d["timed_steps"] >= 6
     assert d["timed_s"] >= 0.9, d["timed_s"]
     assert abs(d["ms_per_step"] * 1e-3 * d["timed_steps"] - d["timed_s"]) < 1e-6

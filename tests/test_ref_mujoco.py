@@ -10,8 +10,8 @@ of the restatement to reference code.  It does not pin the engine arithmetic.
 Calling sequence as in the reference's own C++ test
 (envpool/mujoco/gym/mujoco_gym_envpool_test.cc:27-56)."""
 import ctypes
+import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -120,10 +120,11 @@ def test_frame_stack_is_the_reference_ring():
                 ring[e] = np.concatenate([ring[e, 1:], a["obs"][e][None]], axis=0)
 
 
-REF_XML = "/root/reference/third_party/mujoco_gym_xml_patches"
+# every body of the reference's *_envpool.xml files in document order, world first (tools/mjcf_subset.py's reading;
+# tests/test_models_vs_xml.py::test_golden_is_what_the_xml_says pins it to the XML where the reference tree exists)
+MJCF_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf_models.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_XML), reason="no reference tree")
 @pytest.mark.parametrize("xml,bodies", [
     ("ant", ["torso"]),
     ("reacher", ["fingertip", "target"]),
@@ -132,10 +133,11 @@ REF_XML = "/root/reference/third_party/mujoco_gym_xml_patches"
 ])
 def test_body_ids_are_the_xml_document_order(xml, bodies):
     """mj_name2id of the shim == MuJoCo's rule (body ids in document order, world = 0),
-    re-derived from the reference's XML."""
-    text = open(os.path.join(REF_XML, xml + "_envpool.xml")).read()
-    text = re.sub(r"<!--.*?-->", "", text, flags=re.S)
-    order = [m.group(1) or "" for m in re.finditer(r"<body\b(?:[^>]*?\bname=\"([^\"]*)\")?[^>]*>", text)]
+    the order read from the reference's XML (tests/golden/mjcf_models.json)."""
+    with open(MJCF_GOLDEN) as f:
+        names = [b["name"] for b in json.load(f)[xml]["bodies"]]
+    assert names[0] == "world"
+    order = names[1:]
     lib = ctypes.CDLL(orc.REF_MUJOCO_LIB)
     lib.ref_mujoco_body_id.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     assert lib.ref_mujoco_nbody((xml + ".xml").encode()) == len(order) + 1

@@ -1,6 +1,6 @@
 """The reference's own pybind11 host shim over libenvpool_amd.so.
 
-integration/_build/refbind*.so is `envpool/core/py_envpool.h` (PyEnvSpec, PyEnvPool, the
+oracle/_ref/refbind/refbind*.so is `envpool/core/py_envpool.h` (PyEnvSpec, PyEnvPool, the
 REGISTER macro: py_envpool.h:206-332) compiled IN PLACE from /root/reference, with
 `DeviceEnvPool<Spec>` (integration/refbind/device_envpool.h, an `EnvPool<Spec>` subclass,
 envpool/core/envpool.h:29-56) where the reference instantiates `AsyncEnvPool<Env>`, and the
@@ -24,14 +24,14 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "integration", "_build")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "refbind")
 
 
 def _refbind():
     if not any(f.startswith("refbind") and f.endswith(".so") for f in os.listdir(BUILD)
                ) if os.path.isdir(BUILD) else True:
-        pytest.skip("integration/_build/refbind*.so not built (needs /root/reference: "
-                    "make -C integration)")
+        pytest.skip("oracle/_ref/refbind/refbind*.so not built (needs /root/reference: "
+                    "make -C oracle ref)")
     if BUILD not in sys.path:
         sys.path.insert(0, BUILD)
     return importlib.import_module("refbind")
@@ -224,7 +224,7 @@ def test_pybind_classes_slot_into_the_python_adaptors():
 def test_cc_driver_follows_the_reference_cc_test():
     exe = os.path.join(BUILD, "refbind_cc_test")
     if not os.path.exists(exe):
-        pytest.skip("integration/_build/refbind_cc_test not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/refbind/refbind_cc_test not built (needs /root/reference)")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "refbind_cc_test: OK" in r.stdout
