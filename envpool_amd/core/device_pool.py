@@ -246,6 +246,9 @@ class DevicePool:
         native.check(self._lib.epa_consumer_wait(self._h, ctypes.c_void_p(consumer_stream)))
 
     def recv_device(self) -> tuple[list[int], int]:
+        """Device pointers of the next batch (one per state key) and its row count.  Does not wait for the batch's
+        kernel, so a pool error word (see torch_interop) set by that kernel raises at a later recv or at
+        `synchronize()`, not here."""
         n = len(self.state_keys)
         ptrs = (ctypes.c_void_p * n)()
         k = ctypes.c_int32(0)

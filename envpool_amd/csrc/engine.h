@@ -232,6 +232,13 @@ class Pool {
   virtual void Launch(const int* d_ids, int k, const void* d_action,
                       bool force_reset, const OutPtrs& out) = 0;
   void InitCommon();  // allocates + initialises CommonDev (after derived ctor)
+  // Per-pool error word for families whose kernels can meet a condition they must not spin on (a bounded
+  // rejection loop that ran out): `err_dev_` is a pinned, device-mapped word the kernel stores a nonzero
+  // code into; every recv that has waited for its rows' kernel (recv, recv_block, recv_into, and recv_device
+  // for kernels already finished) then throws std::runtime_error(ErrorText(code)).  The word is sticky.
+  void EnableErrorWord();
+  virtual std::string ErrorText(unsigned code) const;
+  unsigned* err_dev_{nullptr};
   // Generic TypedFrameStackBuffer (envpool/mujoco/frame_stack.h:74-146) for families
   // whose step kernel writes one un-stacked float64 observation per row: the first
   // env key must be "obs" declared with shape [S, nobs] (StackedObsShape).  The
@@ -291,6 +298,8 @@ class Pool {
   void TakeDirect(Batch* b, int take, int got, char* dst, const size_t* dst_off, void* const* dst_ptrs,
                   std::unique_lock<std::mutex>& lk);
   int direct_out_{-1};  // "direct_out" (-1: not read yet)
+  unsigned* err_host_{nullptr};  // EnableErrorWord
+  void CheckErrorWord() const;
   bool HostBlockVisible(const void* p);
   // chooses stream_ for the next launch and orders it behind what it may depend on
   void PickStream(const int32_t* host_ids, int k, bool device_path, const void* d_env_id = nullptr);
@@ -383,6 +392,9 @@ bool DescribeToyText(const std::string& family, const Config& cfg,
 Pool* MakeMujoco(const std::string& family, const Config& cfg);
 bool DescribeMujoco(const std::string& family, const Config& cfg,
                     std::vector<KeySpec>* state, KeySpec* action);
+Pool* MakeMiniGrid(const std::string& family, const Config& cfg);
+bool DescribeMiniGrid(const std::string& family, const Config& cfg,
+                      std::vector<KeySpec>* state, KeySpec* action);
 // Atari (atari_env.hip): needs two strings the numeric epa_config cannot carry
 Pool* MakeAtari(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);
 int AtariNumActions(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);

@@ -1,6 +1,12 @@
 """Zero-copy views of a pool's device-resident result batch as torch tensors
 (the analogue of the reference's XLA path, envpool/core/xla.h, without its
-host staging).  torch is only imported here."""
+host staging).  torch is only imported here.
+
+Errors a step kernel reports through its pool's error word (MiniGrid: a reset's rejection sampling ran out of
+`minigrid_max_tries`) reach this path late: `recv_device` does not wait for the kernel it hands out, so it
+raises only for kernels already finished -- one recv later, or at `pool.synchronize()`.  The host path (`recv`)
+waits and raises for the batch itself.  The word is sticky: every later recv of that pool raises too, and the
+pool has to be recreated."""
 
 from __future__ import annotations
 
