@@ -39,6 +39,7 @@ _DEFAULT_BOUNDS = {
     np.dtype(np.float64): (F64_MIN, F64_MAX),
     np.dtype(np.bool_): (False, True),
     np.dtype(np.uint8): (0, 255),
+    np.dtype(np.int8): (-128, 127),
 }
 
 

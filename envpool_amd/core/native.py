@@ -22,7 +22,7 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("ENVPOOL_AMD_LIB") or os.path.join(_PKG, "lib", "libenvpool_amd.so")
 
 EPA_OK, EPA_ERR_INVALID, EPA_ERR_RUNTIME, EPA_ERR_DEVICE = 0, 1, 2, 3
-DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8}
+DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
 
 class EpaConfig(ctypes.Structure):

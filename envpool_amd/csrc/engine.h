@@ -395,6 +395,9 @@ bool DescribeMujoco(const std::string& family, const Config& cfg,
 Pool* MakeMiniGrid(const std::string& family, const Config& cfg);
 bool DescribeMiniGrid(const std::string& family, const Config& cfg,
                       std::vector<KeySpec>* state, KeySpec* action);
+Pool* MakeJumanji(const std::string& family, const Config& cfg);
+bool DescribeJumanji(const std::string& family, const Config& cfg,
+                     std::vector<KeySpec>* state, KeySpec* action);
 // Atari (atari_env.hip): needs two strings the numeric epa_config cannot carry
 Pool* MakeAtari(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);
 int AtariNumActions(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);

@@ -60,7 +60,8 @@ def to_nested_dict(flatten_dict: dict[str, Any], generator: type = dict) -> dict
         *parents, last = dotted.split(".")
         node = tree
         for name in parents:
-            if name not in node:
+            # a space Dict's `in` tests a sample, not a key: look the key up among its keys (data.py:85)
+            if name not in node.keys():
                 node[name] = generator()
             node = node[name]
         node[last] = leaf

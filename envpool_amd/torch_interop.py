@@ -17,7 +17,7 @@ import numpy as np
 
 _TYPESTR = {np.dtype(np.int32): "<i4", np.dtype(np.float32): "<f4",
             np.dtype(np.float64): "<f8", np.dtype(np.bool_): "|b1",
-            np.dtype(np.uint8): "|u1"}
+            np.dtype(np.uint8): "|u1", np.dtype(np.int8): "|i1"}
 
 
 class _DevArray:

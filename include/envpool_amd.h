@@ -46,6 +46,7 @@ extern "C" {
 #define EPA_F64 2
 #define EPA_BOOL 3 /* 1 byte, numpy bool_ */
 #define EPA_U8 4
+#define EPA_I8 5 /* int8 (Jumanji RubiksCube obs:cube) */
 
 typedef struct epa_pool epa_pool;
 
