@@ -48,11 +48,15 @@
 // over the rows + group sums + stop tests, 3 factor / solve / products with M, 4 line search, 5 the Euler integration
 // with implicit damping), EPA_LG_COUNT(cx, K)
 // counts wave-level loop trips (0 Newton trips, 1 line-search evaluations, 2 forward passes).
+// EPA_LG_TICK_TOP(cx): the tick at the top of a forward pass, booked to category 0 and, separately, to the first
+// forward pass of the chunk or to the others (the split of category 0, mujoco_planar_lg.hip: DevCx::TickTop).
 #if defined(EPA_LG_TIMERS) && defined(__HIP_DEVICE_COMPILE__)
 #define EPA_LG_TICK(cx, K) (cx).template TickEnd<K>()
+#define EPA_LG_TICK_TOP(cx) (cx).TickTop()
 #define EPA_LG_COUNT(cx, K) (cx).template Count<K>()
 #else
 #define EPA_LG_TICK(cx, K) ((void)0)
+#define EPA_LG_TICK_TOP(cx) ((void)0)
 #define EPA_LG_COUNT(cx, K) ((void)0)
 #endif
 // host experiments only (tools/lg_desync/rollout_host.cpp, tools/lg_desync_sim.py): per Newton trip of one env, the line-search evaluations it ran
@@ -918,8 +922,11 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
   // data: LDS / table reads at per-lane addresses, the columns of hinges beyond the slot's body are selected to zero
   // (exact zeros: the sums they enter are unchanged), a lane whose set has run out visits with weight D = 0.
   // (A software pipeline by one slot measured -0.4 % in round 4, profiles/r4f_prefetch_ab.txt.)
+  // A guarded do-while, not a while: with the wave-uniform exit test at the top of the loop the compiler kept the 27
+  // accumulators in two sets of registers and copied one set into the other at every trip -- 27 v_mov_b64 of the
+  // loop's 203 instructions at KL = 2 (round 7).  Same arithmetic, same trips.
   U rem = vis;
-  while (AnyWave(AnySlot(rem))) {
+  if (AnyWave(AnySlot(rem))) do {
     const auto has = AnySlot(rem);
     const U sl = PopSlot(rem);
     const U body = SlotBodyOf<KL>(sl);
@@ -1001,7 +1008,7 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
         }
       });
     }
-  }
+  } while (AnyWave(AnySlot(rem)));
 }
 
 // this lane's part of phi'(alpha), phi''(alpha) from its rows along `s` from `a`, and the lane's active-row mask
@@ -1040,9 +1047,9 @@ EPA_HD void LineEval(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
       });
     }
   }
-  // the lane's own touching slots, as in RowsPass
+  // the lane's own touching slots, as in RowsPass (and a guarded do-while for the same reason)
   U rem = vis;
-  while (AnyWave(AnySlot(rem))) {
+  if (AnyWave(AnySlot(rem))) do {
     const auto has = AnySlot(rem);
     const U sl = PopSlot(rem);
     const U body = SlotBodyOf<KL>(sl);
@@ -1076,7 +1083,7 @@ EPA_HD void LineEval(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
     MaskSetNZAt(mask, c1, sl, 3);
     MaskSetNZAt(mask, c2, sl, 4);
     MaskSetNZAt(mask, c3, sl, 5);
-  }
+  } while (AnyWave(AnySlot(rem)));
 }
 
 // ---- the arrow system ---------------------------------------------------------------------------
@@ -1395,7 +1402,7 @@ template <int KL, typename T, typename V, typename Cx>
 EPA_HD V Forward(const CheetahModel<T>& m, const SolverCfgLg<T>& cfg, Cx& cx, const V* q, const V* v,
                  V* warm, const V* ctrl, Pos<V>& p, V* qacc, V* Ma, V* grad) {
   cx.Refresh();
-  EPA_LG_TICK(cx, 0);
+  EPA_LG_TICK_TOP(cx);
   EPA_LG_COUNT(cx, 2);
   Kinematics<KL>(m, cx, q, p);
   V qfrc_smooth[kLV];

@@ -50,11 +50,18 @@ struct DevCx {
 #ifdef EPA_LG_TIMERS  // diagnostic build only (mj_planar_lg.hip.h: EPA_LG_TICK)
   long long t_last{0};
   long long acc[6]{0, 0, 0, 0, 0, 0};
+  long long top[2]{0, 0};  // category 0 at the top of the chunk's first forward pass / of the others
   unsigned cnt[3]{0, 0, 0};
   template <int K>
   __device__ __forceinline__ void TickEnd() {
     const long long now = clock64();
     acc[K] += now - t_last;
+    t_last = now;
+  }
+  __device__ __forceinline__ void TickTop() {
+    const long long now = clock64();
+    acc[0] += now - t_last;
+    top[cnt[2] == 0 ? 0 : 1] += now - t_last;  // (cnt[2]: forward passes counted so far)
     t_last = now;
   }
   template <int K>
@@ -63,7 +70,11 @@ struct DevCx {
 };
 #ifdef EPA_LG_TIMERS
 // [0..4] cycles per category, [5..7] trip counters, [8] chunks, [9] cycles of whole chunks, [10] category 5
-// (the integration of an mj_step: what follows the forward pass)
+// (the integration of an mj_step: what follows the forward pass); the split of category 0: [11] the top of the
+// chunk's first forward pass, [12] the tops of its other forward passes; outside the chunk's cycles [9]: [13] the
+// head of StepChunk up to the stepping branch (KernArgs() re-reads, done / cur_step loads, the reset branch), [14] the
+// stepping branch up to the first forward pass (q / v / warm / action loads issued, ctrl_cost), [15] the wave's queue
+// between two chunks (longest-first filing, ticket, the next chunk's bucket lookup)
 __device__ unsigned long long g_lg_timers[16];
 #endif
 #ifdef EPA_LG_SCHED_TRACE
@@ -139,6 +150,9 @@ __device__ __forceinline__ void StepChunk(int chunk, const double* tab_lds, doub
   const int leg = G::Leg(c);
   const bool first = c == 0;                  // env-level work
   const bool leg_first = G::Par(c) == 0;      // leg-level outputs
+#ifdef EPA_LG_TIMERS
+  const long long t_head0 = clock64();
+#endif
   const int row = chunk * ap->per + (lane / KL);
   if (lane / KL >= ap->per || row >= a.k) return;
   const int e = a.ids ? a.ids[row] - a.id_offset : row;
@@ -204,6 +218,9 @@ __device__ __forceinline__ void StepChunk(int chunk, const double* tab_lds, doub
       if (any_reset) atomicAdd(&g_lg_reset[2], 1ull);
     }
 #endif
+#ifdef EPA_LG_TIMERS
+    const long long t_head1 = clock64();
+#endif
     ++cur;
     double q[plg::kLV], v[plg::kLV], w[plg::kLV], ctrl[3];
     double x_before = 0.0;
@@ -249,6 +266,10 @@ __device__ __forceinline__ void StepChunk(int chunk, const double* tab_lds, doub
       for (int i = 0; i < 3; ++i) atomicAdd(&g_lg_timers[5 + i], (unsigned long long)cx.cnt[i]);
       atomicAdd(&g_lg_timers[8], 1ull);
       atomicAdd(&g_lg_timers[9], (unsigned long long)(clock64() - t_chunk0));
+      atomicAdd(&g_lg_timers[11], (unsigned long long)cx.top[0]);
+      atomicAdd(&g_lg_timers[12], (unsigned long long)cx.top[1]);
+      atomicAdd(&g_lg_timers[13], (unsigned long long)(t_head1 - t_head0));
+      atomicAdd(&g_lg_timers[14], (unsigned long long)(t_chunk0 - t_head1));
     }
 #endif
 #ifdef EPA_LG_SCHED_TRACE
@@ -355,6 +376,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W, W))) 
     args.lpt[LptGenWords(args.lpt_cap) * ((args.lpt_gen + 2) % 3) + threadIdx.x] = 0u;
   }
   int tk = blockIdx.x;  // position in the queue: the first one is the wave's index, then tickets
+#ifdef EPA_LG_TIMERS
+  long long t_queue = 0;  // end of the previous chunk (0: none yet)
+#endif
   for (;;) {
     LgArgsK* ap = KernArgs();
     int chunk = tk;
@@ -377,6 +401,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W, W))) 
     }
     chunk = __builtin_amdgcn_readfirstlane(chunk);
     const long long t0 = clock64();
+#ifdef EPA_LG_TIMERS
+    if (t_queue != 0 && threadIdx.x == 0) atomicAdd(&g_lg_timers[15], (unsigned long long)(t0 - t_queue));
+#endif
 #ifdef EPA_LG_SCHED_TRACE
     const unsigned long long w0 = wall_clock64();
 #endif
@@ -392,6 +419,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W, W))) 
         g_lg_sched[4 + 4 * i] = w1;
       }
     }
+#endif
+#ifdef EPA_LG_TIMERS
+    t_queue = clock64();
 #endif
     ap = KernArgs();
     unsigned t = 0;

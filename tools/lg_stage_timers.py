@@ -57,6 +57,15 @@ def main():
           f"line-search evaluations {out[6] / chunks:.2f}")
     solver = cyc[2] + cyc[3] + cyc[4]
     print(f"  solver share of the wave's cycles: {100 * solver / tot:.1f} %")
+    # the split of category 0 (and what lies outside a chunk's cycles), ticks per chunk
+    fwd = float(out[7]) / chunks
+    c0 = float(out[0]) / chunks
+    top1, topn = float(out[11]) / chunks, float(out[12]) / chunks
+    print(f"  category 0 split: top of the first forward pass {top1:.0f}, tops of the other {fwd - 1:.2f} "
+          f"{topn:.0f} ({topn / max(fwd - 1, 1e-9):.0f} each), rest (loop glue, end of the chunk) {c0 - top1 - topn:.0f}")
+    print(f"  outside the chunk's cycles: StepChunk head + reset branch {float(out[13]) / chunks:.0f}, "
+          f"state / action load issue {float(out[14]) / chunks:.0f}, queue between chunks "
+          f"{float(out[15]) / chunks:.0f} (per chunk of the launch)")
 
 
 if __name__ == "__main__":
