@@ -253,6 +253,11 @@ inline LV<T, K> Sel(LB<K> c, const LV<T, K>& a, const LV<T, K>& b) {
   for (int i = 0; i < K; ++i) r.v[i] = c.v[i] ? a.v[i] : b.v[i];
   return r;
 }
+// y[i] = c ? f(i) : y[i] for i < N (the device form below computes f only where c holds)
+template <int N, typename T, int K, typename F>
+inline void SetWhere(LB<K> c, LV<T, K>* y, F&& f) {
+  for (int i = 0; i < N; ++i) y[i] = Sel(c, f(i), y[i]);
+}
 template <typename T, int K>
 inline LV<T, K> SqrtV(const LV<T, K>& x) {
   LV<T, K> r;
@@ -371,6 +376,14 @@ struct LaneTypes<LV<T, K>> {
 template <typename T>
 EPA_HD T Sel(bool c, T a, T b) {
   return c ? a : b;
+}
+// A lane-masked block, not N selects: y keeps its registers, the lanes where c fails are switched off (one
+// s_and_saveexec / s_or_b64 exec pair) instead of paying two v_cndmask per double.  Same operations on the lanes that
+// take them, untouched registers on the others.  (The block must hold more than a couple of instructions, or the
+// compiler speculates it and selects again.)
+template <int N, typename T, typename F>
+EPA_HD void SetWhere(bool c, T* y, F&& f) {
+  if (c) static_for<0, N>([&](auto ic) { y[decltype(ic)::value] = f(decltype(ic)::value); });
 }
 EPA_HD double Rsq(double x) { return Rsqrt(x); }
 EPA_HD double SqrtV(double x) { return Sqrt(x); }
@@ -1288,7 +1301,6 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
       } else {
         gc[j] = SumPar<KL>(gc[j]);
       }
-      grad[j] = Sel(live0, (Ma[j] - qfrc_smooth[j]) + gc[j], grad[j]);
       static_for<0, j + 1>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (j < 3) {
@@ -1298,6 +1310,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
         }
       });
     });
+    SetWhere<kLV>(live0, grad, [&](int j) { return (Ma[j] - qfrc_smooth[j]) + gc[j]; });
     const V gn2 = DotEnv<KL>(grad, grad);
     const B same = AllEnvOf<KL>(MaskSame(mask, prev_mask));
     // |grad| <= gstop; or finite termination: same active set after a full Newton step; or at the
@@ -1329,9 +1342,12 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     B searching = live;
     B exact = LT::False();
     EPA_LG_TICK(cx, 3);
-    // one evaluation (at the full step) + one Newton step of the 1-D problem; the exact search only as the fallback
+    // one evaluation (at the full step) + one Newton step of the 1-D problem; the exact search only as the fallback.
+    // The common one-evaluation search is a branch of its own: with alpha = 1, lo = 0, hi = -1 and ls = 0 known it
+    // carries no loop state and no loop control (the same operations on the same values as the loop's first trip).
     const int ls_max = it < kLsExactAfter ? EPA_LG_LS_MAX : 24;
-    for (int ls = 0; ls < ls_max; ++ls) {
+    // one evaluation at alpha; true once the wave has stopped searching
+    auto evaluation = [&](const int ls) {
       EPA_LG_COUNT(cx, 1);
       V d1p = V(0), d2p = V(0);
       U mask1 = LT::Fill(0u);
@@ -1356,17 +1372,22 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
       alpha = Sel(searching, next, alpha);
       if (!AnyWave(searching)) {
         EPA_LG_HOST_TRIP(ls + 1);
-        break;
+        return true;
       }
       if (ls + 1 == ls_max) EPA_LG_HOST_TRIP(ls + 1);
+      return false;
+    };
+    if (ls_max == 1) {  // (EPA_LG_LS_MAX == 1: every trip before kLsExactAfter)
+      evaluation(0);
+    } else {
+      for (int ls = 0; ls < ls_max; ++ls) {
+        if (evaluation(ls)) break;
+      }
     }
     EPA_LG_TICK(cx, 4);
-    static_for<0, kLV>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      // (a select, not a zero step: s of a finished env is built from partial rows)
-      qacc[i] = Sel(live, qacc[i] + alpha * s[i], qacc[i]);
-      Ma[i] = Sel(live, Ma[i] + alpha * Ms[i], Ma[i]);
-    });
+    // (masked, not a zero step: s of a finished env is built from partial rows)
+    SetWhere<kLV>(live, qacc, [&](int i) { return qacc[i] + alpha * s[i]; });
+    SetWhere<kLV>(live, Ma, [&](int i) { return Ma[i] + alpha * Ms[i]; });
     at_min = at_min | exact;
     live = live & !exact;
     if (!AnyWave(live)) break;
