@@ -107,6 +107,8 @@ class FamilyDef:
     unsupported: dict[str, Any] = field(default_factory=dict)
     # (conf, DevicePool kwargs) -> pool, for families with their own constructor (Atari)
     pool_factory: Callable[[dict, dict], Any] | None = None
+    # players per env (the PGX board games: 2); max_num_players must equal it
+    players: int = 1
 
 
 class _ShardedPools:
@@ -196,10 +198,10 @@ class _ShardedPools:
 
             def scatter(s: int, p: DevicePool, idx: Any) -> None:
                 for o, part in zip(outs, p.recv()):
-                    o[idx] = part
+                    o[idx] = part.reshape((-1, *o.shape[1:]))  # (a per-player key: back to one row per env)
 
             self._each(scatter, parts)
-            return outs
+            return self.pools[0].player_rows(outs)
         # one pinned block for the whole batch, laid out like a DevicePool batch of k rows
         row_bytes = [int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
                      for _, dtype, shape in self.state_keys]
@@ -221,8 +223,8 @@ class _ShardedPools:
             p.pop_pending()
 
         self._each(land, parts)
-        return [block[o:o + k * rb].view(dtype).reshape((k, *shape))
-                for (_, dtype, shape), o, rb in zip(self.state_keys, offs, row_bytes)]
+        return self.pools[0].player_rows([block[o:o + k * rb].view(dtype).reshape((k, *shape))
+                                          for (_, dtype, shape), o, rb in zip(self.state_keys, offs, row_bytes)])
 
     def close(self) -> None:
         self._exec.shutdown(wait=True)
@@ -294,8 +296,11 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
 
         def __init__(self, spec: Any) -> None:
             conf = dict(zip(spec._config_keys, spec._config_values))
-            if conf["max_num_players"] != 1:
-                raise ValueError("only single-player envs are on the MI355X path")
+            if fd.players == 1:
+                if conf["max_num_players"] != 1:
+                    raise ValueError("only single-player envs are on the MI355X path")
+            elif conf["max_num_players"] != fd.players:
+                raise ValueError(f"{fd.name}: max_num_players must be {fd.players}, got {conf['max_num_players']}")
             params = {k: float(v) for k, v in fd.native_params(conf).items()}
             if conf["recv_timeout_ms"] != -1:
                 params["recv_timeout_ms"] = float(conf["recv_timeout_ms"])
@@ -328,6 +333,10 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
 
         def _send(self, action: list[np.ndarray]) -> None:
             # list order = _action_keys: env_id, players.env_id, <env action>
+            if fd.players > 1 and not np.array_equal(np.asarray(action[1]), np.asarray(action[0])):
+                # divergence: the reference routes player action rows by players.env_id; here every env takes
+                # the one action row of its env_id
+                raise ValueError(f"{fd.name}: players.env_id must equal env_id (one action row per env)")
             self._pool.send(action[0], action[-1])
 
         def _recv(self) -> list[np.ndarray]:

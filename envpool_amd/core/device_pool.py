@@ -66,6 +66,7 @@ class DevicePool:
     """Low-level pool: numpy in, list-of-numpy out, in `_state_keys` order."""
 
     _SMALL_BATCH_BYTES = 256 * 1024
+    key_players: list[int] | None = None
 
     def __init__(
         self,
@@ -92,6 +93,10 @@ class DevicePool:
         h = self._create(family, cfg, params)
         del keep
         self._h = h
+        # per state key: P if its rows carry the leading player dimension (multi-player families), else 1
+        if self.key_players is None:
+            self.key_players = [1] * len(self.state_keys)
+        self.players = max(self.key_players)
         self._pending: collections.deque[int] = collections.deque()
         # per pending send / reset, the pinned block named at send time (None: recv takes one)
         self._posted: collections.deque[Any] = collections.deque()
@@ -103,6 +108,7 @@ class DevicePool:
     def _create(self, family: str, cfg: Any, params: dict[str, float] | None) -> ctypes.c_void_p:
         """epa_create + the key tables (overridden by families with their own constructor)."""
         self.state_keys = native.describe(family, params, "state")
+        self.key_players = native.describe_state_players(family, params)
         self.action_keys = native.describe(family, params, "action")
         self.action_dtype = self.action_keys[-1][1]
         self.action_shape = self.action_keys[-1][2]
@@ -214,11 +220,23 @@ class DevicePool:
                     left = 0
         rows = k.value
         if small:
-            return outs if rows == cap else [o[:rows] for o in outs]
+            return self.player_rows(outs if rows == cap else [o[:rows] for o in outs])
         # one view per key straight onto the block (each holds the block as its base: the block goes back to the free
         # list when the last of them dies)
-        return [np.ndarray((rows, *shape), dtype=dtype, buffer=block, offset=int(off))
-                for (_, dtype, shape), off in zip(self.state_keys, offs)]
+        return self.player_rows([np.ndarray((rows, *shape), dtype=dtype, buffer=block, offset=int(off))
+                                 for (_, dtype, shape), off in zip(self.state_keys, offs)])
+
+    def view_shape(self, i: int, rows: int) -> tuple[int, ...]:
+        """Shape of state key i for a batch of `rows` env rows as recv hands it out: a per-player key's [rows, P, ...]
+        block as the reference's [rows * P, ...] player rows (env-major: the P rows of an env are adjacent)."""
+        shape, p = self.state_keys[i][2], self.key_players[i]
+        return (rows * p, *shape[1:]) if p > 1 else (rows, *shape)
+
+    def player_rows(self, outs: list[np.ndarray]) -> list[np.ndarray]:
+        """[rows, ...] per-env arrays in state key order -> the arrays recv returns (views, no copy)."""
+        if self.players == 1:
+            return outs
+        return [o.reshape(self.view_shape(i, o.shape[0])) for i, o in enumerate(outs)]
 
     def recv_dict(self) -> dict[str, np.ndarray]:
         return {k[0]: v for k, v in zip(self.state_keys, self.recv())}

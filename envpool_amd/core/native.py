@@ -81,6 +81,8 @@ def lib() -> ctypes.CDLL:
         "epa_family_name": (cp, [i32]),
         "epa_describe_state": (i32, [cp, P(EpaConfig), P(EpaKeyInfo), i32, P(i32)]),
         "epa_describe_action": (i32, [cp, P(EpaConfig), P(EpaKeyInfo), i32, P(i32)]),
+        "epa_family_players": (i32, [cp, P(i32)]),
+        "epa_describe_state_players": (i32, [cp, P(EpaConfig), P(i32), i32, P(i32)]),
         "epa_create": (i32, [cp, P(EpaConfig), P(vp)]),
         "epa_destroy": (i32, [vp]),
         "epa_send": (i32, [vp, vp, i32, vp]),
@@ -129,7 +131,8 @@ def lib() -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = [
     "epa_num_families", "epa_family_name", "epa_describe_state",
-    "epa_describe_action", "epa_create", "epa_destroy", "epa_send", "epa_reset",
+    "epa_describe_action", "epa_family_players", "epa_describe_state_players",
+    "epa_create", "epa_destroy", "epa_send", "epa_reset",
     "epa_recv", "epa_recv_layout", "epa_recv_block", "epa_send_into", "epa_recv_into", "epa_pending_rows",
     "epa_send_device", "epa_recv_device", "epa_step_device", "epa_wait_stream", "epa_consumer_wait",
     "epa_stream", "epa_synchronize", "epa_set_timing", "epa_kernel_time_ms",
@@ -216,3 +219,20 @@ def describe(family: str, params: dict[str, float] | None = None, which: str = "
         out.append((k.name.decode(), DTYPES[k.dtype], tuple(k.shape[: k.ndim])))
     del keep
     return out
+
+
+def family_players(family: str) -> int:
+    """Players P of a family (1 for every single-player family)."""
+    p = ctypes.c_int32(0)
+    check(lib().epa_family_players(family.encode(), ctypes.byref(p)))
+    return p.value
+
+
+def describe_state_players(family: str, params: dict[str, float] | None = None) -> list[int]:
+    """Per state key: P if its rows carry the leading player dimension ([k, P, ...] per batch), 1 otherwise."""
+    cfg, keep = make_config(1, params=params)
+    out = (ctypes.c_int32 * 32)()
+    n = ctypes.c_int32(0)
+    check(lib().epa_describe_state_players(family.encode(), ctypes.byref(cfg), out, 32, ctypes.byref(n)))
+    del keep
+    return [int(out[i]) for i in range(n.value)]

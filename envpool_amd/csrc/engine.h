@@ -58,7 +58,8 @@ inline int DtypeBytes(int dt) {
 struct KeySpec {
   std::string name;
   int dtype;
-  std::vector<int> shape;  // per row
+  std::vector<int> shape;  // per row (= per env); a per-player key's shape starts with the family's player count
+  int players{1};          // P of a per-player key ([P, ...] per row: the reference's P player rows), 1 otherwise
   int row_elems() const {
     int n = 1;
     for (int d : shape) n *= d;
@@ -84,8 +85,9 @@ struct Config {
   static Config From(const epa_config* c);
 };
 
-// Common state keys of every env (envpool/core/env_spec.h:37-43).
-std::vector<KeySpec> CommonStateKeys();
+// Common state keys of every env (envpool/core/env_spec.h:37-43).  A family of P > 1 players gets
+// "info:players.env_id", "reward" and "discount" with per-row shape [P] (one row per env, P player rows in it).
+std::vector<KeySpec> CommonStateKeys(int players = 1);
 constexpr int kNumCommonKeys = 8;
 constexpr int kMaxKeys = 24;
 
@@ -181,8 +183,9 @@ class HostCopier {
 
 class Pool {
  public:
+  // players: P of the family (its per-player keys carry a leading P in env_state_keys already)
   Pool(const Config& cfg, std::vector<KeySpec> env_state_keys, KeySpec action,
-       bool needs_rng);
+       bool needs_rng, int players = 1);
   virtual ~Pool();
 
   const Config& cfg() const { return cfg_; }
@@ -398,6 +401,12 @@ bool DescribeMiniGrid(const std::string& family, const Config& cfg,
 Pool* MakeJumanji(const std::string& family, const Config& cfg);
 bool DescribeJumanji(const std::string& family, const Config& cfg,
                      std::vector<KeySpec>* state, KeySpec* action);
+Pool* MakePgx(const std::string& family, const Config& cfg);
+bool DescribePgx(const std::string& family, const Config& cfg,
+                 std::vector<KeySpec>* state, KeySpec* action);
+int PgxPlayers(const std::string& family);  // 0: not a PGX family
+// players of a family (1 for every single-player family)
+int FamilyPlayers(const std::string& family);
 // Atari (atari_env.hip): needs two strings the numeric epa_config cannot carry
 Pool* MakeAtari(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);
 int AtariNumActions(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);

@@ -1,0 +1,241 @@
+// PGX two-player board games (TicTacToe, ConnectFour, Hex, Othello): batched reset / step kernel, one env per
+// lane, bit-exact with the reference.
+//
+// Replaces, for the whole batch in one launch, XxxEnv::{Reset,Step,WriteState} of envpool/pgx/board_games.h
+// plus the runtime (async_envpool.h:118-132, env.h:184-256) of a pool with max_num_players = 2.  The env bodies
+// are pgx_env.hip.h (shared with the host harness of the tests); one kernel instantiation per game.
+//
+// Data layout (HBM), see DESIGN.md "PGX":
+//   state  pgx::State [N]   64 B per env, env-major: three 128-bit cell sets (stones, legal mask) + four words,
+//                           read once and written once by the env's lane
+//   mt     CommonDev, tiled (envs reset at their own times; one draw per reset)
+// Outputs: every env writes 2 player rows, kept together as the [2, ...] block of its batch row (the reference's
+// env-major player rows).  They are most of the traffic (Hex: 1.6 KB per env-step, obs 968 B of it), so a lane does
+// not store its own row: it leaves its `View` (state + common keys, 96 B) in LDS, and then the block writes each
+// key's section -- one contiguous range for the block's rows -- in 16-byte words, every thread computing the
+// elements of its words from the views (pgx::Elem).  A wave's stores are then 1 KB contiguous instead of 64 rows
+// apart.
+#include <algorithm>
+#include <string>
+
+#include "device_common.hip.h"
+#include "engine.h"
+#include "pgx_env.hip.h"
+
+namespace epa {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr unsigned kErrState = 1;  // set_state words that are no position of the game
+
+// key K's section of rows [row0, row0 + nrows) of the launch, written by the whole block
+template <int G, int K>
+__device__ __forceinline__ void EmitKey(const OutPtrs& out, int row0, int nrows, const pgx::View* lv) {
+  constexpr int re = pgx::RowElems<G>(K), eb = pgx::ElemBytes(K), per = 16 / eb;
+  char* base = static_cast<char*>(out.p[K]) + (size_t)row0 * (re * eb);
+  const int total = nrows * re;
+  // head elements up to the first 16-byte boundary (a pipelined launch's second half may start anywhere)
+  const int mis = (int)((uintptr_t)base & 15);
+  const int head = std::min(total, mis == 0 ? 0 : (16 - mis) / eb);
+  const int words = (total - head) / per;
+  const int tail = head + words * per;
+  auto one = [&](int i) {
+    const int r = i / re;
+    const uint32_t x = pgx::Elem<G>(lv[r], K, i - r * re);
+    if (eb == 1) {
+      base[i] = (char)x;
+    } else {
+      reinterpret_cast<uint32_t*>(base)[i] = x;
+    }
+  };
+  for (int i = threadIdx.x; i < head; i += kBlock) one(i);
+  for (int c = threadIdx.x; c < words; c += kBlock) {
+    const int i0 = head + c * per;
+    int r = i0 / re, e = i0 - r * re;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < per; ++j) {
+      const uint32_t x = pgx::Elem<G>(lv[r], K, e);
+      if (eb == 1) {
+        w[j >> 2] |= (x & 0xffu) << (8 * (j & 3));
+      } else {
+        w[j] = x;
+      }
+      if (++e == re) {
+        e = 0;
+        ++r;
+      }
+    }
+    *reinterpret_cast<uint4*>(base + (size_t)i0 * eb) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  for (int i = tail + threadIdx.x; i < total; i += kBlock) one(i);
+}
+
+template <int G, int... K>
+__device__ __forceinline__ void EmitAll(const OutPtrs& out, int row0, int nrows, const pgx::View* lv,
+                                        std::integer_sequence<int, K...>) {
+  (EmitKey<G, K>(out, row0, nrows, lv), ...);
+}
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void PgxStepKernel(CommonDev cm, StepArgs a, pgx::State* st,
+                                                        const int* __restrict__ action, OutPtrs out) {
+  __shared__ pgx::View lv[kBlock];
+  const int row0 = blockIdx.x * kBlock;
+  const int row = row0 + threadIdx.x;
+  if (row < a.k) {
+    const int e = a.ids ? a.ids[row] - a.id_offset : row;
+    pgx::State s = st[e];
+    int cur = cm.cur_step[e];
+    pgx::Rewards rw{{0.0f, 0.0f}};
+    if (a.force_reset || cm.done[e] != 0) {  // async_envpool.h:127
+      cur = 0;
+      Mt19937 g(cm, e);
+      pgx::Reset<G>(g, s);
+      g.Commit();
+    } else {
+      ++cur;
+      rw = pgx::Step<G>(s, action[row]);
+    }
+    st[e] = s;
+    cm.done[e] = s.done ? 1 : 0;
+    cm.cur_step[e] = cur;
+    pgx::View v{};
+    v.s = s;
+    pgx::Finish(v, e + a.id_offset, cur, rw, a.max_episode_steps);
+    lv[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (row0 >= a.k) return;
+  EmitAll<G>(out, row0, std::min(kBlock, a.k - row0), lv, std::make_integer_sequence<int, pgx::kNumKeys>());
+}
+
+// flat state per env: cur_step, done, then pgx::Hidden's words
+template <int G>
+__global__ void PgxGetState(CommonDev cm, const pgx::State* st, const int* ids, int k, double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const int e = ids[i];
+  constexpr int W = pgx::HiddenWords<G>();
+  double* o = out + (size_t)i * (2 + W);
+  o[0] = cm.cur_step[e];
+  o[1] = cm.done[e];
+  int32_t w[W];
+  pgx::Hidden<G>(st[e], w);
+  for (int j = 0; j < W; ++j) o[2 + j] = w[j];
+}
+
+template <int G>
+__global__ void PgxSetState(CommonDev cm, pgx::State* st, unsigned* err, const int* ids, int k, const double* in) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const int e = ids[i];
+  constexpr int W = pgx::HiddenWords<G>();
+  const double* o = in + (size_t)i * (2 + W);
+  int32_t w[W];
+  for (int j = 0; j < W; ++j) w[j] = (int32_t)o[2 + j];
+  pgx::State s{};
+  bool done = o[1] != 0.0;
+  if (!pgx::SetHidden<G>(s, w)) {
+    *err = kErrState;
+    done = true;  // such an env resets on its next step
+  }
+  s.done = done ? 1 : 0;
+  st[e] = s;
+  cm.cur_step[e] = (int)o[0];
+  cm.done[e] = done ? 1 : 0;
+}
+
+int GameOf(const std::string& family) {
+  if (family == "TicTacToe") return pgx::kTicTacToe;
+  if (family == "ConnectFour") return pgx::kConnectFour;
+  if (family == "Hex") return pgx::kHex;
+  if (family == "Othello") return pgx::kOthello;
+  return -1;
+}
+
+// the reference's StateSpec key order (after the common keys); "obs" and "info:players.id" are per player
+template <int G>
+std::vector<KeySpec> EnvKeys() {
+  using D = pgx::Dims<G>;
+  return {{"obs", EPA_BOOL, {pgx::kPlayers, D::H, D::W, D::C}, pgx::kPlayers},
+          {"info:board", EPA_I32, {D::H, D::W}},
+          {"info:current_player", EPA_I32, {}},
+          {"info:legal_action_mask", EPA_BOOL, {D::A}},
+          {"info:players.id", EPA_I32, {pgx::kPlayers}, pgx::kPlayers}};
+}
+
+std::vector<KeySpec> EnvKeysOf(int g) {
+  switch (g) {
+    case pgx::kTicTacToe: return EnvKeys<pgx::kTicTacToe>();
+    case pgx::kConnectFour: return EnvKeys<pgx::kConnectFour>();
+    case pgx::kHex: return EnvKeys<pgx::kHex>();
+    default: return EnvKeys<pgx::kOthello>();
+  }
+}
+
+template <int G>
+class PgxPool : public Pool {
+ public:
+  bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own rows only
+  explicit PgxPool(const Config& cfg)
+      : Pool(cfg, EnvKeys<G>(), KeySpec{"action", EPA_I32, {}}, /*needs_rng=*/true, pgx::kPlayers) {
+    const size_t n = (size_t)cfg.num_envs;
+    EPA_HIP(hipMalloc(&state_, sizeof(pgx::State) * n));
+    EPA_HIP(hipMemsetAsync(state_, 0, sizeof(pgx::State) * n, stream_));
+    EnableErrorWord();
+    mt_tile_default_ = 16;  // envs reset at their own times
+    InitCommon();
+  }
+  ~PgxPool() override {
+    if (state_) (void)hipFree(state_);
+  }
+  int StateDim() const override { return 2 + pgx::HiddenWords<G>(); }
+  void GetState(const int* d_ids, int k, double* d_out) override {
+    hipLaunchKernelGGL(PgxGetState<G>, dim3((k + 255) / 256), dim3(256), 0, stream_, common_, state_, d_ids, k,
+                       d_out);
+  }
+  void SetState(const int* d_ids, int k, const double* d_in) override {
+    hipLaunchKernelGGL(PgxSetState<G>, dim3((k + 255) / 256), dim3(256), 0, stream_, common_, state_, err_dev_,
+                       d_ids, k, d_in);
+  }
+  std::string ErrorText(unsigned code) const override {
+    if (code == kErrState) return "PGX: set_state was given words that are no position of the game";
+    return Pool::ErrorText(code);
+  }
+
+ protected:
+  void Launch(const int* d_ids, int k, const void* d_action, bool force_reset, const OutPtrs& out) override {
+    StepArgs a{d_ids, k, force_reset ? 1 : 0, cfg_.max_episode_steps, cfg_.env_id_offset};
+    hipLaunchKernelGGL(PgxStepKernel<G>, dim3((k + kBlock - 1) / kBlock), dim3(kBlock), 0, stream_, common_, a,
+                       state_, static_cast<const int*>(d_action), out);
+  }
+
+ private:
+  pgx::State* state_{nullptr};
+};
+
+}  // namespace
+
+int PgxPlayers(const std::string& family) { return GameOf(family) < 0 ? 0 : pgx::kPlayers; }
+
+bool DescribePgx(const std::string& family, const Config& cfg, std::vector<KeySpec>* state, KeySpec* action) {
+  (void)cfg;
+  const int g = GameOf(family);
+  if (g < 0) return false;
+  *state = EnvKeysOf(g);
+  *action = KeySpec{"action", EPA_I32, {}};
+  return true;
+}
+
+Pool* MakePgx(const std::string& family, const Config& cfg) {
+  switch (GameOf(family)) {
+    case pgx::kTicTacToe: return new PgxPool<pgx::kTicTacToe>(cfg);
+    case pgx::kConnectFour: return new PgxPool<pgx::kConnectFour>(cfg);
+    case pgx::kHex: return new PgxPool<pgx::kHex>(cfg);
+    case pgx::kOthello: return new PgxPool<pgx::kOthello>(cfg);
+    default: return nullptr;
+  }
+}
+
+}  // namespace epa

@@ -5,3 +5,4 @@ import envpool_amd.mujoco.gym.registration  # noqa: F401
 import envpool_amd.toy_text.registration  # noqa: F401
 import envpool_amd.minigrid.registration  # noqa: F401
 import envpool_amd.jumanji.registration  # noqa: F401
+import envpool_amd.pgx.registration  # noqa: F401

@@ -80,7 +80,7 @@ class EnvPoolMixin(ABC):
         else:
             adict.setdefault("env_id", self.all_env_ids)
         if "players.env_id" not in adict:
-            # all hot-path envs are single player: players.env_id == env_id
+            # one action row per env (every family here): players.env_id == env_id
             adict["players.env_id"] = _normalize_env_id(adict["env_id"])
         if not hasattr(self, "_action_names"):
             self._action_names = self._spec._action_keys

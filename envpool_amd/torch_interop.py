@@ -90,8 +90,9 @@ def recv_device_tensors(pool: Any, device: Any = None, order_current_stream: boo
     if order_current_stream:
         pool.consumer_wait(torch.cuda.current_stream(dev).cuda_stream)
     out = {}
-    for (name, dtype, shape), ptr in zip(pool.state_keys, ptrs):
+    for i, ((name, dtype, _), ptr) in enumerate(zip(pool.state_keys, ptrs)):
         if k == 0:
             continue
-        out[name] = torch.as_tensor(_DevArray(ptr, (k, *shape), dtype), device=dev)
+        # a per-player key of a multi-player family: its [k, P, ...] block as [k * P, ...] player rows
+        out[name] = torch.as_tensor(_DevArray(ptr, pool.view_shape(i, k), dtype), device=dev)
     return out

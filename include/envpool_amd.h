@@ -146,9 +146,14 @@ typedef struct epa_config {
   const double* param_values;
 } epa_config;
 
-/* One state or action key. `shape` excludes the leading batch dimension
- * (the reference's -1 player dimension is dropped: all hot-path envs are
- * single-player). */
+/* One state or action key. `shape` excludes the leading batch dimension.
+ * Single-player families (epa_family_players == 1) drop the reference's -1
+ * player dimension.  A family of P > 1 players (the PGX board games) keeps it
+ * as the leading P of the per-row shape of its per-player state keys
+ * ("info:players.env_id", "reward", "discount" and the family's own per-player
+ * keys, see epa_describe_state_players): a batch of k rows then holds the
+ * reference's k * P player rows as a [k, P, ...] block, env-major, which is
+ * the reference's [k * P, ...] layout.  Actions stay one row per env. */
 typedef struct epa_key_info {
   const char* name;
   int32_t dtype;
@@ -171,6 +176,14 @@ int epa_describe_state(const char* family, const epa_config* cfg,
                        epa_key_info* keys, int cap, int* n);
 int epa_describe_action(const char* family, const epa_config* cfg,
                         epa_key_info* keys, int cap, int* n);
+
+/* Number of players P of a family (1 for every single-player family). */
+int epa_family_players(const char* family, int32_t* players);
+/* Per state key (epa_describe_state order): P if the key's rows carry the
+ * leading player dimension, 1 otherwise.  Writes up to `cap` entries; returns
+ * the total number through *n. */
+int epa_describe_state_players(const char* family, const epa_config* cfg,
+                               int32_t* players, int cap, int* n);
 
 /* ---- pool lifetime ---------------------------------------------------- */
 
