@@ -259,6 +259,12 @@ inline void SetWhere(LB<K> c, LV<T, K>* y, F&& f) {
   for (int i = 0; i < N; ++i) y[i] = Sel(c, f(i), y[i]);
 }
 template <typename T, int K>
+inline LV<T, K> Mag(const LV<T, K>& x) {
+  LV<T, K> r;
+  for (int i = 0; i < K; ++i) r.v[i] = std::fabs(x.v[i]);
+  return r;
+}
+template <typename T, int K>
 inline LV<T, K> SqrtV(const LV<T, K>& x) {
   LV<T, K> r;
   for (int i = 0; i < K; ++i) r.v[i] = std::sqrt(x.v[i]);
@@ -386,6 +392,7 @@ EPA_HD void SetWhere(bool c, T* y, F&& f) {
   if (c) static_for<0, N>([&](auto ic) { y[decltype(ic)::value] = f(decltype(ic)::value); });
 }
 EPA_HD double Rsq(double x) { return Rsqrt(x); }
+EPA_HD double Mag(double x) { return __builtin_fabs(x); }
 EPA_HD double SqrtV(double x) { return Sqrt(x); }
 EPA_HD float Rsq(float x) { return Rsqrt(x); }
 EPA_HD bool AnyWave(bool c) { return WaveAny(c); }
@@ -503,9 +510,13 @@ template <typename V>
 EPA_HD V Abs(V x) {
   return Sel(x < V(0), -x, x);
 }
+// |x| for the callers that read no sign of a zero or a NaN: the value is only compared, squared, or kept where it is
+// positive -- then Mag(x) and Abs(x) give the same results.  Device: fabs, a source modifier of the instruction that
+// reads it, where Abs costs a compare and two selects.
+// (Abs stays where the result enters a sum: Abs(-0) = -0.)
 template <typename T, typename V>
 EPA_HD V ImpedanceV(T d0, T dmax, T width, V r) {  // mj::Impedance with selects
-  V x = Abs(r) * V(T(1) / width);
+  V x = Mag(r) * V(T(1) / width);  // (x is compared and squared only)
   V y = Sel(x <= V(0.5), V(2) * x * x, V(1) - V(2) * (V(1) - x) * (V(1) - x));
   return Sel(x >= V(1), V(dmax), V(d0) + y * V(dmax - d0));
 }
@@ -808,7 +819,7 @@ EPA_HD unsigned MakeConstraint(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p
       const V u = -(h1x * dfx + h1z * dfz), w = h2x * dfx + h2z * dfz;
       const V det = ma * mc - mb * mb;
       auto clamp1 = [](V x) { return Sel(x > V(1), V(1), Sel(x < V(-1), V(-1), x)); };
-      const auto par = Abs(det) < V(kMinVal);
+      const auto par = Mag(det) < V(kMinVal);
       const V den = Sel(par, V(1), det);
       V x1 = (mc * u - mb * w) / den;
       V x2 = (ma * w - mb * u) / den;
@@ -1259,7 +1270,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
   V fs = V(0);
   static_for<0, kLV>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    const V x = Abs(qfrc_smooth[i]);
+    const V x = Mag(qfrc_smooth[i]);  // (taken where it exceeds fs >= +0 only)
     fs = Sel(x > fs, x, fs);
   });
   fs = MaxLegs<KL>(fs);
@@ -1338,7 +1349,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     const V g1 = DotEnv<KL>(s, r0), g2 = DotEnv<KL>(s, Ms);
     V alpha = V(1), lo = V(0), hi = V(-1);
     full_step = LT::False();
-    const V ls_tol = V(T(EPA_LG_LS_RTOL)) * Abs(g1);
+    const V ls_tol = V(T(EPA_LG_LS_RTOL)) * Mag(g1);  // (compared only)
     B searching = live;
     B exact = LT::False();
     EPA_LG_TICK(cx, 3);
@@ -1353,7 +1364,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
       U mask1 = LT::Fill(0u);
       LineEval<KL>(m, cx, p, lim, ends, vis, qacc, s, alpha, &d1p, &d2p, mask1);
       const V d1 = (g1 + alpha * g2) + SumEnv<KL>(d1p), d2 = g2 + SumEnv<KL>(d2p);
-      const B hit = Abs(d1) <= ls_tol;
+      const B hit = Mag(d1) <= ls_tol;
       // a full Newton step is exact for the active set H was built with: if the rows active at
       // a + s are the rows H was built with, a + s IS the minimiser (finite termination) and the
       // env is done without another pass over the rows
