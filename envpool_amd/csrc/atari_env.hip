@@ -157,7 +157,7 @@ struct Task {
 class AtariPool : public Pool {
  public:
   AtariPool(const Config& cfg, const std::string& rom, const std::string& emulator_lib)
-      : Pool(cfg, AtariKeys(AtariCfg::From(cfg)), KeySpec{"action", EPA_I32, {}}, false),
+      : Pool(cfg, FamilySpec{AtariKeys(AtariCfg::From(cfg)), {"action", EPA_I32, {}}}, false),
         a_(AtariCfg::From(cfg)),
         plugin_(emulator_lib),
         rom_(rom) {

@@ -381,41 +381,32 @@ __global__ void SetStateKernel(ClassicDev dev, CommonDev cm, const int* ids,
   cm.cur_step[e] = (int)o[NS + 1];
 }
 
-struct FamilyInfo {
+struct ClassicFamily {
   const char* name;
   int kind;
-  std::vector<KeySpec> keys;
-  KeySpec action;
+  FamilySpec spec;
 };
 
-const std::vector<FamilyInfo>& Families() {
-  static const std::vector<FamilyInfo> f = {
-      {"CartPole", kCartPole, {{"obs", EPA_F32, {4}}}, {"action", EPA_I32, {}}},
-      {"Pendulum", kPendulum, {{"obs", EPA_F32, {3}}}, {"action", EPA_F32, {1}}},
-      {"MountainCar", kMountainCar, {{"obs", EPA_F32, {2}}},
-       {"action", EPA_I32, {}}},
-      {"MountainCarContinuous", kMountainCarContinuous, {{"obs", EPA_F32, {2}}},
-       {"action", EPA_F32, {1}}},
-      {"Acrobot", kAcrobot,
-       {{"obs", EPA_F32, {6}}, {"info:state", EPA_F32, {2}}},
-       {"action", EPA_I32, {}}},
+const ClassicFamily& Find(const std::string& name) {
+  static const ClassicFamily f[] = {
+      {"CartPole", kCartPole, {{{"obs", EPA_F32, {4}}}, {"action", EPA_I32, {}}}},
+      {"Pendulum", kPendulum, {{{"obs", EPA_F32, {3}}}, {"action", EPA_F32, {1}}}},
+      {"MountainCar", kMountainCar, {{{"obs", EPA_F32, {2}}}, {"action", EPA_I32, {}}}},
+      {"MountainCarContinuous", kMountainCarContinuous, {{{"obs", EPA_F32, {2}}}, {"action", EPA_F32, {1}}}},
+      {"Acrobot", kAcrobot, {{{"obs", EPA_F32, {6}}, {"info:state", EPA_F32, {2}}}, {"action", EPA_I32, {}}}},
   };
-  return f;
-}
-
-const FamilyInfo* Find(const std::string& name) {
-  for (auto& f : Families()) {
-    if (name == f.name) return &f;
+  for (auto& fi : f) {
+    if (name == fi.name) return fi;
   }
-  return nullptr;
+  throw std::logic_error("not a classic_control family: " + name);
 }
 
 template <int KIND>
 class ClassicPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
-  ClassicPool(const Config& cfg, const FamilyInfo& fi)
-      : Pool(cfg, fi.keys, fi.action, /*needs_rng=*/true),
+  ClassicPool(const Config& cfg, const FamilySpec& spec)
+      : Pool(cfg, spec, /*needs_rng=*/true),
         version_((int)cfg.Get("version", 0)) {
     for (int j = 0; j < NS; ++j) {
       EPA_HIP(hipMalloc(&dev_.s[j], sizeof(double) * cfg.num_envs));
@@ -483,26 +474,17 @@ class ClassicPool : public Pool {
 
 }  // namespace
 
-bool DescribeClassicControl(const std::string& family, const Config& cfg,
-                            std::vector<KeySpec>* state, KeySpec* action) {
-  (void)cfg;
-  const FamilyInfo* fi = Find(family);
-  if (!fi) return false;
-  *state = fi->keys;
-  *action = fi->action;
-  return true;
-}
+FamilySpec DescribeClassicControl(const std::string& name, const Config&) { return Find(name).spec; }
 
-Pool* MakeClassicControl(const std::string& family, const Config& cfg) {
-  const FamilyInfo* fi = Find(family);
-  if (!fi) return nullptr;
-  switch (fi->kind) {
-    case kCartPole: return new ClassicPool<kCartPole>(cfg, *fi);
-    case kPendulum: return new ClassicPool<kPendulum>(cfg, *fi);
-    case kMountainCar: return new ClassicPool<kMountainCar>(cfg, *fi);
+Pool* MakeClassicControl(const std::string& name, const Config& cfg) {
+  const ClassicFamily& fi = Find(name);
+  switch (fi.kind) {
+    case kCartPole: return new ClassicPool<kCartPole>(cfg, fi.spec);
+    case kPendulum: return new ClassicPool<kPendulum>(cfg, fi.spec);
+    case kMountainCar: return new ClassicPool<kMountainCar>(cfg, fi.spec);
     case kMountainCarContinuous:
-      return new ClassicPool<kMountainCarContinuous>(cfg, *fi);
-    default: return new ClassicPool<kAcrobot>(cfg, *fi);
+      return new ClassicPool<kMountainCarContinuous>(cfg, fi.spec);
+    default: return new ClassicPool<kAcrobot>(cfg, fi.spec);
   }
 }
 

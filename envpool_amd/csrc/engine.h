@@ -91,6 +91,15 @@ std::vector<KeySpec> CommonStateKeys(int players = 1);
 constexpr int kNumCommonKeys = 8;
 constexpr int kMaxKeys = 24;
 
+// What a pool of a family produces for a config: the family's own state keys (the engine puts
+// CommonStateKeys(players) in front of them), its action key, and P (a per-player key's shape starts with it).
+struct FamilySpec {
+  std::vector<KeySpec> state;
+  KeySpec action;
+  int players{1};
+  std::vector<KeySpec> StateKeys() const;  // every state key of such a pool: the common ones, then `state`
+};
+
 // Output pointers handed to a step kernel: out.p[key] is the base of that
 // key's [k, ...] array inside the batch block.
 struct OutPtrs {
@@ -183,9 +192,8 @@ class HostCopier {
 
 class Pool {
  public:
-  // players: P of the family (its per-player keys carry a leading P in env_state_keys already)
-  Pool(const Config& cfg, std::vector<KeySpec> env_state_keys, KeySpec action,
-       bool needs_rng, int players = 1);
+  // `spec`: the family's describe result for cfg; the state keys become CommonStateKeys(spec.players) + spec.state
+  Pool(const Config& cfg, const FamilySpec& spec, bool needs_rng);
   virtual ~Pool();
 
   const Config& cfg() const { return cfg_; }
@@ -385,33 +393,42 @@ struct WaveTrace {
 // envpool/mujoco/frame_stack.h:42-71); throws like the reference on frame_stack < 1
 std::vector<int> StackedObsShape(const Config& cfg, int nobs);
 
-// family factories (defined next to the kernels)
-Pool* MakeClassicControl(const std::string& family, const Config& cfg);
-bool DescribeClassicControl(const std::string& family, const Config& cfg,
-                            std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeToyText(const std::string& family, const Config& cfg);
-bool DescribeToyText(const std::string& family, const Config& cfg,
-                     std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeMujoco(const std::string& family, const Config& cfg);
-bool DescribeMujoco(const std::string& family, const Config& cfg,
-                    std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeMiniGrid(const std::string& family, const Config& cfg);
-bool DescribeMiniGrid(const std::string& family, const Config& cfg,
-                      std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeJumanji(const std::string& family, const Config& cfg);
-bool DescribeJumanji(const std::string& family, const Config& cfg,
-                     std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakePgx(const std::string& family, const Config& cfg);
-bool DescribePgx(const std::string& family, const Config& cfg,
-                 std::vector<KeySpec>* state, KeySpec* action);
-int PgxPlayers(const std::string& family);  // 0: not a PGX family
-// players of a family (1 for every single-player family)
-int FamilyPlayers(const std::string& family);
-// Atari (atari_env.hip): needs two strings the numeric epa_config cannot carry
+// The family table (engine.hip), one row per name in epa_family_name order.  A family file exports one
+// describe / make pair and is only ever called with the names its rows give it; describe must accept any config
+// (epa_describe_* pass the caller's params alone, epa_family_players a default Config).
+struct Family {
+  const char* name;
+  FamilySpec (*describe)(const std::string& name, const Config& cfg);
+  Pool* (*make)(const std::string& name, const Config& cfg);
+};
+const std::vector<Family>& Families();
+const Family& FindFamily(const std::string& name);  // throws invalid_argument("unknown env family: " + name)
+
+FamilySpec DescribeClassicControl(const std::string& name, const Config& cfg);
+Pool* MakeClassicControl(const std::string& name, const Config& cfg);
+FamilySpec DescribeToyText(const std::string& name, const Config& cfg);
+Pool* MakeToyText(const std::string& name, const Config& cfg);
+FamilySpec DescribeMujocoGym(const std::string& name, const Config& cfg);  // HalfCheetah, Walker2d, Hopper
+Pool* MakeMujocoGym(const std::string& name, const Config& cfg);
+FamilySpec DescribeAnt(const std::string& name, const Config& cfg);
+Pool* MakeAnt(const std::string& name, const Config& cfg);
+// InvertedPendulum, InvertedDoublePendulum, Reacher, Swimmer
+FamilySpec DescribePendulum(const std::string& name, const Config& cfg);
+Pool* MakePendulum(const std::string& name, const Config& cfg);
+FamilySpec DescribeHumanoid(const std::string& name, const Config& cfg);  // Humanoid, HumanoidStandup
+Pool* MakeHumanoid(const std::string& name, const Config& cfg);
+FamilySpec DescribePusher(const std::string& name, const Config& cfg);
+Pool* MakePusher(const std::string& name, const Config& cfg);
+FamilySpec DescribeMiniGrid(const std::string& name, const Config& cfg);
+Pool* MakeMiniGrid(const std::string& name, const Config& cfg);
+FamilySpec DescribeJumanji(const std::string& name, const Config& cfg);
+Pool* MakeJumanji(const std::string& name, const Config& cfg);
+FamilySpec DescribePgx(const std::string& name, const Config& cfg);
+Pool* MakePgx(const std::string& name, const Config& cfg);
+// Atari (atari_env.hip) is not in the table: it needs two strings the numeric epa_config cannot carry
 Pool* MakeAtari(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);
 int AtariNumActions(const Config& cfg, const std::string& rom_path, const std::string& emulator_lib);
 
-const std::vector<std::string>& FamilyNames();
 void SetLastError(const std::string& msg);  // thread-local epa_last_error()
 
 // Launch helpers shared by the family files.

@@ -121,37 +121,36 @@ int PuzzleOf(const std::string& family) {
   if (family == "SlidingTilePuzzle") return jm::kSlidingTile;
   if (family == "RubiksCube") return jm::kRubiksCube;
   if (family == "Snake") return jm::kSnake;
-  if (family == "Maze") return jm::kMaze;
-  return -1;
+  return jm::kMaze;
 }
 
-// the reference's StateSpec key order of each puzzle (after the common keys)
-std::vector<KeySpec> EnvKeys(int p) {
+// the reference's StateSpec key order of each puzzle (after the common keys), and its action
+FamilySpec Spec(int p) {
+  const KeySpec action{"action", EPA_I32, {}};
   switch (p) {
     case jm::kGame2048:
-      return {{"obs:board", EPA_I32, {4, 4}}, {"obs:action_mask", EPA_BOOL, {4}}, {"info:highest_tile", EPA_I32, {}}};
+      return {{{"obs:board", EPA_I32, {4, 4}}, {"obs:action_mask", EPA_BOOL, {4}}, {"info:highest_tile", EPA_I32, {}}},
+              action};
     case jm::kMinesweeper:
-      return {{"obs:board", EPA_I32, {10, 10}}, {"obs:action_mask", EPA_BOOL, {10, 10}},
-              {"obs:num_mines", EPA_I32, {}}, {"obs:step_count", EPA_I32, {}}};
+      return {{{"obs:board", EPA_I32, {10, 10}}, {"obs:action_mask", EPA_BOOL, {10, 10}},
+               {"obs:num_mines", EPA_I32, {}}, {"obs:step_count", EPA_I32, {}}},
+              {"action", EPA_I32, {2}}};
     case jm::kSlidingTile:
-      return {{"obs:puzzle", EPA_I32, {5, 5}}, {"obs:empty_tile_position", EPA_I32, {2}},
-              {"obs:action_mask", EPA_BOOL, {4}}, {"obs:step_count", EPA_I32, {}},
-              {"info:prop_correctly_placed", EPA_F32, {}}};
+      return {{{"obs:puzzle", EPA_I32, {5, 5}}, {"obs:empty_tile_position", EPA_I32, {2}},
+               {"obs:action_mask", EPA_BOOL, {4}}, {"obs:step_count", EPA_I32, {}},
+               {"info:prop_correctly_placed", EPA_F32, {}}},
+              action};
     case jm::kRubiksCube:
-      return {{"obs:cube", EPA_I8, {6, 3, 3}}, {"obs:step_count", EPA_I32, {}}};
+      return {{{"obs:cube", EPA_I8, {6, 3, 3}}, {"obs:step_count", EPA_I32, {}}}, {"action", EPA_I32, {3}}};
     case jm::kSnake:
-      return {{"obs:grid", EPA_F32, {12, 12, 5}}, {"obs:step_count", EPA_I32, {}}, {"obs:action_mask", EPA_BOOL, {4}}};
+      return {{{"obs:grid", EPA_F32, {12, 12, 5}}, {"obs:step_count", EPA_I32, {}}, {"obs:action_mask", EPA_BOOL, {4}}},
+              action};
     default:
-      return {{"obs:agent_position.row", EPA_I32, {}}, {"obs:agent_position.col", EPA_I32, {}},
-              {"obs:target_position.row", EPA_I32, {}}, {"obs:target_position.col", EPA_I32, {}},
-              {"obs:walls", EPA_BOOL, {10, 10}}, {"obs:step_count", EPA_I32, {}}, {"obs:action_mask", EPA_BOOL, {4}}};
+      return {{{"obs:agent_position.row", EPA_I32, {}}, {"obs:agent_position.col", EPA_I32, {}},
+               {"obs:target_position.row", EPA_I32, {}}, {"obs:target_position.col", EPA_I32, {}},
+               {"obs:walls", EPA_BOOL, {10, 10}}, {"obs:step_count", EPA_I32, {}}, {"obs:action_mask", EPA_BOOL, {4}}},
+              action};
   }
-}
-
-KeySpec ActionKey(int p) {
-  if (p == jm::kMinesweeper) return KeySpec{"action", EPA_I32, {2}};
-  if (p == jm::kRubiksCube) return KeySpec{"action", EPA_I32, {3}};
-  return KeySpec{"action", EPA_I32, {}};
 }
 
 size_t StateBytes(int p) {
@@ -199,7 +198,7 @@ Cfg MakeCfg(int p, const Config& cfg, std::vector<int>* init) {
 class JumanjiPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own rows only
-  JumanjiPool(int p, const Config& cfg) : Pool(cfg, EnvKeys(p), ActionKey(p), /*needs_rng=*/true), p_(p) {
+  JumanjiPool(int p, const Config& cfg) : Pool(cfg, Spec(p), /*needs_rng=*/true), p_(p) {
     std::vector<int> init;
     c_ = MakeCfg(p, cfg, &init);
     const size_t n = (size_t)cfg.num_envs;
@@ -209,9 +208,9 @@ class JumanjiPool : public Pool {
     EPA_HIP(hipMalloc(&d_init, sizeof(int) * jm::kInitWords));
     EPA_HIP(hipMemcpy(d_init, init.data(), sizeof(int) * jm::kInitWords, hipMemcpyHostToDevice));
     d_.init = d_init;
-    const auto keys = EnvKeys(p);
-    for (int j = 0; j < kMaxEnvKeys; ++j) d_.key_bytes[j] = j < (int)keys.size() ? keys[j].row_bytes() : 0;
-    d_.act_dim = ActionKey(p).row_elems();
+    const int nkeys = (int)keys_.size() - kNumCommonKeys;  // the puzzle's own keys follow the common ones
+    for (int j = 0; j < kMaxEnvKeys; ++j) d_.key_bytes[j] = j < nkeys ? keys_[kNumCommonKeys + j].row_bytes() : 0;
+    d_.act_dim = action_.row_elems();
     EnableErrorWord();
     d_.err = err_dev_;
     mt_tile_default_ = 16;  // envs reset at their own times
@@ -280,19 +279,8 @@ class JumanjiPool : public Pool {
 
 }  // namespace
 
-bool DescribeJumanji(const std::string& family, const Config& cfg, std::vector<KeySpec>* state, KeySpec* action) {
-  (void)cfg;
-  const int p = PuzzleOf(family);
-  if (p < 0) return false;
-  *state = EnvKeys(p);
-  *action = ActionKey(p);
-  return true;
-}
+FamilySpec DescribeJumanji(const std::string& name, const Config&) { return Spec(PuzzleOf(name)); }
 
-Pool* MakeJumanji(const std::string& family, const Config& cfg) {
-  const int p = PuzzleOf(family);
-  if (p < 0) return nullptr;
-  return new JumanjiPool(p, cfg);
-}
+Pool* MakeJumanji(const std::string& name, const Config& cfg) { return new JumanjiPool(PuzzleOf(name), cfg); }
 
 }  // namespace epa

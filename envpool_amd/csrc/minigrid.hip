@@ -232,12 +232,13 @@ __global__ void MiniGridSetState(MgDev d, CommonDev cm, TaskCfg c, const int* id
   cm.done[e] = done ? 1 : 0;
 }
 
-std::vector<KeySpec> EnvKeys() {
-  return {{"obs:direction", EPA_I32, {}},
-          {"obs:image", EPA_U8, {mg::kView, mg::kView, 3}},
-          {"obs:mission", EPA_U8, {mg::kMissionBytes}},
-          {"info:agent_pos", EPA_I32, {2}},
-          {"info:mission_id", EPA_I32, {}}};
+FamilySpec Spec() {
+  return {{{"obs:direction", EPA_I32, {}},
+           {"obs:image", EPA_U8, {mg::kView, mg::kView, 3}},
+           {"obs:mission", EPA_U8, {mg::kMissionBytes}},
+           {"info:agent_pos", EPA_I32, {2}},
+           {"info:mission_id", EPA_I32, {}}},
+          {"action", EPA_I32, {}}};
 }
 
 // Config -> TaskCfg, with the checks that keep every grid access of the kernel inside the env's block
@@ -314,7 +315,7 @@ class MiniGridPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit MiniGridPool(const Config& cfg)
-      : Pool(cfg, EnvKeys(), KeySpec{"action", EPA_I32, {}}, /*needs_rng=*/true), c_(MakeTaskCfg(cfg)) {
+      : Pool(cfg, Spec(), /*needs_rng=*/true), c_(MakeTaskCfg(cfg)) {
     const size_t n = (size_t)cfg.num_envs;
     d_.n = cfg.num_envs;
     d_.cells = c_.width * c_.height;
@@ -389,17 +390,8 @@ class MiniGridPool : public Pool {
 
 }  // namespace
 
-bool DescribeMiniGrid(const std::string& family, const Config& cfg, std::vector<KeySpec>* state,
-                      KeySpec* action) {
-  if (family != "MiniGrid") return false;
-  *state = EnvKeys();
-  *action = KeySpec{"action", EPA_I32, {}};
-  return true;
-}
+FamilySpec DescribeMiniGrid(const std::string&, const Config&) { return Spec(); }
 
-Pool* MakeMiniGrid(const std::string& family, const Config& cfg) {
-  if (family != "MiniGrid") return nullptr;
-  return new MiniGridPool(cfg);
-}
+Pool* MakeMiniGrid(const std::string&, const Config& cfg) { return new MiniGridPool(cfg); }
 
 }  // namespace epa

@@ -535,7 +535,7 @@ __global__ void AntSetState(AntDev dev, CommonDev cm, const int* ids, int k, con
   dev.navail[e] = t[6] != 0.0;
 }
 
-std::vector<KeySpec> AntKeys(const Config& cfg) {
+FamilySpec AntSpec(const Config& cfg) {
   int no_pos = cfg.Get("exclude_current_positions_from_observation", 1) != 0;
   // ant.h:51-75 (obs 27/29 + 6 per body with use_contact_force); StackSpec, frame_stack.h:42-71
   int ncf = 0;
@@ -549,14 +549,14 @@ std::vector<KeySpec> AntKeys(const Config& cfg) {
         "info:distance_from_origin", "info:x_velocity", "info:y_velocity"}) {
     k.push_back({name, EPA_F64, {}});
   }
-  return k;
+  return {k, {"action", EPA_F64, {A::kNU}}};
 }
 
 class AntPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit AntPool(const Config& cfg)
-      : Pool(cfg, AntKeys(cfg), KeySpec{"action", EPA_F64, {A::kNU}}, true) {
+      : Pool(cfg, AntSpec(cfg), true) {
     // (a unit queue re-reads the action rows per unit: uploaded, not read in place -- engine.h; and with several
     // batches in flight the long Ant kernels overlap their downloads anyway: direct batches measured 5-9 % slower
     // there, profiles/r6m_async_numpy_*.jsonl)
@@ -716,17 +716,8 @@ extern "C" int epa_debug_ant_timers(unsigned long long* out16, int clear) {
 #endif
 namespace epa {
 
-bool DescribeAnt(const std::string& family, const Config& cfg,
-                 std::vector<KeySpec>* state, KeySpec* action) {
-  if (family != "Ant") return false;
-  *state = AntKeys(cfg);
-  *action = KeySpec{"action", EPA_F64, {A::kNU}};
-  return true;
-}
+FamilySpec DescribeAnt(const std::string&, const Config& cfg) { return AntSpec(cfg); }
 
-Pool* MakeAnt(const std::string& family, const Config& cfg) {
-  if (family != "Ant") return nullptr;
-  return new AntPool(cfg);
-}
+Pool* MakeAnt(const std::string&, const Config& cfg) { return new AntPool(cfg); }
 
 }  // namespace epa

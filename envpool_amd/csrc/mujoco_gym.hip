@@ -269,22 +269,25 @@ __global__ void CheetahSetState(CheetahDev dev, CommonDev cm, const int* ids,
   dev.navail[e] = t[6] != 0.0;
 }
 
-std::vector<KeySpec> CheetahKeys(const Config& cfg, bool walker = false, bool hopper = false) {
+FamilySpec CheetahSpec(const Config& cfg, bool walker, bool hopper) {
   int no_pos = cfg.Get("exclude_current_positions_from_observation", 1) != 0;
   int fs = (int)cfg.Get("frame_stack", 1);
   // half_cheetah.h:44-62, hopper.h:51-63 (non-ENVPOOL_TEST build); StackSpec, frame_stack.h:42-71
   std::vector<int> oshape = {(hopper ? 12 : 18) - (no_pos ? 1 : 0)};
   if (fs > 1) oshape.insert(oshape.begin(), fs);
+  const KeySpec action{"action", EPA_F64, {hopper ? 3 : kNU}};
   if (walker) {  // walker2d.h:49-62
-    return {{"obs", EPA_F64, oshape},
-            {"info:x_position", EPA_F64, {}},
-            {"info:x_velocity", EPA_F64, {}}};
+    return {{{"obs", EPA_F64, oshape},
+             {"info:x_position", EPA_F64, {}},
+             {"info:x_velocity", EPA_F64, {}}},
+            action};
   }
-  return {{"obs", EPA_F64, oshape},
-          {"info:reward_run", EPA_F64, {}},
-          {"info:reward_ctrl", EPA_F64, {}},
-          {"info:x_position", EPA_F64, {}},
-          {"info:x_velocity", EPA_F64, {}}};
+  return {{{"obs", EPA_F64, oshape},
+           {"info:reward_run", EPA_F64, {}},
+           {"info:reward_ctrl", EPA_F64, {}},
+           {"info:x_position", EPA_F64, {}},
+           {"info:x_velocity", EPA_F64, {}}},
+          action};
 }
 
 class CheetahPool : public Pool {
@@ -292,9 +295,7 @@ class CheetahPool : public Pool {
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   // model: mj::kPlanarCheetah / kPlanarWalker / kPlanarWalkerV5 / kPlanarHopper
   CheetahPool(const Config& cfg, int model)
-      : Pool(cfg, CheetahKeys(cfg, model != mj::kPlanarCheetah, model == mj::kPlanarHopper),
-             KeySpec{"action", EPA_F64, {model == mj::kPlanarHopper ? 3 : kNU}},
-             /*needs_rng=*/true),
+      : Pool(cfg, CheetahSpec(cfg, model != mj::kPlanarCheetah, model == mj::kPlanarHopper), /*needs_rng=*/true),
         model_id_(model) {
     const bool walker = model != mj::kPlanarCheetah;  // Walker2d or Hopper
     const bool hopper = model == mj::kPlanarHopper;
@@ -543,44 +544,15 @@ class CheetahPool : public Pool {
 
 }  // namespace
 
-bool DescribeAnt(const std::string& family, const Config& cfg,
-                 std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeAnt(const std::string& family, const Config& cfg);
-bool DescribePendulum(const std::string& family, const Config& cfg,
-                      std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakePendulum(const std::string& family, const Config& cfg);
-bool DescribeHumanoid(const std::string& family, const Config& cfg,
-                      std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakeHumanoid(const std::string& family, const Config& cfg);
-bool DescribePusher(const std::string& family, const Config& cfg,
-                    std::vector<KeySpec>* state, KeySpec* action);
-Pool* MakePusher(const std::string& family, const Config& cfg);
-
-bool DescribeMujoco(const std::string& family, const Config& cfg,
-                    std::vector<KeySpec>* state, KeySpec* action) {
-  if (family == "HalfCheetah" || family == "Walker2d" || family == "Hopper") {
-    *state = CheetahKeys(cfg, family != "HalfCheetah", family == "Hopper");
-    *action = KeySpec{"action", EPA_F64, {family == "Hopper" ? 3 : kNU}};
-    return true;
-  }
-  if (DescribePendulum(family, cfg, state, action)) return true;
-  if (DescribeHumanoid(family, cfg, state, action)) return true;
-  if (DescribePusher(family, cfg, state, action)) return true;
-  return DescribeAnt(family, cfg, state, action);
+FamilySpec DescribeMujocoGym(const std::string& name, const Config& cfg) {
+  return CheetahSpec(cfg, name != "HalfCheetah", name == "Hopper");
 }
 
-Pool* MakeMujoco(const std::string& family, const Config& cfg) {
-  if (family == "HalfCheetah") return new CheetahPool(cfg, mj::kPlanarCheetah);
-  if (family == "Hopper") return new CheetahPool(cfg, mj::kPlanarHopper);
-  if (family == "Walker2d") {
-    // "xml_v5" = 1: walker2d_v5.xml (gym/registration.py:79-83)
-    return new CheetahPool(cfg, cfg.Get("xml_v5", 0) != 0 ? mj::kPlanarWalkerV5
-                                                         : mj::kPlanarWalker);
-  }
-  if (Pool* p = MakePendulum(family, cfg)) return p;
-  if (Pool* p = MakeHumanoid(family, cfg)) return p;
-  if (Pool* p = MakePusher(family, cfg)) return p;
-  return MakeAnt(family, cfg);
+Pool* MakeMujocoGym(const std::string& name, const Config& cfg) {
+  if (name == "HalfCheetah") return new CheetahPool(cfg, mj::kPlanarCheetah);
+  if (name == "Hopper") return new CheetahPool(cfg, mj::kPlanarHopper);
+  // Walker2d; "xml_v5" = 1: walker2d_v5.xml (gym/registration.py:79-83)
+  return new CheetahPool(cfg, cfg.Get("xml_v5", 0) != 0 ? mj::kPlanarWalkerV5 : mj::kPlanarWalker);
 }
 
 }  // namespace epa

@@ -274,7 +274,7 @@ int HumObsDim(const Config& cfg) {
   return n;
 }
 
-std::vector<KeySpec> HumKeys(const Config& cfg, bool standup) {
+FamilySpec HumSpec(const Config& cfg, bool standup) {
   std::vector<KeySpec> k = {{"obs", EPA_F64, StackedObsShape(cfg, HumObsDim(cfg))}};
   if (standup) {  // humanoid_standup.h:62-65
     for (const char* name : {"info:reward_linup", "info:reward_quadctrl", "info:reward_alive",
@@ -289,14 +289,13 @@ std::vector<KeySpec> HumKeys(const Config& cfg, bool standup) {
       k.push_back({name, EPA_F64, {}});
     }
   }
-  return k;
+  return {k, {"action", EPA_F64, {kHumanoidModelConst.nu}}};
 }
 
 class HumanoidPool : public Pool {
  public:
   HumanoidPool(const Config& cfg, bool standup)
-      : Pool(cfg, HumKeys(cfg, standup), KeySpec{"action", EPA_F64, {kHumanoidModelConst.nu}},
-             /*needs_rng=*/true),
+      : Pool(cfg, HumSpec(cfg, standup), /*needs_rng=*/true),
         standup_(standup) {
     EnableObsStack();
     // defaults: humanoid.h:32-48, humanoid_standup.h:32-45
@@ -454,18 +453,12 @@ class HumanoidPool : public Pool {
 
 }  // namespace
 
-bool DescribeHumanoid(const std::string& family, const Config& cfg, std::vector<KeySpec>* state,
-                      KeySpec* action) {
-  if (family != "Humanoid" && family != "HumanoidStandup") return false;
-  *state = HumKeys(cfg, family == "HumanoidStandup");
-  *action = KeySpec{"action", EPA_F64, {kHumanoidModelConst.nu}};
-  return true;
+FamilySpec DescribeHumanoid(const std::string& name, const Config& cfg) {
+  return HumSpec(cfg, name == "HumanoidStandup");
 }
 
-Pool* MakeHumanoid(const std::string& family, const Config& cfg) {
-  if (family == "Humanoid") return new HumanoidPool(cfg, false);
-  if (family == "HumanoidStandup") return new HumanoidPool(cfg, true);
-  return nullptr;
+Pool* MakeHumanoid(const std::string& name, const Config& cfg) {
+  return new HumanoidPool(cfg, name == "HumanoidStandup");
 }
 #endif  // !EPA_HUM_STANDUP_TU
 

@@ -343,18 +343,19 @@ __global__ void ReacherSetState(ReacherDev dev, CommonDev cm, const int* ids, in
   cm.cur_step[e] = (int)o[16];
 }
 
-std::vector<KeySpec> ReacherKeys(const Config& cfg) {  // reacher.h:44-60
+FamilySpec ReacherSpec(const Config& cfg) {  // reacher.h:44-60
   int nobs = cfg.Get("obs_include_z_distance", 1) != 0 ? 11 : 10;
-  return {{"obs", EPA_F64, StackedObsShape(cfg, nobs)},
-          {"info:reward_dist", EPA_F64, {}},
-          {"info:reward_ctrl", EPA_F64, {}}};
+  return {{{"obs", EPA_F64, StackedObsShape(cfg, nobs)},
+           {"info:reward_dist", EPA_F64, {}},
+           {"info:reward_ctrl", EPA_F64, {}}},
+          {"action", EPA_F64, {2}}};
 }
 
 class ReacherPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit ReacherPool(const Config& cfg)
-      : Pool(cfg, ReacherKeys(cfg), KeySpec{"action", EPA_F64, {2}}, /*needs_rng=*/true) {
+      : Pool(cfg, ReacherSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
     model_ = P::BuildReacher();
     // defaults: reacher.h:32-43
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(kPendBlock) void SwimmerStepKernel(
   WriteCommon(out, row, e + a.id_offset, cur, done, reward, a.max_episode_steps);
 }
 
-std::vector<KeySpec> SwimmerKeys(const Config& cfg) {  // swimmer.h:44-61
+FamilySpec SwimmerSpec(const Config& cfg) {  // swimmer.h:44-61
   int no_pos = cfg.Get("exclude_current_positions_from_observation", 1) != 0;
   std::vector<KeySpec> k = {{"obs", EPA_F64, StackedObsShape(cfg, no_pos ? 8 : 10)}};
   for (const char* name : {"info:reward_fwd", "info:reward_ctrl", "info:x_position",
@@ -500,14 +501,17 @@ std::vector<KeySpec> SwimmerKeys(const Config& cfg) {  // swimmer.h:44-61
                            "info:y_velocity"}) {
     k.push_back({name, EPA_F64, {}});
   }
-  return k;
+  return {k, {"action", EPA_F64, {2}}};
 }
 
-int PendObsDim(const Config& cfg, int nl) {
-  if (nl == 1) return 4;  // inverted_pendulum.h:43-55
-  int c = (int)cfg.Get("constraint_obs_dim", 3);
-  if (c < 0 || c > 3) throw std::invalid_argument("constraint_obs_dim must be in [0, 3]");
-  return 1 + 2 + 2 + 3 + c;  // inverted_double_pendulum.h:46-60
+FamilySpec PendSpec(const Config& cfg, int nl) {
+  int nobs = 4;  // inverted_pendulum.h:43-55
+  if (nl == 2) {
+    int c = (int)cfg.Get("constraint_obs_dim", 3);
+    if (c < 0 || c > 3) throw std::invalid_argument("constraint_obs_dim must be in [0, 3]");
+    nobs = 1 + 2 + 2 + 3 + c;  // inverted_double_pendulum.h:46-60
+  }
+  return {{{"obs", EPA_F64, StackedObsShape(cfg, nobs)}}, {"action", EPA_F64, {1}}};
 }
 
 template <int NL>
@@ -516,8 +520,7 @@ class PendPool : public Pool {
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   static constexpr int NV = NL + 1;
   explicit PendPool(const Config& cfg)
-      : Pool(cfg, {{"obs", EPA_F64, StackedObsShape(cfg, PendObsDim(cfg, NL))}},
-             KeySpec{"action", EPA_F64, {1}}, /*needs_rng=*/true) {
+      : Pool(cfg, PendSpec(cfg, NL), /*needs_rng=*/true) {
     EnableObsStack();
     if constexpr (NL == 1) {
       model1_ = P::BuildInvertedPendulum();
@@ -592,7 +595,7 @@ class SwimmerPool : public Pool {
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   static constexpr int NV = 5;
   explicit SwimmerPool(const Config& cfg)
-      : Pool(cfg, SwimmerKeys(cfg), KeySpec{"action", EPA_F64, {2}}, /*needs_rng=*/true) {
+      : Pool(cfg, SwimmerSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
     model_ = P::BuildSwimmer();
     // defaults: swimmer.h:32-42
@@ -648,26 +651,17 @@ class SwimmerPool : public Pool {
 
 }  // namespace
 
-bool DescribePendulum(const std::string& family, const Config& cfg,
-                      std::vector<KeySpec>* state, KeySpec* action) {
-  if (family == "Reacher" || family == "Swimmer") {
-    *state = family == "Reacher" ? ReacherKeys(cfg) : SwimmerKeys(cfg);
-    *action = KeySpec{"action", EPA_F64, {2}};
-    return true;
-  }
-  int nl = family == "InvertedPendulum" ? 1 : (family == "InvertedDoublePendulum" ? 2 : 0);
-  if (nl == 0) return false;
-  *state = {{"obs", EPA_F64, StackedObsShape(cfg, PendObsDim(cfg, nl))}};
-  *action = KeySpec{"action", EPA_F64, {1}};
-  return true;
+FamilySpec DescribePendulum(const std::string& name, const Config& cfg) {
+  if (name == "Reacher") return ReacherSpec(cfg);
+  if (name == "Swimmer") return SwimmerSpec(cfg);
+  return PendSpec(cfg, name == "InvertedPendulum" ? 1 : 2);
 }
 
-Pool* MakePendulum(const std::string& family, const Config& cfg) {
-  if (family == "InvertedPendulum") return new PendPool<1>(cfg);
-  if (family == "InvertedDoublePendulum") return new PendPool<2>(cfg);
-  if (family == "Reacher") return new ReacherPool(cfg);
-  if (family == "Swimmer") return new SwimmerPool(cfg);
-  return nullptr;
+Pool* MakePendulum(const std::string& name, const Config& cfg) {
+  if (name == "Reacher") return new ReacherPool(cfg);
+  if (name == "Swimmer") return new SwimmerPool(cfg);
+  if (name == "InvertedPendulum") return new PendPool<1>(cfg);
+  return new PendPool<2>(cfg);
 }
 
 }  // namespace epa

@@ -197,18 +197,19 @@ __global__ void PusherSetState(PusherDev dev, CommonDev cm, const int* ids, int 
   for (int j = 0; j < 5; ++j) dev.lag[(size_t)j * n + e] = t[7 + j];
 }
 
-std::vector<KeySpec> PusherKeys(const Config& cfg) {  // pusher.h:47-60
-  return {{"obs", EPA_F64, StackedObsShape(cfg, 23)},
-          {"info:reward_dist", EPA_F64, {}},
-          {"info:reward_ctrl", EPA_F64, {}},
-          {"info:reward_near", EPA_F64, {}}};
+FamilySpec PusherSpec(const Config& cfg) {  // pusher.h:47-60
+  return {{{"obs", EPA_F64, StackedObsShape(cfg, 23)},
+           {"info:reward_dist", EPA_F64, {}},
+           {"info:reward_ctrl", EPA_F64, {}},
+           {"info:reward_near", EPA_F64, {}}},
+          {"action", EPA_F64, {PU::kNL}}};
 }
 
 class PusherPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit PusherPool(const Config& cfg)
-      : Pool(cfg, PusherKeys(cfg), KeySpec{"action", EPA_F64, {PU::kNL}}, /*needs_rng=*/true) {
+      : Pool(cfg, PusherSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
     v5_ = cfg.Get("xml_v5", 0) != 0;
     // defaults: pusher.h:33-46
@@ -285,17 +286,8 @@ class PusherPool : public Pool {
 
 }  // namespace
 
-bool DescribePusher(const std::string& family, const Config& cfg, std::vector<KeySpec>* state,
-                    KeySpec* action) {
-  if (family != "Pusher") return false;
-  *state = PusherKeys(cfg);
-  *action = KeySpec{"action", EPA_F64, {PU::kNL}};
-  return true;
-}
+FamilySpec DescribePusher(const std::string&, const Config& cfg) { return PusherSpec(cfg); }
 
-Pool* MakePusher(const std::string& family, const Config& cfg) {
-  if (family != "Pusher") return nullptr;
-  return new PusherPool(cfg);
-}
+Pool* MakePusher(const std::string&, const Config& cfg) { return new PusherPool(cfg); }
 
 }  // namespace epa

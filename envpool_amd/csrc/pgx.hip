@@ -150,28 +150,20 @@ int GameOf(const std::string& family) {
   if (family == "TicTacToe") return pgx::kTicTacToe;
   if (family == "ConnectFour") return pgx::kConnectFour;
   if (family == "Hex") return pgx::kHex;
-  if (family == "Othello") return pgx::kOthello;
-  return -1;
+  return pgx::kOthello;
 }
 
 // the reference's StateSpec key order (after the common keys); "obs" and "info:players.id" are per player
 template <int G>
-std::vector<KeySpec> EnvKeys() {
+FamilySpec Spec() {
   using D = pgx::Dims<G>;
-  return {{"obs", EPA_BOOL, {pgx::kPlayers, D::H, D::W, D::C}, pgx::kPlayers},
-          {"info:board", EPA_I32, {D::H, D::W}},
-          {"info:current_player", EPA_I32, {}},
-          {"info:legal_action_mask", EPA_BOOL, {D::A}},
-          {"info:players.id", EPA_I32, {pgx::kPlayers}, pgx::kPlayers}};
-}
-
-std::vector<KeySpec> EnvKeysOf(int g) {
-  switch (g) {
-    case pgx::kTicTacToe: return EnvKeys<pgx::kTicTacToe>();
-    case pgx::kConnectFour: return EnvKeys<pgx::kConnectFour>();
-    case pgx::kHex: return EnvKeys<pgx::kHex>();
-    default: return EnvKeys<pgx::kOthello>();
-  }
+  return {{{"obs", EPA_BOOL, {pgx::kPlayers, D::H, D::W, D::C}, pgx::kPlayers},
+           {"info:board", EPA_I32, {D::H, D::W}},
+           {"info:current_player", EPA_I32, {}},
+           {"info:legal_action_mask", EPA_BOOL, {D::A}},
+           {"info:players.id", EPA_I32, {pgx::kPlayers}, pgx::kPlayers}},
+          {"action", EPA_I32, {}},
+          pgx::kPlayers};
 }
 
 template <int G>
@@ -179,7 +171,7 @@ class PgxPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own rows only
   explicit PgxPool(const Config& cfg)
-      : Pool(cfg, EnvKeys<G>(), KeySpec{"action", EPA_I32, {}}, /*needs_rng=*/true, pgx::kPlayers) {
+      : Pool(cfg, Spec<G>(), /*needs_rng=*/true) {
     const size_t n = (size_t)cfg.num_envs;
     EPA_HIP(hipMalloc(&state_, sizeof(pgx::State) * n));
     EPA_HIP(hipMemsetAsync(state_, 0, sizeof(pgx::State) * n, stream_));
@@ -217,24 +209,21 @@ class PgxPool : public Pool {
 
 }  // namespace
 
-int PgxPlayers(const std::string& family) { return GameOf(family) < 0 ? 0 : pgx::kPlayers; }
-
-bool DescribePgx(const std::string& family, const Config& cfg, std::vector<KeySpec>* state, KeySpec* action) {
-  (void)cfg;
-  const int g = GameOf(family);
-  if (g < 0) return false;
-  *state = EnvKeysOf(g);
-  *action = KeySpec{"action", EPA_I32, {}};
-  return true;
+FamilySpec DescribePgx(const std::string& name, const Config&) {
+  switch (GameOf(name)) {
+    case pgx::kTicTacToe: return Spec<pgx::kTicTacToe>();
+    case pgx::kConnectFour: return Spec<pgx::kConnectFour>();
+    case pgx::kHex: return Spec<pgx::kHex>();
+    default: return Spec<pgx::kOthello>();
+  }
 }
 
-Pool* MakePgx(const std::string& family, const Config& cfg) {
-  switch (GameOf(family)) {
+Pool* MakePgx(const std::string& name, const Config& cfg) {
+  switch (GameOf(name)) {
     case pgx::kTicTacToe: return new PgxPool<pgx::kTicTacToe>(cfg);
     case pgx::kConnectFour: return new PgxPool<pgx::kConnectFour>(cfg);
     case pgx::kHex: return new PgxPool<pgx::kHex>(cfg);
-    case pgx::kOthello: return new PgxPool<pgx::kOthello>(cfg);
-    default: return nullptr;
+    default: return new PgxPool<pgx::kOthello>(cfg);
   }
 }
 

@@ -392,20 +392,15 @@ __global__ void ToySetState(ToyDev dev, CommonDev cm, const int* ids, int k,
   cm.cur_step[e] = (int)o[3];
 }
 
-struct FamilyInfo {
-  const char* name;
-  int kind;
-};
-const FamilyInfo kFamilies[] = {
-    {"Catch", kCatch},   {"FrozenLake", kFrozenLake}, {"Taxi", kTaxi},
-    {"NChain", kNChain}, {"CliffWalking", kCliffWalking},
-    {"Blackjack", kBlackjack}};
-
-const FamilyInfo* Find(const std::string& name) {
-  for (auto& f : kFamilies) {
-    if (name == f.name) return &f;
+int KindOf(const std::string& name) {
+  static const std::pair<const char*, int> kinds[] = {
+      {"Catch", kCatch},   {"FrozenLake", kFrozenLake}, {"Taxi", kTaxi},
+      {"NChain", kNChain}, {"CliffWalking", kCliffWalking},
+      {"Blackjack", kBlackjack}};
+  for (auto& k : kinds) {
+    if (name == k.first) return k.second;
   }
-  return nullptr;
+  throw std::logic_error("not a toy_text family: " + name);
 }
 
 ToyCfg MakeCfg(const Config& cfg) {
@@ -419,13 +414,14 @@ ToyCfg MakeCfg(const Config& cfg) {
   return c;
 }
 
-std::vector<KeySpec> EnvKeys(int kind, const ToyCfg& c) {
+FamilySpec Spec(int kind, const ToyCfg& c) {
+  const KeySpec action{"action", EPA_I32, {}};
   switch (kind) {
-    case kCatch: return {{"obs", EPA_F32, {c.height, c.width}}};
+    case kCatch: return {{{"obs", EPA_F32, {c.height, c.width}}}, action};
     case kCliffWalking:
-      return {{"obs", EPA_I32, {}}, {"info:prob", EPA_F32, {}}};
-    case kBlackjack: return {{"obs", EPA_I32, {3}}};
-    default: return {{"obs", EPA_I32, {}}};
+      return {{{"obs", EPA_I32, {}}, {"info:prob", EPA_F32, {}}}, action};
+    case kBlackjack: return {{{"obs", EPA_I32, {3}}}, action};
+    default: return {{{"obs", EPA_I32, {}}}, action};
   }
 }
 
@@ -434,8 +430,7 @@ class ToyPool : public Pool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit ToyPool(const Config& cfg)
-      : Pool(cfg, EnvKeys(KIND, MakeCfg(cfg)), KeySpec{"action", EPA_I32, {}},
-             /*needs_rng=*/true),
+      : Pool(cfg, Spec(KIND, MakeCfg(cfg)), /*needs_rng=*/true),
         tcfg_(MakeCfg(cfg)) {
     if (KIND == kCatch && (tcfg_.height < 2 || tcfg_.height > 255 ||
                            tcfg_.width < 1 || tcfg_.width > 255)) {
@@ -488,19 +483,12 @@ class ToyPool : public Pool {
 
 }  // namespace
 
-bool DescribeToyText(const std::string& family, const Config& cfg,
-                     std::vector<KeySpec>* state, KeySpec* action) {
-  const FamilyInfo* fi = Find(family);
-  if (!fi) return false;
-  *state = EnvKeys(fi->kind, MakeCfg(cfg));
-  *action = KeySpec{"action", EPA_I32, {}};
-  return true;
+FamilySpec DescribeToyText(const std::string& name, const Config& cfg) {
+  return Spec(KindOf(name), MakeCfg(cfg));
 }
 
-Pool* MakeToyText(const std::string& family, const Config& cfg) {
-  const FamilyInfo* fi = Find(family);
-  if (!fi) return nullptr;
-  switch (fi->kind) {
+Pool* MakeToyText(const std::string& name, const Config& cfg) {
+  switch (KindOf(name)) {
     case kCatch: return new ToyPool<kCatch>(cfg);
     case kFrozenLake: return new ToyPool<kFrozenLake>(cfg);
     case kTaxi: return new ToyPool<kTaxi>(cfg);
