@@ -232,8 +232,10 @@ __device__ __forceinline__ void AntUnit(int ci, int s0, int s1, T* lds_buf) {
     z = z < task.contact_force_max ? z : task.contact_force_max;
     for (int i = 0; i < ncf; ++i) obs_c[i] = z;
     // WriteState(0.0, 0, ...): info[6] = sqrt(0); reward_ctrl / reward_contact are stored as
-    // `-ctrl_cost` / `-contact_cost` of +0.0, i.e. -0.0 (ant.h:262-263)
+    // `-ctrl_cost` / `-contact_cost` of +0.0, i.e. -0.0 (ant.h:262-263); reward_forward as
+    // `xv * forward_reward_weight_` of xv = 0.0, -0.0 for a negative weight (ant.h:261)
     for (int i = 0; i < 9; ++i) ((double*)out.p[kKeyEnv0 + 1 + i])[row] = (i == 1 || i == 2) ? -0.0 : 0.0;
+    ((double*)out.p[kKeyEnv0 + 1])[row] = 0.0 * task.forward_reward_weight;
     WriteCommon(out, row, e + a.id_offset, 0, false, 0.0f, a.max_episode_steps);
     return;
   }
@@ -470,7 +472,7 @@ __attribute__((amdgpu_waves_per_eu(kAntWavesPerEu<T>, kAntWavesPerEu<T>))) void 
     EPA_ANT_TICK(7);
     EPA_ANT_COUNT(2);
     const int s0 = j * ap->sub;
-    const int s1 = s0 + ap->sub;
+    const int s1 = min(s0 + ap->sub, ap->task.frame_skip);
     AntUnit<T, kWrench>(ci, s0, s1, lds_buf);
     ap = AntKernArgs();
     if (j + 1 < ap->units_per_chunk) {

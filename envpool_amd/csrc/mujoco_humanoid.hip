@@ -158,7 +158,9 @@ __global__ __launch_bounds__(kHumBlock) void HumanoidStepKernel(
       info[8] = yv;
     }
   } else {
-    // the reset WriteState stores `-ctrl_cost` / `-contact_cost` of +0.0: -0.0 (humanoid.h:272-274)
+    // the reset WriteState stores `-ctrl_cost` / `-contact_cost` of +0.0: -0.0 (humanoid.h:272-274), and
+    // `xv * forward_reward_weight_` of xv = 0.0: -0.0 for a negative weight (humanoid.h:271)
+    info[0] = 0.0 * task.forward_reward_weight;
     info[1] = -0.0;
     info[3] = -0.0;
     if (kStandup) info[2] = task.healthy_reward;  // WriteState(0, 0, 0, 0): reward_alive is the constant

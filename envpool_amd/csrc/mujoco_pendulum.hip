@@ -367,6 +367,12 @@ class ReacherPool : public Pool {
     task_.reset_qpos_scale = cfg.Get("reset_qpos_scale", 0.1);
     task_.reset_qvel_scale = cfg.Get("reset_qvel_scale", 0.005);
     task_.reset_goal_scale = cfg.Get("reset_goal_scale", 0.2);
+    // the kernel keeps the target's two slides at their reset values (mj_pendulum_model.h, BuildReacher): exact
+    // while the goal is inside their range (reacher_envpool.xml:46-47, -.27 .27), where no limit acts on them
+    if (task_.reset_goal_scale > 0.27) {
+      throw std::invalid_argument("Reacher: reset_goal_scale > 0.27 is not supported (the target's slide limits, "
+                                  "range -0.27 0.27, are not modelled)");
+    }
     size_t n = cfg.num_envs;
     for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) {
       EPA_HIP(hipMalloc(p, sizeof(double) * 4 * n));
@@ -447,6 +453,7 @@ __global__ __launch_bounds__(kPendBlock) void SwimmerStepKernel(
     P::PendForward(m, scfg, q, v, zero, w, qacc, aux);  // mj_forward (warm start)
     info[4] = sqrt(0.0);  // WriteState(0, 0, 0, 0, 0, 0, true): swimmer.h:127
     info[1] = -0.0;       // `-ctrl_cost` of +0.0 (swimmer.h:172)
+    info[0] = 0.0 * task.forward_reward_weight;  // xv = 0.0 times the weight: -0.0 if negative (:171)
   } else {
     ++cur;
     mj::static_for<0, NV>([&](auto ic) {

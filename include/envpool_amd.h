@@ -105,7 +105,8 @@ typedef struct epa_pool epa_pool;
  *                 reference's benchmark/numa_test.sh does with numactl
  *   "ant_sub"     Ant: mj_steps per unit of the step kernel's work queue (default 1: an env-step of a 16-env chunk is
  *                 frame_skip units, the chunk's state goes through HBM between them; frame_skip = one unit per chunk,
- *                 the schedule of rounds 2-5).  Never changes results.
+ *                 the schedule of rounds 2-5; a sub that does not divide frame_skip makes the last unit of an
+ *                 env-step shorter).  Never changes results.
  *   "selftest"    MuJoCo families with a self-test table (HalfCheetah, Walker2d, Hopper, Ant, Humanoid,
  *                 HumanoidStandup): 0 skips the load-time self-test for this pool (see epa_create); the environment
  *                 variable EPA_SELFTEST=0 skips it for the process

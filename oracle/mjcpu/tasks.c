@@ -45,7 +45,9 @@ typedef struct {
   double ctrl_cost_weight, forward_reward_weight, reset_noise_scale;
   double healthy_reward, healthy_z_min, healthy_z_max;
   double healthy_angle_min, healthy_angle_max, velocity_min, velocity_max;
+  double healthy_state_min, healthy_state_max; /* Hopper (hopper.h:44-45) */
   int terminate_when_unhealthy, legacy_healthy_reward;
+  int obs_skip; /* exclude_current_positions_from_observation: qpos entries left out of obs */
   int reward_if_not_terminated, constraint_obs_dim; /* inverted pendulums */
   /* Ant-v3 / v5 (gym/registration.py:39-46) */
   int use_contact_force, post_constraint, exclude_worldbody;
@@ -76,8 +78,22 @@ static double extra_or(const double* e, int n, int i, double d) {
   return (e && i < n) ? e[i] : d;
 }
 
+/* positions 25.. of `extra`: NaN (or absent) keeps the family's default, since legitimate
+ * values of several of them are negative */
+static double extra_nan_or(const double* e, int n, int i, double d) {
+  return (e && i < n && !isnan(e[i])) ? e[i] : d;
+}
+
 /* extra (optional): [frame_skip, ctrl_cost_weight, forward_reward_weight,
- * reset_noise_scale, disable_contact, disable_limit, disable_actuation] */
+ * reset_noise_scale, disable_contact, disable_limit, disable_actuation, ...]; the task options
+ * of the reference's DefaultConfig() that the code below otherwise fixes (NaN = default):
+ *   25 exclude_current_positions_from_observation  26 terminate_when_unhealthy
+ *   27 healthy_reward  28 healthy_z_min  29 healthy_z_max  30 healthy_angle_min
+ *   31 healthy_angle_max  32 velocity_min  33 velocity_max  34 healthy_state_min
+ *   35 healthy_state_max  36 contact_cost_weight  37 contact_cost_max  38 contact_force_min
+ *   39 contact_force_max  40 observation_min  41 observation_max  42 reset_qpos_scale
+ *   43 reset_qvel_scale  44 reset_goal_scale  45 cylinder_x_min  46 cylinder_x_max
+ *   47 cylinder_y_min  48 cylinder_y_max  49 cylinder_dist_min */
 void* mjcpu_create(const char* task, int num_envs, int seed,
                    int max_episode_steps, const double* extra, int n_extra) {
   int is_ant = 0, kind;
@@ -150,10 +166,10 @@ void* mjcpu_create(const char* task, int num_envs, int seed,
                                     : (reacher ? 1.0 : (swimmer ? 1e-4 : 0.1)));
   p->reward_after_step = extra_or(extra, n_extra, 16, 0) != 0; /* Reacher-v5 */
   p->obs_include_z = extra_or(extra, n_extra, 17, 1) != 0;
-  p->dist_cost_weight = 1.0;
-  p->reset_qpos_scale = 0.1;
-  p->reset_qvel_scale = 0.005;
-  p->reset_goal_scale = 0.2;
+  p->dist_cost_weight = extra_or(extra, n_extra, 20, 1.0); /* Reacher, Pusher */
+  p->reset_qpos_scale = extra_nan_or(extra, n_extra, 42, 0.1);
+  p->reset_qvel_scale = extra_nan_or(extra, n_extra, 43, 0.005);
+  p->reset_goal_scale = extra_nan_or(extra, n_extra, 44, 0.2);
   /* humanoid.h:39 (1.25), humanoid_standup.h:35 (1.0) */
   p->forward_reward_weight = extra_or(extra, n_extra, 2, kind == TASK_HUMANOID ? 1.25 : 1.0);
   /* inverted_pendulum.h:32-41 (noise 0.01), inverted_double_pendulum.h:32-44 (0.1) */
@@ -161,16 +177,17 @@ void* mjcpu_create(const char* task, int num_envs, int seed,
       extra_or(extra, n_extra, 3, (walker || hopper) ? 0.005 : ((kind == TASK_IPEND || humanoid) ? 0.01 : 0.1));
   p->reward_if_not_terminated = extra_or(extra, n_extra, 10, 0) != 0;
   p->constraint_obs_dim = (int)extra_or(extra, n_extra, 11, 3);
-  p->observation_min = -10.0;
-  p->observation_max = 10.0;
+  p->observation_min = extra_nan_or(extra, n_extra, 40, -10.0);
+  p->observation_max = extra_nan_or(extra, n_extra, 41, 10.0);
   p->use_contact_force = extra_or(extra, n_extra, 12, 0) != 0;
   p->post_constraint = extra_or(extra, n_extra, 13, 0) != 0;
   p->exclude_worldbody = extra_or(extra, n_extra, 14, 0) != 0;
   p->exclude_root_actuator = extra_or(extra, n_extra, 19, 0) != 0;
-  p->contact_cost_weight = humanoid ? 5e-7 : 5e-4; /* ant.h:44-47, humanoid.h:45-46 */
-  p->contact_cost_max = 10.0;
-  p->contact_force_min = -1.0;
-  p->contact_force_max = 1.0;
+  /* ant.h:44-47, humanoid.h:45-46 */
+  p->contact_cost_weight = extra_nan_or(extra, n_extra, 36, humanoid ? 5e-7 : 5e-4);
+  p->contact_cost_max = extra_nan_or(extra, n_extra, 37, 10.0);
+  p->contact_force_min = extra_nan_or(extra, n_extra, 38, -1.0);
+  p->contact_force_max = extra_nan_or(extra, n_extra, 39, 1.0);
   p->m.disable_contact = extra_or(extra, n_extra, 4, 0) != 0;
   p->m.disable_limit = extra_or(extra, n_extra, 5, 0) != 0;
   p->m.disable_actuation = extra_or(extra, n_extra, 6, 0) != 0;
@@ -182,14 +199,27 @@ void* mjcpu_create(const char* task, int num_envs, int seed,
   }
   if (extra_or(extra, n_extra, 8, -1) >= 0) p->m.integrator = (int)extra[8];
   if (extra_or(extra, n_extra, 9, 0) > 0) p->m.timestep = extra[9];
-  p->healthy_reward = kind == TASK_IDPEND ? 10.0 : (kind == TASK_HUMANOID ? 5.0 : 1.0);
-  p->healthy_z_min = walker ? 0.8 : (hopper ? 0.7 : (kind == TASK_IPEND ? -0.2 : (humanoid ? 1.0 : 0.2)));
-  p->healthy_z_max = (walker || humanoid) ? 2.0 : (kind == TASK_IPEND ? 0.2 : 1.0);
-  p->healthy_angle_min = hopper ? -0.2 : -1.0; /* hopper.h:44-46 */
-  p->healthy_angle_max = hopper ? 0.2 : 1.0;
-  p->velocity_min = -10.0;
-  p->velocity_max = 10.0;
-  p->terminate_when_unhealthy = 1;
+  p->healthy_reward = extra_nan_or(extra, n_extra, 27,
+                                   kind == TASK_IDPEND ? 10.0 : (kind == TASK_HUMANOID ? 5.0 : 1.0));
+  p->healthy_z_min = extra_nan_or(
+      extra, n_extra, 28,
+      walker ? 0.8 : (hopper ? 0.7 : (kind == TASK_IPEND ? -0.2 : (humanoid ? 1.0 : 0.2))));
+  p->healthy_z_max = extra_nan_or(extra, n_extra, 29,
+                                  (walker || humanoid) ? 2.0 : (kind == TASK_IPEND ? 0.2 : 1.0));
+  /* hopper.h:44-46 */
+  p->healthy_angle_min = extra_nan_or(extra, n_extra, 30, hopper ? -0.2 : -1.0);
+  p->healthy_angle_max = extra_nan_or(extra, n_extra, 31, hopper ? 0.2 : 1.0);
+  p->velocity_min = extra_nan_or(extra, n_extra, 32, -10.0);
+  p->velocity_max = extra_nan_or(extra, n_extra, 33, 10.0);
+  p->healthy_state_min = extra_nan_or(extra, n_extra, 34, -100.0);
+  p->healthy_state_max = extra_nan_or(extra, n_extra, 35, 100.0);
+  p->terminate_when_unhealthy = extra_nan_or(extra, n_extra, 26, 1) != 0;
+  {
+    /* half_cheetah.h:169, walker2d.h:207, hopper.h (1: rootx); ant.h, swimmer.h, humanoid.h (2) */
+    const int no_pos = extra_nan_or(extra, n_extra, 25, 1) != 0;
+    const int planar = kind == TASK_CHEETAH || walker || hopper;
+    p->obs_skip = no_pos ? (planar ? 1 : 2) : 0;
+  }
   p->legacy_healthy_reward = v5 ? 0 : 1; /* gym/registration.py:79-83 */
   if (extra_or(extra, n_extra, 15, -1) >= 0) p->legacy_healthy_reward = extra[15] != 0;
   p->torso = 1; /* mj_name2id(model, mjOBJ_XBODY, "torso"), ant.h:119 */
@@ -203,11 +233,11 @@ void* mjcpu_create(const char* task, int num_envs, int seed,
     p->dist_cost_weight = extra_or(extra, n_extra, 20, 1.0);
     p->near_cost_weight = extra_or(extra, n_extra, 21, 0.5);
     p->weighted_reward_info = extra_or(extra, n_extra, 22, 0) != 0;
-    p->cyl_x_min = -0.3;
-    p->cyl_x_max = 0.0;
-    p->cyl_y_min = -0.2;
-    p->cyl_y_max = 0.2;
-    p->cyl_dist_min = 0.17;
+    p->cyl_x_min = extra_nan_or(extra, n_extra, 45, -0.3);
+    p->cyl_x_max = extra_nan_or(extra, n_extra, 46, 0.0);
+    p->cyl_y_min = extra_nan_or(extra, n_extra, 47, -0.2);
+    p->cyl_y_max = extra_nan_or(extra, n_extra, 48, 0.2);
+    p->cyl_dist_min = extra_nan_or(extra, n_extra, 49, 0.17);
     p->tips = 10;   /* mj_name2id(model, mjOBJ_XBODY, "tips_arm") */
     p->object = 11;
     p->goal = 12;
@@ -221,18 +251,18 @@ void* mjcpu_create(const char* task, int num_envs, int seed,
   int k = 8;
   p->key_names[k] = "obs";
   p->key_dtype[k] = DT_F64;
-  p->key_elems[k++] = is_ant ? 27 + (p->use_contact_force
-                                         ? 6 * (p->m.nbody - (p->exclude_worldbody ? 1 : 0))
-                                         : 0)
+  /* qpos without the skipped root coordinates, qvel, and the family's extra blocks */
+  const int nqv = p->m.nq - p->obs_skip + p->m.nv;
+  p->key_elems[k++] = is_ant ? nqv + (p->use_contact_force
+                                          ? 6 * (p->m.nbody - (p->exclude_worldbody ? 1 : 0))
+                                          : 0)
                       : kind == TASK_IPEND ? 4
                       : kind == TASK_IDPEND ? 8 + p->constraint_obs_dim
                       : reacher ? (p->obs_include_z ? 11 : 10)
                       : pusher ? 23
-                      : swimmer ? 8
-                      : hopper ? 11
-                      : humanoid ? 376 - (p->exclude_worldbody ? 22 : 0) -
+                      : humanoid ? nqv + 331 - (p->exclude_worldbody ? 22 : 0) -
                                        (p->exclude_root_actuator ? 6 : 0)
-                                            : 17;
+                                 : nqv; /* HalfCheetah, Walker2d, Hopper, Swimmer */
   static const char* cheetah_info[4] = {"info:reward_run", "info:reward_ctrl",
                                         "info:x_position", "info:x_velocity"};
   static const char* ant_info[9] = {
@@ -371,7 +401,7 @@ static void write_obs(mj_pool* p, mj_env* e, void** out, int row) {
   if (p->task == TASK_HUMANOID || p->task == TASK_STANDUP) { /* humanoid.h:229-257 */
     double* obs = (double*)out[8] + (size_t)row * p->key_elems[8];
     int b0 = p->exclude_worldbody ? 1 : 0;
-    for (int i = 2; i < p->m.nq; ++i) *(obs++) = e->d.qpos[i];
+    for (int i = p->obs_skip; i < p->m.nq; ++i) *(obs++) = e->d.qpos[i];
     for (int i = 0; i < p->m.nv; ++i) *(obs++) = e->d.qvel[i];
     for (int b = b0; b < p->m.nbody; ++b) {
       for (int j = 0; j < 10; ++j) *(obs++) = e->d.cinert[b][j];
@@ -402,10 +432,8 @@ static void write_obs(mj_pool* p, mj_env* e, void** out, int row) {
     for (int i = 0; i < p->constraint_obs_dim; ++i) *(obs++) = clip_obs(p, e->d.qfrc_constraint[i]);
     return;
   }
-  int skip = (p->is_ant || p->task == TASK_SWIMMER) ? 2 : 1; /* exclude_current_positions... */
-  int n = (p->is_ant || p->task == TASK_SWIMMER || p->task == TASK_HOPPER) ? p->key_elems[8] : 17;
-  double* obs = (double*)out[8] + (size_t)row * n;
-  for (int i = skip; i < p->m.nq; ++i) *(obs++) = e->d.qpos[i];
+  double* obs = (double*)out[8] + (size_t)row * p->key_elems[8];
+  for (int i = p->obs_skip; i < p->m.nq; ++i) *(obs++) = e->d.qpos[i];
   for (int i = 0; i < p->m.nv; ++i) {
     double x = e->d.qvel[i];
     if (p->task == TASK_WALKER || p->task == TASK_HOPPER) { /* walker2d.h:196-201, hopper.h */
@@ -553,6 +581,12 @@ static void env_step(mj_pool* p, int eid, int force_reset, const double* act,
     }
     /* humanoid_standup.h:226: WriteState stores the member healthy_reward_ on resets too */
     if (p->task == TASK_STANDUP) info[2] = p->healthy_reward;
+    /* the forward term is stored as xv * forward_reward_weight_ with xv = 0.0: -0.0 for a negative
+     * weight (half_cheetah.h:177, ant.h:261, swimmer.h:171, humanoid.h:271, humanoid_standup.h:226) */
+    if (p->task == TASK_CHEETAH || p->task == TASK_ANT || p->task == TASK_SWIMMER ||
+        p->task == TASK_HUMANOID || p->task == TASK_STANDUP) {
+      info[0] = 0.0 * p->forward_reward_weight;
+    }
     e->lag_set = 0;
   } else {
     ++e->current_step;
@@ -619,10 +653,10 @@ static void env_step(mj_pool* p, int eid, int force_reset, const double* act,
       int healthy = !(e->d.qpos[2] <= p->healthy_angle_min || e->d.qpos[2] >= p->healthy_angle_max ||
                       e->d.qpos[1] <= p->healthy_z_min);
       for (int i = 2; i < p->m.nq; ++i) {
-        if (e->d.qpos[i] <= -100.0 || e->d.qpos[i] >= 100.0) healthy = 0;
+        if (e->d.qpos[i] <= p->healthy_state_min || e->d.qpos[i] >= p->healthy_state_max) healthy = 0;
       }
       for (int i = 0; i < p->m.nv; ++i) {
-        if (e->d.qvel[i] <= -100.0 || e->d.qvel[i] >= 100.0) healthy = 0;
+        if (e->d.qvel[i] <= p->healthy_state_min || e->d.qvel[i] >= p->healthy_state_max) healthy = 0;
       }
       int give = healthy;
       if (p->legacy_healthy_reward) give = p->terminate_when_unhealthy || healthy;

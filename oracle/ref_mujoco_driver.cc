@@ -18,6 +18,7 @@
 //
 // Task names and the positions of `extra` are those of mjcpu_create (oracle/mjcpu/tasks.c), so
 // a test can run the same case through kind="port" and kind="reference_mujoco".
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -43,7 +44,16 @@ struct Extra_ {
   bool Has(int i) const { return e != nullptr && i < n; }
   double Get(int i, double d) const { return Has(i) ? e[i] : d; }
   bool Flag(int i, bool d) const { return Has(i) ? e[i] != 0 : d; }
+  // positions 25.. (oracle/mjcpu/tasks.c): NaN = the family's default, the key is left alone
+  bool Set(int i) const { return Has(i) && !std::isnan(e[i]); }
 };
+
+// the task options of positions 25.. of `extra`, set only where given; each family lists the
+// keys its DefaultConfig() has
+#define OPT(i, key, T) \
+  if (x.Set(i)) c[key##_] = static_cast<T>(x.e[i])
+#define OPT_FLAG(i, key) \
+  if (x.Set(i)) c[key##_] = x.e[i] != 0
 
 // weights every task shares (positions 0-3 of `extra`); post_constraint follows the port's
 // default (the v4 registration: gym/registration.py:93 passes version == "v5")
@@ -57,6 +67,10 @@ void Basic(C& c, const Extra_& x) {
 }  // namespace
 
 extern "C" {
+
+// positions of `extra` this build understands (0-24 engine and registration switches, 25-49 task options):
+// a library built from an older driver ignores the options, which a test must not mistake for a mismatch
+int ref_mujoco_extra_positions() { return 50; }
 
 void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps,
                  const double* extra, int n_extra, int num_threads) {
@@ -77,6 +91,7 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(1)) c["ctrl_cost_weight"_] = x.e[1];
         if (x.Has(2)) c["forward_reward_weight"_] = x.e[2];
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
       });
     }
     if (t == "Ant") {
@@ -88,6 +103,14 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         c["use_contact_force"_] = x.Flag(12, false);
         c["exclude_worldbody_contact_forces"_] = x.Flag(14, false);
         if (x.Get(15, -1) >= 0) c["legacy_healthy_reward"_] = x.e[15] != 0;
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
+        OPT_FLAG(26, "terminate_when_unhealthy");
+        OPT(27, "healthy_reward", double);
+        OPT(28, "healthy_z_min", double);
+        OPT(29, "healthy_z_max", double);
+        OPT(36, "contact_cost_weight", double);
+        OPT(38, "contact_force_min", double);
+        OPT(39, "contact_force_max", double);
       });
     }
     if (t == "Walker2d" || t == "Walker2dV5") {
@@ -101,6 +124,15 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (v5) c["xml_file"_] = std::string("walker2d_v5.xml");
         c["legacy_healthy_reward"_] = !v5;  // gym/registration.py:79-83
         if (x.Get(15, -1) >= 0) c["legacy_healthy_reward"_] = x.e[15] != 0;
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
+        OPT_FLAG(26, "terminate_when_unhealthy");
+        OPT(27, "healthy_reward", double);
+        OPT(28, "healthy_z_min", double);
+        OPT(29, "healthy_z_max", double);
+        OPT(30, "healthy_angle_min", double);
+        OPT(31, "healthy_angle_max", double);
+        OPT(32, "velocity_min", double);
+        OPT(33, "velocity_max", double);
       });
     }
     if (t == "Hopper") {
@@ -111,6 +143,16 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(2)) c["forward_reward_weight"_] = x.e[2];
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
         if (x.Get(15, -1) >= 0) c["legacy_healthy_reward"_] = x.e[15] != 0;
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
+        OPT_FLAG(26, "terminate_when_unhealthy");
+        OPT(27, "healthy_reward", double);
+        OPT(28, "healthy_z_min", double);
+        OPT(30, "healthy_angle_min", double);
+        OPT(31, "healthy_angle_max", double);
+        OPT(32, "velocity_min", double);
+        OPT(33, "velocity_max", double);
+        OPT(34, "healthy_state_min", double);
+        OPT(35, "healthy_state_max", double);
       });
     }
     if (t == "Swimmer") {
@@ -120,6 +162,7 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(1)) c["ctrl_cost_weight"_] = x.e[1];
         if (x.Has(2)) c["forward_reward_weight"_] = x.e[2];
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
       });
     }
     if (t == "Reacher") {
@@ -129,6 +172,10 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(1)) c["ctrl_cost_weight"_] = x.e[1];
         c["reward_after_step"_] = x.Flag(16, false);
         c["obs_include_z_distance"_] = x.Flag(17, true);
+        if (x.Has(20)) c["dist_cost_weight"_] = x.e[20];
+        OPT(42, "reset_qpos_scale", double);
+        OPT(43, "reset_qvel_scale", double);
+        OPT(44, "reset_goal_scale", double);
       });
     }
     if (t == "Pusher" || t == "PusherV5") {
@@ -142,6 +189,12 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(20)) c["dist_cost_weight"_] = x.e[20];
         if (x.Has(21)) c["near_cost_weight"_] = x.e[21];
         c["weighted_reward_info"_] = x.Flag(22, false);
+        OPT(43, "reset_qvel_scale", double);
+        OPT(45, "cylinder_x_min", double);
+        OPT(46, "cylinder_x_max", double);
+        OPT(47, "cylinder_y_min", double);
+        OPT(48, "cylinder_y_max", double);
+        OPT(49, "cylinder_dist_min", double);
       });
     }
     if (t == "InvertedPendulum") {
@@ -150,6 +203,9 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         Basic(c, x);
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
         c["reward_if_not_terminated"_] = x.Flag(10, false);
+        OPT(27, "healthy_reward", double);
+        OPT(28, "healthy_z_min", double);
+        OPT(29, "healthy_z_max", double);
       });
     }
     if (t == "InvertedDoublePendulum") {
@@ -159,6 +215,10 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
         c["reward_if_not_terminated"_] = x.Flag(10, false);
         c["constraint_obs_dim"_] = static_cast<int>(x.Get(11, 3));
+        OPT(27, "healthy_reward", double);
+        OPT(29, "healthy_z_max", double);
+        OPT(40, "observation_min", double);
+        OPT(41, "observation_max", double);
       });
     }
     if (t == "Humanoid") {
@@ -172,6 +232,13 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         c["exclude_worldbody_observations"_] = x.Flag(14, false);
         c["exclude_root_actuator_forces"_] = x.Flag(19, false);
         if (x.Get(15, -1) >= 0) c["legacy_healthy_reward"_] = x.e[15] != 0;
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
+        OPT_FLAG(26, "terminate_when_unhealthy");
+        OPT(27, "healthy_reward", double);
+        OPT(28, "healthy_z_min", double);
+        OPT(29, "healthy_z_max", double);
+        OPT(36, "contact_cost_weight", double);
+        OPT(37, "contact_cost_max", double);
       });
     }
     if (t == "HumanoidStandup") {
@@ -183,6 +250,10 @@ void* orc_create(const char* task, int num_envs, int seed, int max_episode_steps
         if (x.Has(3)) c["reset_noise_scale"_] = x.e[3];
         c["exclude_worldbody_observations"_] = x.Flag(14, false);
         c["exclude_root_actuator_forces"_] = x.Flag(19, false);
+        OPT_FLAG(25, "exclude_current_positions_from_observation");
+        OPT(27, "healthy_reward", double);
+        OPT(36, "contact_cost_weight", double);
+        OPT(37, "contact_cost_max", double);
       });
     }
   } catch (const std::exception& e) {

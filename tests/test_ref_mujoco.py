@@ -18,7 +18,7 @@ import pytest
 
 from oracle import orc
 from oracle.orc import Oracle
-from tests.mj_util import GYM_VARIANTS, mj_extra
+from tests.mj_util import GYM_VARIANTS, MJ_OPTION_CASES, mj_extra, option_case
 
 pytestmark = pytest.mark.skipif(not (orc.have_ref_mujoco() and orc.have_port()),
                                 reason="oracle/_ref/libref_mujoco.so not built (no /root/reference)")
@@ -28,7 +28,7 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint8)
 
 
-def _run_pair(task, max_steps, extra, n, steps, seed, threads=3):
+def _run_pair(task, max_steps, extra, n, steps, seed, threads=3, stats=None):
     port = Oracle(task, n, seed=seed, max_episode_steps=max_steps, extra=extra, kind="port")
     ref = Oracle(task, n, seed=seed, max_episode_steps=max_steps, extra=extra,
                  kind="reference_mujoco", num_threads=threads)
@@ -43,6 +43,9 @@ def _run_pair(task, max_steps, extra, n, steps, seed, threads=3):
             assert np.array_equal(_bits(a[k]), _bits(b[k])), (task, t, k, a[k].ravel()[:8], b[k].ravel()[:8])
         dones += int(a["done"].sum())
         resets += int((a["elapsed_step"] == 0).sum())
+        if stats is not None:  # per-step outputs for the caller's checks of what the run exercised
+            for k in a:
+                stats.setdefault(k, []).append(a[k].copy())
         act = rng.uniform(-1.0, 1.0, size=(n, port.action_elems))
         a, b = port.step(act), ref.step(act)
     return dones, resets
@@ -75,6 +78,54 @@ def test_short_episodes_truncate_like_the_reference(name):
 def test_non_default_options(name, over):
     task, max_steps, base = GYM_VARIANTS[name]
     _run_pair(task, max_steps, mj_extra(task, **{**base, **over}), n=4, steps=150, seed=5)
+
+
+@pytest.mark.parametrize("case", sorted(MJ_OPTION_CASES))
+def test_task_options_are_the_reference_config(case):
+    """Every option of the MJ_OPTION_CASES table (tests/mj_util.py) through positions 25.. of `extra`
+    against the same option set in the reference's config, bit for bit; the run must exercise what the
+    case is about (terminations, their absence, clamps, resets)."""
+    task, max_steps, extra, _, _, _, expect = option_case(case)
+    lib = ctypes.CDLL(orc.REF_MUJOCO_LIB)
+    if not hasattr(lib, "ref_mujoco_extra_positions") or lib.ref_mujoco_extra_positions() < len(extra):
+        pytest.skip("oracle/_ref/libref_mujoco.so predates positions 25.. of `extra` (rebuild: make -C oracle ref)")
+    opts = MJ_OPTION_CASES[case][2]
+    humanoid = task.startswith("Humanoid")
+    n, steps = (3, 40) if humanoid else (6, 150)
+    st = {}
+    _run_pair(task, max_steps, extra, n=n, steps=steps, seed=13, stats=st)
+    done, trunc = np.stack(st["done"]).reshape(-1, n), np.stack(st["trunc"]).reshape(-1, n)
+    elapsed = np.stack(st["elapsed_step"]).reshape(-1, n)
+    obs = np.stack(st["obs"])
+    terms = int((done & ~trunc).sum())
+    resets = int((elapsed[1:] == 0).sum())  # auto-resets after the initial one
+    assert resets >= n, (case, resets)
+    if expect == "term":
+        assert terms >= n, (case, terms)
+    else:
+        assert terms == 0 and trunc.any(), (case, terms)
+    stepped = elapsed[1:] > 0
+    if opts.get("exclude_current_positions_from_observation") == 0 and task not in ("Ant",) and not humanoid:
+        # the planar root's x (Swimmer: x, y) leads the row: it is info:x_position of every step row
+        x = np.stack(st["info:x_position"]).reshape(-1, n)[1:]
+        assert np.array_equal(obs[1:, :, 0][stepped], x[stepped]), case
+    if "contact_force_max" in opts:  # the clamp of the contact-force observation is active
+        assert (np.abs(obs[..., -78:]) == opts["contact_force_max"]).sum() > 100, case
+    if "contact_cost_max" in opts:  # the clamp of the contact cost is active
+        impact = np.stack(st["info:reward_impact"])
+        assert (impact == -opts["contact_cost_max"]).sum() > n, case
+    if "observation_max" in opts:
+        assert (np.abs(obs[..., 5:]) == opts["observation_max"]).sum() > n, case
+    alive_key = {"Ant": "info:reward_survive", "Humanoid": "info:reward_alive"}.get(task)
+    if alive_key:
+        alive = np.stack(st[alive_key]).reshape(-1, n)[1:]
+        hr = opts.get("healthy_reward", 1.0 if task == "Ant" else 5.0)
+        if expect == "noterm":  # paid only while healthy: the run has both
+            assert (alive[stepped] == 0).any() and (alive[stepped] == hr).any(), case
+        else:  # the terminal step: paid under the legacy rule only
+            legacy = {**GYM_VARIANTS[MJ_OPTION_CASES[case][0]][2], **opts}.get("legacy_healthy_reward", 1)
+            term = (done & ~trunc)[1:]
+            assert (alive[term] == (hr if legacy else 0.0)).all(), case
 
 
 def test_partial_id_sends_and_reset_subsets():
