@@ -258,7 +258,7 @@ TaskCfg MakeTaskCfg(const Config& cfg) {
     c.width = c.height = mg::kMaxSide;
   }
   if (c.width < 5 || c.height < 5 || c.width > mg::kMaxSide || c.height > mg::kMaxSide) {
-    throw std::invalid_argument("MiniGrid: grid sides must be in [5, 19]");
+    throw std::invalid_argument("MiniGrid: the grid sides (size, or width and height of distshift) must be in [5, 19]");
   }
   c.start_x = (int)cfg.Get("start_x", 1);
   c.start_y = (int)cfg.Get("start_y", 1);
@@ -287,7 +287,7 @@ TaskCfg MakeTaskCfg(const Config& cfg) {
     const int n = (int)cfg.Get("n_obstacles", 4);
     c.n_obstacles = n <= c.size / 2 + 1 ? n : c.size / 2;
     if (c.n_obstacles < 0 || c.n_obstacles > mg::kMaxObstacles || c.size > 16) {
-      throw std::invalid_argument("MiniGrid dynamic_obstacles: at most 8 obstacles, size at most 16");
+      throw std::invalid_argument("MiniGrid dynamic_obstacles: n_obstacles must be in [0, 8] after the clamp to size / 2, size at most 16");
     }
   }
   c.max_steps = cfg.max_episode_steps;

@@ -5,6 +5,15 @@ the whole config key set with the reference's defaults, string and pair keys inc
 env_name empty / doorkey / distshift / crossing / lava_gap / dynamic_obstacles / four_rooms
 (csrc/minigrid.hip); any other env_name raises.
 
+Within those, `make(id, size=..., agent_start_pos=..., ...)` takes every config the engine can run bit for bit
+with the reference: grid sides 5..19 (dynamic_obstacles: up to 16), DistShift `width` / `height` / `strip2_row`
+inside the walls, a fixed `agent_start_pos` inside the walls with `agent_start_dir` 0..3 or `(-1, -1)` for a
+random start, `n_obstacles` 0..8 after the reference's clamp, any `max_episode_steps`.  Everything else raises
+ValueError when the pool is constructed, before anything runs.  Two refusals are stricter than the reference:
+crossing needs an odd `size` (the reference CHECK-fails) and `num_crossings` in 1..2 * ((size - 3) / 2): with
+more crossings than rivers the reference pads the river list with entries that put lava on the top wall row,
+and `num_crossings = 0`, which the reference does run (a grid without rivers), is refused as well.
+
 Every rejection-sampling loop of a reset is bounded by the engine key `minigrid_max_tries` (default 2^20;
 `DevicePool("MiniGrid", ..., params={"minigrid_max_tries": n})`).  A reset that runs out raises RuntimeError
 from `recv` (on the device path: from a later recv or `synchronize()`), where the reference would throw in a

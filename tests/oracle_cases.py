@@ -23,11 +23,16 @@ CASES = {
         task="CliffWalking", max_steps=0, extra=(1,), act=("int", 4)
     ),
     "Blackjack-v1": dict(task="Blackjack", max_steps=0, extra=(0, 1), act=("int", 2)),
+    # extra = (natural, sab): the 1.5 reward of a natural, and the branch without either rule
+    "Blackjack-natural-v1": dict(task="Blackjack", max_steps=0, extra=(1, 0), act=("int", 2)),
+    "Blackjack-plain-v1": dict(task="Blackjack", max_steps=0, extra=(0, 0), act=("int", 2)),
+    "Blackjack-natural-sab-v1": dict(task="Blackjack", max_steps=0, extra=(1, 1), act=("int", 2)),
 }
 
 INTEGER_EXACT = {
     "Catch-v0", "FrozenLake-v1", "FrozenLake8x8-v1", "Taxi-v3", "NChain-v0",
     "CliffWalking-v0", "CliffWalkingSlippery-v1", "Blackjack-v1",
+    "Blackjack-natural-v1", "Blackjack-plain-v1", "Blackjack-natural-sab-v1",
 }
 
 

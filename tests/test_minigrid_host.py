@@ -1,7 +1,8 @@
 """MiniGrid navigation family, CPU side: the spec and the registry against what the reference itself
 reports (tests/golden/minigrid_spec.json, minigrid_registry.json), and the env logic of the kernel
 (envpool_amd/csrc/minigrid_env.hip.h) built for the host by g++ and replayed against every reference
-fixture, grids included."""
+fixture, grids included; the same for the option cases (configs outside the registered ids,
+tests/golden/minigrid_option_cases.json), plus the route of their kwargs into the engine parameters."""
 import ctypes
 import os
 import subprocess
@@ -10,7 +11,8 @@ import numpy as np
 import pytest
 
 import envpool_amd as envpool
-from minigrid_util import IDS, REGISTRY, SPECS, config, fixture
+from minigrid_util import (IDS, OPTION_CASES, OPTION_TABLE, REGISTRY, SPECS, config, fixture, option_config,
+                           option_fixture, option_kwargs, option_params)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -49,10 +51,7 @@ def test_out_of_scope_ids_are_not_registered(task_id):
         envpool.make(task_id, "gymnasium", num_envs=1)
 
 
-@pytest.mark.parametrize("task_id", IDS)
-def test_spec_matches_reference(task_id):
-    gold = SPECS[task_id]
-    spec = envpool.make_spec(task_id)
+def _assert_spec_matches(spec, gold):
     keys = list(spec._config_keys)
     defaults = list(type(spec)._default_config_values) if hasattr(type(spec), "_default_config_values") else None
     ref_keys = [k for k, _ in gold["default_config"]]
@@ -66,6 +65,30 @@ def test_spec_matches_reference(task_id):
             assert np.dtype(s[0]) == np.dtype(r["dtype"]), k
             assert list(s[1]) == r["shape"], k
             assert _plain(list(s[2])) == _plain(r["bounds"]), k
+
+
+@pytest.mark.parametrize("task_id", IDS)
+def test_spec_matches_reference(task_id):
+    _assert_spec_matches(envpool.make_spec(task_id), SPECS[task_id])
+
+
+@pytest.mark.parametrize("case", OPTION_CASES)
+def test_option_spec_matches_reference(case):
+    """make_spec(<a registered id of the env_name>, **kwargs) against the reference's spec of that config."""
+    task_id, kw = option_kwargs(case)
+    spec = envpool.make_spec(task_id, **kw)
+    _assert_spec_matches(spec, OPTION_TABLE[case]["spec"])
+    # the config is the reference's defaults plus the case's kwargs: the registered id adds nothing of its own
+    conf = spec.config._asdict()
+    from envpool_amd.core.binding import COMMON_CONFIG
+
+    common = {k for k, _ in COMMON_CONFIG}
+    want = dict((k, v) for k, v in OPTION_TABLE[case]["spec"]["default_config"] if k not in common)
+    want.update(OPTION_TABLE[case]["kwargs"])
+    assert {k: _plain(conf[k]) for k in want} == {k: _plain(v) for k, v in want.items()}
+    by_key = dict(zip(spec._state_keys, spec._state_spec))
+    assert tuple(by_key["info:agent_pos"][2]) == (0, max(conf["size"], conf["width"], conf["height"], 25))
+    assert tuple(dict(zip(spec._action_keys, spec._action_spec))["action"][2]) == (0, conf["action_max"])
 
 
 def test_unsupported_config_raises():
@@ -120,6 +143,40 @@ def task_cfg(conf: dict, max_tries: int = 1 << 20) -> np.ndarray:
                      conf["strip2_row"], n_obst, conf["max_episode_steps"], max_tries, see], np.int32)
 
 
+def params_task_cfg(p: dict, max_episode_steps: int, max_tries: int = 1 << 20) -> np.ndarray:
+    """mg::TaskCfg of the engine parameters `_native_params` gives: the keys csrc/minigrid.hip's MakeTaskCfg reads."""
+    task = int(p["env_name_code"])
+    size = int(p["size"])
+    w, h = (int(p["width"]), int(p["height"])) if task == 2 else (19, 19) if task == 6 else (size, size)
+    n = int(p["n_obstacles"])
+    n_obst = (n if n <= size // 2 + 1 else size // 2) if task == 5 else 0
+    return np.array([task, w, h, size, p["start_x"], p["start_y"], p["start_dir"], p["num_crossings"],
+                     (2 | (5 << 4)) if p["obstacle_wall"] else 9, p["strip2_row"], n_obst, max_episode_steps, max_tries,
+                     int(task in (0, 2, 5))], np.int32)
+
+
+@pytest.mark.parametrize("case", OPTION_CASES)
+def test_option_engine_params_give_the_task_cfg(case):
+    """The kwargs' route into the engine (make_spec -> _native_params) and the host harness (task_cfg) agree."""
+    conf = option_config(case)
+    got = params_task_cfg(option_params(case), conf["max_episode_steps"])
+    np.testing.assert_array_equal(got, task_cfg(conf))
+    g = option_fixture(case)
+    assert (got[1], got[2]) == (int(g["width"]), int(g["height"]))
+    assert got[11] == OPTION_TABLE[case]["kwargs"]["max_episode_steps"]
+
+
+@pytest.mark.parametrize("case", [c for c in OPTION_CASES if "agent_start_pos" in OPTION_TABLE[c]["kwargs"]])
+def test_option_pair_key_as_tuple_and_list(case):
+    want = tuple(OPTION_TABLE[case]["kwargs"]["agent_start_pos"])
+    for pair in (tuple, list):
+        conf = option_config(case, pair)
+        assert tuple(conf["agent_start_pos"]) == want
+        p = option_params(case, pair)
+        assert (p["start_x"], p["start_y"]) == want
+    assert option_params(case, tuple) == option_params(case, list)
+
+
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
@@ -139,10 +196,13 @@ def host_replay(lib, conf, g, max_tries=1 << 20):
     return rc, out
 
 
-@pytest.mark.parametrize("task_id", IDS)
+@pytest.mark.parametrize("task_id", IDS + [f"opt__{c}" for c in OPTION_CASES])
 def test_host_build_replays_reference_fixture(harness, task_id):
-    g = fixture(task_id)
-    rc, o = host_replay(harness, config(task_id), g)
+    if task_id.startswith("opt__"):
+        g, conf = option_fixture(task_id[5:]), option_config(task_id[5:])
+    else:
+        g, conf = fixture(task_id), config(task_id)
+    rc, o = host_replay(harness, conf, g)
     assert rc == 0
     np.testing.assert_array_equal(o["dir"], g["obs__direction"])
     np.testing.assert_array_equal(o["pos"], g["info__agent_pos"])
