@@ -116,7 +116,19 @@ __all__ = ["AtariEnvSpec", "AtariDMEnvPool", "AtariGymnasiumEnvPool", "AtariPost
 
 
 class AtariPostProcess:
-    """frames [k, 2, 210, 160] u8 -> obs [k, stack_num (x3), img_height, img_width] u8."""
+    """frames [k, 2, 210, 160] u8 -> obs [k, stack_num (x3), img_height, img_width] u8.
+
+    `reset_mask` holds the per-row flags of include/envpool_amd.h: 0 max of both frames, 1 frame 0
+    shown in every stack slot, 2 frame 0 pushed like a step, 4 the newest stacked frame again.
+
+    Raises ValueError at construction for what the kernel cannot run: `stack_num < 1`; an output
+    larger than the raw frame; `raw_height * raw_width` above 60000 or not a multiple of 16 (the
+    frames are read with aligned 16-byte loads); more than 65536 bytes of LDS per block
+    (`ceil16(raw_height * raw_width) + 28 * (img_height + img_width) + 256 * planes`: 240x244 ->
+    100x100 RGB is the largest such output accepted); INTER_AREA with more than 6 taps on an axis
+    (36x28) or integer scale factors, INTER_LINEAR with an exact 2x2 reduction; RGB without a
+    palette.  Tested bit for bit in all six kernel forms -- gray / RGB x 84x84 area, generic area,
+    linear -- with stack_num 1, 2 and 4 (tests/test_gpu_atari_post_forms.py)."""
 
     def __init__(self, num_envs: int, stack_num: int = 4, img_height: int = 84,
                  img_width: int = 84, raw_height: int = 210, raw_width: int = 160,

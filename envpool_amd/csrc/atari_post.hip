@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "engine.h"
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(kPostBlock) void AtariPostKernel(
       return (unsigned int)lc[w & 255u] | ((unsigned int)lc[(w >> 8) & 255u] << 8) |
              ((unsigned int)lc[(w >> 16) & 255u] << 16) | ((unsigned int)lc[w >> 24] << 24);
     };
-    const int nvec = fsz / 16;
+    const int nvec = fsz / 16;  // fsz % 16 == 0 (checked at create): no tail, every load aligned
     constexpr int kBatch = 6;  // independent 16-B loads in flight per thread and frame
     for (int base = 0; base < nvec; base += kBatch * kPostBlock) {
       uint4 a[kBatch], b[kBatch];
@@ -183,14 +184,6 @@ __global__ __launch_bounds__(kPostBlock) void AtariPostKernel(
           reinterpret_cast<uint4*>(pooled)[i] = r;
         }
       }
-    }
-    for (int i = nvec * 16 + threadIdx.x; i < fsz; i += kPostBlock) {
-      unsigned char a = f0[i], b = f1[i];
-      if (indexed) {
-        a = lc[a];
-        b = lc[b];
-      }
-      pooled[i] = rst ? a : (a > b ? a : b);
     }
     __syncthreads();
     // 2. area resize of this plane
@@ -393,12 +386,18 @@ void UploadTab(const std::vector<short>& ofs, const std::vector<short>& cnt,
   EPA_HIP(hipMemcpy(t->alpha, alpha.data(), alpha.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
+// dynamic LDS of one block: the pooled raw frame, both tap tables, the palette
+size_t PostLdsBytes(int sh, int sw, int dh, int dw, int chan) {
+  return ((size_t)sh * sw + 15) / 16 * 16 + sizeof(epa::TabEntry) * (size_t)(dw + dh) +
+         (size_t)chan * 256;
+}
+// what a launch may ask for without a per-kernel opt-in
+constexpr size_t kPostMaxLds = 65536;
+
 void LaunchPost(epa_atari_post* p, const int* d_ids, int k,
                 const unsigned char* d_frames, const unsigned char* d_mask,
                 unsigned char* d_obs) {
-  size_t lds = (size_t)p->d.sh * p->d.sw;
-  lds = (lds + 15) / 16 * 16 + sizeof(epa::TabEntry) * (size_t)(p->d.dw + p->d.dh) +
-        (size_t)p->d.chan * 256;
+  const size_t lds = PostLdsBytes(p->d.sh, p->d.sw, p->d.dh, p->d.dw, p->d.chan);
 #define EPA_POST_LAUNCH(XT, YT, LIN, CH)                                                     \
   hipLaunchKernelGGL((epa::AtariPostKernel<XT, YT, LIN, CH>), dim3(k), dim3(epa::kPostBlock), \
                      lds, p->stream, p->d, d_ids, k, d_frames, d_mask, d_obs)
@@ -439,6 +438,18 @@ int epa_atari_post_create_ex(int32_t num_envs, int32_t stack_num, int32_t in_h,
     if (num_envs < 1 || stack_num < 1 || out_h > in_h || out_w > in_w ||
         out_h < 1 || out_w < 1 || (size_t)in_h * in_w > 60000) {
       throw std::invalid_argument("atari_post: bad dimensions");
+    }
+    const size_t lds = PostLdsBytes(in_h, in_w, out_h, out_w, gray_scale ? 1 : 3);
+    if (lds > kPostMaxLds) {
+      throw std::invalid_argument(
+          "atari_post: the kernel stages the raw frame, the tap tables and the palette in LDS: " +
+          std::to_string(lds) + " bytes for this configuration, the limit is " +
+          std::to_string(kPostMaxLds));
+    }
+    if ((size_t)in_h * in_w % 16 != 0) {
+      throw std::invalid_argument(
+          "atari_post: in_h * in_w = " + std::to_string((size_t)in_h * in_w) +
+          " is not a multiple of 16: the kernel reads the raw frames with aligned 16-byte loads");
     }
     if (!use_inter_area && in_h == 2 * out_h && in_w == 2 * out_w) {
       throw std::invalid_argument(

@@ -361,7 +361,16 @@ int epa_atari_post_create(int32_t num_envs, int32_t stack_num, int32_t in_h,
  *     applied on the device, per frame before the max-pool.
  *   gray_scale = 0 (needs the palette): a stacked frame is three planes [3, out_h, out_w]
  *     (the transpose of atari_env.h:320-335), observations are
- *     [k, stack_num * 3, out_h, out_w]. */
+ *     [k, stack_num * 3, out_h, out_w].
+ * Refused with EPA_ERR_INVALID (the message names the reason):
+ *   - stack_num < 1, an output larger than the raw frame, in_h * in_w > 60000;
+ *   - in_h * in_w not a multiple of 16 (the kernel reads the raw frames with aligned 16-byte
+ *     loads; Atari's 210 x 160 is);
+ *   - ceil16(in_h * in_w) + 28 * (out_h + out_w) + 256 * planes > 65536: one block stages the
+ *     raw frame, both tap tables and the palette in LDS (240 x 244 -> 100 x 100 RGB, 64928
+ *     bytes, is accepted; 240 x 248 is not);
+ *   - INTER_AREA with more than 6 taps on an axis (scale > ~5) or with integer scale factors,
+ *     INTER_LINEAR with an exact 2 x 2 reduction (OpenCV fast paths that are not restated). */
 int epa_atari_post_create_ex(int32_t num_envs, int32_t stack_num, int32_t in_h,
                              int32_t in_w, int32_t out_h, int32_t out_w,
                              int32_t use_inter_area, int32_t gray_scale,
@@ -379,7 +388,9 @@ int epa_atari_post_destroy(epa_atari_post* p);
 int epa_atari_post_push(epa_atari_post* p, const int32_t* env_id, int32_t k,
                         const uint8_t* frames, const uint8_t* reset_mask,
                         uint8_t* obs_out);
-/* device-resident variant: all pointers are device pointers. */
+/* device-resident variant: all pointers are device pointers (d_frames and d_obs_out
+ * 16-byte aligned; d_env_id NULL = rows 0..k-1), the launch goes to
+ * epa_atari_post_stream() and shares the frame-stack ring with epa_atari_post_push. */
 int epa_atari_post_push_device(epa_atari_post* p, const int32_t* d_env_id,
                                int32_t k, const uint8_t* d_frames,
                                const uint8_t* d_reset_mask, uint8_t* d_obs_out);
