@@ -226,6 +226,27 @@ class _ShardedPools:
         return self.pools[0].player_rows([block[o:o + k * rb].view(dtype).reshape((k, *shape))
                                           for (_, dtype, shape), o, rb in zip(self.state_keys, offs, row_bytes)])
 
+    def render_size(self, width: int = 0, height: int = 0) -> tuple[int, int]:
+        return self.pools[0].render_size(width, height)
+
+    def render(self, env_ids: Any, width: int = 0, height: int = 0, camera_id: int = -1) -> np.ndarray:
+        """Frames of envs of any shards, in request order: every shard renders its ids, all shards at once."""
+        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        w, h = self.render_size(width, height)
+        if len(ids) == 0:
+            raise ValueError("render env_ids must not be empty")
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        out = np.empty((len(ids), h, w, 3), dtype=np.uint8)
+
+        def paint(s: int, p: DevicePool, idx: Any) -> None:
+            out[idx] = p.render(ids[idx], width, height, camera_id)
+
+        self._each(paint, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
+        return out
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -347,8 +368,12 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
 
         def _render(self, env_ids: np.ndarray, width: int, height: int,
                     camera_id: int) -> np.ndarray:
-            # async_envpool.h:192-194
-            raise RuntimeError("render not implemented for this environment")
+            # async_envpool.h:183-222; a family without a render kernel raises the reference's
+            # RuntimeError("render not implemented for this environment") from the engine
+            render = getattr(self._pool, "render", None)
+            if render is None:  # a pool with its own executor
+                raise RuntimeError("render not implemented for this environment")
+            return render(env_ids, width, height, camera_id)
 
         def _xla(self) -> Any:
             raise RuntimeError("XLA is not available for the MI355X engine")

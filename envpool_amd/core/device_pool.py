@@ -334,6 +334,31 @@ class DevicePool:
             self._lib.epa_set_state(self._h, ids.ctypes.data, len(ids), state.ctypes.data)
         )
 
+    # -- render ----------------------------------------------------------------
+    def render_size(self, width: int = 0, height: int = 0) -> tuple[int, int]:
+        """(width, height) of the frames `render` returns: a width / height <= 0 is the env's default.  Raises
+        RuntimeError("render not implemented for this environment") for a family that does not render."""
+        w, h = ctypes.c_int32(0), ctypes.c_int32(0)
+        native.check(self._lib.epa_render_size(self._h, int(width), int(height), ctypes.byref(w), ctypes.byref(h)))
+        return w.value, h.value
+
+    def render(self, env_ids: Any, width: int = 0, height: int = 0, camera_id: int = -1) -> np.ndarray:
+        """uint8 [k, H, W, 3] RGB frames of the listed envs (global ids, duplicates allowed), painted on the device
+        from the state every send so far has left them in; byte-identical with the reference's `render`."""
+        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        w, h = self.render_size(width, height)
+        out = np.empty((len(ids), h, w, 3), dtype=np.uint8)
+        native.check(self._lib.epa_render(self._h, ids.ctypes.data, len(ids), int(width), int(height),
+                                          int(camera_id), out.ctypes.data))
+        return out
+
+    def render_device(self, d_out: int, env_ids: Any, width: int = 0, height: int = 0, camera_id: int = -1) -> None:
+        """`render` into device memory at the raw address `d_out` (room for [k, H, W, 3] bytes, see `render_size`):
+        enqueued on the pool's stream, nothing is copied to the host (torch_interop.render_device wraps it)."""
+        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        native.check(self._lib.epa_render_device(self._h, ids.ctypes.data, len(ids), int(width), int(height),
+                                                 int(camera_id), ctypes.c_void_p(d_out)))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

@@ -105,6 +105,9 @@ def lib() -> ctypes.CDLL:
         "epa_state_dim": (i32, [vp, P(i32)]),
         "epa_get_state": (i32, [vp, vp, i32, vp]),
         "epa_set_state": (i32, [vp, vp, i32, vp]),
+        "epa_render_size": (i32, [vp, i32, i32, P(i32), P(i32)]),
+        "epa_render": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+        "epa_render_device": (i32, [vp, vp, i32, i32, i32, i32, vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -136,7 +139,8 @@ EXPORTED_SYMBOLS = [
     "epa_recv", "epa_recv_layout", "epa_recv_block", "epa_send_into", "epa_recv_into", "epa_pending_rows",
     "epa_send_device", "epa_recv_device", "epa_step_device", "epa_wait_stream", "epa_consumer_wait",
     "epa_stream", "epa_synchronize", "epa_set_timing", "epa_kernel_time_ms",
-    "epa_state_dim", "epa_get_state", "epa_set_state", "epa_atari_post_create",
+    "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
+    "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
     "epa_atari_post_destroy", "epa_atari_post_push",

@@ -236,6 +236,18 @@ class Pool {
   virtual void SetState(const int* d_ids, int k, const double* d_in) = 0;
   void GetStateHost(const int32_t* ids, int k, double* out);
   void SetStateHost(const int32_t* ids, int k, const double* in);
+  // render (rgb_array mode; RenderableEnv of envpool/core/env.h, AsyncEnvPool::Render): RenderSize resolves a
+  // width / height <= 0 to the env's default, Render paints uint8 [k, h, w, 3] frames of the listed local envs
+  // from their persistent state on stream_ (d_rgb: any alignment).  A family that does not render keeps the
+  // defaults, which throw the reference's std::runtime_error("render not implemented for this environment").
+  virtual void RenderSize(int width, int height, int* w, int* h) const;
+  virtual void Render(const int* d_ids, int k, int w, int h, int camera_id, void* d_rgb);
+  // The host entry points (epa_render_size / epa_render / epa_render_device).  A frame shows its env after every
+  // send issued before the call, received or not.  RenderHost returns the frames in host memory; RenderDevice
+  // only enqueues (no host copy, no host wait): the frames are complete once the pool's stream has passed.
+  void RenderSizeHost(int width, int height, int* w, int* h) const;
+  void RenderHost(const int32_t* ids, int k, int width, int height, int camera_id, uint8_t* out);
+  void RenderDevice(const int32_t* ids, int k, int width, int height, int camera_id, void* d_out);
 
  protected:
   // Launch the family's batched step kernel for k rows on stream_.
@@ -358,6 +370,12 @@ class Pool {
   char* recv_stage_{nullptr};  // pinned D2H landing block
   size_t recv_stage_bytes_{0};
   hipEvent_t order_ev_{nullptr};  // WaitStream's producer marker
+  // render: uploads the launch's env ids and calls the family's Render at the resolved size (the caller holds mu_)
+  void RenderLaunch(const int32_t* ids, int k, int w, int h, int camera_id, void* d_rgb);
+  int* render_ids_{nullptr};      // [render_ids_cap_] local ids of the last render launch
+  int render_ids_cap_{0};
+  std::vector<int> render_local_;
+  hipEvent_t render_ev_{nullptr};  // behind the last RenderDevice launch
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream
   std::vector<hipEvent_t> join_ev_;      // one per compute stream (JoinCompute)

@@ -16,12 +16,15 @@
 // and report trunc against that limit + 1 (their CurrentMaxEpisodeSteps), i.e. never; Game2048 and
 // Minesweeper against the config's max_episode_steps.  Snake's reset fruit loop is bounded by the engine key
 // "snake_max_tries": an exhausted bound sets the pool's error word (Pool::EnableErrorWord).
+// Render: jumanji_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
 #include <algorithm>
 #include <string>
 
 #include "device_common.hip.h"
 #include "engine.h"
 #include "jumanji_env.hip.h"
+#include "jumanji_render.hip.h"
+#include "render_kernel.hip.h"
 
 namespace epa {
 namespace {
@@ -114,6 +117,13 @@ __global__ void JumanjiSetState(JmDev d, CommonDev cm, const int* ids, int k, co
   cm.cur_step[e] = (int)o[0];
   cm.done[e] = done ? 1 : 0;
 }
+
+// the render kernel's painter of puzzle P (render_kernel.hip.h)
+template <int P>
+struct JmPainter {
+  using State = typename jm::State<P>::T;
+  static __device__ void Paint(render::Canvas& cv, const State& s) { jm::Render(cv, s); }
+};
 
 int PuzzleOf(const std::string& family) {
   if (family == "Game2048") return jm::kGame2048;
@@ -245,6 +255,17 @@ class JumanjiPool : public Pool {
     }
     hipLaunchKernelGGL(kernel, dim3((k + 255) / 256), dim3(256), 0, stream_, d_, common_, d_ids, k, d_in);
   }
+  void RenderSize(int width, int height, int* w, int* h) const override { jm::RenderSize(width, height, w, h); }
+  void Render(const int* d_ids, int k, int w, int h, int /*camera_id*/, void* d_rgb) override {
+    switch (p_) {
+      case jm::kGame2048: return RenderP<jm::kGame2048>(d_ids, k, w, h, d_rgb);
+      case jm::kMinesweeper: return RenderP<jm::kMinesweeper>(d_ids, k, w, h, d_rgb);
+      case jm::kSlidingTile: return RenderP<jm::kSlidingTile>(d_ids, k, w, h, d_rgb);
+      case jm::kRubiksCube: return RenderP<jm::kRubiksCube>(d_ids, k, w, h, d_rgb);
+      case jm::kSnake: return RenderP<jm::kSnake>(d_ids, k, w, h, d_rgb);
+      default: return RenderP<jm::kMaze>(d_ids, k, w, h, d_rgb);
+    }
+  }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrTries) {
       return "Snake: a reset's fruit placement ran out of tries (snake_max_tries = " + std::to_string(c_.max_tries) +
@@ -272,6 +293,11 @@ class JumanjiPool : public Pool {
   }
 
  private:
+  template <int P>
+  void RenderP(const int* d_ids, int k, int w, int h, void* d_rgb) {
+    render::LaunchRender<JmPainter<P>>(static_cast<const typename jm::State<P>::T*>(d_.state), d_ids, k, w, h, d_rgb,
+                                       stream_);
+  }
   int p_;
   Cfg c_{};
   JmDev d_{};

@@ -15,12 +15,15 @@
 // key's section -- one contiguous range for the block's rows -- in 16-byte words, every thread computing the
 // elements of its words from the views (pgx::Elem).  A wave's stores are then 1 KB contiguous instead of 64 rows
 // apart.
+// Render: pgx_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
 #include <algorithm>
 #include <string>
 
 #include "device_common.hip.h"
 #include "engine.h"
 #include "pgx_env.hip.h"
+#include "pgx_render.hip.h"
+#include "render_kernel.hip.h"
 
 namespace epa {
 namespace {
@@ -146,6 +149,13 @@ __global__ void PgxSetState(CommonDev cm, pgx::State* st, unsigned* err, const i
   cm.done[e] = done ? 1 : 0;
 }
 
+// the render kernel's painter of game G (render_kernel.hip.h)
+template <int G>
+struct PgxPainter {
+  using State = pgx::State;
+  static __device__ void Paint(render::Canvas& cv, const State& s) { pgx::Render<G>(cv, s); }
+};
+
 int GameOf(const std::string& family) {
   if (family == "TicTacToe") return pgx::kTicTacToe;
   if (family == "ConnectFour") return pgx::kConnectFour;
@@ -190,6 +200,10 @@ class PgxPool : public Pool {
   void SetState(const int* d_ids, int k, const double* d_in) override {
     hipLaunchKernelGGL(PgxSetState<G>, dim3((k + 255) / 256), dim3(256), 0, stream_, common_, state_, err_dev_,
                        d_ids, k, d_in);
+  }
+  void RenderSize(int width, int height, int* w, int* h) const override { pgx::RenderSize<G>(width, height, w, h); }
+  void Render(const int* d_ids, int k, int w, int h, int /*camera_id*/, void* d_rgb) override {
+    render::LaunchRender<PgxPainter<G>>(state_, d_ids, k, w, h, d_rgb, stream_);
   }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";

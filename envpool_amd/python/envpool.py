@@ -2,8 +2,9 @@
 pool's `_send / _recv / _reset`.
 
 Host-side mirror of envpool/python/envpool.py:61-384 (same method names,
-argument meaning and error behaviour).  Rendering stays out of scope: `render`
-keeps the reference's checks and then surfaces the pool's RuntimeError.
+argument meaning and error behaviour).  `render` keeps the reference's checks and
+env id forms; the frames come from the pool's render kernel (Jumanji, PGX), and a
+family without one surfaces the pool's RuntimeError.
 """
 
 from __future__ import annotations
@@ -116,15 +117,32 @@ class EnvPoolMixin(ABC):
             raise RuntimeError(
                 "render_mode must be set to 'rgb_array' or 'human' when creating this env"
             )
+        # envpool.py:51-58: None is render_env_id; an int, a list or an array name the envs
         if env_ids is None:
-            env_ids = [int(getattr(self, "_render_env_id", 0))]
-        ids = np.atleast_1d(np.asarray(env_ids, dtype=np.int32))
-        return self._render(
+            ids = np.asarray([int(getattr(self, "_render_env_id", 0))], dtype=np.int32)
+        elif isinstance(env_ids, (int, np.integer)):
+            ids = np.asarray([env_ids], dtype=np.int32)
+        else:
+            ids = np.asarray(_normalize_env_id(env_ids), dtype=np.int32)
+        frames = self._render(
             ids,
             int(getattr(self, "_render_width", 0)),
             int(getattr(self, "_render_height", 0)),
             int(getattr(self, "_render_camera_id", -1) if camera_id is None else camera_id),
         )
+        if render_mode == "human":  # envpool.py:288-294 (the window itself needs opencv, which is optional)
+            if ids.shape[0] != 1:
+                raise ValueError("render_mode='human' only supports a single env_id")
+            try:
+                import cv2
+            except ImportError as exc:
+                raise RuntimeError("render_mode='human' requires opencv-python to be installed") from exc
+            name = getattr(self, "_render_window_name", f"{self.__class__.__name__}-render")
+            cv2.imshow(name, np.ascontiguousarray(frames[0][:, :, ::-1]))
+            cv2.waitKey(1)
+            self._render_window_name = name
+            return None
+        return frames
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -1,8 +1,9 @@
 """Global env registry: make / make_gym / make_dm / make_spec / list_all_envs.
 
 Host-side mirror of envpool/registration.py (same functions, kwargs checks and
-errors); pixel/render variants are out of scope, so `from_pixels=True` raises
-and render kwargs are only carried as attributes like the reference does.
+errors); pixel variants are out of scope, so `from_pixels=True` raises.  The render
+kwargs are carried as attributes like the reference does; `render()` reads them
+(envpool_amd/python/envpool.py) and the Jumanji and PGX families paint the frames.
 """
 
 from __future__ import annotations

@@ -96,3 +96,30 @@ def recv_device_tensors(pool: Any, device: Any = None, order_current_stream: boo
         # a per-player key of a multi-player family: its [k, P, ...] block as [k * P, ...] player rows
         out[name] = torch.as_tensor(_DevArray(ptr, pool.view_shape(i, k), dtype), device=dev)
     return out
+
+
+def render_device(pool: Any, env_ids: Any, width: int = 0, height: int = 0, camera_id: int = -1,
+                  out: Any = None) -> Any:
+    """`pool.render` without the way down: a torch.uint8 [k, H, W, 3] tensor on the pool's device, painted by the
+    render kernel straight into torch's memory (no PCIe transfer, no host synchronisation).  The kernel is ordered
+    behind torch's CURRENT stream (whatever still uses the memory there) and the current stream behind the kernel,
+    so the tensor can be consumed right away.  `out`: a contiguous uint8 tensor of that many bytes to paint into
+    (any storage offset) instead of a fresh one."""
+    import torch
+
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    w, h = pool.render_size(width, height)
+    dev = torch.device("cuda", pool.device)
+    shape = (len(ids), h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != int(np.prod(shape)) \
+            or out.device != dev:
+        raise RuntimeError(f"render_device: out must be a contiguous uint8 tensor of {shape} on {dev}")
+    cur = torch.cuda.current_stream(dev)
+    pool.wait_stream(cur.cuda_stream)
+    pool.render_device(out.data_ptr(), ids, width, height, camera_id)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.ExternalStream(pool.stream, device=dev))
+    cur.wait_event(ev)
+    return out.view(shape)

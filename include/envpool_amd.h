@@ -343,6 +343,28 @@ int epa_get_state(epa_pool* pool, const int32_t* env_ids, int32_t k,
 int epa_set_state(epa_pool* pool, const int32_t* env_ids, int32_t k,
                   const double* in);
 
+/* Replaces AsyncEnvPool::Render (async_envpool.h:183-222, render_mode "rgb_array"): uint8 [k, H, W, 3] row-major
+ * RGB frames of the listed envs, painted on the device from their persistent state, byte-identical with the
+ * reference's RenderableEnv::Render.  Families: the six Jumanji puzzles and the four PGX board games; every other
+ * family fails with EPA_ERR_RUNTIME "render not implemented for this environment", like an env of the reference that
+ * is no RenderableEnv.
+ *   width / height <= 0: the env's default (256 x 256; TicTacToe 192 x 192, ConnectFour 280 x 240, Hex 352 x 352);
+ *     epa_render_size resolves them the same way, so the caller can size its buffer.  A side above 4096 is refused.
+ *   camera_id: accepted and ignored, as in the reference.
+ *   env_ids: global ids (env_id_offset included), any count >= 1, duplicates allowed.  EPA_ERR_INVALID for k <= 0
+ *     ("render env_ids must not be empty") and for an id outside the pool (as epa_get_state).
+ * A frame shows its env after every send / reset issued before the call, received or not; a finished env shows its
+ * terminal state until its next step resets it.  Rendering changes nothing a later send or recv sees.
+ * epa_render returns the frames in host memory.  epa_render_device writes them to device memory of the pool's
+ * device (any alignment) and copies nothing to the host: it only enqueues, stream-ordered like epa_recv_device --
+ * order the consumer behind epa_stream(pool), and call epa_wait_stream first if the buffer is still in use on
+ * another stream. */
+int epa_render_size(epa_pool* pool, int32_t width, int32_t height, int32_t* w, int32_t* h);
+int epa_render(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t width, int32_t height, int32_t camera_id,
+               uint8_t* host_out);
+int epa_render_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t width, int32_t height,
+                      int32_t camera_id, void* device_out);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
