@@ -408,11 +408,7 @@ class ClassicPool : public Pool {
   ClassicPool(const Config& cfg, const FamilySpec& spec)
       : Pool(cfg, spec, /*needs_rng=*/true),
         version_((int)cfg.Get("version", 0)) {
-    for (int j = 0; j < NS; ++j) {
-      EPA_HIP(hipMalloc(&dev_.s[j], sizeof(double) * cfg.num_envs));
-      EPA_HIP(hipMemsetAsync(dev_.s[j], 0, sizeof(double) * cfg.num_envs,
-                             stream_));
-    }
+    for (int j = 0; j < NS; ++j) dev_.s[j] = DevAlloc<double>(cfg.num_envs);
     // CartPole / Acrobot episodes end at their own times under any policy: tiled generator words
     // (engine.h: mt_tile_default_); Pendulum and the MountainCars run to the step limit together
     if (KIND == kCartPole || KIND == kAcrobot) mt_tile_default_ = 16;
@@ -423,11 +419,6 @@ class ClassicPool : public Pool {
       throw std::invalid_argument("classic_block must be 64, 128 or 256 and classic_rows 1 .. 8");
     }
     InitCommon();
-  }
-  ~ClassicPool() override {
-    for (int j = 0; j < NS; ++j) {
-      if (dev_.s[j]) (void)hipFree(dev_.s[j]);
-    }
   }
   int StateDim() const override { return NS + 2; }
   void GetState(const int* d_ids, int k, double* d_out) override {

@@ -255,6 +255,22 @@ class Pool {
   virtual void Launch(const int* d_ids, int k, const void* d_action,
                       bool force_reset, const OutPtrs& out) = 0;
   void InitCommon();  // allocates + initialises CommonDev (after derived ctor)
+  // device memory that lives as long as the pool: zeroed on `s` (default stream_), freed by ~Pool after every
+  // stream has drained -- also when the derived constructor throws
+  template <class T>
+  T* DevAlloc(size_t count, hipStream_t s = nullptr) {
+    void* p = DevMalloc(sizeof(T) * count);
+    EPA_HIP(hipMemsetAsync(p, 0, sizeof(T) * count, s ? s : stream_));
+    return static_cast<T*>(p);
+  }
+  // the same for a table: holds a copy of host[0, count), complete on return
+  template <class T>
+  T* DevUpload(const T* host, size_t count) {
+    void* p = DevMalloc(sizeof(T) * count);
+    EPA_HIP(hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice));
+    return static_cast<T*>(p);
+  }
+  int WaveSlots();  // SIMDs of the device: one wave per SIMD, four SIMDs per CU (queried at the first call)
   // Per-pool error word for families whose kernels can meet a condition they must not spin on (a bounded
   // rejection loop that ran out): `err_dev_` is a pinned, device-mapped word the kernel stores a nonzero
   // code into; every recv that has waited for its rows' kernel (recv, recv_block, recv_into, and recv_device
@@ -320,6 +336,9 @@ class Pool {
   // block the kernel wrote (CopyRowsToHost / RecvInto)
   void TakeDirect(Batch* b, int take, int got, char* dst, const size_t* dst_off, void* const* dst_ptrs,
                   std::unique_lock<std::mutex>& lk);
+  void* DevMalloc(size_t bytes);   // hipMalloc, entered in dev_owned_
+  std::vector<void*> dev_owned_;   // DevAlloc / DevUpload: freed by ~Pool, by nobody else
+  int n_simd_{0};                  // WaveSlots (0: not asked yet)
   int direct_out_{-1};  // "direct_out" (-1: not read yet)
   unsigned* err_host_{nullptr};  // EnableErrorWord
   void CheckErrorWord() const;
@@ -392,6 +411,48 @@ class Pool {
   int win_launches_{0};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> timers_;
   std::vector<hipEvent_t> timer_pool_;
+};
+
+// Where the flat state of a gym-MuJoCo pool lives on the device.  The flat state is the one oracle/mjcpu uses:
+//   qpos[nq] qvel[nv] warm[nv] | time xlag ylag done cur_step normal_saved normal_avail [| lag[lag_rows]]
+// GetState writes all of it, SetState takes everything but `time`; done is stored as (x != 0), cur_step as
+// (int)x, normal_avail as (x != 0).  A part a family does not have reads 0 and is ignored on SetState:
+//                                    time (read only)               xlag ylag                  normal_saved / _avail
+//   HalfCheetah, Walker2d            Newton iterations, last step   -                          yes
+//   Hopper (3 ghost rows)            Newton iterations, last step   -                          yes
+//   Ant                              profiling counters, last step  lagged torso x, y          yes
+//   Inverted(Double)Pendulum         -                              -                          yes
+//   Swimmer                          -                              -                          yes (never drawn from)
+//   Reacher                          -                              lagged fingertip x, y      -
+//   Humanoid, HumanoidStandup        -                              lagged mass centre x, y    -
+//   Pusher                           -                              copies of lag rows 0, 1    -
+// The Pusher has five lag rows (xpos of tips_arm, x / y of the object, of the last forward evaluation): they follow
+// the common part as lag[5], SetState takes them from there and ignores xlag / ylag.
+struct MjStateView {
+  double* qpos;  // [nq + ghost][N]
+  double* qvel;  // [nv + ghost][N]
+  double* warm;  // [nv + ghost][N]
+  int nq, nv;    // as they appear in the flat state
+  // the optional parts
+  int ghost{0};            // rows the device arrays have beyond that (the Hopper's second leg): SetState zeroes them
+  double* lag{nullptr};    // [lag_rows][N]
+  int lag_rows{0};         // 0, 2 (xlag ylag), or more (appended)
+  double* nsaved{nullptr};         // [N], with
+  unsigned char* navail{nullptr};  // [N]
+  const int* time_i{nullptr};      // [N] what `time` reports: one of the two, or neither (0)
+  const double* time_d{nullptr};
+};
+
+// A pool whose state hooks are the flat state of its view; the family fills view_ from the pointers it steps.
+class MjPool : public Pool {
+ public:
+  using Pool::Pool;
+  int StateDim() const override;
+  void GetState(const int* d_ids, int k, double* d_out) override;
+  void SetState(const int* d_ids, int k, const double* d_in) override;
+
+ protected:
+  MjStateView view_{};  // (a copy of pointers the family's own *Dev struct holds: the step kernels take that)
 };
 
 // Diagnostic per-wave trace of a family's step kernel: when the environment variable

@@ -212,12 +212,8 @@ class JumanjiPool : public Pool {
     std::vector<int> init;
     c_ = MakeCfg(p, cfg, &init);
     const size_t n = (size_t)cfg.num_envs;
-    EPA_HIP(hipMalloc(&d_.state, StateBytes(p) * n));
-    EPA_HIP(hipMemsetAsync(d_.state, 0, StateBytes(p) * n, stream_));
-    int* d_init = nullptr;
-    EPA_HIP(hipMalloc(&d_init, sizeof(int) * jm::kInitWords));
-    EPA_HIP(hipMemcpy(d_init, init.data(), sizeof(int) * jm::kInitWords, hipMemcpyHostToDevice));
-    d_.init = d_init;
+    d_.state = DevAlloc<char>(StateBytes(p) * n);
+    d_.init = DevUpload(init.data(), jm::kInitWords);
     const int nkeys = (int)keys_.size() - kNumCommonKeys;  // the puzzle's own keys follow the common ones
     for (int j = 0; j < kMaxEnvKeys; ++j) d_.key_bytes[j] = j < nkeys ? keys_[kNumCommonKeys + j].row_bytes() : 0;
     d_.act_dim = action_.row_elems();
@@ -225,10 +221,6 @@ class JumanjiPool : public Pool {
     d_.err = err_dev_;
     mt_tile_default_ = 16;  // envs reset at their own times
     InitCommon();
-  }
-  ~JumanjiPool() override {
-    if (d_.state) (void)hipFree(d_.state);
-    if (d_.init) (void)hipFree(const_cast<int*>(d_.init));
   }
   int StateDim() const override { return 2 + jm::HiddenWords(p_); }
   void GetState(const int* d_ids, int k, double* d_out) override {

@@ -319,33 +319,19 @@ class MiniGridPool : public Pool {
     const size_t n = (size_t)cfg.num_envs;
     d_.n = cfg.num_envs;
     d_.cells = c_.width * c_.height;
-    EPA_HIP(hipMalloc(&d_.grid, sizeof(uint16_t) * n * d_.cells));
-    EPA_HIP(hipMalloc(&d_.agent, sizeof(int) * n));
-    EPA_HIP(hipMalloc(&d_.carry, sizeof(uint16_t) * n));
-    EPA_HIP(hipMalloc(&d_.obst, sizeof(uint64_t) * n));
-    EPA_HIP(hipMemsetAsync(d_.grid, 0, sizeof(uint16_t) * n * d_.cells, stream_));
-    EPA_HIP(hipMemsetAsync(d_.agent, 0, sizeof(int) * n, stream_));
-    EPA_HIP(hipMemsetAsync(d_.carry, 0, sizeof(uint16_t) * n, stream_));
-    EPA_HIP(hipMemsetAsync(d_.obst, 0, sizeof(uint64_t) * n, stream_));
+    d_.grid = DevAlloc<uint16_t>(n * d_.cells);
+    d_.agent = DevAlloc<int>(n);
+    d_.carry = DevAlloc<uint16_t>(n);
+    d_.obst = DevAlloc<uint64_t>(n);
     // WriteMission (minigrid_render.cc:371-376): the text, zero-padded, at most mission_bytes - 1 bytes
     char text[mg::kMissionBytes] = {};
     const std::string m = MissionText(c_);
     std::memcpy(text, m.data(), std::min<size_t>(m.size(), mg::kMissionBytes - 1));
-    uint4* mission = nullptr;
-    EPA_HIP(hipMalloc(&mission, mg::kMissionBytes));
-    EPA_HIP(hipMemcpy(mission, text, mg::kMissionBytes, hipMemcpyHostToDevice));
-    d_.mission = mission;
+    d_.mission = reinterpret_cast<const uint4*>(DevUpload(text, mg::kMissionBytes));
     EnableErrorWord();
     d_.err = err_dev_;
     mt_tile_default_ = 16;  // envs reset at their own times
     InitCommon();
-  }
-  ~MiniGridPool() override {
-    if (d_.grid) (void)hipFree(d_.grid);
-    if (d_.agent) (void)hipFree(d_.agent);
-    if (d_.carry) (void)hipFree(d_.carry);
-    if (d_.obst) (void)hipFree(d_.obst);
-    if (d_.mission) (void)hipFree(const_cast<uint4*>(d_.mission));
   }
   int StateDim() const override { return kHead + 3 * d_.cells; }
   void GetState(const int* d_ids, int k, double* d_out) override {

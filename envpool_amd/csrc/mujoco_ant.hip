@@ -77,7 +77,7 @@ struct AntDev {
   double* lag;   // [2][N]
   double* nsaved;
   unsigned char* navail;
-  double* cost;  // [N] profiling: Newton iterations of the last step, see AntGetState
+  double* cost;  // [N] profiling: Newton iterations of the last step, reported as `time` of the flat state
   // diagnostic (EPA_ANT_TRACE=<file>): per wave of the last launch {wall clock begin, end
   // (100 MHz), core clock begin, end, slot, HW_ID}; nullptr otherwise
   long long* trace;
@@ -496,47 +496,6 @@ __attribute__((amdgpu_waves_per_eu(kAntWavesPerEu<T>, kAntWavesPerEu<T>))) void 
 #endif
 }
 
-// flat state like oracle/mjcpu: qpos[15] qvel[14] warm[14] time xlag ylag done
-// cur_step normal_saved normal_avail
-constexpr int kAntStateDim = A::kNQ + 2 * A::kNV + 7;
-__global__ void AntGetState(AntDev dev, CommonDev cm, const int* ids, int k, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  double* o = out + (size_t)i * kAntStateDim;
-  for (int j = 0; j < A::kNQ; ++j) o[j] = dev.qpos[(size_t)j * n + e];
-  for (int j = 0; j < A::kNV; ++j) {
-    o[A::kNQ + j] = dev.qvel[(size_t)j * n + e];
-    o[A::kNQ + A::kNV + j] = dev.warm[(size_t)j * n + e];
-  }
-  double* t = o + A::kNQ + 2 * A::kNV;
-  t[0] = dev.cost[e];  // (oracle: time) profiling counters of the last step
-  t[1] = dev.lag[e];
-  t[2] = dev.lag[(size_t)n + e];
-  t[3] = cm.done[e];
-  t[4] = cm.cur_step[e];
-  t[5] = dev.nsaved[e];
-  t[6] = dev.navail[e];
-}
-__global__ void AntSetState(AntDev dev, CommonDev cm, const int* ids, int k, const double* in) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  const double* o = in + (size_t)i * kAntStateDim;
-  for (int j = 0; j < A::kNQ; ++j) dev.qpos[(size_t)j * n + e] = o[j];
-  for (int j = 0; j < A::kNV; ++j) {
-    dev.qvel[(size_t)j * n + e] = o[A::kNQ + j];
-    dev.warm[(size_t)j * n + e] = o[A::kNQ + A::kNV + j];
-  }
-  const double* t = o + A::kNQ + 2 * A::kNV;
-  dev.lag[e] = t[1];
-  dev.lag[(size_t)n + e] = t[2];
-  cm.done[e] = t[3] != 0.0;
-  cm.cur_step[e] = (int)t[4];
-  dev.nsaved[e] = t[5];
-  dev.navail[e] = t[6] != 0.0;
-}
-
 FamilySpec AntSpec(const Config& cfg) {
   int no_pos = cfg.Get("exclude_current_positions_from_observation", 1) != 0;
   // ant.h:51-75 (obs 27/29 + 6 per body with use_contact_force); StackSpec, frame_stack.h:42-71
@@ -554,11 +513,11 @@ FamilySpec AntSpec(const Config& cfg) {
   return {k, {"action", EPA_F64, {A::kNU}}};
 }
 
-class AntPool : public Pool {
+class AntPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit AntPool(const Config& cfg)
-      : Pool(cfg, AntSpec(cfg), true) {
+      : MjPool(cfg, AntSpec(cfg), true) {
     // (a unit queue re-reads the action rows per unit: uploaded, not read in place -- engine.h; and with several
     // batches in flight the long Ant kernels overlap their downloads anyway: direct batches measured 5-9 % slower
     // there, profiles/r6m_async_numpy_*.jsonl)
@@ -571,11 +530,7 @@ class AntPool : public Pool {
     task_.contact_force_max = cfg.Get("contact_force_max", 1.0);
     fp64_ = (int)cfg.Get("precision", 1) == 1;
     sub_ = (int)cfg.Get("ant_sub", 1);
-    {
-      hipDeviceProp_t prop;
-      EPA_HIP(hipGetDeviceProperties(&prop, cfg.device));
-      wave_slots_ = prop.multiProcessorCount * 4;
-    }
+    wave_slots_ = WaveSlots();
     model_ = A::BuildAntModel();
     task_.frame_skip = (int)cfg.Get("frame_skip", 5);
     task_.obs_skip = cfg.Get("exclude_current_positions_from_observation", 1) != 0 ? 2 : 0;
@@ -590,50 +545,26 @@ class AntPool : public Pool {
     task_.dt = task_.frame_skip * model_.timestep;
     if (sub_ < 1 || sub_ > task_.frame_skip) sub_ = task_.frame_skip;
     size_t n = cfg.num_envs;
-    EPA_HIP(hipMalloc(&dev_.qpos, sizeof(double) * A::kNQ * n));
-    EPA_HIP(hipMalloc(&dev_.qvel, sizeof(double) * A::kNV * n));
-    EPA_HIP(hipMalloc(&dev_.warm, sizeof(double) * A::kNV * n));
-    EPA_HIP(hipMalloc(&dev_.lag, sizeof(double) * 2 * n));
-    EPA_HIP(hipMalloc(&dev_.nsaved, sizeof(double) * n));
-    EPA_HIP(hipMalloc(&dev_.navail, n));
-    EPA_HIP(hipMalloc(&dev_.cost, sizeof(double) * n));
-    EPA_HIP(hipMemsetAsync(dev_.cost, 0, sizeof(double) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.qpos, 0, sizeof(double) * A::kNQ * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.qvel, 0, sizeof(double) * A::kNV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.warm, 0, sizeof(double) * A::kNV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.lag, 0, sizeof(double) * 2 * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.nsaved, 0, sizeof(double) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.navail, 0, n, stream_));
+    dev_.qpos = DevAlloc<double>(A::kNQ * n);
+    dev_.qvel = DevAlloc<double>(A::kNV * n);
+    dev_.warm = DevAlloc<double>(A::kNV * n);
+    dev_.lag = DevAlloc<double>(2 * n);
+    dev_.nsaved = DevAlloc<double>(n);
+    dev_.navail = DevAlloc<unsigned char>(n);
+    dev_.cost = DevAlloc<double>(n);
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, A::kNQ, A::kNV};
+    view_.lag = dev_.lag;
+    view_.lag_rows = 2;
+    view_.nsaved = dev_.nsaved;
+    view_.navail = dev_.navail;
+    view_.time_d = dev_.cost;
     trace_.Init("EPA_ANT_TRACE", (n + kAntEnvsPerBlock - 1) / kAntEnvsPerBlock, stream_);
     dev_.trace = trace_.d;
     mt_tile_default_ = 16;  // unhealthy terminations: every env resets at its own time
     InitCommon();
     EnableObsStack();  // frame_stack > 1: generic ring (envpool/mujoco/frame_stack.h:74-146)
   }
-  ~AntPool() override {
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.lag);
-    (void)hipFree(dev_.nsaved);
-    (void)hipFree(dev_.navail);
-    trace_.DumpAndFree();
-    (void)hipFree(dev_.cost);
-    for (auto& kv : queues_) {
-      (void)hipFree(kv.second.ticket);
-      (void)hipFree(kv.second.rowflag);
-      (void)hipFree(kv.second.progress);
-    }
-  }
-  int StateDim() const override { return kAntStateDim; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(AntGetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(AntSetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_in);
-  }
+  ~AntPool() override { trace_.DumpAndFree(); }
 
  protected:
   void Launch(const int* d_ids, int k, const void* d_action, bool force_reset,
@@ -643,11 +574,9 @@ class AntPool : public Pool {
     Queue& qu = queues_[stream_];
     if (qu.ticket == nullptr) {
       const size_t n = (size_t)cfg_.num_envs, nch = (n + kAntEnvsPerBlock - 1) / kAntEnvsPerBlock;
-      EPA_HIP(hipMalloc(&qu.ticket, sizeof(unsigned)));
-      EPA_HIP(hipMalloc(&qu.rowflag, n));
-      EPA_HIP(hipMalloc(&qu.progress, sizeof(unsigned) * nch));
-      EPA_HIP(hipMemsetAsync(qu.ticket, 0, sizeof(unsigned), stream_));
-      EPA_HIP(hipMemsetAsync(qu.progress, 0, sizeof(unsigned) * nch, stream_));
+      qu.ticket = DevAlloc<unsigned>(1);
+      qu.rowflag = DevAlloc<unsigned char>(n);
+      qu.progress = DevAlloc<unsigned>(nch);
     }
     AntArgs args{};
     args.dev = dev_;

@@ -223,52 +223,6 @@ __global__ __launch_bounds__(kCheetahBlock) void CheetahStepKernel(
               a.max_episode_steps);
 }
 
-// flat state, same layout as oracle/mjcpu: qpos[9] qvel[9] warm[9] time xlag
-// ylag done cur_step normal_saved normal_avail
-// `nv`: dofs of the model (9, Hopper: 6 -- its ghost dofs are not part of the state)
-__global__ void CheetahGetState(CheetahDev dev, CommonDev cm, const int* ids,
-                                int k, double* out, int nv) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  double* o = out + (size_t)i * (3 * nv + 7);
-  for (int j = 0; j < nv; ++j) {
-    o[j] = dev.qpos[(size_t)j * n + e];
-    o[nv + j] = dev.qvel[(size_t)j * n + e];
-    o[2 * nv + j] = dev.warm[(size_t)j * n + e];
-  }
-  double* t = o + 3 * nv;
-  t[0] = dev.iters[e];  // (oracle: time) Newton iterations of the last step
-  t[1] = 0;
-  t[2] = 0;
-  t[3] = cm.done[e];
-  t[4] = cm.cur_step[e];
-  t[5] = dev.nsaved[e];
-  t[6] = dev.navail[e];
-}
-__global__ void CheetahSetState(CheetahDev dev, CommonDev cm, const int* ids,
-                                int k, const double* in, int nv) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  const double* o = in + (size_t)i * (3 * nv + 7);
-  for (int j = 0; j < nv; ++j) {
-    dev.qpos[(size_t)j * n + e] = o[j];
-    dev.qvel[(size_t)j * n + e] = o[nv + j];
-    dev.warm[(size_t)j * n + e] = o[2 * nv + j];
-  }
-  for (int j = nv; j < kNV; ++j) {  // ghost dofs stay at rest
-    dev.qpos[(size_t)j * n + e] = 0.0;
-    dev.qvel[(size_t)j * n + e] = 0.0;
-    dev.warm[(size_t)j * n + e] = 0.0;
-  }
-  const double* t = o + 3 * nv;
-  cm.done[e] = t[3] != 0.0;
-  cm.cur_step[e] = (int)t[4];
-  dev.nsaved[e] = t[5];
-  dev.navail[e] = t[6] != 0.0;
-}
-
 FamilySpec CheetahSpec(const Config& cfg, bool walker, bool hopper) {
   int no_pos = cfg.Get("exclude_current_positions_from_observation", 1) != 0;
   int fs = (int)cfg.Get("frame_stack", 1);
@@ -290,12 +244,12 @@ FamilySpec CheetahSpec(const Config& cfg, bool walker, bool hopper) {
           action};
 }
 
-class CheetahPool : public Pool {
+class CheetahPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   // model: mj::kPlanarCheetah / kPlanarWalker / kPlanarWalkerV5 / kPlanarHopper
   CheetahPool(const Config& cfg, int model)
-      : Pool(cfg, CheetahSpec(cfg, model != mj::kPlanarCheetah, model == mj::kPlanarHopper), /*needs_rng=*/true),
+      : MjPool(cfg, CheetahSpec(cfg, model != mj::kPlanarCheetah, model == mj::kPlanarHopper), /*needs_rng=*/true),
         model_id_(model) {
     const bool walker = model != mj::kPlanarCheetah;  // Walker2d or Hopper
     const bool hopper = model == mj::kPlanarHopper;
@@ -333,12 +287,19 @@ class CheetahPool : public Pool {
     task_.terminate_when_unhealthy = cfg.Get("terminate_when_unhealthy", 1) != 0;
     task_.legacy_healthy_reward = cfg.Get("legacy_healthy_reward", 1) != 0;
     size_t n = cfg.num_envs;
-    EPA_HIP(hipMalloc(&dev_.qpos, sizeof(double) * kNV * n));
-    EPA_HIP(hipMalloc(&dev_.qvel, sizeof(double) * kNV * n));
-    EPA_HIP(hipMalloc(&dev_.warm, sizeof(double) * kNV * n));
-    EPA_HIP(hipMalloc(&dev_.nsaved, sizeof(double) * n));
-    EPA_HIP(hipMalloc(&dev_.navail, n));
-    EPA_HIP(hipMalloc(&dev_.iters, sizeof(int) * n));
+    dev_.qpos = DevAlloc<double>(kNV * n);
+    dev_.qvel = DevAlloc<double>(kNV * n);
+    dev_.warm = DevAlloc<double>(kNV * n);
+    dev_.nsaved = DevAlloc<double>(n);
+    dev_.navail = DevAlloc<unsigned char>(n);
+    dev_.iters = DevAlloc<int>(n);
+    // the Hopper's ghost dofs (rows 6 .. 8) are not part of the flat state
+    const int nv = hopper ? 6 : kNV;
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, nv, nv};
+    view_.ghost = kNV - nv;
+    view_.nsaved = dev_.nsaved;
+    view_.navail = dev_.navail;
+    view_.time_i = dev_.iters;
     trace_.Init("EPA_PLANAR_TRACE", (n + kCheetahBlock - 1) / kCheetahBlock, stream_);
     dev_.trace = trace_.d;
     spread_ = cfg.Get("planar_spread", 1) != 0;  // extension key, see Launch
@@ -394,22 +355,10 @@ class CheetahPool : public Pool {
         if (hopper && i == 1) break;  // one table: a group of one lane
         std::vector<double> tab(kPlanarLgTabMax, 0.0);
         const int cnt = PlanarLgBuildTable(hopper ? 1 : (i == 0 ? 2 : 4), model_id_, tab.data());
-        EPA_HIP(hipMalloc(&d_tab_[i], sizeof(double) * cnt));
-        EPA_HIP(hipMemcpy(d_tab_[i], tab.data(), sizeof(double) * cnt, hipMemcpyHostToDevice));
+        d_tab_[i] = DevUpload(tab.data(), cnt);
       }
     }
-    {
-      hipDeviceProp_t prop;
-      EPA_HIP(hipGetDeviceProperties(&prop, cfg.device));
-      wave_slots_ = prop.multiProcessorCount * 4;  // one wave per SIMD, four SIMDs per CU
-      if (wave_slots_ < 1) wave_slots_ = 1;
-    }
-    EPA_HIP(hipMemsetAsync(dev_.iters, 0, sizeof(int) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.qpos, 0, sizeof(double) * kNV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.qvel, 0, sizeof(double) * kNV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.warm, 0, sizeof(double) * kNV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.nsaved, 0, sizeof(double) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.navail, 0, n, stream_));
+    wave_slots_ = WaveSlots();
     // Walker2d / Hopper terminate when unhealthy, each env at its own time: tiled generator words; the
     // HalfCheetah never terminates early (all envs draw in the same launch)
     if (walker) mt_tile_default_ = 16;
@@ -420,30 +369,7 @@ class CheetahPool : public Pool {
     if (layout_ == 2) pipeline_default_ = 32768;
     InitCommon();
   }
-  ~CheetahPool() override {
-    trace_.DumpAndFree();
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.nsaved);
-    (void)hipFree(dev_.navail);
-    (void)hipFree(dev_.iters);
-    for (double* t : d_tab_) {
-      if (t) (void)hipFree(t);
-    }
-    for (auto& kv : tickets_) (void)hipFree(kv.second.d);
-    if (order_.d) (void)hipFree(order_.d);
-  }
-  int ModelNv() const { return model_id_ == mj::kPlanarHopper ? 6 : kNV; }
-  int StateDim() const override { return 3 * ModelNv() + 7; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(CheetahGetState, dim3((k + 255) / 256), dim3(256), 0,
-                       stream_, dev_, common_, d_ids, k, d_out, ModelNv());
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(CheetahSetState, dim3((k + 255) / 256), dim3(256), 0,
-                       stream_, dev_, common_, d_ids, k, d_in, ModelNv());
-  }
+  ~CheetahPool() override { trace_.DumpAndFree(); }
 
  protected:
   void Launch(const int* d_ids, int k, const void* d_action, bool force_reset,
@@ -459,10 +385,7 @@ class CheetahPool : public Pool {
     int layout = lg_ok_ && trace_.d == nullptr ? layout_ : 1;
     if (layout > 1) {
       Ticket& tk = tickets_[stream_];  // launches on different streams run concurrently: a queue each
-      if (tk.d == nullptr) {
-        EPA_HIP(hipMalloc(&tk.d, sizeof(unsigned)));
-        EPA_HIP(hipMemsetAsync(tk.d, 0, sizeof(unsigned), stream_));
-      }
+      if (tk.d == nullptr) tk.d = DevAlloc<unsigned>(1);
       // longest-chunk-first dispatch: whole-pool batches only (the chunks are then the same envs
       // from launch to launch); "planar_lpt" = 0 switches it off (A/B)
       planar::LgOrder lo;
@@ -471,8 +394,7 @@ class CheetahPool : public Pool {
       if (chain) {
         if (order_.d == nullptr) {
           order_.cap = (cfg_.num_envs + 3) / 4;  // the smallest chunk is a quarter wave of 4 lanes per env
-          EPA_HIP(hipMalloc(&order_.d, PlanarLgOrderBytes(order_.cap)));
-          EPA_HIP(hipMemsetAsync(order_.d, 0, PlanarLgOrderBytes(order_.cap), stream_));
+          order_.d = DevAlloc<unsigned>(PlanarLgOrderBytes(order_.cap) / sizeof(unsigned));
           order_.gen = 0;
           order_shape_ = -1;
         }

@@ -185,43 +185,6 @@ __global__ __launch_bounds__(kHumBlock) void HumanoidStepKernel(
 
 #endif  // EPA_ALT_KERNELS
 
-// flat state like oracle/mjcpu: qpos[24] qvel[23] warm[23] time xlag ylag done cur_step
-// normal_saved normal_avail (the last two unused: uniform noise only; xlag / ylag: the lagged
-// mass centre)
-template <class MP>
-__global__ void HumGetState(HumDev dev, CommonDev cm, const int* ids, int k, double* out) {
-  using E = T::Tree<MP>;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  const int e = ids[i], n = cm.n;
-  constexpr int np = E::kL.npersist;  // qpos qvel warm lag[2], in this order
-  double* o = out + (size_t)i * (np + 5);
-  for (int j = 0; j < np - 2; ++j) o[j] = dev.state[(size_t)j * n + e];
-  double* t = o + np - 2;
-  t[0] = 0;
-  t[1] = dev.state[(size_t)(np - 2) * n + e];
-  t[2] = dev.state[(size_t)(np - 1) * n + e];
-  t[3] = cm.done[e];
-  t[4] = cm.cur_step[e];
-  t[5] = 0;
-  t[6] = 0;
-}
-template <class MP>
-__global__ void HumSetState(HumDev dev, CommonDev cm, const int* ids, int k, const double* in) {
-  using E = T::Tree<MP>;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  const int e = ids[i], n = cm.n;
-  constexpr int np = E::kL.npersist;
-  const double* o = in + (size_t)i * (np + 5);
-  for (int j = 0; j < np - 2; ++j) dev.state[(size_t)j * n + e] = o[j];
-  const double* t = o + np - 2;
-  dev.state[(size_t)(np - 2) * n + e] = t[1];
-  dev.state[(size_t)(np - 1) * n + e] = t[2];
-  cm.done[e] = t[3] != 0.0;
-  cm.cur_step[e] = (int)t[4];
-}
-
 }  // namespace
 
 // The two models are compiled in separate translation units (the step kernel takes ~1.5 min
@@ -246,23 +209,11 @@ void EPA_HUM_FN(HumLaunchStep)(hipStream_t st, int blocks, HumDev dev, CommonDev
   throw std::runtime_error("the one-env-per-lane Humanoid kernel is not in this build (make EPA_ALT_KERNELS=1)");
 #endif
 }
-void EPA_HUM_FN(HumLaunchGet)(hipStream_t st, int k, HumDev dev, CommonDev cm, const int* ids,
-                              double* out) {
-  hipLaunchKernelGGL(HumGetState<HumModelP>, dim3((k + 255) / 256), dim3(256), 0, st, dev, cm, ids,
-                     k, out);
-}
-void EPA_HUM_FN(HumLaunchSet)(hipStream_t st, int k, HumDev dev, CommonDev cm, const int* ids,
-                              const double* in) {
-  hipLaunchKernelGGL(HumSetState<HumModelP>, dim3((k + 255) / 256), dim3(256), 0, st, dev, cm, ids,
-                     k, in);
-}
 int EPA_HUM_FN(HumWorkspaceSlots)() { return T::Tree<HumModelP>::kL.total; }
 
 #ifndef EPA_HUM_STANDUP_TU
 void HumLaunchStepStandup(hipStream_t, int, HumDev, CommonDev, StepArgs, const double*, OutPtrs,
                           HumTask);
-void HumLaunchGetStandup(hipStream_t, int, HumDev, CommonDev, const int*, double*);
-void HumLaunchSetStandup(hipStream_t, int, HumDev, CommonDev, const int*, const double*);
 int HumWorkspaceSlotsStandup();
 
 namespace {
@@ -294,10 +245,10 @@ FamilySpec HumSpec(const Config& cfg, bool standup) {
   return {k, {"action", EPA_F64, {kHumanoidModelConst.nu}}};
 }
 
-class HumanoidPool : public Pool {
+class HumanoidPool : public MjPool {
  public:
   HumanoidPool(const Config& cfg, bool standup)
-      : Pool(cfg, HumSpec(cfg, standup), /*needs_rng=*/true),
+      : MjPool(cfg, HumSpec(cfg, standup), /*needs_rng=*/true),
         standup_(standup) {
     EnableObsStack();
     // defaults: humanoid.h:32-48, humanoid_standup.h:32-45
@@ -339,43 +290,31 @@ class HumanoidPool : public Pool {
 #endif
     // "hum_sort": 1 (default) waves are formed from envs of similar solver cost (Hum4SortKernel)
     sort_ = quad_ && cfg.Get("hum_sort", 1) != 0;
-    EPA_HIP(hipMalloc(&dev_.cost, sizeof(int) * (size_t)cfg.num_envs));
-    EPA_HIP(hipMemsetAsync(dev_.cost, 0, sizeof(int) * (size_t)cfg.num_envs, stream_));
+    const size_t n = (size_t)cfg.num_envs;
+    dev_.cost = DevAlloc<int>(n);
     if (!quad_) {  // (the quad kernel's per-launch scratch is per compute stream: ScratchFor)
       const size_t blocks = ((size_t)cfg.num_envs + 63) / 64;
-      ws_bytes_ = sizeof(double) * blocks * 64 * (size_t)Total();
-      EPA_HIP(hipMalloc(&dev_.ws, ws_bytes_));
-      EPA_HIP(hipMemsetAsync(dev_.ws, 0, ws_bytes_, stream_));
+      dev_.ws = DevAlloc<double>(blocks * 64 * (size_t)Total());
     }
-    const size_t sb = sizeof(double) * (size_t)T::MakeLayout(kHumanoidModelConst).npersist * cfg.num_envs;
-    EPA_HIP(hipMalloc(&dev_.state, sb));
-    EPA_HIP(hipMemsetAsync(dev_.state, 0, sb, stream_));
+    // what persists per env, one block of rows: qpos[nq] qvel[nv] warm[nv] lag[2] (the lagged mass centre)
+    constexpr int nq = kHumanoidModelConst.nq, nv = kHumanoidModelConst.nv;
+    static_assert(T::MakeLayout(kHumanoidModelConst).npersist == nq + 2 * nv + 2 &&
+                  T::MakeLayout(kHumanoidStandupModelConst).npersist == nq + 2 * nv + 2);
+    dev_.state = DevAlloc<double>((nq + 2 * nv + 2) * n);
+    double* const s = dev_.state;
+    view_ = {s, s + nq * n, s + (nq + nv) * n, nq, nv};
+    view_.lag = s + (nq + 2 * nv) * n;
+    view_.lag_rows = 2;
     mt_tile_default_ = 16;  // unhealthy terminations: every env resets at its own time
     InitCommon();
   }
   ~HumanoidPool() override {
-    if (!quad_) (void)hipFree(dev_.ws);
-    for (auto& kv : scratch_) {
-      (void)hipFree(kv.second.ws);
-      (void)hipFree(kv.second.perm);
-    }
-    (void)hipFree(big_.ws);
-    (void)hipFree(big_.perm);
     if (big_ev_) (void)hipEventDestroy(big_ev_);
-    (void)hipFree(dev_.state);
-    (void)hipFree(dev_.cost);
   }
   // The quad kernel keeps what persists per ENV (dev_.state, dev_.cost); its workspace and the cost-sort
   // permutation belong to a LAUNCH, so with one copy per compute stream batches of an async pool run
   // concurrently like every other family's (round 4; they used to share one copy and one stream).
   bool ConcurrentSafe() const override { return quad_; }
-  int StateDim() const override { return kHumanoidModelConst.nq + 2 * kHumanoidModelConst.nv + 7; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    (standup_ ? HumLaunchGetStandup : HumLaunchGetHumanoid)(stream_, k, dev_, common_, d_ids, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    (standup_ ? HumLaunchSetStandup : HumLaunchSetHumanoid)(stream_, k, dev_, common_, d_ids, d_in);
-  }
 
  protected:
   void Launch(const int* d_ids, int k, const void* d_action, bool force_reset,
@@ -420,10 +359,8 @@ class HumanoidPool : public Pool {
   };
   void AllocScratch(Scratch& sc, int rows, hipStream_t st) {
     sc.rows = rows;
-    const size_t bytes = Hum4WorkspaceBytes(sc.rows);
-    EPA_HIP(hipMalloc(&sc.ws, bytes));
-    EPA_HIP(hipMemsetAsync(sc.ws, 0, bytes, st));
-    EPA_HIP(hipMalloc(&sc.perm, sizeof(int) * (size_t)sc.rows));
+    sc.ws = DevAlloc<double>(Hum4WorkspaceBytes(sc.rows) / sizeof(double), st);
+    sc.perm = DevAlloc<int>((size_t)sc.rows, st);
   }
   const Scratch& ScratchFor(hipStream_t st, int k) {
     const bool async = cfg_.batch_size > 0 && cfg_.batch_size < cfg_.num_envs;
@@ -444,7 +381,6 @@ class HumanoidPool : public Pool {
   }
   HumDev dev_{};
   HumTask task_{};
-  size_t ws_bytes_{0};
   bool standup_;
   bool quad_{true}, sort_{true};
   std::map<hipStream_t, Scratch> scratch_;

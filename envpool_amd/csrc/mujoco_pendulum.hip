@@ -154,44 +154,6 @@ __global__ __launch_bounds__(kPendBlock) void PendStepKernel(
   WriteCommon(out, row, e + a.id_offset, cur, done, reward, a.max_episode_steps);
 }
 
-// flat state, same layout as oracle/mjcpu: qpos[nv] qvel[nv] warm[nv] time xlag
-// ylag done cur_step normal_saved normal_avail
-template <int NV>
-__global__ void PendGetState(PendDev dev, CommonDev cm, const int* ids, int k, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  double* o = out + (size_t)i * (3 * NV + 7);
-  for (int j = 0; j < NV; ++j) {
-    o[j] = dev.qpos[(size_t)j * n + e];
-    o[NV + j] = dev.qvel[(size_t)j * n + e];
-    o[2 * NV + j] = dev.warm[(size_t)j * n + e];
-  }
-  double* t = o + 3 * NV;
-  t[0] = t[1] = t[2] = 0;
-  t[3] = cm.done[e];
-  t[4] = cm.cur_step[e];
-  t[5] = dev.nsaved[e];
-  t[6] = dev.navail[e];
-}
-template <int NV>
-__global__ void PendSetState(PendDev dev, CommonDev cm, const int* ids, int k, const double* in) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  const double* o = in + (size_t)i * (3 * NV + 7);
-  for (int j = 0; j < NV; ++j) {
-    dev.qpos[(size_t)j * n + e] = o[j];
-    dev.qvel[(size_t)j * n + e] = o[NV + j];
-    dev.warm[(size_t)j * n + e] = o[2 * NV + j];
-  }
-  const double* t = o + 3 * NV;
-  cm.done[e] = t[3] != 0.0;
-  cm.cur_step[e] = (int)t[4];
-  dev.nsaved[e] = t[5];
-  dev.navail[e] = t[6] != 0.0;
-}
-
 // ---- Reacher ------------------------------------------------------------------
 // qpos = [joint0, joint1, target_x, target_y]; the target never moves (see
 // BuildReacher), so the dynamics only see the two arm hinges.  The reference reads
@@ -308,41 +270,6 @@ __global__ __launch_bounds__(kPendBlock) void ReacherStepKernel(
   WriteCommon(out, row, e + a.id_offset, cur, done, reward, a.max_episode_steps);
 }
 
-// flat state like oracle/mjcpu: qpos[4] qvel[4] warm[4] time xlag ylag done cur_step 0 0
-__global__ void ReacherGetState(ReacherDev dev, CommonDev cm, const int* ids, int k, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  double* o = out + (size_t)i * 19;
-  for (int j = 0; j < 4; ++j) {
-    o[j] = dev.qpos[(size_t)j * n + e];
-    o[4 + j] = dev.qvel[(size_t)j * n + e];
-    o[8 + j] = dev.warm[(size_t)j * n + e];
-  }
-  o[12] = 0;
-  o[13] = dev.lag[e];
-  o[14] = dev.lag[(size_t)n + e];
-  o[15] = cm.done[e];
-  o[16] = cm.cur_step[e];
-  o[17] = o[18] = 0;
-}
-__global__ void ReacherSetState(ReacherDev dev, CommonDev cm, const int* ids, int k,
-                                const double* in) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  const double* o = in + (size_t)i * 19;
-  for (int j = 0; j < 4; ++j) {
-    dev.qpos[(size_t)j * n + e] = o[j];
-    dev.qvel[(size_t)j * n + e] = o[4 + j];
-    dev.warm[(size_t)j * n + e] = o[8 + j];
-  }
-  dev.lag[e] = o[13];
-  dev.lag[(size_t)n + e] = o[14];
-  cm.done[e] = o[15] != 0.0;
-  cm.cur_step[e] = (int)o[16];
-}
-
 FamilySpec ReacherSpec(const Config& cfg) {  // reacher.h:44-60
   int nobs = cfg.Get("obs_include_z_distance", 1) != 0 ? 11 : 10;
   return {{{"obs", EPA_F64, StackedObsShape(cfg, nobs)},
@@ -351,13 +278,12 @@ FamilySpec ReacherSpec(const Config& cfg) {  // reacher.h:44-60
           {"action", EPA_F64, {2}}};
 }
 
-class ReacherPool : public Pool {
+class ReacherPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit ReacherPool(const Config& cfg)
-      : Pool(cfg, ReacherSpec(cfg), /*needs_rng=*/true) {
+      : MjPool(cfg, ReacherSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
-    model_ = P::BuildReacher();
     // defaults: reacher.h:32-43
     task_.frame_skip = (int)cfg.Get("frame_skip", 2);
     task_.reward_after_step = cfg.Get("reward_after_step", 0) != 0;
@@ -374,28 +300,12 @@ class ReacherPool : public Pool {
                                   "range -0.27 0.27, are not modelled)");
     }
     size_t n = cfg.num_envs;
-    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) {
-      EPA_HIP(hipMalloc(p, sizeof(double) * 4 * n));
-      EPA_HIP(hipMemsetAsync(*p, 0, sizeof(double) * 4 * n, stream_));
-    }
-    EPA_HIP(hipMalloc(&dev_.lag, sizeof(double) * 2 * n));
-    EPA_HIP(hipMemsetAsync(dev_.lag, 0, sizeof(double) * 2 * n, stream_));
+    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) *p = DevAlloc<double>(4 * n);
+    dev_.lag = DevAlloc<double>(2 * n);
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, 4, 4};
+    view_.lag = dev_.lag;
+    view_.lag_rows = 2;
     InitCommon();
-  }
-  ~ReacherPool() override {
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.lag);
-  }
-  int StateDim() const override { return 19; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(ReacherGetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(ReacherSetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_in);
   }
 
  protected:
@@ -410,7 +320,6 @@ class ReacherPool : public Pool {
 
  private:
   ReacherDev dev_{};
-  P::PendModel<double, 2, P::kBaseFixed> model_{};
   ReacherTask task_{};
 };
 
@@ -522,18 +431,13 @@ FamilySpec PendSpec(const Config& cfg, int nl) {
 }
 
 template <int NL>
-class PendPool : public Pool {
+class PendPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   static constexpr int NV = NL + 1;
   explicit PendPool(const Config& cfg)
-      : Pool(cfg, PendSpec(cfg, NL), /*needs_rng=*/true) {
+      : MjPool(cfg, PendSpec(cfg, NL), /*needs_rng=*/true) {
     EnableObsStack();
-    if constexpr (NL == 1) {
-      model1_ = P::BuildInvertedPendulum();
-    } else {
-      model2_ = P::BuildInvertedDoublePendulum();
-    }
     // defaults: inverted_pendulum.h:32-41 / inverted_double_pendulum.h:32-44
     task_.frame_skip = (int)cfg.Get("frame_skip", NL == 1 ? 2 : 5);
     task_.reward_if_not_terminated = cfg.Get("reward_if_not_terminated", 0) != 0;
@@ -545,34 +449,14 @@ class PendPool : public Pool {
     task_.observation_min = cfg.Get("observation_min", -10.0);
     task_.observation_max = cfg.Get("observation_max", 10.0);
     size_t n = cfg.num_envs;
-    EPA_HIP(hipMalloc(&dev_.qpos, sizeof(double) * NV * n));
-    EPA_HIP(hipMalloc(&dev_.qvel, sizeof(double) * NV * n));
-    EPA_HIP(hipMalloc(&dev_.warm, sizeof(double) * NV * n));
-    EPA_HIP(hipMalloc(&dev_.nsaved, sizeof(double) * n));
-    EPA_HIP(hipMalloc(&dev_.navail, n));
-    EPA_HIP(hipMemsetAsync(dev_.qpos, 0, sizeof(double) * NV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.qvel, 0, sizeof(double) * NV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.warm, 0, sizeof(double) * NV * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.nsaved, 0, sizeof(double) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.navail, 0, n, stream_));
+    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) *p = DevAlloc<double>(NV * n);
+    dev_.nsaved = DevAlloc<double>(n);
+    dev_.navail = DevAlloc<unsigned char>(n);
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, NV, NV};
+    view_.nsaved = dev_.nsaved;
+    view_.navail = dev_.navail;
     mt_tile_default_ = 16;  // the inverted pendulums fall over at their own times
     InitCommon();
-  }
-  ~PendPool() override {
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.nsaved);
-    (void)hipFree(dev_.navail);
-  }
-  int StateDim() const override { return 3 * NV + 7; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(PendGetState<NV>, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(PendSetState<NV>, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_in);
   }
 
  protected:
@@ -592,52 +476,31 @@ class PendPool : public Pool {
 
  private:
   PendDev dev_{};
-  P::PendModel<double, 1, P::kBaseCart> model1_{};
-  P::PendModel<double, 2, P::kBaseCart> model2_{};
   PendTask task_{};
 };
 
-class SwimmerPool : public Pool {
+class SwimmerPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   static constexpr int NV = 5;
   explicit SwimmerPool(const Config& cfg)
-      : Pool(cfg, SwimmerSpec(cfg), /*needs_rng=*/true) {
+      : MjPool(cfg, SwimmerSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
-    model_ = P::BuildSwimmer();
     // defaults: swimmer.h:32-42
     task_.frame_skip = (int)cfg.Get("frame_skip", 4);
     task_.obs_skip = cfg.Get("exclude_current_positions_from_observation", 1) != 0 ? 2 : 0;
     task_.ctrl_cost_weight = cfg.Get("ctrl_cost_weight", 1e-4);
     task_.forward_reward_weight = cfg.Get("forward_reward_weight", 1.0);
     task_.reset_noise_scale = cfg.Get("reset_noise_scale", 0.1);
-    task_.dt = task_.frame_skip * model_.timestep;
+    task_.dt = task_.frame_skip * kSwimmerModelConst.timestep;
     size_t n = cfg.num_envs;
-    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) {
-      EPA_HIP(hipMalloc(p, sizeof(double) * NV * n));
-      EPA_HIP(hipMemsetAsync(*p, 0, sizeof(double) * NV * n, stream_));
-    }
-    EPA_HIP(hipMalloc(&dev_.nsaved, sizeof(double) * n));  // unused (uniform noise only);
-    EPA_HIP(hipMalloc(&dev_.navail, n));                   // kept for the shared state layout
-    EPA_HIP(hipMemsetAsync(dev_.nsaved, 0, sizeof(double) * n, stream_));
-    EPA_HIP(hipMemsetAsync(dev_.navail, 0, n, stream_));
+    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) *p = DevAlloc<double>(NV * n);
+    dev_.nsaved = DevAlloc<double>(n);          // unused (uniform noise only);
+    dev_.navail = DevAlloc<unsigned char>(n);  // kept for the shared state layout
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, NV, NV};
+    view_.nsaved = dev_.nsaved;
+    view_.navail = dev_.navail;
     InitCommon();
-  }
-  ~SwimmerPool() override {
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.nsaved);
-    (void)hipFree(dev_.navail);
-  }
-  int StateDim() const override { return 3 * NV + 7; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(PendGetState<NV>, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(PendSetState<NV>, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_in);
   }
 
  protected:
@@ -652,7 +515,6 @@ class SwimmerPool : public Pool {
 
  private:
   PendDev dev_{};
-  P::PendModel<double, 3, P::kBaseFree> model_{};
   SwimmerTask task_{};
 };
 

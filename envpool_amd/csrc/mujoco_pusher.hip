@@ -39,7 +39,6 @@ struct PusherTask {
 };
 
 constexpr int kPusherBlock = 64;
-constexpr int kPusherStateDim = 3 * PU::kNQ + 7 + 5;
 
 // The model is a compile-time constant (immediates / folded arithmetic): as a kernel argument
 // its 170 doubles live in -- and spill out of -- SGPRs, and ROCm 7.2 builds of this kernel with
@@ -160,43 +159,6 @@ __global__ __launch_bounds__(kPusherBlock) void PusherStepKernel(
   WriteCommon(out, row, e + a.id_offset, cur, done, reward, a.max_episode_steps);
 }
 
-// flat state like oracle/mjcpu: qpos[11] qvel[11] warm[11] time xlag ylag done cur_step 0 0
-// + xpos of tips_arm (3) and object (x, y) of the last forward evaluation
-__global__ void PusherGetState(PusherDev dev, CommonDev cm, const int* ids, int k, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  double* o = out + (size_t)i * kPusherStateDim;
-  for (int j = 0; j < PU::kNQ; ++j) {
-    o[j] = dev.qpos[(size_t)j * n + e];
-    o[PU::kNQ + j] = dev.qvel[(size_t)j * n + e];
-    o[2 * PU::kNQ + j] = dev.warm[(size_t)j * n + e];
-  }
-  double* t = o + 3 * PU::kNQ;
-  t[0] = 0;
-  t[1] = dev.lag[e];
-  t[2] = dev.lag[(size_t)n + e];
-  t[3] = cm.done[e];
-  t[4] = cm.cur_step[e];
-  t[5] = t[6] = 0;
-  for (int j = 0; j < 5; ++j) t[7 + j] = dev.lag[(size_t)j * n + e];
-}
-__global__ void PusherSetState(PusherDev dev, CommonDev cm, const int* ids, int k, const double* in) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  int e = ids[i], n = cm.n;
-  const double* o = in + (size_t)i * kPusherStateDim;
-  for (int j = 0; j < PU::kNQ; ++j) {
-    dev.qpos[(size_t)j * n + e] = o[j];
-    dev.qvel[(size_t)j * n + e] = o[PU::kNQ + j];
-    dev.warm[(size_t)j * n + e] = o[2 * PU::kNQ + j];
-  }
-  const double* t = o + 3 * PU::kNQ;
-  cm.done[e] = t[3] != 0.0;
-  cm.cur_step[e] = (int)t[4];
-  for (int j = 0; j < 5; ++j) dev.lag[(size_t)j * n + e] = t[7 + j];
-}
-
 FamilySpec PusherSpec(const Config& cfg) {  // pusher.h:47-60
   return {{{"obs", EPA_F64, StackedObsShape(cfg, 23)},
            {"info:reward_dist", EPA_F64, {}},
@@ -205,11 +167,11 @@ FamilySpec PusherSpec(const Config& cfg) {  // pusher.h:47-60
           {"action", EPA_F64, {PU::kNL}}};
 }
 
-class PusherPool : public Pool {
+class PusherPool : public MjPool {
  public:
   bool ConcurrentSafe() const override { return true; }  // per-env state + the launch's own block only
   explicit PusherPool(const Config& cfg)
-      : Pool(cfg, PusherSpec(cfg), /*needs_rng=*/true) {
+      : MjPool(cfg, PusherSpec(cfg), /*needs_rng=*/true) {
     EnableObsStack();
     v5_ = cfg.Get("xml_v5", 0) != 0;
     // defaults: pusher.h:33-46
@@ -226,34 +188,14 @@ class PusherPool : public Pool {
     task_.cyl_y_max = cfg.Get("cylinder_y_max", 0.2);
     task_.cyl_dist_min = cfg.Get("cylinder_dist_min", 0.17);
     spread_ = cfg.Get("planar_spread", 1) != 0;
-    {
-      hipDeviceProp_t prop;
-      EPA_HIP(hipGetDeviceProperties(&prop, cfg.device));
-      wave_slots_ = prop.multiProcessorCount * 4 < 1 ? 1 : prop.multiProcessorCount * 4;
-    }
+    wave_slots_ = WaveSlots();
     size_t n = cfg.num_envs;
-    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) {
-      EPA_HIP(hipMalloc(p, sizeof(double) * PU::kNQ * n));
-      EPA_HIP(hipMemsetAsync(*p, 0, sizeof(double) * PU::kNQ * n, stream_));
-    }
-    EPA_HIP(hipMalloc(&dev_.lag, sizeof(double) * 5 * n));
-    EPA_HIP(hipMemsetAsync(dev_.lag, 0, sizeof(double) * 5 * n, stream_));
+    for (double** p : {&dev_.qpos, &dev_.qvel, &dev_.warm}) *p = DevAlloc<double>(PU::kNQ * n);
+    dev_.lag = DevAlloc<double>(5 * n);
+    view_ = {dev_.qpos, dev_.qvel, dev_.warm, PU::kNQ, PU::kNQ};
+    view_.lag = dev_.lag;
+    view_.lag_rows = 5;
     InitCommon();
-  }
-  ~PusherPool() override {
-    (void)hipFree(dev_.qpos);
-    (void)hipFree(dev_.qvel);
-    (void)hipFree(dev_.warm);
-    (void)hipFree(dev_.lag);
-  }
-  int StateDim() const override { return kPusherStateDim; }
-  void GetState(const int* d_ids, int k, double* d_out) override {
-    hipLaunchKernelGGL(PusherGetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_out);
-  }
-  void SetState(const int* d_ids, int k, const double* d_in) override {
-    hipLaunchKernelGGL(PusherSetState, dim3((k + 255) / 256), dim3(256), 0, stream_, dev_,
-                       common_, d_ids, k, d_in);
   }
 
  protected:

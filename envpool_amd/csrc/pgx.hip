@@ -183,14 +183,10 @@ class PgxPool : public Pool {
   explicit PgxPool(const Config& cfg)
       : Pool(cfg, Spec<G>(), /*needs_rng=*/true) {
     const size_t n = (size_t)cfg.num_envs;
-    EPA_HIP(hipMalloc(&state_, sizeof(pgx::State) * n));
-    EPA_HIP(hipMemsetAsync(state_, 0, sizeof(pgx::State) * n, stream_));
+    state_ = DevAlloc<pgx::State>(n);
     EnableErrorWord();
     mt_tile_default_ = 16;  // envs reset at their own times
     InitCommon();
-  }
-  ~PgxPool() override {
-    if (state_) (void)hipFree(state_);
   }
   int StateDim() const override { return 2 + pgx::HiddenWords<G>(); }
   void GetState(const int* d_ids, int k, double* d_out) override {

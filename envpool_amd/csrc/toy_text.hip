@@ -441,19 +441,11 @@ class ToyPool : public Pool {
       // (frozen_lake.h:64-69); only the two registered sizes are supported.
       throw std::invalid_argument("FrozenLake: size must be 4 or 8");
     }
-    EPA_HIP(hipMalloc(&dev_.w0, sizeof(int) * cfg.num_envs));
-    EPA_HIP(hipMemsetAsync(dev_.w0, 0, sizeof(int) * cfg.num_envs, stream_));
-    if (KIND == kBlackjack) {
-      EPA_HIP(hipMalloc(&dev_.w1, sizeof(int) * cfg.num_envs));
-      EPA_HIP(hipMemsetAsync(dev_.w1, 0, sizeof(int) * cfg.num_envs, stream_));
-    }
+    dev_.w0 = DevAlloc<int>(cfg.num_envs);
+    if (KIND == kBlackjack) dev_.w1 = DevAlloc<int>(cfg.num_envs);
     // envs that draw at their own times (a reset row draws, or skips the step's draw): tiled generator words
     if (KIND == kFrozenLake || KIND == kTaxi || KIND == kBlackjack) mt_tile_default_ = 16;
     InitCommon();
-  }
-  ~ToyPool() override {
-    if (dev_.w0) (void)hipFree(dev_.w0);
-    if (dev_.w1) (void)hipFree(dev_.w1);
   }
   int StateDim() const override { return 4; }
   void GetState(const int* d_ids, int k, double* d_out) override {

@@ -66,6 +66,21 @@ def test_step_kernels_do_not_spill_sgprs_heavily():
     assert not bad, bad
 
 
+# ---- Pool owns device memory (engine.h: DevAlloc / DevUpload, freed by ~Pool alone) ----
+def test_family_sources_do_not_manage_device_memory():
+    csrc = os.path.join(ROOT, "envpool_amd", "csrc")
+    # engine.hip is the owner; atari_post.hip's plugin object is no Pool, atari_env.hip's executor is its own
+    families = sorted(f for f in os.listdir(csrc)
+                      if f.endswith(".hip") and f not in ("engine.hip", "atari_post.hip", "atari_env.hip"))
+    assert len(families) >= 12, families
+    bad = []
+    for f in families:
+        for n, line in enumerate(open(os.path.join(csrc, f)).read().splitlines(), 1):
+            if "hipMalloc(" in line or "hipFree(" in line:
+                bad.append(f"{f}:{n}: {line.strip()}")
+    assert bad == [], bad
+
+
 # ---- the product never reaches the checker (oracle/ is test infrastructure) ----
 def test_product_python_never_touches_oracle():
     pkg = os.path.join(ROOT, "envpool_amd")
