@@ -25,6 +25,7 @@ from typing import Any, Callable, Sequence
 
 import numpy as np
 
+from .. import sharding
 from . import native
 from .device_pool import DevicePool
 
@@ -247,6 +248,38 @@ class _ShardedPools:
         self._each(paint, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
         return out
 
+    def snapshot(self, env_ids: Any = None, rng: bool = True) -> list[np.ndarray]:
+        """One blob per shard, all shards at once; only of the whole pool."""
+        if env_ids is not None:
+            raise ValueError("snapshot of a sharded pool takes no env_ids: it is one blob per shard")
+        blobs: list[Any] = [None] * len(self.pools)
+
+        def take(s: int, p: DevicePool, _: Any) -> None:
+            blobs[s] = p.snapshot(None, rng)
+
+        self._each(take, [slice(0, self.per)] * len(self.pools))
+        return blobs
+
+    def restore(self, blobs: Any, env_ids: Any = None) -> None:
+        """The list `snapshot` returned (of this pool or of one sharded the same way), shard by shard."""
+        if env_ids is not None:
+            raise ValueError("restore of a sharded pool takes no env_ids: it is one blob per shard")
+        if not isinstance(blobs, (list, tuple)) or len(blobs) != len(self.pools):
+            raise ValueError(f"restore of a sharded pool takes a list of {len(self.pools)} blobs, one per shard")
+        for b in blobs:
+            if native.snapshot_header(np.ascontiguousarray(b))[0] != self.per:
+                raise ValueError(f"restore of a sharded pool: every blob must hold the {self.per} envs of its shard")
+        self._each(lambda s, p, _: p.restore(blobs[s], None), [slice(0, self.per)] * len(self.pools))
+
+    def fork(self, src: Any, dst: Any, rng: bool = True) -> None:
+        """Within shards only: a pair whose envs live on different devices is refused."""
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+        if len(src) != len(dst):
+            raise ValueError(f"fork: {len(src)} source ids for {len(dst)} targets")
+        parts = sharding.fork_parts(src, dst, self.offset, self.per, len(self.pools))
+        self._each(lambda s, p, idx: p.fork(src[idx], dst[idx], rng), parts)
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -374,6 +407,15 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
             if render is None:  # a pool with its own executor
                 raise RuntimeError("render not implemented for this environment")
             return render(env_ids, width, height, camera_id)
+
+        def _snapshot(self, env_ids: Any, rng: bool) -> Any:
+            return self._pool.snapshot(env_ids, rng)
+
+        def _restore(self, blob: Any, env_ids: Any) -> None:
+            self._pool.restore(blob, env_ids)
+
+        def _fork(self, src: Any, dst: Any, rng: bool) -> None:
+            self._pool.fork(src, dst, rng)
 
         def _xla(self) -> Any:
             raise RuntimeError("XLA is not available for the MI355X engine")

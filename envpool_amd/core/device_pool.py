@@ -359,6 +359,68 @@ class DevicePool:
         native.check(self._lib.epa_render_device(self._h, ids.ctypes.data, len(ids), int(width), int(height),
                                                  int(camera_id), ctypes.c_void_p(d_out)))
 
+    # -- snapshot / restore / fork -----------------------------------------------
+    def snapshot_bytes(self, k: int, rng: bool = True) -> int:
+        """Bytes of a snapshot blob of `k` envs, with (`rng`) or without the generator section."""
+        n = ctypes.c_size_t(0)
+        native.check(self._lib.epa_snapshot_bytes(self._h, int(k), native.EPA_SNAP_RNG if rng else 0,
+                                                  ctypes.byref(n)))
+        return int(n.value)
+
+    def snapshot(self, env_ids: Any = None, rng: bool = True) -> np.ndarray:
+        """Everything that makes the listed envs (global ids; None: the whole pool) continue bit for bit, as an
+        opaque uint8 blob: the flat state, with `rng` the generators, and the observation ring of frame_stack > 1.
+        Shows each env after every send issued so far, received or not."""
+        ids = self._ids(env_ids).reshape(-1)
+        flags = native.EPA_SNAP_RNG if rng else 0
+        n = ctypes.c_size_t(0)
+        native.check(self._lib.epa_snapshot_bytes(self._h, len(ids), flags, ctypes.byref(n)))
+        out = np.empty(int(n.value), dtype=np.uint8)
+        native.check(self._lib.epa_snapshot(self._h, ids.ctypes.data, len(ids), flags, out.ctypes.data, out.nbytes))
+        return out
+
+    def _restore_ids(self, env_ids: Any, k: int) -> np.ndarray:
+        if env_ids is None:  # ids 0 .. k-1 of this pool, k from the header
+            return np.arange(self.env_id_offset, self.env_id_offset + k, dtype=np.int32)
+        return np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+
+    def restore(self, blob: np.ndarray, env_ids: Any = None) -> None:
+        """Put a snapshot's envs into the listed envs of this pool (None: envs 0 .. k-1, k from the blob).  The blob
+        may come from any pool of the same family and frame_stack.  Takes effect before every later send."""
+        blob = np.ascontiguousarray(blob)
+        k, _ = native.snapshot_header(blob)
+        ids = self._restore_ids(env_ids, k)
+        native.check(self._lib.epa_restore(self._h, ids.ctypes.data, len(ids), blob.ctypes.data, blob.nbytes))
+
+    def snapshot_device(self, d_blob: int, env_ids: Any = None, rng: bool = True) -> bytes:
+        """`snapshot` into device memory at the raw address `d_blob` (16-byte aligned, `snapshot_bytes` long): only
+        enqueued on the pool's stream.  Returns the blob's 64-byte header, which `restore_device` wants back."""
+        ids = self._ids(env_ids).reshape(-1)
+        header = ctypes.create_string_buffer(native.SNAP_HEADER_BYTES)
+        native.check(self._lib.epa_snapshot_device(self._h, ids.ctypes.data, len(ids),
+                                                   native.EPA_SNAP_RNG if rng else 0, ctypes.c_void_p(d_blob), header))
+        return header.raw
+
+    def restore_device(self, d_blob: int, header: bytes, env_ids: Any = None) -> None:
+        """`restore` from device memory at the raw address `d_blob`; `header`: the blob's first 64 bytes on the host
+        (the engine checks them without reading device memory)."""
+        head = np.frombuffer(bytes(header), dtype=np.uint8)
+        if head.nbytes < native.SNAP_HEADER_BYTES:
+            raise ValueError(f"snapshot header of {head.nbytes} bytes is shorter than a header")
+        ids = self._restore_ids(env_ids, int(head[20:24].view("<i4")[0]))
+        native.check(self._lib.epa_restore_device(self._h, ids.ctypes.data, len(ids), ctypes.c_void_p(d_blob),
+                                                  head.ctypes.data))
+
+    def fork(self, src: Any, dst: Any, rng: bool = True) -> None:
+        """Env dst[i] becomes env src[i], on the device (global ids): `src` may repeat and overlap `dst`, `dst` must
+        not repeat.  With `rng` the copies draw the same numbers from then on."""
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+        if len(src) != len(dst):
+            raise ValueError(f"fork: {len(src)} source ids for {len(dst)} targets")
+        native.check(self._lib.epa_fork(self._h, src.ctypes.data, dst.ctypes.data, len(src),
+                                        native.EPA_SNAP_RNG if rng else 0))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

@@ -22,6 +22,8 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("ENVPOOL_AMD_LIB") or os.path.join(_PKG, "lib", "libenvpool_amd.so")
 
 EPA_OK, EPA_ERR_INVALID, EPA_ERR_RUNTIME, EPA_ERR_DEVICE = 0, 1, 2, 3
+EPA_SNAP_RNG = 1
+SNAP_HEADER_BYTES = 64
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
 
@@ -108,6 +110,12 @@ def lib() -> ctypes.CDLL:
         "epa_render_size": (i32, [vp, i32, i32, P(i32), P(i32)]),
         "epa_render": (i32, [vp, vp, i32, i32, i32, i32, vp]),
         "epa_render_device": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+        "epa_snapshot_bytes": (i32, [vp, i32, ctypes.c_uint32, P(ctypes.c_size_t)]),
+        "epa_snapshot": (i32, [vp, vp, i32, ctypes.c_uint32, vp, ctypes.c_size_t]),
+        "epa_restore": (i32, [vp, vp, i32, vp, ctypes.c_size_t]),
+        "epa_snapshot_device": (i32, [vp, vp, i32, ctypes.c_uint32, vp, vp]),
+        "epa_restore_device": (i32, [vp, vp, i32, vp, vp]),
+        "epa_fork": (i32, [vp, vp, vp, i32, ctypes.c_uint32]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -140,6 +148,7 @@ EXPORTED_SYMBOLS = [
     "epa_send_device", "epa_recv_device", "epa_step_device", "epa_wait_stream", "epa_consumer_wait",
     "epa_stream", "epa_synchronize", "epa_set_timing", "epa_kernel_time_ms",
     "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
+    "epa_snapshot_bytes", "epa_snapshot", "epa_restore", "epa_snapshot_device", "epa_restore_device", "epa_fork",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -158,6 +167,21 @@ def check(code: int) -> None:
     if code == EPA_ERR_INVALID:
         raise ValueError(msg)
     raise RuntimeError(msg)
+
+
+def snapshot_header(blob: np.ndarray) -> tuple[int, int]:
+    """(env count, byte count) a snapshot blob's header states.  ValueError for a blob shorter than a header, or
+    shorter than its header says: checked here, before any native call sees the blob."""
+    blob = np.asarray(blob)
+    if blob.dtype != np.uint8 or blob.ndim != 1:
+        raise ValueError("snapshot blob must be a one-dimensional uint8 array")
+    if blob.nbytes < SNAP_HEADER_BYTES:
+        raise ValueError(f"snapshot blob of {blob.nbytes} bytes is shorter than a header")
+    k = int(blob[20:24].view("<i4")[0])
+    total = int(blob[48:56].view("<u8")[0])
+    if blob.nbytes < total:
+        raise ValueError(f"snapshot blob of {blob.nbytes} bytes is shorter than its header says ({total})")
+    return k, total
 
 
 def device_count() -> int:

@@ -33,6 +33,10 @@
 
 namespace epa {
 
+namespace snap {
+struct PoolDesc;  // snapshot.hip.h
+}
+
 struct DeviceError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
@@ -249,7 +253,30 @@ class Pool {
   void RenderHost(const int32_t* ids, int k, int width, int height, int camera_id, uint8_t* out);
   void RenderDevice(const int32_t* ids, int k, int width, int height, int camera_id, void* d_out);
 
+  // Snapshots (snapshot.hip.h: blob layout and kernels): everything that makes the listed envs continue bit for bit --
+  // the flat state, with EPA_SNAP_RNG the generator words and their position, the observation ring of frame_stack > 1
+  // and the family's extra section -- as one opaque blob, written and read on stream_.  A snapshot shows each env after
+  // every send issued before the call, received or not; a restore takes effect before every send issued after it and
+  // leaves rows already in the result queue alone.  Ids are global, from the host; restore and fork targets must not
+  // repeat.  A family without a flat state (StateDim() == 0) throws
+  // std::runtime_error("snapshot not implemented for this environment") from all of them.
+  // The *Device forms only enqueue (the blob is device memory, 16-byte aligned); *Host go through a scratch block the
+  // pool owns: one copy across and one stream synchronisation.  Fork: env dst[i] becomes env src[i] (src may repeat and
+  // overlap dst: it is a snapshot into the scratch block followed by a restore).
+  void SetFamily(const std::string& name);  // what the blob's family hash is taken from (epa_create)
+  size_t SnapshotBytes(int k, unsigned flags) const;
+  // host_header (optional): receives the blob's 64-byte header, which RestoreDevice wants back from the host
+  void SnapshotDevice(const int32_t* ids, int k, unsigned flags, void* d_blob, void* host_header = nullptr);
+  void RestoreDevice(const int32_t* ids, int k, const void* d_blob, const void* host_header);
+  void SnapshotHost(const int32_t* ids, int k, unsigned flags, void* out, size_t out_bytes);
+  void RestoreHost(const int32_t* ids, int k, const void* blob, size_t blob_bytes);
+  void Fork(const int32_t* src, const int32_t* dst, int k, unsigned flags);
+
  protected:
+  // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
+  // kernel that packs (unpack: restores) it for the listed local envs, row i at d_buf + i * ExtraBytes(), on stream_.
+  virtual size_t ExtraBytes() const { return 0; }
+  virtual void PackExtra(const int* d_ids, int k, void* d_buf, bool unpack);
   // Launch the family's batched step kernel for k rows on stream_.
   // d_ids == nullptr means rows 0..k-1 map to local envs 0..k-1.
   virtual void Launch(const int* d_ids, int k, const void* d_action,
@@ -395,6 +422,29 @@ class Pool {
   int render_ids_cap_{0};
   std::vector<int> render_local_;
   hipEvent_t render_ev_{nullptr};  // behind the last RenderDevice launch
+  // snapshots
+  snap::PoolDesc SnapPoolDesc() const;  // what a header has to fit (snapshot.hip.h)
+  void SnapCheck(const int32_t* ids, int k, bool unique) const;  // "not implemented", ids, duplicates
+  const int* SnapIds(const int32_t* ids, int k);  // the launch's local ids on the device (the caller holds mu_)
+  char* SnapScratch(size_t bytes);                // the pool's scratch blob, at least that big
+  void SnapPack(const int* d_ids, int k, unsigned flags, char* d_blob, void* host_header);
+  void SnapUnpack(const int* d_ids, int k, const char* d_blob, const void* header);
+  void SnapEnter(bool host_waits);  // behind the steps enqueued on the other compute streams
+  void SnapLeave();                 // ... and their next steps behind what was enqueued here
+  uint64_t family_hash_{0};
+  int* snap_iota_{nullptr};  // [num_envs] 0, 1, ...: the id list of a whole-pool call in order
+  struct SnapSlot {          // pinned + device id lists of the other calls, two in rotation
+    int* h{nullptr};
+    int* d{nullptr};
+    int cap{0};
+    hipEvent_t ev{nullptr};  // the upload out of `h` has finished
+    bool used{false};
+  };
+  SnapSlot snap_slot_[2];
+  int snap_next_{0};
+  hipEvent_t snap_ev_{nullptr};  // behind the last *Device / Fork launch (SnapLeave)
+  char* snap_scratch_{nullptr};
+  size_t snap_scratch_bytes_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream
   std::vector<hipEvent_t> join_ev_;      // one per compute stream (JoinCompute)

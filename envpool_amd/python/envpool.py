@@ -144,6 +144,22 @@ class EnvPoolMixin(ABC):
             return None
         return frames
 
+    def snapshot(self, env_ids: Any = None, rng: bool = True) -> Any:
+        """Extension: everything that makes the listed envs (global ids; None: all) continue bit for bit, as an opaque
+        uint8 blob -- with `rng` their generators too, so that resets and random transitions repeat as well.  A pool
+        sharded over several devices returns one blob per shard and takes no `env_ids`."""
+        return self._snapshot(None if env_ids is None else _normalize_env_id(env_ids), bool(rng))
+
+    def restore(self, blob: Any, env_ids: Any = None) -> None:
+        """Extension: put a `snapshot` (of this pool, or of another pool of the same task and frame_stack) into the
+        listed envs; None: envs 0 .. k-1 of this pool, k being the number of envs in the blob."""
+        self._restore(blob, None if env_ids is None else _normalize_env_id(env_ids))
+
+    def fork(self, src: Any, dst: Any, rng: bool = True) -> None:
+        """Extension: env dst[i] becomes env src[i] without leaving the device (tree search: one position into many
+        envs).  `src` may repeat, `dst` must not."""
+        self._fork(_normalize_env_id(src), _normalize_env_id(dst), bool(rng))
+
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:
         converted_action = self._from(action, env_id)

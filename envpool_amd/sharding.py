@@ -37,6 +37,25 @@ def make_shard(family: str, num_envs_total: int, rank: int, world_size: int,
                       env_id_offset=offset, env_seed=env_seed, **kwargs)
 
 
+def fork_parts(src: Any, dst: Any, offset: int, per: int, shards: int) -> list[Any]:
+    """Rows of a fork of a pool sharded as `shards` runs of `per` envs from global id `offset`, by shard.  A fork
+    copies env to env on ONE device: ValueError for an id outside the pool and for a pair that crosses shards."""
+    import numpy as np
+
+    src, dst = np.asarray(src), np.asarray(dst)
+    s_src, s_dst = (src - offset) // per, (dst - offset) // per
+    for ids, sh in ((src, s_src), (dst, s_dst)):
+        bad = ids[(sh < 0) | (sh >= shards)]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+    cross = np.flatnonzero(s_src != s_dst)
+    if len(cross):
+        i = int(cross[0])
+        raise ValueError(f"fork across shards: env {int(src[i])} and env {int(dst[i])} live on different devices "
+                         "(restore(other.snapshot(ids), ids2) on the shards' pools moves envs between devices)")
+    return [np.flatnonzero(s_dst == s) for s in range(shards)]
+
+
 def all_gather_rows(local: Any, num_envs_total: int, group: Any = None) -> Any:
     """All-gather a per-shard `[count, ...]` tensor into `[num_envs_total, ...]`
     ordered by env id.  Works with the RCCL ("nccl") and gloo backends; shards

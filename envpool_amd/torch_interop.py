@@ -123,3 +123,66 @@ def render_device(pool: Any, env_ids: Any, width: int = 0, height: int = 0, came
     ev.record(torch.cuda.ExternalStream(pool.stream, device=dev))
     cur.wait_event(ev)
     return out.view(shape)
+
+
+def _order_both_ways(pool: Any, dev: Any, launch: Any) -> None:
+    """The pool's stream behind torch's CURRENT stream, `launch()`, the current stream behind the pool's stream."""
+    import torch
+
+    cur = torch.cuda.current_stream(dev)
+    pool.wait_stream(cur.cuda_stream)
+    launch()
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.ExternalStream(pool.stream, device=dev))
+    cur.wait_event(ev)
+
+
+def snapshot_device(pool: Any, env_ids: Any = None, rng: bool = True, out: Any = None) -> Any:
+    """`pool.snapshot` without the way down: the blob as a torch.uint8 tensor on the pool's device, written by the
+    snapshot kernels straight into torch's memory (no PCIe transfer, no host synchronisation), ordered against torch's
+    current stream like `render_device`.  `out`: a contiguous, 16-byte aligned uint8 tensor of at least
+    `pool.snapshot_bytes(k, rng)` bytes to write into.  The tensor remembers its header (`restore_device` needs it on
+    the host); a copy of the tensor does not, and costs `restore_device` a 64-byte read from the device."""
+    import torch
+
+    k = pool.num_envs if env_ids is None else len(np.asarray(env_ids).reshape(-1))
+    nbytes = pool.snapshot_bytes(k, rng)
+    dev = torch.device("cuda", pool.device)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != dev \
+            or out.data_ptr() % 16 != 0:
+        raise RuntimeError(f"snapshot_device: out must be a contiguous, 16-byte aligned uint8 tensor of at least "
+                           f"{nbytes} bytes on {dev}")
+    blob = out.view(-1)[:nbytes]
+    header: list = []
+    _order_both_ways(pool, dev, lambda: header.append(pool.snapshot_device(blob.data_ptr(), env_ids, rng)))
+    blob._epa_snapshot_header = header[0]
+    return blob
+
+
+def restore_device(pool: Any, blob: Any, env_ids: Any = None) -> None:
+    """`pool.restore` from a blob that lives on the pool's device (`snapshot_device` of this or another pool of the
+    same family), stream-ordered like `snapshot_device`.  `env_ids=None`: envs 0 .. k-1, k from the blob."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    if blob.dtype != torch.uint8 or not blob.is_contiguous() or blob.device != dev or blob.dim() != 1:
+        raise RuntimeError(f"restore_device: blob must be a contiguous one-dimensional uint8 tensor on {dev}")
+    header = getattr(blob, "_epa_snapshot_header", None)
+    if header is None:
+        if blob.numel() < 64:
+            raise ValueError(f"snapshot blob of {blob.numel()} bytes is shorter than a header")
+        header = blob[:64].cpu().numpy().tobytes()
+    total = int(np.frombuffer(header, dtype="<u8", count=1, offset=48)[0])
+    if blob.numel() < total:
+        raise ValueError(f"snapshot blob of {blob.numel()} bytes is shorter than its header says ({total})")
+    _order_both_ways(pool, dev, lambda: pool.restore_device(blob.data_ptr(), header, env_ids))
+
+
+def fork(pool: Any, src: Any, dst: Any, rng: bool = True) -> None:
+    """`pool.fork` ordered against torch's current stream: behind what torch has enqueued, and in front of what it
+    enqueues next."""
+    import torch
+
+    _order_both_ways(pool, torch.device("cuda", pool.device), lambda: pool.fork(src, dst, rng))

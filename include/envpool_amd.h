@@ -365,6 +365,37 @@ int epa_render(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t width,
 int epa_render_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t width, int32_t height,
                       int32_t camera_id, void* device_out);
 
+/* Snapshot, restore and fork (no reference analogue): everything that makes the listed envs continue bit for bit, as
+ * one opaque blob -- a 64-byte header (magic, version, hash of the family name, state_dim, env count, flags, generator
+ * layout, frame stack, byte count), the flat state of epa_get_state, with EPA_SNAP_RNG the 624 generator words and the
+ * position of every env, and the observation ring of frame_stack > 1.  A pool restored from a snapshot with
+ * EPA_SNAP_RNG returns the same rows as the pool the snapshot was taken from, resets and their draws included; without
+ * the flag a restore leaves the target's generators alone (what epa_set_state does, plus the observation ring).
+ *   env_ids: global ids, k >= 1; a restore's ids and a fork's dst_ids must not repeat (EPA_ERR_INVALID).
+ *   A snapshot shows each env after every send / reset issued before the call, received or not; a restore takes
+ *   effect before every send issued after it and leaves rows already waiting for recv alone.
+ *   A blob may be restored into any pool of the same family with the same state_dim and frame_stack, whatever its
+ *   seed, size or engine keys; EPA_ERR_INVALID when the header does not fit the pool or the ids, or the blob is
+ *   shorter than its header says (the blob's body is read only after that).
+ *   Atari (the console lives in the host plugin) fails with EPA_ERR_RUNTIME "snapshot not implemented for this
+ *   environment" in all six calls.
+ * epa_snapshot / epa_restore move the blob to / from host memory: one copy across and one stream synchronisation.
+ * epa_snapshot_device / epa_restore_device work on device memory of the pool's device (16-byte aligned, at least
+ * epa_snapshot_bytes) and only enqueue on epa_stream(pool), like epa_render_device; host_header (64 bytes of host
+ * memory) receives the header from epa_snapshot_device (NULL: not wanted) and hands it back to epa_restore_device,
+ * which checks it without reading device memory.
+ * epa_fork: env dst_ids[i] becomes env src_ids[i], on the device; src_ids may repeat and may overlap dst_ids. */
+#define EPA_SNAP_RNG 1u
+int epa_snapshot_bytes(epa_pool* pool, int32_t k, uint32_t flags, size_t* bytes);
+int epa_snapshot(epa_pool* pool, const int32_t* env_ids, int32_t k, uint32_t flags, void* host_blob,
+                 size_t blob_bytes);
+int epa_restore(epa_pool* pool, const int32_t* env_ids, int32_t k, const void* host_blob, size_t blob_bytes);
+int epa_snapshot_device(epa_pool* pool, const int32_t* env_ids, int32_t k, uint32_t flags, void* device_blob,
+                        void* host_header);
+int epa_restore_device(epa_pool* pool, const int32_t* env_ids, int32_t k, const void* device_blob,
+                       const void* host_header);
+int epa_fork(epa_pool* pool, const int32_t* src_ids, const int32_t* dst_ids, int32_t k, uint32_t flags);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
