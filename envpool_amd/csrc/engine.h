@@ -257,12 +257,10 @@ class Pool {
   // the flat state, with EPA_SNAP_RNG the generator words and their position, the observation ring of frame_stack > 1
   // and the family's extra section -- as one opaque blob, written and read on stream_.  A snapshot shows each env after
   // every send issued before the call, received or not; a restore takes effect before every send issued after it and
-  // leaves rows already in the result queue alone.  Ids are global, from the host; restore and fork targets must not
-  // repeat.  A family without a flat state (StateDim() == 0) throws
-  // std::runtime_error("snapshot not implemented for this environment") from all of them.
-  // The *Device forms only enqueue (the blob is device memory, 16-byte aligned); *Host go through a scratch block the
-  // pool owns: one copy across and one stream synchronisation.  Fork: env dst[i] becomes env src[i] (src may repeat and
-  // overlap dst: it is a snapshot into the scratch block followed by a restore).
+  // leaves rows already in the result queue alone.  Restore and fork targets must not repeat.  A family without a flat
+  // state (StateDim() == 0) throws std::runtime_error("snapshot not implemented for this environment") from all of
+  // them.  The *Device forms only enqueue (the blob is device memory, 16-byte aligned); *Host copy the blob across
+  // once.  Fork: env dst[i] becomes env src[i] (src may repeat and overlap dst: it is a snapshot followed by a restore).
   void SetFamily(const std::string& name);  // what the blob's family hash is taken from (epa_create)
   size_t SnapshotBytes(int k, unsigned flags) const;
   // host_header (optional): receives the blob's 64-byte header, which RestoreDevice wants back from the host
@@ -387,7 +385,8 @@ class Pool {
   Staging& NextStaging(size_t bytes);
 
  protected:
-  void CheckIds(const int32_t* ids, int k) const;
+  void CheckIds(const int32_t* ids, int k) const;      // 0 <= k <= num_envs, then CheckIdRange
+  void CheckIdRange(const int32_t* ids, int k) const;  // every id inside [env_id_offset, env_id_offset + num_envs)
 
  private:
   // generic observation frame stack (EnableObsStack)
@@ -400,7 +399,9 @@ class Pool {
   std::condition_variable pending_cv_;  // signalled by Enqueue; WantRows waits on it
   int recv_timeout_ms_{-1};
   int pipeline_rows_{-1};            // "step_pipeline": whole-pool host-path steps of at least this many rows (0: never)
-  int* iota_dev_{nullptr};           // [num_envs] global env ids in order (the second half's id list)
+  // [num_envs] GLOBAL env ids in order (SendPipelined: the second half's id list; a step launch takes the ids as the
+  // caller sent them).  Not side_iota_, whose ids are local: with an env_id_offset the two tables differ
+  int* iota_dev_{nullptr};
   int zero_copy_small_{-1};          // "small_zero_copy" (-1: not read yet)
   bool ZeroCopySmall() {
     if (zero_copy_small_ < 0) zero_copy_small_ = cfg_.Get("small_zero_copy", 1) != 0 ? 1 : 0;
@@ -416,35 +417,45 @@ class Pool {
   char* recv_stage_{nullptr};  // pinned D2H landing block
   size_t recv_stage_bytes_{0};
   hipEvent_t order_ev_{nullptr};  // WaitStream's producer marker
-  // render: uploads the launch's env ids and calls the family's Render at the resolved size (the caller holds mu_)
-  void RenderLaunch(const int32_t* ids, int k, int w, int h, int camera_id, void* d_rgb);
-  int* render_ids_{nullptr};      // [render_ids_cap_] local ids of the last render launch
-  int render_ids_cap_{0};
-  std::vector<int> render_local_;
-  hipEvent_t render_ev_{nullptr};  // behind the last RenderDevice launch
-  // snapshots
-  snap::PoolDesc SnapPoolDesc() const;  // what a header has to fit (snapshot.hip.h)
-  void SnapCheck(const int32_t* ids, int k, bool unique) const;  // "not implemented", ids, duplicates
-  const int* SnapIds(const int32_t* ids, int k);  // the launch's local ids on the device (the caller holds mu_)
-  char* SnapScratch(size_t bytes);                // the pool's scratch blob, at least that big
-  void SnapPack(const int* d_ids, int k, unsigned flags, char* d_blob, void* host_header);
-  void SnapUnpack(const int* d_ids, int k, const char* d_blob, const void* header);
-  void SnapEnter(bool host_waits);  // behind the steps enqueued on the other compute streams
-  void SnapLeave();                 // ... and their next steps behind what was enqueued here
-  uint64_t family_hash_{0};
-  int* snap_iota_{nullptr};  // [num_envs] 0, 1, ...: the id list of a whole-pool call in order
-  struct SnapSlot {          // pinned + device id lists of the other calls, two in rotation
+  // Side operations: a call that reads or writes the state of listed envs outside the step path (get_state /
+  // set_state, render, snapshot / restore / fork) is one launch on stream_ between these pieces; the caller holds mu_.
+  // Ids are global, from the host.
+  //   SideEnter    selects the device and puts the call behind the steps enqueued on the other compute streams: the
+  //                host waits for them (host forms, which end in ONE hipStreamSynchronize(stream_)), or stream_ does
+  //                (device forms, which end in SideLeave)
+  //   SideIds      the launch's local ids on the device: the iota table for offset, offset + 1, ... (nothing to
+  //                upload), otherwise a pinned + device slot, two in rotation; k may exceed num_envs (render)
+  //   SideScratch  the pool's one device scratch block, at least that big, grow-only
+  //   SideLeave    device forms: the other compute streams' next steps wait for what was enqueued here
+  // The scratch block is shared by all of them although stream_ rotates between calls.  That is correct only because
+  // every user enters through SideEnter -- so the previous user's work, on whichever stream, is ordered before this
+  // one's -- and either synchronises stream_ or leaves through SideLeave before it releases mu_.
+  void SideEnter(bool host_waits);
+  const int* SideIds(const int32_t* ids, int k);
+  char* SideScratch(size_t bytes);
+  void SideLeave();
+  int* side_iota_{nullptr};  // [num_envs] LOCAL ids 0, 1, ... (iota_dev_ holds global ones)
+  struct IdSlot {
     int* h{nullptr};
     int* d{nullptr};
     int cap{0};
     hipEvent_t ev{nullptr};  // the upload out of `h` has finished
     bool used{false};
   };
-  SnapSlot snap_slot_[2];
-  int snap_next_{0};
-  hipEvent_t snap_ev_{nullptr};  // behind the last *Device / Fork launch (SnapLeave)
-  char* snap_scratch_{nullptr};
-  size_t snap_scratch_bytes_{0};
+  IdSlot side_slot_[2];
+  int side_next_{0};
+  hipEvent_t side_ev_{nullptr};  // behind the last device-form launch (SideLeave)
+  char* side_scratch_{nullptr};
+  size_t side_scratch_bytes_{0};
+  void StateHost(const int32_t* ids, int k, double* out, const double* in);  // GetStateHost / SetStateHost
+  // render's checks and the resolved size; throws before anything is enqueued
+  void CheckRender(const int32_t* ids, int k, const void* out, int width, int height, int* w, int* h) const;
+  // snapshots
+  snap::PoolDesc SnapPoolDesc() const;  // what a header has to fit (snapshot.hip.h)
+  void SnapCheck(const int32_t* ids, int k, bool unique) const;  // "not implemented", ids, duplicates
+  void SnapPack(const int* d_ids, int k, unsigned flags, char* d_blob, void* host_header);
+  void SnapUnpack(const int* d_ids, int k, const char* d_blob, const void* header);
+  uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream
   std::vector<hipEvent_t> join_ev_;      // one per compute stream (JoinCompute)

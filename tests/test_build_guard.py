@@ -81,6 +81,20 @@ def test_family_sources_do_not_manage_device_memory():
     assert bad == [], bad
 
 
+def test_engine_frees_device_memory_in_the_listed_functions_only():
+    """Everything else in engine.hip allocates through DevMalloc / DevAlloc / DevUpload and frees nothing: a buffer
+    that lives for one call comes from Pool::SideScratch, an id list from Pool::SideIds."""
+    allowed = {"Pool::~Pool", "Pool::NextStaging", "Pool::SideIds", "Pool::SideScratch", "WaveTrace::DumpAndFree"}
+    found, fn = set(), None
+    for line in open(os.path.join(ROOT, "envpool_amd", "csrc", "engine.hip")).read().splitlines():
+        m = re.match(r"(?:[\w:<>*&]+\s+)*((?:\w+::)?~?\w+)\(", line)  # a definition starts in column 0
+        if m and not line.rstrip().endswith(";"):
+            fn = m.group(1)
+        if "hipFree(" in line:
+            found.add(fn)
+    assert found == allowed, sorted(found ^ allowed)
+
+
 # ---- the product never reaches the checker (oracle/ is test infrastructure) ----
 def test_product_python_never_touches_oracle():
     pkg = os.path.join(ROOT, "envpool_amd")
