@@ -280,6 +280,28 @@ class _ShardedPools:
         parts = sharding.fork_parts(src, dst, self.offset, self.per, len(self.pools))
         self._each(lambda s, p, idx: p.fork(src[idx], dst[idx], rng), parts)
 
+    def playout(self, env_ids: Any = None, repeats: int = 1, max_plies: int = 0, seed: int = 0,
+                commit: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Playouts of envs of any shards, rows in request order: every shard plays its ids, all shards at once.
+        The draws are keyed by the global env id, so the rows are those of the unsharded pool."""
+        if env_ids is None:
+            env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
+        ids = native.check_playout(env_ids, repeats, max_plies, commit)
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        k, r = len(ids), int(repeats)
+        returns = np.empty((k, r, 2), dtype=np.float32)
+        plies = np.empty((k, r), dtype=np.int32)
+        status = np.empty((k, r), dtype=np.uint8)
+
+        def play(s: int, p: DevicePool, idx: Any) -> None:
+            returns[idx], plies[idx], status[idx] = p.playout(ids[idx], repeats, max_plies, seed, commit)
+
+        self._each(play, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
+        return returns, plies, status
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -416,6 +438,12 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
 
         def _fork(self, src: Any, dst: Any, rng: bool) -> None:
             self._pool.fork(src, dst, rng)
+
+        def _playout(self, env_ids: Any, repeats: int, max_plies: int, seed: int, commit: bool) -> Any:
+            playout = getattr(self._pool, "playout", None)
+            if playout is None:  # a pool with its own executor
+                raise RuntimeError("playout not implemented for this environment")
+            return playout(env_ids, repeats, max_plies, seed, commit)
 
         def _xla(self) -> Any:
             raise RuntimeError("XLA is not available for the MI355X engine")

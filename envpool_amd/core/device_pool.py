@@ -421,6 +421,37 @@ class DevicePool:
         native.check(self._lib.epa_fork(self._h, src.ctypes.data, dst.ctypes.data, len(src),
                                         native.EPA_SNAP_RNG if rng else 0))
 
+    # -- playouts ----------------------------------------------------------------
+    def playout(self, env_ids: Any = None, repeats: int = 1, max_plies: int = 0, seed: int = 0,
+                commit: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`repeats` uniform-random playouts of every listed env (global ids; None: the whole pool) from the state
+        every send so far has left it in, in one kernel launch (the PGX board games; RuntimeError("playout not
+        implemented for this environment") elsewhere).  Returns (returns float32 [k, R, 2], plies int32 [k, R],
+        status uint8 [k, R]: 0 the game is over, 1 stopped at `max_plies`; 0 = 256).  The picks depend on (seed,
+        env id, repeat, ply) and the position only.  Nothing of the pool changes unless `commit` (repeats = 1, ids
+        that do not repeat) writes the final states back, as if the plies had been stepped without rows."""
+        ids = native.check_playout(self._ids(env_ids), repeats, max_plies, commit)
+        k, r = len(ids), int(repeats)
+        returns = np.empty((k, r, 2), dtype=np.float32)
+        plies = np.empty((k, r), dtype=np.int32)
+        status = np.empty((k, r), dtype=np.uint8)
+        native.check(self._lib.epa_playout(self._h, ids.ctypes.data, k, r, int(max_plies),
+                                           int(seed) & (2**64 - 1), native.EPA_PLAYOUT_COMMIT if commit else 0,
+                                           returns.ctypes.data, plies.ctypes.data, status.ctypes.data))
+        return returns, plies, status
+
+    def playout_device(self, d_returns: int, d_plies: int, d_status: int, env_ids: Any = None, repeats: int = 1,
+                       max_plies: int = 0, seed: int = 0, commit: bool = False) -> None:
+        """`playout` into device memory at the raw addresses `d_returns` (8 k R bytes, 8-byte aligned), `d_plies`
+        (4 k R bytes, 4-byte aligned) and `d_status` (k R bytes): only enqueued on the pool's stream, nothing is
+        copied to the host (torch_interop.playout_device wraps it)."""
+        ids = native.check_playout(self._ids(env_ids), repeats, max_plies, commit)
+        native.check(self._lib.epa_playout_device(self._h, ids.ctypes.data, len(ids), int(repeats), int(max_plies),
+                                                  int(seed) & (2**64 - 1),
+                                                  native.EPA_PLAYOUT_COMMIT if commit else 0,
+                                                  ctypes.c_void_p(d_returns), ctypes.c_void_p(d_plies),
+                                                  ctypes.c_void_p(d_status)))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Sequence
+from typing import Any, Sequence
 
 import numpy as np
 
@@ -24,6 +24,9 @@ LIB_PATH = os.environ.get("ENVPOOL_AMD_LIB") or os.path.join(_PKG, "lib", "liben
 EPA_OK, EPA_ERR_INVALID, EPA_ERR_RUNTIME, EPA_ERR_DEVICE = 0, 1, 2, 3
 EPA_SNAP_RNG = 1
 SNAP_HEADER_BYTES = 64
+EPA_PLAYOUT_COMMIT = 1
+PLAYOUT_MAX_PLIES = 256
+PLAYOUT_MAX_REPEATS = 4096
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
 
@@ -116,6 +119,8 @@ def lib() -> ctypes.CDLL:
         "epa_snapshot_device": (i32, [vp, vp, i32, ctypes.c_uint32, vp, vp]),
         "epa_restore_device": (i32, [vp, vp, i32, vp, vp]),
         "epa_fork": (i32, [vp, vp, vp, i32, ctypes.c_uint32]),
+        "epa_playout": (i32, [vp, vp, i32, i32, i32, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp]),
+        "epa_playout_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -149,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "epa_stream", "epa_synchronize", "epa_set_timing", "epa_kernel_time_ms",
     "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
     "epa_snapshot_bytes", "epa_snapshot", "epa_restore", "epa_snapshot_device", "epa_restore_device", "epa_fork",
+    "epa_playout", "epa_playout_device",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -182,6 +188,25 @@ def snapshot_header(blob: np.ndarray) -> tuple[int, int]:
     if blob.nbytes < total:
         raise ValueError(f"snapshot blob of {blob.nbytes} bytes is shorter than its header says ({total})")
     return k, total
+
+
+def check_playout(env_ids: Any, repeats: int, max_plies: int, commit: bool) -> np.ndarray:
+    """The ids of a playout call as a flat int32 array, after the argument checks every layer makes before the native
+    call: ValueError for repeats outside 1 .. 4096, max_plies outside 0 .. 256, no ids, and a commit with
+    repeats != 1 or with an id that repeats.  (Ids outside the pool are the engine's to refuse.)"""
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    if not 1 <= int(repeats) <= PLAYOUT_MAX_REPEATS:
+        raise ValueError(f"playout: repeats = {repeats} must be 1 .. {PLAYOUT_MAX_REPEATS}")
+    if not 0 <= int(max_plies) <= PLAYOUT_MAX_PLIES:
+        raise ValueError(f"playout: max_plies = {max_plies} must be 0 .. {PLAYOUT_MAX_PLIES}")
+    if len(ids) == 0:
+        raise ValueError("playout env_ids must not be empty")
+    if commit:
+        if int(repeats) != 1:
+            raise ValueError("playout: commit takes repeats = 1")
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("playout: commit takes env_ids that do not repeat")
+    return ids
 
 
 def device_count() -> int:

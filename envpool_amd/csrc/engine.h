@@ -110,6 +110,19 @@ struct OutPtrs {
   void* p[kMaxKeys];
 };
 
+// One playout launch (Pool::Playout): k listed envs x `repeats` playouts each, entry i * repeats + r of the three
+// device arrays being env row i's repeat r.
+struct PlayoutArgs {
+  int k;
+  int repeats;
+  int max_plies;            // 0: the cap
+  unsigned flags;           // EPA_PLAYOUT_*
+  uint64_t seed;
+  float* returns;           // [k * repeats][2], 8-byte aligned
+  int32_t* plies;           // [k * repeats]
+  unsigned char* status;    // [k * repeats]
+};
+
 struct Batch {
   // where the batch's kernels write and recv reads: the block's own device allocation (`dev_buf`), or -- a DIRECT
   // step, Pool::SendInto -- the caller's pinned host block, where the results then already are when recv wants them
@@ -269,6 +282,21 @@ class Pool {
   void SnapshotHost(const int32_t* ids, int k, unsigned flags, void* out, size_t out_bytes);
   void RestoreHost(const int32_t* ids, int k, const void* blob, size_t blob_bytes);
   void Fork(const int32_t* src, const int32_t* dst, int k, unsigned flags);
+
+  // Random playouts (include/envpool_amd.h: epa_playout; the PGX board games, pgx_playout.hip.h): every listed env is
+  // played on `repeats` times from the state every send issued before the call has left it in, to the end of its game
+  // or for max_plies plies, with uniformly drawn legal actions; what comes back is the per-player return, the plies
+  // played and a status per playout.  Nothing of the pool changes -- unless EPA_PLAYOUT_COMMIT asks for the final
+  // states to be written back, which then takes effect before every send issued after the call, like a restore.
+  // The family hook launches on stream_ for local ids; a family without one keeps the defaults, and both entry points
+  // throw std::runtime_error("playout not implemented for this environment").  PlayoutHost returns the results in host
+  // memory (one stream synchronisation); PlayoutDevice only enqueues.
+  virtual bool HasPlayout() const { return false; }
+  virtual void Playout(const int* d_ids, const PlayoutArgs& a);
+  void PlayoutHost(const int32_t* ids, int k, int repeats, int max_plies, uint64_t seed, unsigned flags, float* returns,
+                   int32_t* plies, uint8_t* status);
+  void PlayoutDevice(const int32_t* ids, int k, int repeats, int max_plies, uint64_t seed, unsigned flags,
+                     void* d_returns, void* d_plies, void* d_status);
 
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
@@ -455,6 +483,8 @@ class Pool {
   void SnapCheck(const int32_t* ids, int k, bool unique) const;  // "not implemented", ids, duplicates
   void SnapPack(const int* d_ids, int k, unsigned flags, char* d_blob, void* host_header);
   void SnapUnpack(const int* d_ids, int k, const char* d_blob, const void* header);
+  // playout's checks; throws before anything is enqueued
+  void CheckPlayout(const int32_t* ids, int k, int repeats, int max_plies, unsigned flags) const;
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

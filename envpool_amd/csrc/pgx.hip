@@ -16,12 +16,14 @@
 // elements of its words from the views (pgx::Elem).  A wave's stores are then 1 KB contiguous instead of 64 rows
 // apart.
 // Render: pgx_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
+// Playout: pgx_playout.hip.h, one (env, repeat) per lane, the whole game in registers (PgxPlayoutKernel).
 #include <algorithm>
 #include <string>
 
 #include "device_common.hip.h"
 #include "engine.h"
 #include "pgx_env.hip.h"
+#include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
 #include "render_kernel.hip.h"
 
@@ -149,6 +151,41 @@ __global__ void PgxSetState(CommonDev cm, pgx::State* st, unsigned* err, const i
   cm.done[e] = done ? 1 : 0;
 }
 
+// Random playouts (pgx_playout.hip.h): lane i plays repeat i % R of listed env i / R, so the repeats of one env sit
+// in adjacent lanes -- they load the same 64-byte State (one sector for the group) and their games, from one position,
+// are the likeliest to be of similar length -- and result i of each of the three arrays is lane i's, stored coalesced.
+// No barrier, no memory traffic per ply and no LDS of its own (the compiler keeps Step's seat-indexed reward pairs in
+// 16 bytes of LDS per lane): a block is one wave, which leaves its SIMD as soon as its own longest game is over.
+// The loop is divergent per lane (a wave runs for its longest game, and Hex's flood fill for the lane with the
+// largest group); lanes whose game is over idle until then.
+// Commit (R == 1, ids that do not repeat: the engine checks both) also writes back what the plies' step launches
+// would have: the State, done and cur_step.  An env that is over at the call -- cm.done, which an env before its first
+// reset has set while its State is still all zeros -- plays nothing and is left as it is.
+constexpr int kPlayoutBlock = 64;
+static_assert(pgx::kPlayoutMaxPlies == EPA_PLAYOUT_MAX_PLIES && pgx::kPlayoutMaxRepeats == EPA_PLAYOUT_MAX_REPEATS,
+              "the C ABI states the header's limits");
+
+template <int G>
+__global__ __launch_bounds__(kPlayoutBlock) void PgxPlayoutKernel(CommonDev cm, pgx::State* st,
+                                                                  const int* __restrict__ ids, PlayoutArgs a,
+                                                                  int id_offset) {
+  const long long i = (long long)blockIdx.x * kPlayoutBlock + threadIdx.x;
+  if (i >= (long long)a.k * a.repeats) return;
+  const int row = (int)(i / a.repeats), r = (int)(i - (long long)row * a.repeats);
+  const int e = ids[row];
+  pgx::State s = st[e];
+  const uint64_t h = pgx::PlayoutStream(a.seed, e + id_offset, r);
+  const pgx::PlayoutResult res = pgx::Playout<G>(s, cm.done[e] != 0, h, pgx::PlayoutLimit(a.max_plies));
+  reinterpret_cast<float2*>(a.returns)[i] = make_float2(res.ret[0], res.ret[1]);
+  a.plies[i] = res.plies;
+  a.status[i] = (unsigned char)res.status;
+  if ((a.flags & EPA_PLAYOUT_COMMIT) != 0 && res.plies > 0) {
+    st[e] = s;
+    cm.done[e] = s.done ? 1 : 0;
+    cm.cur_step[e] += res.plies;
+  }
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -200,6 +237,12 @@ class PgxPool : public Pool {
   void RenderSize(int width, int height, int* w, int* h) const override { pgx::RenderSize<G>(width, height, w, h); }
   void Render(const int* d_ids, int k, int w, int h, int /*camera_id*/, void* d_rgb) override {
     render::LaunchRender<PgxPainter<G>>(state_, d_ids, k, w, h, d_rgb, stream_);
+  }
+  bool HasPlayout() const override { return true; }
+  void Playout(const int* d_ids, const PlayoutArgs& a) override {
+    const long long lanes = (long long)a.k * a.repeats;
+    hipLaunchKernelGGL(PgxPlayoutKernel<G>, dim3((unsigned)((lanes + kPlayoutBlock - 1) / kPlayoutBlock)),
+                       dim3(kPlayoutBlock), 0, stream_, common_, state_, d_ids, a, cfg_.env_id_offset);
   }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";

@@ -12,9 +12,19 @@ from __future__ import annotations
 import pprint
 import warnings
 from abc import ABC
-from typing import Any
+from typing import Any, NamedTuple
 
 import numpy as np
+
+from envpool_amd.core import native
+
+
+class Playout(NamedTuple):
+    """What `playout` returns: numpy arrays over [k listed envs, R repeats]."""
+
+    returns: np.ndarray  # float32 [k, R, 2]: per-player sum of the step rewards
+    plies: np.ndarray    # int32 [k, R]: plies played
+    status: np.ndarray   # uint8 [k, R]: 0 the game is over, 1 stopped at max_plies
 
 
 def _normalize_env_id(env_id: Any) -> Any:
@@ -159,6 +169,17 @@ class EnvPoolMixin(ABC):
         """Extension: env dst[i] becomes env src[i] without leaving the device (tree search: one position into many
         envs).  `src` may repeat, `dst` must not."""
         self._fork(_normalize_env_id(src), _normalize_env_id(dst), bool(rng))
+
+    def playout(self, env_ids: Any = None, repeats: int = 1, max_plies: int = 0, seed: int = 0,
+                commit: bool = False) -> Playout:
+        """Extension (the PGX board games): `repeats` uniform-random playouts of every listed env (global ids; None:
+        all) from its current position to the end of the game, or for `max_plies` plies (0: 256), in one kernel
+        launch -- the leaf evaluation of a tree search.  The picks depend on (seed, env id, repeat, ply) and the
+        position only.  Nothing of the pool changes, unless `commit` (repeats = 1, ids that do not repeat) writes the
+        final positions back as if the plies had been stepped.  The arguments are checked before any native call."""
+        ids = native.check_playout(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
+                                   repeats, max_plies, commit)
+        return Playout(*self._playout(ids, int(repeats), int(max_plies), int(seed), bool(commit)))
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -15,6 +15,8 @@ from typing import Any
 
 import numpy as np
 
+from envpool_amd.core import native
+
 _TYPESTR = {np.dtype(np.int32): "<i4", np.dtype(np.float32): "<f4",
             np.dtype(np.float64): "<f8", np.dtype(np.bool_): "|b1",
             np.dtype(np.uint8): "|u1", np.dtype(np.int8): "|i1"}
@@ -186,3 +188,25 @@ def fork(pool: Any, src: Any, dst: Any, rng: bool = True) -> None:
     import torch
 
     _order_both_ways(pool, torch.device("cuda", pool.device), lambda: pool.fork(src, dst, rng))
+
+
+def playout_device(pool: Any, env_ids: Any = None, repeats: int = 1, max_plies: int = 0, seed: int = 0,
+                   commit: bool = False) -> tuple[Any, Any, Any]:
+    """`pool.playout` without the way down: (returns float32 [k, R, 2], plies int32 [k, R], status uint8 [k, R]) as
+    torch tensors on the pool's device, written by the playout kernel straight into torch's memory (no PCIe transfer,
+    no host synchronisation) and ordered against torch's current stream like `snapshot_device`: the kernel behind what
+    torch has enqueued, the current stream behind the kernel.  With `commit` a step sent afterwards sees the final
+    positions."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_playout(env_ids, repeats, max_plies, commit)
+    k, r = len(ids), int(repeats)
+    dev = torch.device("cuda", pool.device)
+    returns = torch.empty((k, r, 2), dtype=torch.float32, device=dev)
+    plies = torch.empty((k, r), dtype=torch.int32, device=dev)
+    status = torch.empty((k, r), dtype=torch.uint8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.playout_device(returns.data_ptr(), plies.data_ptr(), status.data_ptr(),
+                                                            ids, repeats, max_plies, seed, commit))
+    return returns, plies, status

@@ -396,6 +396,41 @@ int epa_restore_device(epa_pool* pool, const int32_t* env_ids, int32_t k, const 
                        const void* host_header);
 int epa_fork(epa_pool* pool, const int32_t* src_ids, const int32_t* dst_ids, int32_t k, uint32_t flags);
 
+/* Random playouts (no reference analogue; the four PGX board games): every listed env is played on `repeats` times
+ * from its current state -- the state after every send / reset issued before the call, received or not, as for
+ * epa_snapshot -- with uniformly drawn legal actions, until its game is over or max_plies plies are played
+ * (max_plies = 0: EPA_PLAYOUT_MAX_PLIES, which no game of the four reaches).  One kernel launch, one playout per lane,
+ * no result rows.  The draws (all arithmetic mod 2^64):
+ *   SM(x):  x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31)
+ *   stream  h = SM(seed ^ SM((uint64(env_id) << 32) | uint32(r)))       env_id: the global id; r: the repeat, from 0
+ *   ply t   (from 0 inside the playout)  u = SM(h + t); n = legal actions; j = ((u >> 32) * n) >> 32;
+ *           the action is the (j+1)-th lowest legal one
+ * so a playout depends on (seed, env_id, r) and the position only, not on the order of the ids or on how the pool
+ * is sharded.  Results, entry i * repeats + r for env_ids[i]'s repeat r:
+ *   returns [k, repeats, 2] float   per-player sum of the step rewards (0 and +-1: exact)
+ *   plies   [k, repeats]    int32   plies played
+ *   status  [k, repeats]    uint8   0 the game is over, 1 stopped at max_plies
+ * An env that is over at the call (every env before its first reset is) reports 0 plies, zero returns and status 0;
+ * a playout never resets an env.  By default nothing of the pool changes: not the envs, their step counts and
+ * generators, nor the rows waiting for recv.  With EPA_PLAYOUT_COMMIT (repeats = 1, ids that do not repeat) the final
+ * state is written back, done set and the step count advanced by `plies`, exactly as if those actions had been stepped
+ * except that no rows are produced; it takes effect before every send issued after the call, like epa_restore.
+ *   EPA_ERR_INVALID: repeats outside 1 .. EPA_PLAYOUT_MAX_REPEATS, max_plies outside 0 .. EPA_PLAYOUT_MAX_PLIES,
+ *     unknown flags, k <= 0, more than num_envs ids or an id outside the pool (global ids, as epa_snapshot), k * repeats
+ *     above 2^31 - 1, commit with repeats != 1 or with a repeated id.
+ *   Every other family fails with EPA_ERR_RUNTIME "playout not implemented for this environment".
+ * epa_playout returns the results in host memory (one stream synchronisation).  epa_playout_device writes them to
+ * device memory of the pool's device (returns 8-byte, plies 4-byte aligned) and only enqueues on epa_stream(pool),
+ * like epa_snapshot_device. */
+#define EPA_PLAYOUT_COMMIT 1u
+#define EPA_PLAYOUT_MAX_PLIES 256
+#define EPA_PLAYOUT_MAX_REPEATS 4096
+int epa_playout(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t repeats, int32_t max_plies, uint64_t seed,
+                uint32_t flags, float* returns, int32_t* plies, uint8_t* status);
+int epa_playout_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t repeats, int32_t max_plies,
+                       uint64_t seed, uint32_t flags, void* device_returns, void* device_plies, void* device_status);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
