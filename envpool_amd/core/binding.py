@@ -302,6 +302,29 @@ class _ShardedPools:
         self._each(play, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
         return returns, plies, status
 
+    def search(self, env_ids: Any = None, simulations: int = 64, leaf_playouts: int = 8, c_puct: float = 1.25,
+               max_plies: int = 0, seed: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Searches from envs of any shards, rows in request order: every shard searches its ids, all shards at once.
+        The leaf playouts are keyed by the global env id, so the rows are those of the unsharded pool."""
+        if env_ids is None:
+            env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
+        ids = native.check_search(env_ids, simulations, leaf_playouts, c_puct, max_plies)
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        k, a = len(ids), self.pools[0].search_actions()
+        visits = np.empty((k, a), dtype=np.int32)
+        returns = np.empty((k, a), dtype=np.int32)
+        action = np.empty(k, dtype=np.int32)
+
+        def run(s: int, p: DevicePool, idx: Any) -> None:
+            visits[idx], returns[idx], action[idx] = p.search(ids[idx], simulations, leaf_playouts, c_puct,
+                                                              max_plies, seed)
+
+        self._each(run, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
+        return visits, returns, action
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -444,6 +467,13 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
             if playout is None:  # a pool with its own executor
                 raise RuntimeError("playout not implemented for this environment")
             return playout(env_ids, repeats, max_plies, seed, commit)
+
+        def _search(self, env_ids: Any, simulations: int, leaf_playouts: int, c_puct: float, max_plies: int,
+                    seed: int) -> Any:
+            search = getattr(self._pool, "search", None)
+            if search is None:  # a pool with its own executor
+                raise RuntimeError("search not implemented for this environment")
+            return search(env_ids, simulations, leaf_playouts, c_puct, max_plies, seed)
 
         def _xla(self) -> Any:
             raise RuntimeError("XLA is not available for the MI355X engine")

@@ -452,6 +452,45 @@ class DevicePool:
                                                   ctypes.c_void_p(d_returns), ctypes.c_void_p(d_plies),
                                                   ctypes.c_void_p(d_status)))
 
+    # -- tree search -------------------------------------------------------------
+    def search_actions(self) -> int:
+        """A, the width of a search's result rows, as the engine states it; a family without search raises."""
+        n = ctypes.c_int32(0)
+        native.check(self._lib.epa_search_actions(self._h, ctypes.byref(n)))
+        if n.value <= 0:
+            raise RuntimeError("search not implemented for this environment")
+        return int(n.value)
+
+    def search(self, env_ids: Any = None, simulations: int = 64, leaf_playouts: int = 8, c_puct: float = 1.25,
+               max_plies: int = 0, seed: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """A tree search from the current position of every listed env (global ids; None: the whole pool), in one
+        kernel launch, one wave per root (the PGX board games; RuntimeError("search not implemented for this
+        environment") elsewhere): `simulations` rounds of PUCT selection with uniform priors, every new leaf valued
+        by the sum of `leaf_playouts` random playouts -- repeats t * leaf_playouts + r of `playout(seed)` for
+        simulation t.  Returns (visits int32 [k, A], returns int32 [k, A]: the summed playout returns through each
+        root action, seen from the root's mover, action int32 [k]: the most visited action, the lowest on ties; -1
+        and zeros for an env that is over).  Nothing of the pool changes."""
+        ids = native.check_search(self._ids(env_ids), simulations, leaf_playouts, c_puct, max_plies)
+        k, a = len(ids), self.search_actions()
+        visits = np.empty((k, a), dtype=np.int32)
+        returns = np.empty((k, a), dtype=np.int32)
+        action = np.empty(k, dtype=np.int32)
+        native.check(self._lib.epa_search(self._h, ids.ctypes.data, k, int(simulations), int(leaf_playouts),
+                                          float(c_puct), int(max_plies), int(seed) & (2**64 - 1),
+                                          visits.ctypes.data, returns.ctypes.data, action.ctypes.data))
+        return visits, returns, action
+
+    def search_device(self, d_visits: int, d_returns: int, d_action: int, env_ids: Any = None, simulations: int = 64,
+                      leaf_playouts: int = 8, c_puct: float = 1.25, max_plies: int = 0, seed: int = 0) -> None:
+        """`search` into device memory at the raw addresses `d_visits`, `d_returns` (4 k A bytes each) and `d_action`
+        (4 k bytes), all 4-byte aligned: only enqueued on the pool's stream, nothing is copied to the host
+        (torch_interop.search_device wraps it)."""
+        ids = native.check_search(self._ids(env_ids), simulations, leaf_playouts, c_puct, max_plies)
+        native.check(self._lib.epa_search_device(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                 int(leaf_playouts), float(c_puct), int(max_plies),
+                                                 int(seed) & (2**64 - 1), ctypes.c_void_p(d_visits),
+                                                 ctypes.c_void_p(d_returns), ctypes.c_void_p(d_action)))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

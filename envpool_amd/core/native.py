@@ -27,6 +27,8 @@ SNAP_HEADER_BYTES = 64
 EPA_PLAYOUT_COMMIT = 1
 PLAYOUT_MAX_PLIES = 256
 PLAYOUT_MAX_REPEATS = 4096
+SEARCH_MAX_SIMULATIONS = 4096
+SEARCH_MAX_LEAF_PLAYOUTS = 64
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
 
@@ -121,6 +123,9 @@ def lib() -> ctypes.CDLL:
         "epa_fork": (i32, [vp, vp, vp, i32, ctypes.c_uint32]),
         "epa_playout": (i32, [vp, vp, i32, i32, i32, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp]),
         "epa_playout_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp]),
+        "epa_search_actions": (i32, [vp, P(i32)]),
+        "epa_search": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, i32, ctypes.c_uint64, vp, vp, vp]),
+        "epa_search_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, i32, ctypes.c_uint64, vp, vp, vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -154,7 +159,7 @@ EXPORTED_SYMBOLS = [
     "epa_stream", "epa_synchronize", "epa_set_timing", "epa_kernel_time_ms",
     "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
     "epa_snapshot_bytes", "epa_snapshot", "epa_restore", "epa_snapshot_device", "epa_restore_device", "epa_fork",
-    "epa_playout", "epa_playout_device",
+    "epa_playout", "epa_playout_device", "epa_search_actions", "epa_search", "epa_search_device",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -206,6 +211,30 @@ def check_playout(env_ids: Any, repeats: int, max_plies: int, commit: bool) -> n
             raise ValueError("playout: commit takes repeats = 1")
         if len(np.unique(ids)) != len(ids):
             raise ValueError("playout: commit takes env_ids that do not repeat")
+    return ids
+
+
+def check_search(env_ids: Any, simulations: int, leaf_playouts: int, c_puct: float, max_plies: int) -> np.ndarray:
+    """The ids of a search call as a flat int32 array, after the argument checks every layer makes before the native
+    call: ValueError for simulations outside 1 .. 4096, leaf_playouts outside 1 .. 64, simulations * leaf_playouts
+    above 4096 (the leaf playouts are repeats of `playout`), max_plies outside 0 .. 256, a c_puct that is not finite
+    or negative, and no ids.  (Ids outside the pool and the size of the tree scratch are the engine's to refuse.)"""
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    if not 1 <= int(simulations) <= SEARCH_MAX_SIMULATIONS:
+        raise ValueError(f"search: simulations = {simulations} must be 1 .. {SEARCH_MAX_SIMULATIONS}")
+    if not 1 <= int(leaf_playouts) <= SEARCH_MAX_LEAF_PLAYOUTS:
+        raise ValueError(f"search: leaf_playouts = {leaf_playouts} must be 1 .. {SEARCH_MAX_LEAF_PLAYOUTS}")
+    if int(simulations) * int(leaf_playouts) > PLAYOUT_MAX_REPEATS:
+        raise ValueError(f"search: simulations * leaf_playouts = {int(simulations) * int(leaf_playouts)} must be at "
+                         f"most {PLAYOUT_MAX_REPEATS}")
+    if not 0 <= int(max_plies) <= PLAYOUT_MAX_PLIES:
+        raise ValueError(f"search: max_plies = {max_plies} must be 0 .. {PLAYOUT_MAX_PLIES}")
+    with np.errstate(over="ignore"):
+        c = np.float32(c_puct)
+    if not np.isfinite(c) or c < 0:
+        raise ValueError(f"search: c_puct = {c_puct} must be finite and >= 0")
+    if len(ids) == 0:
+        raise ValueError("search env_ids must not be empty")
     return ids
 
 

@@ -123,6 +123,21 @@ struct PlayoutArgs {
   unsigned char* status;    // [k * repeats]
 };
 
+// One search launch (Pool::Search): k listed envs, row i of the three device result arrays being env row i's, and
+// the tree scratch of k * (simulations + 1) nodes of the family's node size (Pool::SearchNodeBytes).
+struct SearchArgs {
+  int k;
+  int simulations;
+  int leaf_playouts;
+  int max_plies;            // 0: the playouts' cap
+  float c_puct;
+  uint64_t seed;
+  int32_t* visits;          // [k][A]
+  int32_t* returns;         // [k][A]
+  int32_t* action;          // [k]
+  void* nodes;              // 16-byte aligned
+};
+
 struct Batch {
   // where the batch's kernels write and recv reads: the block's own device allocation (`dev_buf`), or -- a DIRECT
   // step, Pool::SendInto -- the caller's pinned host block, where the results then already are when recv wants them
@@ -297,6 +312,22 @@ class Pool {
                    int32_t* plies, uint8_t* status);
   void PlayoutDevice(const int32_t* ids, int k, int repeats, int max_plies, uint64_t seed, unsigned flags,
                      void* d_returns, void* d_plies, void* d_status);
+
+  // Tree search (include/envpool_amd.h: epa_search; the PGX board games, pgx_search.hip.h): for every listed env,
+  // `simulations` rounds of PUCT selection from the state every send issued before the call has left it in, with
+  // uniform priors and `leaf_playouts` random playouts per new leaf; what comes back is the root's visit counts and
+  // summed returns per action and the most visited action.  Nothing of the pool changes.  The family hook launches on
+  // stream_ for local ids, its tree in `a.nodes` (the side scratch block); a family without one keeps the defaults,
+  // and both entry points throw std::runtime_error("search not implemented for this environment").  SearchHost returns
+  // the results in host memory (one stream synchronisation); SearchDevice only enqueues.
+  virtual bool HasSearch() const { return false; }
+  virtual int SearchActions() const { return 0; }        // A: the width of a result row
+  virtual size_t SearchNodeBytes() const { return 0; }   // a multiple of 16
+  virtual void Search(const int* d_ids, const SearchArgs& a);
+  void SearchHost(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies,
+                  uint64_t seed, int32_t* visits, int32_t* returns, int32_t* action);
+  void SearchDevice(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies,
+                    uint64_t seed, void* d_visits, void* d_returns, void* d_action);
 
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
@@ -485,6 +516,8 @@ class Pool {
   void SnapUnpack(const int* d_ids, int k, const char* d_blob, const void* header);
   // playout's checks; throws before anything is enqueued
   void CheckPlayout(const int32_t* ids, int k, int repeats, int max_plies, unsigned flags) const;
+  // search's checks; throws before anything is enqueued.  Returns the bytes of the tree scratch.
+  size_t CheckSearch(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies) const;
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

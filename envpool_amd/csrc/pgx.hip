@@ -17,6 +17,7 @@
 // apart.
 // Render: pgx_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
 // Playout: pgx_playout.hip.h, one (env, repeat) per lane, the whole game in registers (PgxPlayoutKernel).
+// Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
 #include <algorithm>
 #include <string>
 
@@ -25,13 +26,15 @@
 #include "pgx_env.hip.h"
 #include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
+#include "pgx_search.hip.h"
 #include "render_kernel.hip.h"
 
 namespace epa {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr unsigned kErrState = 1;  // set_state words that are no position of the game
+constexpr unsigned kErrState = 1;   // set_state words that are no position of the game
+constexpr unsigned kErrSearch = 2;  // a search met a running position without a legal action, or a path past the cap
 
 // key K's section of rows [row0, row0 + nrows) of the launch, written by the whole block
 template <int G, int K>
@@ -186,6 +189,191 @@ __global__ __launch_bounds__(kPlayoutBlock) void PgxPlayoutKernel(CommonDev cm, 
   }
 }
 
+// Tree search (pgx_search.hip.h): one wave per root, one block per wave; block i searches listed env i in its own
+// S + 1 nodes of the tree scratch.  Everything that steers the control flow -- the node, the picked action, the child,
+// val0 -- is wave-uniform: it comes out of a butterfly reduction or a broadcast, so every lane holds the same value
+// and the loops need no divergence handling.
+//   lane ownership  lane j owns actions j and j + 64 (Hex: two per lane; Othello's pass, action 64, is lane 0's second
+//                   slot) of every node: it loads their child / v / w0 (contiguous over the wave), scores them, and
+//                   is the only lane that writes them -- at the node's making, at expansion (child) and in backup.
+//                   Edge statistics never pass between lanes through memory; the picked edge's child index reaches
+//                   the other lanes by a register broadcast from its owner.
+//   selection       V is a wave integer sum, the pick a wave arg-max of pgx::SearchBetter (lowest action on ties)
+//   expansion       every lane runs the same pgx::Step on its copy of the node's State; lane 0 stores the new node's
+//                   State and term0, every lane clears its own edges of it
+//   leaf            lane r < R plays leaf playout r (the other 64 - R lanes idle); val0 is a wave integer sum
+//   backup          the path's (node, action) pairs are kept in LDS by lane 0; each pair's owner lane adds to v, w0
+// A node's State is written by lane 0 and read by all lanes on later simulations: a hand-off between lanes through
+// memory.  A wavefront-scope release fence follows the stores of an expansion and an acquire fence precedes the loads
+// of a descent (the same pair brackets the path in LDS), so neither the compiler nor the memory pipeline reorders them.
+constexpr int kSearchBlock = pgx::kSearchWave;
+static_assert(pgx::kSearchMaxSimulations == EPA_SEARCH_MAX_SIMULATIONS &&
+                  pgx::kSearchMaxLeafPlayouts == EPA_SEARCH_MAX_LEAF_PLAYOUTS,
+              "the C ABI states the header's limits");
+
+__device__ __forceinline__ void WaveRelease() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); }
+__device__ __forceinline__ void WaveAcquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+
+__device__ __forceinline__ int WaveSum(int x) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kSearchBlock);
+  return x;
+}
+__device__ __forceinline__ pgx::SearchPick WaveBest(pgx::SearchPick p) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
+    const pgx::SearchPick o{__shfl_xor(p.key, m, kSearchBlock), __shfl_xor(p.action, m, kSearchBlock),
+                            __shfl_xor(p.ok, m, kSearchBlock)};
+    p = pgx::SearchBetter(p, o);
+  }
+  return p;
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, const pgx::State* st,
+                                                                const int* __restrict__ ids, SearchArgs a,
+                                                                int id_offset, unsigned* err) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::SearchNode<G>;
+  __shared__ int path[pgx::kSearchMaxPath];  // node << 8 | action
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int e = ids[row];
+  const int S = a.simulations, R = a.leaf_playouts;
+  const int limit = pgx::PlayoutLimit(a.max_plies);
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)(S + 1);
+  int32_t* visits = a.visits + (size_t)row * A;
+  int32_t* returns = a.returns + (size_t)row * A;
+  if (cm.done[e] != 0) {  // over at the call (an env before its first reset is)
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+      const int act = lane + kSearchBlock * j;
+      if (act < A) visits[act] = returns[act] = 0;
+    }
+    if (lane == 0) a.action[row] = -1;
+    return;
+  }
+  const pgx::State root = st[e];
+  if (lane == 0) {
+    nodes[0].s = root;
+    nodes[0].term0 = 0;
+  }
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    if (lane + kSearchBlock * j < A) pgx::SearchClearEdge<G>(nodes[0], lane + kSearchBlock * j);
+  }
+  WaveRelease();
+  int count = 1;
+  bool broken = false;
+  for (int t = 0; t < S && !broken; ++t) {
+    int node = 0, depth = 0, val0 = 0;
+    for (;;) {
+      WaveAcquire();
+      Node& nd = nodes[node];
+      const pgx::State s = nd.s;
+      if (s.done) {
+        val0 = R * nd.term0;
+        break;
+      }
+      int child[SL], v[SL], w0[SL];
+      int own = 0;
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        const int act = lane + kSearchBlock * j;
+        child[j] = -1;
+        v[j] = w0[j] = 0;
+        if (act < A) {
+          child[j] = nd.child[act];
+          v[j] = nd.v[act];
+          w0[j] = nd.w0[act];
+        }
+        own += v[j];
+      }
+      const int total = WaveSum(own);
+      const int sign = pgx::SearchSign<G>(s);
+      pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        const int act = lane + kSearchBlock * j;
+        if (act < A && pgx::Has(s.m, act)) {
+          mine = pgx::SearchBetter(
+              mine, pgx::SearchPick{pgx::SearchScore(v[j], w0[j], total, sign, R, a.c_puct), act, 1});
+        }
+      }
+      const int act = WaveBest(mine).action;
+      // A running game has a legal action and a path is a line of play, far shorter than the LDS array: this is
+      // unreachable from a position of the game.  A broken one is reported through the pool's error word, like
+      // set_state's, and the root gives the rows of an env that is over (the host harness returns -3 here).
+      if (act < 0 || depth >= pgx::kSearchMaxPath) {
+        broken = true;
+        break;
+      }
+      if (lane == 0) path[depth] = node << 8 | act;
+      ++depth;
+      const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
+      int c = __shfl(child[0], owner, kSearchBlock);
+      if (SL > 1) {
+        const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
+        c = slot == 1 ? c1 : c;
+      }
+      if (c < 0) {
+        c = count++;
+        if (lane == owner) nd.child[act] = c;
+        Node& nn = nodes[c];
+        pgx::State s2;
+        const int term0 = pgx::SearchExpand<G>(s, act, s2);
+        if (lane == 0) {
+          nn.s = s2;
+          nn.term0 = term0;
+        }
+#pragma unroll
+        for (int j = 0; j < SL; ++j) {
+          if (lane + kSearchBlock * j < A) pgx::SearchClearEdge<G>(nn, lane + kSearchBlock * j);
+        }
+        WaveRelease();
+        if (s2.done) {
+          val0 = R * term0;
+        } else {
+          val0 = WaveSum(lane < R ? pgx::SearchLeaf<G>(s2, a.seed, e + id_offset, t, R, lane, limit) : 0);
+        }
+        break;
+      }
+      node = c;
+    }
+    WaveRelease();
+    __syncthreads();
+    WaveAcquire();
+    if (broken) depth = 0;
+    for (int d = 0; d < depth; ++d) {
+      const int p = path[d];
+      const int act = p & 255;
+      if ((act & (kSearchBlock - 1)) == lane) {
+        Node& nd = nodes[p >> 8];
+        nd.v[act] += 1;
+        nd.w0[act] += val0;
+      }
+    }
+    __syncthreads();  // the path is read before the next simulation overwrites it
+  }
+  WaveAcquire();
+  const int sign = pgx::SearchSign<G>(root);
+  pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    if (act < A) {
+      const int v = broken ? 0 : nodes[0].v[act];
+      visits[act] = v;
+      returns[act] = broken ? 0 : sign * nodes[0].w0[act];
+      if (!broken && pgx::Has(root.m, act)) mine = pgx::SearchBetter(mine, pgx::SearchPick{(float)v, act, 1});
+    }
+  }
+  const int best = WaveBest(mine).action;  // (-1 without a legal action)
+  if (lane == 0) {
+    a.action[row] = best;
+    if (broken) *err = kErrSearch;
+  }
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -244,8 +432,16 @@ class PgxPool : public Pool {
     hipLaunchKernelGGL(PgxPlayoutKernel<G>, dim3((unsigned)((lanes + kPlayoutBlock - 1) / kPlayoutBlock)),
                        dim3(kPlayoutBlock), 0, stream_, common_, state_, d_ids, a, cfg_.env_id_offset);
   }
+  bool HasSearch() const override { return true; }
+  int SearchActions() const override { return pgx::Dims<G>::A; }
+  size_t SearchNodeBytes() const override { return sizeof(pgx::SearchNode<G>); }
+  void Search(const int* d_ids, const SearchArgs& a) override {
+    hipLaunchKernelGGL(PgxSearchKernel<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
+                       a, cfg_.env_id_offset, err_dev_);
+  }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";
+    if (code == kErrSearch) return "PGX: search met a position that is no position of the game";
     return Pool::ErrorText(code);
   }
 

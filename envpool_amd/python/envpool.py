@@ -27,6 +27,14 @@ class Playout(NamedTuple):
     status: np.ndarray   # uint8 [k, R]: 0 the game is over, 1 stopped at max_plies
 
 
+class Search(NamedTuple):
+    """What `search` returns: numpy arrays over [k listed envs, A actions]."""
+
+    visits: np.ndarray   # int32 [k, A]: simulations through each root action
+    returns: np.ndarray  # int32 [k, A]: summed playout returns through it, seen from the root's mover
+    action: np.ndarray   # int32 [k]: the most visited action (the lowest on ties); -1: the env is over
+
+
 def _normalize_env_id(env_id: Any) -> Any:
     """env ids as an int32 array of at least one dimension (envpool.py:38-48).  Array-likes with their own `astype`
     (device arrays) keep their type; everything else goes through numpy."""
@@ -180,6 +188,18 @@ class EnvPoolMixin(ABC):
         ids = native.check_playout(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                    repeats, max_plies, commit)
         return Playout(*self._playout(ids, int(repeats), int(max_plies), int(seed), bool(commit)))
+
+    def search(self, env_ids: Any = None, simulations: int = 64, leaf_playouts: int = 8, c_puct: float = 1.25,
+               max_plies: int = 0, seed: int = 0) -> Search:
+        """Extension (the PGX board games): a tree search from the current position of every listed env (global ids;
+        None: all) in one kernel launch -- `simulations` rounds of PUCT selection with uniform priors, every new leaf
+        valued by `leaf_playouts` random playouts (`max_plies`, `seed` as for `playout`, whose repeats
+        0 .. simulations * leaf_playouts - 1 they are).  The result depends on the arguments, the env id and the
+        position only.  Nothing of the pool changes.  The arguments are checked before any native call."""
+        ids = native.check_search(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
+                                  simulations, leaf_playouts, c_puct, max_plies)
+        return Search(*self._search(ids, int(simulations), int(leaf_playouts), float(c_puct), int(max_plies),
+                                    int(seed)))
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -210,3 +210,23 @@ def playout_device(pool: Any, env_ids: Any = None, repeats: int = 1, max_plies: 
     _order_both_ways(pool, dev, lambda: pool.playout_device(returns.data_ptr(), plies.data_ptr(), status.data_ptr(),
                                                             ids, repeats, max_plies, seed, commit))
     return returns, plies, status
+
+
+def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_playouts: int = 8, c_puct: float = 1.25,
+                  max_plies: int = 0, seed: int = 0) -> tuple[Any, Any, Any]:
+    """`pool.search` without the way down: (visits int32 [k, A], returns int32 [k, A], action int32 [k]) as torch
+    tensors on the pool's device, written by the search kernel straight into torch's memory (no PCIe transfer, no host
+    synchronisation) and ordered against torch's current stream like `playout_device`."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_search(env_ids, simulations, leaf_playouts, c_puct, max_plies)
+    k, a = len(ids), pool.search_actions()
+    dev = torch.device("cuda", pool.device)
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    returns = torch.empty((k, a), dtype=torch.int32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.search_device(visits.data_ptr(), returns.data_ptr(), action.data_ptr(),
+                                                           ids, simulations, leaf_playouts, c_puct, max_plies, seed))
+    return visits, returns, action

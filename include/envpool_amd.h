@@ -431,6 +431,60 @@ int epa_playout(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t repea
 int epa_playout_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t repeats, int32_t max_plies,
                        uint64_t seed, uint32_t flags, void* device_returns, void* device_plies, void* device_status);
 
+/* Tree search (no reference analogue; the four PGX board games): for every listed env, `simulations` (S) rounds of PUCT
+ * selection from its current state -- the state after every send / reset issued before the call, as for epa_snapshot --
+ * with uniform priors, every new leaf valued by the sum of `leaf_playouts` (R) uniform-random playouts.  One kernel
+ * launch, one wave per root; nothing of the pool changes and no result rows are produced.  The contract, with e the
+ * root's GLOBAL env id (csrc/pgx_search.hip.h):
+ *   A node holds its position, term0 (seat 0's reward of the step that made it) and per action a: child[a] (-1: none),
+ *   v[a] (simulations through the edge), w0[a] (seat 0's summed playout returns through the edge), all int32.  Node 0
+ *   is the env's position; a root has at most S + 1 nodes.
+ *   simulation t = 0 .. S-1:
+ *     node = 0; path = []
+ *     loop:
+ *       if node's game is over:  val0 = R * node.term0; break
+ *       a = the legal action of the largest score(node, a); ties: the lowest a
+ *       path += (node, a)
+ *       if node.child[a] < 0:
+ *           c = a new node: node's position stepped by a, term0 = seat 0's reward of that step; node.child[a] = c
+ *           if c's game is over:  val0 = R * c.term0
+ *           else:  val0 = sum over r < R of seat 0's return of repeat t * R + r of epa_playout(seed, env e, max_plies)
+ *                         played from c's position
+ *           break
+ *       node = node.child[a]
+ *     for (n, a) in path:  n.v[a] += 1;  n.w0[a] += val0
+ *   score(node, a), float, every operation correctly rounded, in this order, nothing fused:
+ *     V = sum over b of node.v[b];  sign = +1 if seat 0 moves at the node else -1   (the seat info:current_player reports)
+ *     q = node.v[a] > 0 ? (float)(sign * node.w0[a]) / (float)(node.v[a] * R) : 0
+ *     score = q + (c_puct * sqrtf((float)V)) / (float)(1 + node.v[a])
+ * Only seat 0's value is kept: legal play in the four games is zero-sum with step rewards 0 and +-1.  Results, row i
+ * for env_ids[i], A the game's number of actions:
+ *   visits  [k, A] int32   the root's v
+ *   returns [k, A] int32   the root's w0, times the sign of the root's mover
+ *   action  [k]    int32   the action with most visits; ties: the lowest
+ * Illegal root actions have visits 0 and returns 0.  An env that is over at the call (every env before its first reset
+ * is) reports zeros and action -1.  A result depends on (seed, e, S, R, c_puct, max_plies) and the position only, not
+ * on the order of the ids or on how the pool is sharded.
+ *   EPA_ERR_INVALID: S outside 1 .. EPA_SEARCH_MAX_SIMULATIONS, R outside 1 .. EPA_SEARCH_MAX_LEAF_PLAYOUTS,
+ *     S * R above EPA_PLAYOUT_MAX_REPEATS, max_plies outside 0 .. EPA_PLAYOUT_MAX_PLIES, c_puct not finite or negative,
+ *     k <= 0, more than num_envs ids or an id outside the pool (global ids, as epa_snapshot), and a tree scratch
+ *     (k * (S + 1) nodes) above EPA_SEARCH_MAX_TREE_BYTES: the message names the largest k that fits.
+ *   Every other family fails with EPA_ERR_RUNTIME "search not implemented for this environment".
+ *   A position that is no position of the game (a running game without a legal action) sets the pool's error word:
+ *   epa_search and the next recv fail with EPA_ERR_RUNTIME, and that root's rows are those of an env that is over.
+ * epa_search_actions gives A, the width of a result row (0 for a family without search).
+ * epa_search returns the results in host memory (one stream synchronisation).  epa_search_device writes them to device
+ * memory of the pool's device (4-byte aligned) and only enqueues on epa_stream(pool), like epa_snapshot_device. */
+#define EPA_SEARCH_MAX_SIMULATIONS 4096
+#define EPA_SEARCH_MAX_LEAF_PLAYOUTS 64
+#define EPA_SEARCH_MAX_TREE_BYTES 2147483648ull
+int epa_search_actions(epa_pool* pool, int32_t* out);
+int epa_search(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t leaf_playouts,
+               float c_puct, int32_t max_plies, uint64_t seed, int32_t* visits, int32_t* returns, int32_t* action);
+int epa_search_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t leaf_playouts,
+                      float c_puct, int32_t max_plies, uint64_t seed, void* device_visits, void* device_returns,
+                      void* device_action);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
