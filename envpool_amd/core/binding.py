@@ -325,6 +325,71 @@ class _ShardedPools:
         self._each(run, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
         return visits, returns, action
 
+    # -- guided tree search: one session per shard, rows in request order (host forms only) --
+    def guided_shape(self) -> tuple[int, int, int, int]:
+        return self.pools[0].guided_shape()
+
+    def guided_begin(self, env_ids: Any = None, simulations: int = 64,
+                     c_puct: float = 1.25) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """A session in every shard that owns listed envs, all shards at once.  The search has no random numbers and
+        no dependence on the env id, so the rows are those of the unsharded pool."""
+        if env_ids is None:
+            env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
+        ids = native.check_guided(env_ids, simulations, c_puct)
+        h, w, c, a = self.guided_shape()
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        parts = [np.flatnonzero(shard == s) for s in range(len(self.pools))]
+        k = len(ids)
+        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
+                  np.empty(k, dtype=np.uint8))
+
+        def begin(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct)):
+                o[idx] = part
+
+        self._each(begin, parts)
+        self._guided = (k, a, parts)
+        return leaves
+
+    def _guided_session(self, what: str) -> tuple:
+        g = getattr(self, "_guided", None)
+        if g is None:
+            raise ValueError(f"{what}: the pool has no guided-search session")
+        return g
+
+    def guided_advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        k, a, parts = self._guided_session("guided_advance")
+        priors, values = native.check_guided_rows(priors, values, k, a)
+        h, w, c, _ = self.guided_shape()
+        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
+                  np.empty(k, dtype=np.uint8))
+
+        def advance(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(leaves, p.guided_advance(priors[idx], values[idx])):
+                o[idx] = part
+
+        self._each(advance, parts)
+        return leaves
+
+    def guided_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        k, a, parts = self._guided_session("guided_result")
+        out = (np.empty((k, a), dtype=np.int32), np.empty((k, a), dtype=np.float32), np.empty(k, dtype=np.int32))
+
+        def result(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(out, p.guided_result()):
+                o[idx] = part
+
+        self._each(result, parts)
+        return out
+
+    def guided_end(self) -> None:
+        _, _, parts = self._guided_session("guided_end")
+        self._each(lambda s, p, idx: p.guided_end(), parts)
+        self._guided = None
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -474,6 +539,11 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
             if search is None:  # a pool with its own executor
                 raise RuntimeError("search not implemented for this environment")
             return search(env_ids, simulations, leaf_playouts, c_puct, max_plies, seed)
+
+        def _guided(self) -> Any:
+            if getattr(self._pool, "guided_begin", None) is None:  # a pool with its own executor
+                raise RuntimeError("guided search not implemented for this environment")
+            return self._pool
 
         def _xla(self) -> Any:
             raise RuntimeError("XLA is not available for the MI355X engine")

@@ -491,6 +491,93 @@ class DevicePool:
                                                  int(seed) & (2**64 - 1), ctypes.c_void_p(d_visits),
                                                  ctypes.c_void_p(d_returns), ctypes.c_void_p(d_action)))
 
+    # -- guided tree search --------------------------------------------------------
+    def guided_shape(self) -> tuple[int, int, int, int]:
+        """(H, W, C, A) of a guided search's leaf arrays, as the engine states them; a family without raises."""
+        out = (ctypes.c_int32 * 4)()
+        native.check(self._lib.epa_guided_shape(self._h, out))
+        if out[3] <= 0:
+            raise RuntimeError("guided search not implemented for this environment")
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def _guided_leaves(self, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        h, w, c, a = self.guided_shape()
+        return np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_), np.empty(k, dtype=np.uint8)
+
+    def guided_begin(self, env_ids: Any = None, simulations: int = 64,
+                     c_puct: float = 1.25) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Opens the pool's guided-search session (the PGX board games; RuntimeError("guided search not implemented
+        for this environment") elsewhere) on the current positions of the listed envs (global ids; None: the whole
+        pool), replacing any earlier one: a PUCT search whose tree stays on the device and that stops at every new
+        leaf for the caller's priors and value (include/envpool_amd.h: epa_guided_begin has the contract).  Returns
+        the first leaves (obs bool [k, H, W, C] of the seat to move, mask bool [k, A], status uint8 [k]: 0 evaluate,
+        1 a finished game, 2 nothing pending).  Nothing of the pool changes, and later steps of the pool change
+        nothing in the session."""
+        ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
+        self.guided_shape()
+        obs, mask, status = self._guided_leaves(len(ids))
+        native.check(self._lib.epa_guided_begin(self._h, ids.ctypes.data, len(ids), int(simulations), float(c_puct),
+                                                obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
+        self._guided_k = len(ids)
+        return obs, mask, status
+
+    def guided_advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """One simulation of every root of the session, one launch: `priors` float32 [k, A] and `values` float32 [k]
+        (for the seat that moves at the leaf) answer the leaves handed out last; returns the next leaves.  Call it
+        simulations + 1 times.  Rows that are not finite, negative priors and values outside -1 .. 1 raise ValueError
+        before any launch."""
+        k = getattr(self, "_guided_k", None)
+        if k is None:
+            raise ValueError("guided_advance: the pool has no guided-search session")
+        priors, values = native.check_guided_rows(priors, values, k, self.guided_shape()[3])
+        obs, mask, status = self._guided_leaves(k)
+        native.check(self._lib.epa_guided_advance(self._h, priors.ctypes.data, values.ctypes.data, k, obs.ctypes.data,
+                                                  mask.ctypes.data, status.ctypes.data))
+        return obs, mask, status
+
+    def guided_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(visits int32 [k, A], values float32 [k, A]: the summed values through each root action, seen from the
+        root's mover, action int32 [k]: the most visited legal action, the lowest on ties; -1 and zeros for an env
+        that was over).  Valid any time after guided_begin, complete after simulations + 1 advances."""
+        k = getattr(self, "_guided_k", None)
+        if k is None:
+            raise ValueError("guided_result: the pool has no guided-search session")
+        a = self.guided_shape()[3]
+        visits = np.empty((k, a), dtype=np.int32)
+        values = np.empty((k, a), dtype=np.float32)
+        action = np.empty(k, dtype=np.int32)
+        native.check(self._lib.epa_guided_result(self._h, visits.ctypes.data, values.ctypes.data, action.ctypes.data))
+        return visits, values, action
+
+    def guided_end(self) -> None:
+        """Closes the session and releases its device memory; ValueError without one."""
+        native.check(self._lib.epa_guided_end(self._h))
+        self._guided_k = None
+
+    def guided_begin_device(self, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None, simulations: int = 64,
+                            c_puct: float = 1.25) -> int:
+        """`guided_begin` with the leaves written to device memory at the raw addresses `d_obs` (k H W C bytes),
+        `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k."""
+        ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
+        native.check(self._lib.epa_guided_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                       float(c_puct), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                       ctypes.c_void_p(d_status)))
+        self._guided_k = len(ids)
+        return len(ids)
+
+    def guided_advance_device(self, d_priors: int, d_values: int, k: int, d_obs: int, d_mask: int,
+                              d_status: int) -> None:
+        """`guided_advance` on device memory: `d_priors` (float32 [k, A]) and `d_values` (float32 [k]), 4-byte
+        aligned, are read by the kernel, which treats entries outside their range as 0; only enqueued."""
+        native.check(self._lib.epa_guided_advance_device(self._h, ctypes.c_void_p(d_priors), ctypes.c_void_p(d_values),
+                                                         int(k), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                         ctypes.c_void_p(d_status)))
+
+    def guided_result_device(self, d_visits: int, d_values: int, d_action: int) -> None:
+        """`guided_result` into device memory (4 k A, 4 k A and 4 k bytes, 4-byte aligned); only enqueued."""
+        native.check(self._lib.epa_guided_result_device(self._h, ctypes.c_void_p(d_visits), ctypes.c_void_p(d_values),
+                                                        ctypes.c_void_p(d_action)))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

@@ -126,6 +126,14 @@ def lib() -> ctypes.CDLL:
         "epa_search_actions": (i32, [vp, P(i32)]),
         "epa_search": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, i32, ctypes.c_uint64, vp, vp, vp]),
         "epa_search_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, i32, ctypes.c_uint64, vp, vp, vp]),
+        "epa_guided_shape": (i32, [vp, P(i32)]),
+        "epa_guided_begin": (i32, [vp, vp, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_begin_device": (i32, [vp, vp, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_advance": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "epa_guided_advance_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "epa_guided_result": (i32, [vp, vp, vp, vp]),
+        "epa_guided_result_device": (i32, [vp, vp, vp, vp]),
+        "epa_guided_end": (i32, [vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -160,6 +168,8 @@ EXPORTED_SYMBOLS = [
     "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
     "epa_snapshot_bytes", "epa_snapshot", "epa_restore", "epa_snapshot_device", "epa_restore_device", "epa_fork",
     "epa_playout", "epa_playout_device", "epa_search_actions", "epa_search", "epa_search_device",
+    "epa_guided_shape", "epa_guided_begin", "epa_guided_begin_device", "epa_guided_advance",
+    "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -236,6 +246,39 @@ def check_search(env_ids: Any, simulations: int, leaf_playouts: int, c_puct: flo
     if len(ids) == 0:
         raise ValueError("search env_ids must not be empty")
     return ids
+
+
+def check_guided(env_ids: Any, simulations: int, c_puct: float) -> np.ndarray:
+    """The ids of a guided_begin call as a flat int32 array, after the argument checks every layer makes before the
+    native call: ValueError for simulations outside 1 .. 4096, a c_puct that is not finite or negative, and no ids.
+    (Ids outside the pool and the size of the trees are the engine's to refuse.)"""
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    if not 1 <= int(simulations) <= SEARCH_MAX_SIMULATIONS:
+        raise ValueError(f"guided_begin: simulations = {simulations} must be 1 .. {SEARCH_MAX_SIMULATIONS}")
+    with np.errstate(over="ignore"):
+        c = np.float32(c_puct)
+    if not np.isfinite(c) or c < 0:
+        raise ValueError(f"guided_begin: c_puct = {c_puct} must be finite and >= 0")
+    if len(ids) == 0:
+        raise ValueError("guided_begin env_ids must not be empty")
+    return ids
+
+
+def check_guided_rows(priors: Any, values: Any, k: int, actions: int) -> tuple[np.ndarray, np.ndarray]:
+    """The rows of a host-form guided_advance as contiguous float32 arrays [k, A] and [k]: ValueError for another
+    number of rows, a prior that is negative or not finite, a value outside -1 .. 1 or not a number.  (The device form
+    cannot look at its rows; there the kernel replaces such entries by 0.)"""
+    priors = np.ascontiguousarray(priors, dtype=np.float32)
+    values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if priors.shape != (k, actions):
+        raise ValueError(f"guided_advance: priors of shape {priors.shape} for a session of [{k}, {actions}]")
+    if values.shape != (k,):
+        raise ValueError(f"guided_advance: {len(values)} values for a session of {k} roots")
+    if not (np.isfinite(priors) & (priors >= 0)).all():
+        raise ValueError("guided_advance: priors must be finite and >= 0")
+    if not ((values >= -1) & (values <= 1)).all():
+        raise ValueError("guided_advance: values must be in -1 .. 1")
+    return priors, values
 
 
 def device_count() -> int:

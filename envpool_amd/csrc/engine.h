@@ -138,6 +138,49 @@ struct SearchArgs {
   void* nodes;              // 16-byte aligned
 };
 
+// A device allocation whose life is shorter than its pool's: it has ONE owner, which holds it by value, and goes when
+// the owner says so or dies.  (Everything that lives as long as the pool comes from Pool::DevAlloc and is freed by
+// ~Pool; a buffer of one call comes from Pool::SideScratch.  This is for what a caller opens and closes: the
+// guided-search session.)  Alloc and Free are called with the owner's device selected.
+struct DeviceBlock {
+  char* p{nullptr};
+  size_t bytes{0};
+  DeviceBlock() = default;
+  DeviceBlock(const DeviceBlock&) = delete;
+  DeviceBlock& operator=(const DeviceBlock&) = delete;
+  ~DeviceBlock() { Free(); }
+  void Alloc(size_t n) {
+    Free();
+    EPA_HIP(hipMalloc(reinterpret_cast<void**>(&p), n));
+    bytes = n;
+  }
+  void Free() {  // (hipFree waits for the launches that still use the block)
+    if (p != nullptr) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// One launch of a guided-search session (Pool::GuidedBegin / GuidedAdvance / GuidedResult): the session's k roots,
+// its root records and nodes (family types: Pool::GuidedRootBytes / GuidedNodeBytes), and the device arrays the
+// launch reads or writes -- begin and advance the three leaf arrays, advance the caller's rows, result its three.
+struct GuidedArgs {
+  int k;
+  int simulations;
+  int call;                 // advance: its number t = 0 .. simulations
+  float c_puct;
+  void* roots;              // [k], 16-byte aligned
+  void* nodes;              // [k][simulations + 1], 16-byte aligned
+  const float* priors;      // [k][A]
+  const float* values;      // [k]
+  unsigned char* obs;       // [k][H][W][C]
+  unsigned char* mask;      // [k][A]
+  unsigned char* status;    // [k]
+  int32_t* visits;          // [k][A]
+  float* vals;              // [k][A]
+  int32_t* action;          // [k]
+};
+
 struct Batch {
   // where the batch's kernels write and recv reads: the block's own device allocation (`dev_buf`), or -- a DIRECT
   // step, Pool::SendInto -- the caller's pinned host block, where the results then already are when recv wants them
@@ -329,6 +372,31 @@ class Pool {
   void SearchDevice(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies,
                     uint64_t seed, void* d_visits, void* d_returns, void* d_action);
 
+  // Guided tree search (include/envpool_amd.h: epa_guided_begin; the PGX board games, pgx_guided.hip.h): a search
+  // whose tree stays on the device between launches and that stops at every new leaf, so that the caller supplies
+  // the priors and the leaf values.  A pool has at most one session.  Its memory -- root records, nodes and the
+  // staging of the host forms -- is ONE device allocation of its own (not the side scratch block, which search, render
+  // and snapshot reuse between two advances), released by GuidedEnd, by the next begin and by ~Pool.  Every call
+  // enters through SideEnter like the other side operations: begin sees the state every send issued before it has
+  // left, and the session's launches are ordered behind each other on whichever stream they land.  The host forms
+  // copy through the session's pinned block and synchronise once; the device forms only enqueue and leave through
+  // SideLeave.  A family without the hooks keeps the defaults, and every entry point throws
+  // std::runtime_error("guided search not implemented for this environment").
+  virtual bool HasGuided() const { return false; }
+  virtual void GuidedShape(int32_t shape[4]) const { shape[0] = shape[1] = shape[2] = shape[3] = 0; }  // H, W, C, A
+  virtual size_t GuidedNodeBytes() const { return 0; }   // multiples of 16
+  virtual size_t GuidedRootBytes() const { return 0; }
+  virtual void GuidedBegin(const int* d_ids, const GuidedArgs& a);
+  virtual void GuidedAdvance(const GuidedArgs& a);
+  virtual void GuidedResult(const GuidedArgs& a);
+  // obs / mask / status: host arrays (device == false) or device pointers
+  void GuidedBeginCall(const int32_t* ids, int k, int simulations, float c_puct, void* obs, void* mask, void* status,
+                       bool device);
+  void GuidedAdvanceCall(const void* priors, const void* values, int k, void* obs, void* mask, void* status,
+                         bool device);
+  void GuidedResultCall(void* visits, void* values, void* action, bool device);
+  void GuidedEnd();
+
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
   // kernel that packs (unpack: restores) it for the listed local envs, row i at d_buf + i * ExtraBytes(), on stream_.
@@ -518,6 +586,21 @@ class Pool {
   void CheckPlayout(const int32_t* ids, int k, int repeats, int max_plies, unsigned flags) const;
   // search's checks; throws before anything is enqueued.  Returns the bytes of the tree scratch.
   size_t CheckSearch(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies) const;
+  // the pool's guided-search session
+  struct GuidedSession {
+    bool open{false};
+    DeviceBlock mem;        // the session's one device allocation: roots, nodes, then the host forms' staging
+    char* pinned{nullptr};  // the host forms' pinned block, laid out like the staging
+    int k{0}, simulations{0}, calls{0};
+    float c_puct{0.0f};
+    size_t nodes_off{0}, stage_off{0};
+    // offsets into the staging: priors, values, obs, mask, status, visits, vals, action, the end
+    size_t off[9]{};
+  };
+  GuidedSession guided_;
+  void GuidedFree();                                   // (no session: nothing)
+  void GuidedRequire(const char* what) const;          // throws without a session
+  GuidedArgs GuidedArgsOf(bool device) const;          // the session's pointers; staging arrays for a host form
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

@@ -18,12 +18,15 @@
 // Render: pgx_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
 // Playout: pgx_playout.hip.h, one (env, repeat) per lane, the whole game in registers (PgxPlayoutKernel).
 // Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
+// Guided search: pgx_guided.hip.h, one wave per root and one launch per simulation, the tree in the session's own
+// memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult).
 #include <algorithm>
 #include <string>
 
 #include "device_common.hip.h"
 #include "engine.h"
 #include "pgx_env.hip.h"
+#include "pgx_guided.hip.h"
 #include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
 #include "pgx_search.hip.h"
@@ -35,6 +38,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr unsigned kErrState = 1;   // set_state words that are no position of the game
 constexpr unsigned kErrSearch = 2;  // a search met a running position without a legal action, or a path past the cap
+constexpr unsigned kErrGuided = 3;  // the same, met by a guided search
 
 // key K's section of rows [row0, row0 + nrows) of the launch, written by the whole block
 template <int G, int K>
@@ -374,6 +378,229 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
   }
 }
 
+// Guided search (pgx_guided.hip.h): the search above cut into launches at every new leaf, so that the caller's model
+// supplies the priors and the leaf value.  One wave per root, one block per wave; block i works on root i of the
+// session: its GuidedRoot record and its S + 1 nodes, which stay in the session's memory between launches.
+//   lane ownership  as in PgxSearchKernel: lane j owns actions j and j + 64 of every node and is the only lane that
+//                   writes their child / v / w0 / p -- at the node's making, when the priors arrive, at expansion and
+//                   in backup.  The priors row of the root is read coalesced by the owning lanes.
+//   control flow    the status, the pending leaf, the picked action and the child are wave-uniform: they come out of a
+//                   load of one address, a butterfly reduction or a register broadcast.
+//   hand-offs       lane 0 stores a new node's State and term0 and the root record with its path; other lanes load
+//                   them in a LATER launch.  Inside a launch the backup's owner lanes store v / w0 that the same lanes
+//                   load in the descent.  Both sit between wavefront-scope release and acquire fences, so neither the
+//                   compiler nor the memory pipeline reorders them.
+//   leaves          the pending leaf's obs and mask rows are written by the whole wave from the leaf's State, which
+//                   every lane holds in registers, in 16-byte words where the row's alignment allows (as EmitKey).
+template <class F>
+__device__ __forceinline__ void GuidedEmitRow(unsigned char* base, int total, int lane, F elem) {
+  const int mis = (int)((uintptr_t)base & 15);
+  const int head = std::min(total, mis == 0 ? 0 : 16 - mis);
+  const int words = (total - head) / 16;
+  const int tail = head + words * 16;
+  for (int i = lane; i < head; i += kSearchBlock) base[i] = (unsigned char)elem(i);
+  for (int c = lane; c < words; c += kSearchBlock) {
+    const int i0 = head + c * 16;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j >> 2] |= (elem(i0 + j) & 0xffu) << (8 * (j & 3));
+    *reinterpret_cast<uint4*>(base + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  for (int i = tail + lane; i < total; i += kSearchBlock) base[i] = (unsigned char)elem(i);
+}
+
+// row `row` of the three leaf arrays: the position `s` for status 0, zeros otherwise
+template <int G>
+__device__ __forceinline__ void GuidedEmitLeaf(const GuidedArgs& a, int row, int lane, int status,
+                                               const pgx::State& s) {
+  constexpr int A = pgx::Dims<G>::A, OB = pgx::GuidedObsElems<G>();
+  pgx::View view{};
+  view.s = s;
+  const int mover = pgx::SearchMover<G>(s);
+  const bool live = status == pgx::kGuidedEvaluate;
+  GuidedEmitRow(a.obs + (size_t)row * OB, OB, lane,
+                [&](int i) { return live ? pgx::GuidedObsElem<G>(view, mover, i) : 0u; });
+  GuidedEmitRow(a.mask + (size_t)row * A, A, lane, [&](int i) { return live ? pgx::GuidedMaskElem<G>(view, i) : 0u; });
+  if (lane == 0) a.status[row] = (unsigned char)status;
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedBegin(CommonDev cm, const pgx::State* st,
+                                                               const int* __restrict__ ids, GuidedArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int e = ids[row];
+  const bool over = cm.done[e] != 0;  // (an env before its first reset is)
+  const pgx::State root = st[e];
+  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  if (lane == 0) {
+    n0.s = root;
+    n0.term0 = 0;
+    pgx::GuidedClearRoot(static_cast<pgx::GuidedRoot*>(a.roots)[row], over);
+  }
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(n0, lane + kSearchBlock * j);
+  }
+  WaveRelease();
+  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, unsigned* err) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int S = a.simulations;
+  pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[row];
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)(S + 1);
+  WaveAcquire();
+  int status = rec.status;
+  pgx::State s{};  // the pending leaf's position when the launch ends
+  if (status != pgx::kGuidedIdle) {
+    Node& leaf = nodes[rec.pending];
+    float val0;
+    if (status == pgx::kGuidedEvaluate) {
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        const int act = lane + kSearchBlock * j;
+        if (act < A) leaf.p[act] = pgx::GuidedClean(a.priors[(size_t)row * A + act]);
+      }
+      val0 = (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[row]);
+    } else {
+      val0 = (float)leaf.term0;
+    }
+    const int backed = rec.depth;
+    for (int d = 0; d < backed; ++d) {
+      const int p = rec.path[d];
+      const int act = p & 255;
+      if ((act & (kSearchBlock - 1)) == lane) {
+        Node& nd = nodes[p >> 8];
+        nd.v[act] += 1;
+        nd.w0[act] += val0;
+      }
+    }
+    WaveRelease();
+    if (a.call >= S) {
+      status = pgx::kGuidedIdle;
+      if (lane == 0) rec.status = status;
+    } else {
+      int node = 0, depth = 0, count = rec.count;
+      bool broken = false;
+      WaveAcquire();
+      s = nodes[0].s;
+      for (;;) {
+        Node& nd = nodes[node];
+        int child[SL], v[SL];
+        float w0[SL], pr[SL];
+        int own = 0;
+#pragma unroll
+        for (int j = 0; j < SL; ++j) {
+          const int act = lane + kSearchBlock * j;
+          child[j] = -1;
+          v[j] = 0;
+          w0[j] = pr[j] = 0.0f;
+          if (act < A) {
+            child[j] = nd.child[act];
+            v[j] = nd.v[act];
+            w0[j] = nd.w0[act];
+            pr[j] = nd.p[act];
+          }
+          own += v[j];
+        }
+        const int total = WaveSum(own);
+        const int sign = pgx::SearchSign<G>(s);
+        pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+        for (int j = 0; j < SL; ++j) {
+          const int act = lane + kSearchBlock * j;
+          if (act < A && pgx::Has(s.m, act)) {
+            mine = pgx::SearchBetter(
+                mine, pgx::SearchPick{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), act, 1});
+          }
+        }
+        const int act = WaveBest(mine).action;
+        // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
+        if (act < 0 || depth >= pgx::kSearchMaxPath) {
+          broken = true;
+          break;
+        }
+        if (lane == 0) rec.path[depth] = node << 8 | act;
+        ++depth;
+        const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
+        int c = __shfl(child[0], owner, kSearchBlock);
+        if (SL > 1) {
+          const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
+          c = slot == 1 ? c1 : c;
+        }
+        if (c < 0) {
+          if (count > S) {  // (one node per call: never; the session's memory ends here)
+            broken = true;
+            break;
+          }
+          c = count++;
+          if (lane == owner) nd.child[act] = c;
+          Node& nn = nodes[c];
+          pgx::State s2;
+          const int term0 = pgx::SearchExpand<G>(s, act, s2);
+          if (lane == 0) {
+            nn.s = s2;
+            nn.term0 = term0;
+          }
+#pragma unroll
+          for (int j = 0; j < SL; ++j) {
+            if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(nn, lane + kSearchBlock * j);
+          }
+          node = c;
+          s = s2;
+          break;
+        }
+        node = c;
+        WaveAcquire();
+        s = nodes[node].s;
+        if (s.done) break;
+      }
+      status = broken ? pgx::kGuidedIdle : s.done ? pgx::kGuidedTerminal : pgx::kGuidedEvaluate;
+      if (lane == 0) {
+        rec.count = count;
+        rec.pending = node;
+        rec.status = status;
+        rec.depth = broken ? 0 : depth;
+        if (broken) *err = kErrGuided;
+      }
+    }
+    WaveRelease();
+  }
+  GuidedEmitLeaf<G>(a, row, lane, status, s);
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const pgx::GuidedRoot& rec = static_cast<const pgx::GuidedRoot*>(a.roots)[row];
+  const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  WaveAcquire();
+  const bool over = rec.over != 0;
+  const pgx::State root = n0.s;
+  const float sign = (float)pgx::SearchSign<G>(root);
+  pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    if (act < A) {
+      const int v = over ? 0 : n0.v[act];
+      a.visits[(size_t)row * A + act] = v;
+      a.vals[(size_t)row * A + act] = over ? 0.0f : sign * n0.w0[act];
+      if (!over && pgx::Has(root.m, act)) mine = pgx::SearchBetter(mine, pgx::SearchPick{(float)v, act, 1});
+    }
+  }
+  const int best = WaveBest(mine).action;  // (-1 without a legal action)
+  if (lane == 0) a.action[row] = best;
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -439,7 +666,24 @@ class PgxPool : public Pool {
     hipLaunchKernelGGL(PgxSearchKernel<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
                        a, cfg_.env_id_offset, err_dev_);
   }
+  bool HasGuided() const override { return true; }
+  void GuidedShape(int32_t shape[4]) const override {
+    shape[0] = pgx::Dims<G>::H, shape[1] = pgx::Dims<G>::W, shape[2] = pgx::Dims<G>::C, shape[3] = pgx::Dims<G>::A;
+  }
+  size_t GuidedNodeBytes() const override { return sizeof(pgx::GuidedNode<G>); }
+  size_t GuidedRootBytes() const override { return sizeof(pgx::GuidedRoot); }
+  void GuidedBegin(const int* d_ids, const GuidedArgs& a) override {
+    hipLaunchKernelGGL(PgxGuidedBegin<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
+                       a);
+  }
+  void GuidedAdvance(const GuidedArgs& a) override {
+    hipLaunchKernelGGL(PgxGuidedAdvance<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a, err_dev_);
+  }
+  void GuidedResult(const GuidedArgs& a) override {
+    hipLaunchKernelGGL(PgxGuidedResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+  }
   std::string ErrorText(unsigned code) const override {
+    if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";
     if (code == kErrSearch) return "PGX: search met a position that is no position of the game";
     return Pool::ErrorText(code);

@@ -1,0 +1,136 @@
+// PGX guided tree search: PUCT selection over a tree that lives on the device between launches, with the priors and
+// the leaf values supplied by the caller (AlphaZero-style), as __host__ __device__ pieces shared by the stepwise
+// kernels (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult in pgx.hip, one wave per root) and the g++ host harness
+// of the tests (tests/cpu_harness/pgx_guided_host.cpp, which walks a wave's lanes as loops).
+//
+// The contract (DESIGN.md "PGX guided search").  S = simulations, A = Dims<G>::A.  A session covers k listed roots of
+// one pool; each root has up to S + 1 nodes.  A node holds its State, `term0` (seat 0's reward of the step that made
+// the node, int) and per action a: child[a] (int32, -1: none), v[a] (int32 visits), w0[a] (float32, seat 0's summed
+// value through the edge) and p[a] (float32 prior).  Per root the session keeps the node count, the PENDING LEAF (a
+// node index), its status and the current path of (node, action) pairs, at most kSearchMaxPath.
+//   status 0: evaluate this leaf;  1: the leaf is a finished game, its value is known and the caller's row is ignored;
+//          2: nothing is pending: the root was over at begin, or the session has used all its simulations.
+//
+//   begin(ids, S, c_puct):
+//     per root: node 0 = the env's position; path = []; pending = 0; status = the env is over ? 2 : 0
+//     emit leaves.
+//   advance(priors[k, A], values[k]) -- call number t = 0 .. S:
+//     per root with status != 2, L = pending:
+//       status 0: for every a: L.p[a] = clean(priors[i, a]);  val0 = sign(L) * cleanv(values[i])
+//       status 1: val0 = (float) L.term0
+//       for (n, a) in path:  n.v[a] += 1;  n.w0[a] += val0            (float32 add)
+//       if t == S:  status = 2
+//       else:  node = 0; path = []
+//         loop:
+//           a = the legal action (bit of node.state.m) of the largest score(node, a); ties: the lowest a
+//           path += (node, a)
+//           if node.child[a] < 0:
+//               c = new node {Step<G>(copy of node.state, a), term0};  node.child[a] = c;  node = c;  break
+//           node = node.child[a]
+//           if node.state.done: break
+//         pending = node;  status = node.state.done ? 1 : 0
+//     emit leaves.
+//   score(node, a), float32, every operation correctly rounded, in this order, nothing fused:
+//     V = sum over b of node.v[b] (int);  sign = +1 if seat 0 moves at the node else -1  (SearchSign<G>)
+//     q = node.v[a] > 0 ? (sign * node.w0[a]) / (float) node.v[a] : 0.0f
+//     score = q + ((c_puct * node.p[a]) * sqrtf((float)(V + 1))) / (float)(1 + node.v[a])
+//   clean(x) = (x >= 0 && x <= FLT_MAX) ? x : 0.0f       cleanv(x) = (x >= -1 && x <= 1) ? x : 0.0f
+// values[i] is the value of the leaf for the seat that moves there -- the seat whose observation was emitted.  Priors
+// are used as given (the caller normalises them and mixes in root noise); entries of illegal actions are never read
+// by a pick.  clean / cleanv make every input bit pattern give a defined result.
+//
+// Emitted leaves, for all k rows: obs bool [k, H, W, C], the observation row of the seat that moves at the pending
+// leaf, element for element what a step into that position returns for that seat (pgx::Elem, kObs); mask bool [k, A],
+// the position's legal-action mask; status uint8 [k].  Rows of status 1 or 2 are all zeros in obs and mask.
+// Result: visits = the root's v, values = the root's w0 times the root mover's sign, action = the most visited legal
+// action (ties: the lowest), -1 and zero rows for a root that was over at begin.
+// A running position without a legal action, or a path past kSearchMaxPath, is no position of the game: that root
+// ends with status 2 (the kernel also sets the pool's error word, the harness returns -3).
+//
+// There are no random numbers.  Only seat 0's value is stored, as in pgx_search.hip.h: the games are zero-sum.  Build
+// without fast-math and with -ffp-contract=off.
+#ifndef ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
+#define ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
+
+#include <cfloat>
+#include <cmath>
+
+#include "pgx_search.hip.h"
+
+namespace epa {
+namespace pgx {
+
+enum GuidedStatus : int { kGuidedEvaluate = 0, kGuidedTerminal = 1, kGuidedIdle = 2 };
+
+// One node in the session's memory.  The per-action arrays are action-major, so the loads of a wave's lanes (lane j:
+// entries j and j + 64) are contiguous.  The State is written by one lane when the node is made and read by every
+// lane afterwards; an edge entry is only ever read and written by the lane that owns its action.
+template <int G>
+struct alignas(16) GuidedNode {
+  State s;
+  int32_t term0;
+  int32_t pad[3];
+  int32_t child[SearchEdges<G>()];
+  int32_t v[SearchEdges<G>()];
+  float w0[SearchEdges<G>()];
+  float p[SearchEdges<G>()];
+};
+
+// What the session keeps per root beside its nodes.  A path entry is node << 8 | action.
+struct alignas(16) GuidedRoot {
+  int32_t count;    // nodes made
+  int32_t pending;  // the pending leaf
+  int32_t status;   // GuidedStatus
+  int32_t depth;    // entries of `path`
+  int32_t over;     // the env was over at begin
+  int32_t pad[3];
+  int32_t path[kSearchMaxPath];
+};
+
+PGX_HD inline float GuidedClean(float x) { return (x >= 0.0f && x <= FLT_MAX) ? x : 0.0f; }
+PGX_HD inline float GuidedCleanV(float x) { return (x >= -1.0f && x <= 1.0f) ? x : 0.0f; }
+
+// score(node, a): `v`, `w0`, `p` the edge's, `total` = V, `sign` the node's
+PGX_HD inline float GuidedScore(int v, float w0, float p, int total, int sign, float c_puct) {
+  const float q = v > 0 ? ((float)sign * w0) / (float)v : 0.0f;
+  const float u = (c_puct * p) * sqrtf((float)(total + 1));
+  return q + u / (float)(1 + v);
+}
+
+// a fresh node's edge entry
+template <int G>
+PGX_HD inline void GuidedClearEdge(GuidedNode<G>& n, int a) {
+  n.child[a] = -1;
+  n.v[a] = 0;
+  n.w0[a] = 0.0f;
+  n.p[a] = 0.0f;
+}
+
+// a fresh root record
+PGX_HD inline void GuidedClearRoot(GuidedRoot& r, bool over) {
+  r.count = 1;
+  r.pending = 0;
+  r.status = over ? kGuidedIdle : kGuidedEvaluate;
+  r.depth = 0;
+  r.over = over ? 1 : 0;
+}
+
+// bytes of one emitted obs row: the mover's [H, W, C] block of the kObs key
+template <int G>
+PGX_HD constexpr int GuidedObsElems() {
+  return Dims<G>::H * Dims<G>::W * Dims<G>::C;
+}
+// byte `e` of the emitted obs row of the position in `v` (only v.s is read), mover = SearchMover<G>(v.s)
+template <int G>
+PGX_HD inline uint32_t GuidedObsElem(const View& v, int mover, int e) {
+  return Elem<G>(v, kObs, mover * GuidedObsElems<G>() + e);
+}
+template <int G>
+PGX_HD inline uint32_t GuidedMaskElem(const View& v, int e) {
+  return Elem<G>(v, kMask, e);
+}
+
+}  // namespace pgx
+}  // namespace epa
+
+#endif  // ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_

@@ -35,6 +35,60 @@ class Search(NamedTuple):
     action: np.ndarray   # int32 [k]: the most visited action (the lowest on ties); -1: the env is over
 
 
+class GuidedResult(NamedTuple):
+    """What a guided search returns: numpy arrays over [k listed envs, A actions]."""
+
+    visits: np.ndarray  # int32 [k, A]: simulations through each root action
+    values: np.ndarray  # float32 [k, A]: summed leaf values through it, seen from the root's mover
+    action: np.ndarray  # int32 [k]: the most visited legal action (the lowest on ties); -1: the env was over
+
+
+class GuidedSearch:
+    """A pool's guided-search session (`env.guided_search`): a PUCT search of every listed env whose tree stays on
+    the device and that stops at every new leaf for the caller's priors and value.
+
+        gs = env.guided_search(ids, simulations=64)
+        result = gs.run(lambda obs, mask, status: model(obs, mask))     # S + 1 evaluations, then closes
+
+    or step by step: `leaves` -> (obs bool [k, H, W, C] of the seat to move, mask bool [k, A], status uint8 [k]:
+    0 evaluate, 1 a finished game (the row is ignored), 2 nothing pending); `advance(priors [k, A], values [k])`
+    answers them and fetches the next; `result()` at any time; `close()` releases the device memory."""
+
+    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float):
+        self._pool = pool
+        self.simulations = int(simulations)
+        self.calls = 0
+        self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct))
+
+    def advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        if self._pool is None:
+            raise ValueError("guided search: the session is closed")
+        if self.calls > self.simulations:
+            raise ValueError(f"guided_advance: call number {self.calls} is above simulations = {self.simulations}")
+        self.leaves = self._pool.guided_advance(priors, values)
+        self.calls += 1
+        return self.leaves
+
+    def result(self) -> GuidedResult:
+        if self._pool is None:
+            raise ValueError("guided search: the session is closed")
+        return GuidedResult(*self._pool.guided_result())
+
+    def run(self, evaluate: Any) -> GuidedResult:
+        """Calls `evaluate(obs, mask, status) -> (priors, values)` until simulations + 1 advances are made, returns
+        the result and closes the session."""
+        while self.calls <= self.simulations:
+            self.advance(*evaluate(*self.leaves))
+        out = self.result()
+        self.close()
+        return out
+
+    def close(self) -> None:
+        if self._pool is not None:
+            pool, self._pool = self._pool, None
+            pool.guided_end()
+
+
 def _normalize_env_id(env_id: Any) -> Any:
     """env ids as an int32 array of at least one dimension (envpool.py:38-48).  Array-likes with their own `astype`
     (device arrays) keep their type; everything else goes through numpy."""
@@ -200,6 +254,16 @@ class EnvPoolMixin(ABC):
                                   simulations, leaf_playouts, c_puct, max_plies)
         return Search(*self._search(ids, int(simulations), int(leaf_playouts), float(c_puct), int(max_plies),
                                     int(seed)))
+
+    def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25) -> GuidedSearch:
+        """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
+        (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
+        launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
+        pool has one at a time, and a new one replaces it.  Nothing of the pool changes.  The arguments are checked
+        before any native call."""
+        ids = native.check_guided(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
+                                  simulations, c_puct)
+        return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct))
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -230,3 +230,44 @@ def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_pl
     _order_both_ways(pool, dev, lambda: pool.search_device(visits.data_ptr(), returns.data_ptr(), action.data_ptr(),
                                                            ids, simulations, leaf_playouts, c_puct, max_plies, seed))
     return visits, returns, action
+
+
+def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
+                         c_puct: float = 1.25) -> tuple[Any, Any, Any]:
+    """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
+    gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
+    and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
+    Every launch is ordered against torch's current stream like `search_device`: the kernel behind what torch has
+    enqueued (the evaluator), the current stream behind the kernel.  Returns (visits int32 [k, A], values float32
+    [k, A], action int32 [k]) on the device and closes the session."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_guided(env_ids, simulations, c_puct)
+    h, w, c, a = pool.guided_shape()
+    k = len(ids)
+    dev = torch.device("cuda", pool.device)
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(),
+                                                                 ids, simulations, c_puct))
+    for _ in range(int(simulations) + 1):
+        priors, values = evaluate(obs, mask, status)
+        priors = priors.to(device=dev, dtype=torch.float32).contiguous()
+        values = values.to(device=dev, dtype=torch.float32).contiguous().view(-1)
+        if tuple(priors.shape) != (k, a) or tuple(values.shape) != (k,):
+            pool.guided_end()
+            raise ValueError(f"guided_search_device: evaluate returned priors {tuple(priors.shape)} and values "
+                             f"{tuple(values.shape)} for a session of [{k}, {a}]")
+        _order_both_ways(pool, dev, lambda: pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k,
+                                                                       obs.data_ptr(), mask.data_ptr(),
+                                                                       status.data_ptr()))
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_result_device(visits.data_ptr(), vals.data_ptr(),
+                                                                  action.data_ptr()))
+    pool.guided_end()
+    return visits, vals, action

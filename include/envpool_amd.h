@@ -485,6 +485,85 @@ int epa_search_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t
                       float c_puct, int32_t max_plies, uint64_t seed, void* device_visits, void* device_returns,
                       void* device_action);
 
+/* Guided tree search (no reference analogue; the four PGX board games): a PUCT search whose tree lives on the device
+ * between calls and that stops at every new leaf, so that the caller -- a policy / value model next to the pool in
+ * HBM -- supplies the priors and the leaf values (AlphaZero-style).  One kernel launch per simulation, one wave per
+ * root; no random numbers anywhere.  The contract (csrc/pgx_guided.hip.h), S = simulations, A = the game's actions:
+ *   A SESSION belongs to one pool and covers the k listed roots; a root has up to S + 1 nodes.  A node holds its
+ *   position, term0 (seat 0's reward of the step that made it) and per action a: child[a] (-1: none), v[a] (int32
+ *   visits), w0[a] (float, seat 0's summed value through the edge), p[a] (float prior).  Per root the session keeps the
+ *   node count, the PENDING LEAF, its status and the current path of (node, action) pairs.
+ *   status 0: evaluate this leaf; 1: the leaf is a finished game, its value is known and the caller's row is ignored;
+ *          2: nothing is pending (the root was over at begin, or the session has used all its simulations).
+ *   begin(ids, S, c_puct):
+ *     per root: node 0 = the env's position; path = []; pending = 0; status = 2 if the env is over else 0
+ *     emit leaves.
+ *   advance(priors[k, A], values[k]) -- call number t = 0 .. S:
+ *     per root with status != 2, L = pending:
+ *       status 0: for every a: L.p[a] = clean(priors[i, a]);  val0 = sign(L) * cleanv(values[i])
+ *       status 1: val0 = (float) L.term0
+ *       for (n, a) in path:  n.v[a] += 1;  n.w0[a] += val0            (float add)
+ *       if t == S:  status = 2
+ *       else:  node = 0; path = []
+ *         loop:
+ *           a = the legal action of the largest score(node, a); ties: the lowest a
+ *           path += (node, a)
+ *           if node.child[a] < 0:
+ *               c = a new node: node's position stepped by a, term0 = seat 0's reward of that step
+ *               node.child[a] = c;  node = c;  break
+ *           node = node.child[a]
+ *           if node's game is over: break
+ *         pending = node;  status = 1 if node's game is over else 0
+ *     emit leaves.
+ *   score(node, a), float, every operation correctly rounded, in this order, nothing fused:
+ *     V = sum over b of node.v[b];  sign = +1 if seat 0 moves at the node else -1
+ *     q = node.v[a] > 0 ? (sign * node.w0[a]) / (float) node.v[a] : 0
+ *     score = q + ((c_puct * node.p[a]) * sqrtf((float)(V + 1))) / (float)(1 + node.v[a])
+ *   clean(x) = (x >= 0 && x <= FLT_MAX) ? x : 0       cleanv(x) = (x >= -1 && x <= 1) ? x : 0
+ * values[i] is the leaf's value for the seat that moves there, the seat whose observation was emitted.  Priors are used
+ * as given: the caller normalises them and mixes in root noise; entries of illegal actions are never read by a pick.
+ * clean / cleanv give every bit pattern a defined result in the _device forms, which cannot look at their rows; the
+ * host forms refuse such a row (any row, ignored ones included) with EPA_ERR_INVALID before any launch.
+ * Emitted leaves -- epa_guided_begin and every epa_guided_advance write, for all k rows:
+ *   obs    [k, H, W, C] bool   the observation of the seat that moves at the pending leaf, element for element what a
+ *                              step into that position returns in that seat's "obs" row
+ *   mask   [k, A]       bool   the position's legal-action mask
+ *   status [k]          uint8
+ * Rows of status 1 or 2 are all zeros in obs and mask.
+ * epa_guided_result is valid any time after begin and complete after S + 1 advances:
+ *   visits [k, A] int32   the root's v
+ *   values [k, A] float   the root's w0 times the sign of the root's mover
+ *   action [k]    int32   the most visited legal action, the lowest on ties; -1, and zero rows, for a root that was over
+ * Session rules.  A pool has at most one session; a second begin replaces it.  begin sees the state after every send /
+ * reset issued before it, as epa_snapshot does.  The session works on its own copies of the positions: stepping the
+ * pool between advances changes nothing in the session, and the session changes nothing in the pool.  Its memory is
+ * one device allocation owned by the pool -- not the scratch block epa_search, epa_render and epa_snapshot reuse --
+ * released by epa_guided_end, by the next begin and by epa_destroy.  A result depends on the arguments, the positions
+ * and the caller's numbers only: not on id order, repeated ids or sharding.
+ *   EPA_ERR_INVALID, before any launch: S outside 1 .. EPA_SEARCH_MAX_SIMULATIONS; c_puct negative or not finite; the
+ *     id checks of epa_search; trees (k * (S + 1) nodes) above EPA_SEARCH_MAX_TREE_BYTES: the message names the largest k
+ *     that fits; advance, result or end without a session; a call number above S; priors / values of k != the session's
+ *     rows.
+ *   Every other family fails with EPA_ERR_RUNTIME "guided search not implemented for this environment".
+ *   A position that is no position of the game (a running game without a legal action, or a path past the cap) ends
+ *   that root with status 2 and sets the pool's error word, as for epa_search.
+ * epa_guided_shape gives {H, W, C, A} (zeros for a family without guided search).
+ * The host forms copy through pinned memory and synchronise once.  The _device forms take and write device pointers
+ * of the pool's device (float and int32 arrays 4-byte aligned) and only enqueue on epa_stream(pool).  epa_guided_end
+ * has one form: it moves no data. */
+int epa_guided_shape(epa_pool* pool, int32_t* out);
+int epa_guided_begin(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, float c_puct,
+                     uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_guided_begin_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, float c_puct,
+                            void* device_obs, void* device_mask, void* device_status);
+int epa_guided_advance(epa_pool* pool, const float* priors, const float* values, int32_t k, uint8_t* obs,
+                       uint8_t* mask, uint8_t* status);
+int epa_guided_advance_device(epa_pool* pool, const void* device_priors, const void* device_values, int32_t k,
+                              void* device_obs, void* device_mask, void* device_status);
+int epa_guided_result(epa_pool* pool, int32_t* visits, float* values, int32_t* action);
+int epa_guided_result_device(epa_pool* pool, void* device_visits, void* device_values, void* device_action);
+int epa_guided_end(epa_pool* pool);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).

@@ -1,0 +1,116 @@
+"""Guided tree search of the PGX games on one MI355X: the time of one `advance` launch in the device form and the
+roots x simulations per second of whole sessions, with a constant-prior evaluator so that the kernels are timed and
+not a model; beside them `search()` with one leaf playout on the same positions.
+
+    python tools/bench_guided.py [--games Othello,Hex] [--sizes 4096] [--reps 5] [--warmup 1] [--out FILE]
+
+Per game and k freshly reset roots, S = 64 simulations, one JSON line:
+  advance   after `warmup` whole sessions, `reps` sessions; every one of a session's S + 1 `guided_advance_device`
+            launches sits between its own pair of events on the pool's stream; the median over all of them, and the
+            median of the launches t = S/2 .. S-1 alone (deep trees).  The priors (1 / A everywhere) and values (0) are
+            two tensors made once: no evaluator runs between the launches.
+  session   one pair of events around a session's begin and all its advances; the median over the sessions, and
+            roots x simulations per second = k * S / median
+  search    `torch_interop.search_device(simulations=S, leaf_playouts=1)` on the same pool: 2 warm-up launches, then
+            `reps` launches (a new seed each) each between its own pair of events; the median
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+S, C_PUCT = 64, 1.25
+
+
+def measure(torch, ti, DevicePool, fam, k, args):
+    pool = DevicePool(fam, k, seed=0)
+    dev = torch.device("cuda", pool.device)
+    stream = torch.cuda.ExternalStream(pool.stream, device=dev)
+    ids = torch.arange(k, dtype=torch.int32, device=dev)
+    ti.send_device_tensors(pool, None, ids)  # reset: every env at the start of a game
+    ti.recv_device_tensors(pool)
+    h, w, c, a = pool.guided_shape()
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    priors = torch.full((k, a), 1.0 / a, dtype=torch.float32, device=dev)
+    values = torch.zeros((k,), dtype=torch.float32, device=dev)
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    launches, deep, sessions = [], [], []
+    for rep in range(args.warmup + args.reps):
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(S + 3)]
+        evs[0].record(stream)
+        pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, S, C_PUCT)
+        evs[1].record(stream)
+        for t in range(S + 1):
+            pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k, obs.data_ptr(), mask.data_ptr(),
+                                       status.data_ptr())
+            evs[t + 2].record(stream)
+        pool.guided_result_device(visits.data_ptr(), vals.data_ptr(), action.data_ptr())
+        evs[-1].synchronize()
+        torch.cuda.synchronize(dev)
+        if rep >= args.warmup:
+            ms = [evs[t + 1].elapsed_time(evs[t + 2]) for t in range(S + 1)]
+            launches += ms
+            deep += ms[S // 2:S]
+            sessions.append(evs[0].elapsed_time(evs[-1]))
+    assert bool((visits.sum(1) == S).all()) and bool((status == 2).all())
+    pool.guided_end()
+    for wu in range(2):
+        ti.search_device(pool, None, S, 1, C_PUCT, 0, seed=1000 + wu)
+    torch.cuda.synchronize(dev)
+    search = []
+    for i in range(args.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        ti.search_device(pool, None, S, 1, C_PUCT, 0, seed=i)
+        e1.record(stream)
+        e1.synchronize()
+        search.append(e0.elapsed_time(e1))
+    pool.close()
+    session_ms = float(np.median(sessions))
+    return {"game": fam, "roots": k, "simulations": S,
+            "advance_us_per_launch": round(float(np.median(launches)) * 1e3, 2),
+            "advance_us_per_launch_deep": round(float(np.median(deep)) * 1e3, 2),
+            "advance_us_min_max": [round(min(launches) * 1e3, 2), round(max(launches) * 1e3, 2)],
+            "session_ms": round(session_ms, 3), "session_ms_all": [round(x, 3) for x in sessions],
+            "roots_simulations_per_s": float(k * S / (session_ms * 1e-3)),
+            "search_r1_ms": round(float(np.median(search)), 3),
+            "search_r1_roots_simulations_per_s": float(k * S / (float(np.median(search)) * 1e-3))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", default="Othello,Hex")
+    ap.add_argument("--sizes", default="4096")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    from envpool_amd import torch_interop as ti
+    from envpool_amd.core.device_pool import DevicePool
+
+    sink = open(args.out, "w") if args.out else None
+    for fam in args.games.split(","):
+        for k in [int(x) for x in args.sizes.split(",")]:
+            text = json.dumps(measure(torch, ti, DevicePool, fam, k, args))
+            print(text, flush=True)
+            if sink:
+                sink.write(text + "\n")
+                sink.flush()
+    if sink:
+        sink.close()
+
+
+if __name__ == "__main__":
+    main()
