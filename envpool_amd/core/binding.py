@@ -390,6 +390,65 @@ class _ShardedPools:
         self._each(lambda s, p, idx: p.guided_end(), parts)
         self._guided = None
 
+    # -- Gumbel search: the same sessions with the Gumbel policy; the noise rows follow their ids --
+    def gumbel_actions(self) -> int:
+        return self.pools[0].gumbel_actions()
+
+    def gumbel_begin(self, gumbel: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
+                     c_visit: float = 50.0, c_scale: float = 0.1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """A Gumbel session in every shard that owns listed envs, all shards at once; row i of `gumbel` goes with
+        env_ids[i].  The search depends on the positions and the caller's numbers only, so the rows are those of the
+        unsharded pool."""
+        if env_ids is None:
+            env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
+        ids = native.check_gumbel(env_ids, simulations, max_considered, c_visit, c_scale)
+        self.gumbel_actions()
+        h, w, c, a = self.guided_shape()
+        gumbel = native.check_gumbel_noise(gumbel, len(ids), a)
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        parts = [np.flatnonzero(shard == s) for s in range(len(self.pools))]
+        k = len(ids)
+        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
+                  np.empty(k, dtype=np.uint8))
+
+        def begin(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(leaves, p.gumbel_begin(gumbel[idx], ids[idx], simulations, max_considered, c_visit,
+                                                      c_scale)):
+                o[idx] = part
+
+        self._each(begin, parts)
+        self._guided = (k, a, parts)
+        return leaves
+
+    def gumbel_advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        k, a, parts = self._guided_session("gumbel_advance")
+        logits, values = native.check_gumbel_rows(logits, values, k, a)
+        h, w, c, _ = self.guided_shape()
+        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
+                  np.empty(k, dtype=np.uint8))
+
+        def advance(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(leaves, p.gumbel_advance(logits[idx], values[idx])):
+                o[idx] = part
+
+        self._each(advance, parts)
+        return leaves
+
+    def gumbel_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        k, a, parts = self._guided_session("gumbel_result")
+        out = (np.empty((k, a), dtype=np.int32), np.empty((k, a), dtype=np.float32), np.empty(k, dtype=np.int32),
+               np.empty((k, a), dtype=np.float32))
+
+        def result(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(out, p.gumbel_result()):
+                o[idx] = part
+
+        self._each(result, parts)
+        return out
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -543,6 +602,11 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
         def _guided(self) -> Any:
             if getattr(self._pool, "guided_begin", None) is None:  # a pool with its own executor
                 raise RuntimeError("guided search not implemented for this environment")
+            return self._pool
+
+        def _gumbel(self) -> Any:
+            if getattr(self._pool, "gumbel_begin", None) is None:  # a pool with its own executor
+                raise RuntimeError("gumbel search not implemented for this environment")
             return self._pool
 
         def _xla(self) -> Any:

@@ -518,17 +518,27 @@ class DevicePool:
         obs, mask, status = self._guided_leaves(len(ids))
         native.check(self._lib.epa_guided_begin(self._h, ids.ctypes.data, len(ids), int(simulations), float(c_puct),
                                                 obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
-        self._guided_k = len(ids)
+        self._guided_k, self._guided_policy = len(ids), "puct"
         return obs, mask, status
+
+    def _guided_open(self, what: str, policy: str) -> int:
+        """The open session's k; ValueError without a session, or with one of the other policy (before any native
+        call)."""
+        k = getattr(self, "_guided_k", None)
+        if k is None:
+            raise ValueError(f"{what}: the pool has no guided-search session")
+        if getattr(self, "_guided_policy", "puct") != policy:
+            other = "guided" if policy == "gumbel" else "gumbel"
+            raise ValueError(f"{what}: the pool's session is a {'PUCT guided' if other == 'guided' else 'Gumbel'} "
+                             f"search: use {other}_{what.split('_', 1)[1]}")
+        return k
 
     def guided_advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """One simulation of every root of the session, one launch: `priors` float32 [k, A] and `values` float32 [k]
         (for the seat that moves at the leaf) answer the leaves handed out last; returns the next leaves.  Call it
         simulations + 1 times.  Rows that are not finite, negative priors and values outside -1 .. 1 raise ValueError
         before any launch."""
-        k = getattr(self, "_guided_k", None)
-        if k is None:
-            raise ValueError("guided_advance: the pool has no guided-search session")
+        k = self._guided_open("guided_advance", "puct")
         priors, values = native.check_guided_rows(priors, values, k, self.guided_shape()[3])
         obs, mask, status = self._guided_leaves(k)
         native.check(self._lib.epa_guided_advance(self._h, priors.ctypes.data, values.ctypes.data, k, obs.ctypes.data,
@@ -539,9 +549,7 @@ class DevicePool:
         """(visits int32 [k, A], values float32 [k, A]: the summed values through each root action, seen from the
         root's mover, action int32 [k]: the most visited legal action, the lowest on ties; -1 and zeros for an env
         that was over).  Valid any time after guided_begin, complete after simulations + 1 advances."""
-        k = getattr(self, "_guided_k", None)
-        if k is None:
-            raise ValueError("guided_result: the pool has no guided-search session")
+        k = self._guided_open("guided_result", "puct")
         a = self.guided_shape()[3]
         visits = np.empty((k, a), dtype=np.int32)
         values = np.empty((k, a), dtype=np.float32)
@@ -550,7 +558,7 @@ class DevicePool:
         return visits, values, action
 
     def guided_end(self) -> None:
-        """Closes the session and releases its device memory; ValueError without one."""
+        """Closes the session (of either policy) and releases its device memory; ValueError without one."""
         native.check(self._lib.epa_guided_end(self._h))
         self._guided_k = None
 
@@ -562,7 +570,7 @@ class DevicePool:
         native.check(self._lib.epa_guided_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
                                                        float(c_puct), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
                                                        ctypes.c_void_p(d_status)))
-        self._guided_k = len(ids)
+        self._guided_k, self._guided_policy = len(ids), "puct"
         return len(ids)
 
     def guided_advance_device(self, d_priors: int, d_values: int, k: int, d_obs: int, d_mask: int,
@@ -577,6 +585,90 @@ class DevicePool:
         """`guided_result` into device memory (4 k A, 4 k A and 4 k bytes, 4-byte aligned); only enqueued."""
         native.check(self._lib.epa_guided_result_device(self._h, ctypes.c_void_p(d_visits), ctypes.c_void_p(d_values),
                                                         ctypes.c_void_p(d_action)))
+
+    # -- Gumbel search: the guided-search session's second policy ------------------
+    def gumbel_actions(self) -> int:
+        """A of a Gumbel search's rows; a family without raises."""
+        out = (ctypes.c_int32 * 4)()
+        native.check(self._lib.epa_guided_shape(self._h, out))
+        if out[3] <= 0:
+            raise RuntimeError("gumbel search not implemented for this environment")
+        return int(out[3])
+
+    def gumbel_begin(self, gumbel: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
+                     c_visit: float = 50.0, c_scale: float = 0.1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Opens the pool's guided-search session with the Gumbel policy (include/envpool_amd.h: epa_gumbel_begin has
+        the contract), replacing any earlier session of either policy: Gumbel top-`max_considered` sampling with
+        sequential halving at the root, the caller's logits and values at every new leaf.  `gumbel` float32 [k, A] is
+        the caller's Gumbel(0, 1) noise per root action (zeros: the noise-free evaluation mode); the library draws no
+        random numbers.  Returns the first leaves as `guided_begin` does.  Nothing of the pool changes."""
+        ids = native.check_gumbel(self._ids(env_ids), simulations, max_considered, c_visit, c_scale)
+        a = self.gumbel_actions()
+        gumbel = native.check_gumbel_noise(gumbel, len(ids), a)
+        obs, mask, status = self._guided_leaves(len(ids))
+        native.check(self._lib.epa_gumbel_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                min(int(max_considered), a), float(c_visit), float(c_scale),
+                                                gumbel.ctypes.data, obs.ctypes.data, mask.ctypes.data,
+                                                status.ctypes.data))
+        self._guided_k, self._guided_policy = len(ids), "gumbel"
+        return obs, mask, status
+
+    def gumbel_advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """One simulation of every root of the Gumbel session, one launch: `logits` float32 [k, A] (any sign) and
+        `values` float32 [k] (for the seat that moves at the leaf) answer the leaves handed out last; returns the next
+        leaves.  Call it simulations + 1 times.  Rows that are not finite, logits above 1e30 in magnitude and values
+        outside -1 .. 1 raise ValueError before any launch."""
+        k = self._guided_open("gumbel_advance", "gumbel")
+        logits, values = native.check_gumbel_rows(logits, values, k, self.guided_shape()[3])
+        obs, mask, status = self._guided_leaves(k)
+        native.check(self._lib.epa_gumbel_advance(self._h, logits.ctypes.data, values.ctypes.data, k, obs.ctypes.data,
+                                                  mask.ctypes.data, status.ctypes.data))
+        return obs, mask, status
+
+    def gumbel_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(visits int32 [k, A], values float32 [k, A], action int32 [k]: the recommended move -- the best of the most
+        visited root actions by gumbel + logit + sigma(q); -1 for an env that was over --, weights float32 [k, A]: the
+        improved policy softmax(logits + sigma(completed q)) of the root, the training target).  Valid any time after
+        gumbel_begin, complete after simulations + 1 advances."""
+        k = self._guided_open("gumbel_result", "gumbel")
+        a = self.guided_shape()[3]
+        visits = np.empty((k, a), dtype=np.int32)
+        values = np.empty((k, a), dtype=np.float32)
+        action = np.empty(k, dtype=np.int32)
+        weights = np.empty((k, a), dtype=np.float32)
+        native.check(self._lib.epa_gumbel_result(self._h, visits.ctypes.data, values.ctypes.data, action.ctypes.data,
+                                                 weights.ctypes.data))
+        return visits, values, action, weights
+
+    def gumbel_begin_device(self, d_gumbel: int, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None,
+                            simulations: int = 32, max_considered: int = 16, c_visit: float = 50.0,
+                            c_scale: float = 0.1) -> int:
+        """`gumbel_begin` on device memory: the noise is read at the raw address `d_gumbel` (float32 [k, A], 4-byte
+        aligned; the kernel takes entries that are not finite as 0) and the leaves are written at `d_obs`, `d_mask`
+        and `d_status`: only enqueued on the pool's stream.  Returns k."""
+        ids = native.check_gumbel(self._ids(env_ids), simulations, max_considered, c_visit, c_scale)
+        a = self.gumbel_actions()
+        native.check(self._lib.epa_gumbel_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                       min(int(max_considered), a), float(c_visit), float(c_scale),
+                                                       ctypes.c_void_p(d_gumbel), ctypes.c_void_p(d_obs),
+                                                       ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        self._guided_k, self._guided_policy = len(ids), "gumbel"
+        return len(ids)
+
+    def gumbel_advance_device(self, d_logits: int, d_values: int, k: int, d_obs: int, d_mask: int,
+                              d_status: int) -> None:
+        """`gumbel_advance` on device memory: `d_logits` (float32 [k, A]) and `d_values` (float32 [k]), 4-byte
+        aligned, are read by the kernel, which treats entries outside their range as 0; only enqueued."""
+        self._guided_open("gumbel_advance", "gumbel")
+        native.check(self._lib.epa_gumbel_advance_device(self._h, ctypes.c_void_p(d_logits), ctypes.c_void_p(d_values),
+                                                         int(k), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                         ctypes.c_void_p(d_status)))
+
+    def gumbel_result_device(self, d_visits: int, d_values: int, d_action: int, d_weights: int) -> None:
+        """`gumbel_result` into device memory (4 k A, 4 k A, 4 k and 4 k A bytes, 4-byte aligned); only enqueued."""
+        self._guided_open("gumbel_result", "gumbel")
+        native.check(self._lib.epa_gumbel_result_device(self._h, ctypes.c_void_p(d_visits), ctypes.c_void_p(d_values),
+                                                        ctypes.c_void_p(d_action), ctypes.c_void_p(d_weights)))
 
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:

@@ -134,6 +134,12 @@ def lib() -> ctypes.CDLL:
         "epa_guided_result": (i32, [vp, vp, vp, vp]),
         "epa_guided_result_device": (i32, [vp, vp, vp, vp]),
         "epa_guided_end": (i32, [vp]),
+        "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
+        "epa_gumbel_begin_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
+        "epa_gumbel_advance": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "epa_gumbel_advance_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "epa_gumbel_result": (i32, [vp, vp, vp, vp, vp]),
+        "epa_gumbel_result_device": (i32, [vp, vp, vp, vp, vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -170,6 +176,8 @@ EXPORTED_SYMBOLS = [
     "epa_playout", "epa_playout_device", "epa_search_actions", "epa_search", "epa_search_device",
     "epa_guided_shape", "epa_guided_begin", "epa_guided_begin_device", "epa_guided_advance",
     "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
+    "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
+    "epa_gumbel_result", "epa_gumbel_result_device",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -279,6 +287,54 @@ def check_guided_rows(priors: Any, values: Any, k: int, actions: int) -> tuple[n
     if not ((values >= -1) & (values <= 1)).all():
         raise ValueError("guided_advance: values must be in -1 .. 1")
     return priors, values
+
+
+def check_gumbel(env_ids: Any, simulations: int, max_considered: int, c_visit: float, c_scale: float) -> np.ndarray:
+    """The ids of a gumbel_begin call as a flat int32 array, after the argument checks every layer makes before the
+    native call: ValueError for simulations outside 1 .. 4096, max_considered below 1 (one above the game's actions
+    counts as all of them), a c_visit or c_scale that is not finite or negative, and no ids."""
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    if not 1 <= int(simulations) <= SEARCH_MAX_SIMULATIONS:
+        raise ValueError(f"gumbel_begin: simulations = {simulations} must be 1 .. {SEARCH_MAX_SIMULATIONS}")
+    if not 1 <= int(max_considered) < 2**31:
+        raise ValueError(f"gumbel_begin: max_considered = {max_considered} must be at least 1")
+    for name, c in (("c_visit", c_visit), ("c_scale", c_scale)):
+        with np.errstate(over="ignore"):
+            c32 = np.float32(c)
+        if not np.isfinite(c32) or c32 < 0:
+            raise ValueError(f"gumbel_begin: {name} = {c} must be finite and >= 0")
+    if len(ids) == 0:
+        raise ValueError("gumbel_begin env_ids must not be empty")
+    return ids
+
+
+def check_gumbel_noise(gumbel: Any, k: int, actions: int) -> np.ndarray:
+    """The Gumbel noise of a host-form gumbel_begin as a contiguous float32 array [k, A]: ValueError for another
+    shape or an entry that is not finite."""
+    gumbel = np.ascontiguousarray(gumbel, dtype=np.float32)
+    if gumbel.shape != (k, actions):
+        raise ValueError(f"gumbel_begin: gumbel of shape {gumbel.shape} for a session of [{k}, {actions}]")
+    if not np.isfinite(gumbel).all():
+        raise ValueError("gumbel_begin: gumbel must be finite")
+    return gumbel
+
+
+def check_gumbel_rows(logits: Any, values: Any, k: int, actions: int) -> tuple[np.ndarray, np.ndarray]:
+    """The rows of a host-form gumbel_advance as contiguous float32 arrays [k, A] and [k]: ValueError for another
+    number of rows, a logit that is not finite or above 1e30 in magnitude (negative logits are fine), a value outside
+    -1 .. 1 or not a number.  (The device form cannot look at its rows; there the kernel replaces such entries by 0.)"""
+    with np.errstate(over="ignore"):
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+    values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if logits.shape != (k, actions):
+        raise ValueError(f"gumbel_advance: logits of shape {logits.shape} for a session of [{k}, {actions}]")
+    if values.shape != (k,):
+        raise ValueError(f"gumbel_advance: {len(values)} values for a session of {k} roots")
+    if not (np.abs(logits) <= np.float32(1e30)).all():
+        raise ValueError("gumbel_advance: logits must be finite and at most 1e30 in magnitude")
+    if not ((values >= -1) & (values <= 1)).all():
+        raise ValueError("gumbel_advance: values must be in -1 .. 1")
+    return logits, values
 
 
 def device_count() -> int:

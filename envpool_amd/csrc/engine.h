@@ -181,6 +181,29 @@ struct GuidedArgs {
   int32_t* action;          // [k]
 };
 
+// One launch of a Gumbel-search session (Pool::GumbelBegin / GumbelAdvance / GumbelResult; pgx_gumbel.hip.h): as
+// GuidedArgs, with the Gumbel noise at begin, logits instead of priors, and the improved policy among the results.
+struct GumbelArgs {
+  int k;
+  int simulations;
+  int call;                 // advance: its number t = 0 .. simulations
+  int considered;           // m: the most root actions considered
+  float c_visit;
+  float c_scale;
+  void* roots;              // [k], 16-byte aligned
+  void* nodes;              // [k][simulations + 1], 16-byte aligned
+  const float* gumbel;      // begin: [k][A]
+  const float* logits;      // [k][A]
+  const float* values;      // [k]
+  unsigned char* obs;       // [k][H][W][C]
+  unsigned char* mask;      // [k][A]
+  unsigned char* status;    // [k]
+  int32_t* visits;          // [k][A]
+  float* vals;              // [k][A]
+  int32_t* action;          // [k]
+  float* weights;           // [k][A]
+};
+
 struct Batch {
   // where the batch's kernels write and recv reads: the block's own device allocation (`dev_buf`), or -- a DIRECT
   // step, Pool::SendInto -- the caller's pinned host block, where the results then already are when recv wants them
@@ -397,6 +420,23 @@ class Pool {
   void GuidedResultCall(void* visits, void* values, void* action, bool device);
   void GuidedEnd();
 
+  // Gumbel search (include/envpool_amd.h: epa_gumbel_begin; pgx_gumbel.hip.h): the guided-search session with a
+  // second selection policy.  It IS the pool's guided-search session -- the same single-owner allocation, released by
+  // GuidedEnd, by the next begin of either policy and by ~Pool -- and enters through the side-operation path as the
+  // Guided calls do.  The other policy's advance and result refuse an open session with std::invalid_argument.  A
+  // family that has guided search has Gumbel search; the others throw
+  // std::runtime_error("gumbel search not implemented for this environment").
+  virtual size_t GumbelNodeBytes() const { return 0; }   // multiples of 16
+  virtual size_t GumbelRootBytes() const { return 0; }
+  virtual void GumbelBegin(const int* d_ids, const GumbelArgs& a);
+  virtual void GumbelAdvance(const GumbelArgs& a);
+  virtual void GumbelResult(const GumbelArgs& a);
+  void GumbelBeginCall(const int32_t* ids, int k, int simulations, int considered, float c_visit, float c_scale,
+                       const void* gumbel, void* obs, void* mask, void* status, bool device);
+  void GumbelAdvanceCall(const void* logits, const void* values, int k, void* obs, void* mask, void* status,
+                         bool device);
+  void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
+
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
   // kernel that packs (unpack: restores) it for the listed local envs, row i at d_buf + i * ExtraBytes(), on stream_.
@@ -591,16 +631,22 @@ class Pool {
     bool open{false};
     DeviceBlock mem;        // the session's one device allocation: roots, nodes, then the host forms' staging
     char* pinned{nullptr};  // the host forms' pinned block, laid out like the staging
+    bool gumbel{false};     // the session's policy: PUCT or Gumbel
     int k{0}, simulations{0}, calls{0};
     float c_puct{0.0f};
+    int considered{0};      // Gumbel: m, c_visit, c_scale
+    float c_visit{0.0f}, c_scale{0.0f};
     size_t nodes_off{0}, stage_off{0};
-    // offsets into the staging: priors, values, obs, mask, status, visits, vals, action, the end
-    size_t off[9]{};
+    // offsets into the staging: priors (Gumbel: the noise at begin, then logits), values, obs, mask, status, visits,
+    // vals, action, the end of a PUCT session's staging, and behind it a Gumbel session's weights and their end
+    size_t off[10]{};
   };
   GuidedSession guided_;
   void GuidedFree();                                   // (no session: nothing)
   void GuidedRequire(const char* what) const;          // throws without a session
+  void GuidedRequirePolicy(const char* what, bool gumbel) const;  // ... or with one of the other policy
   GuidedArgs GuidedArgsOf(bool device) const;          // the session's pointers; staging arrays for a host form
+  GumbelArgs GumbelArgsOf(bool device) const;
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

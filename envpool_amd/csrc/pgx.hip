@@ -20,6 +20,8 @@
 // Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
 // Guided search: pgx_guided.hip.h, one wave per root and one launch per simulation, the tree in the session's own
 // memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult).
+// Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
+// policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
 #include <algorithm>
 #include <string>
 
@@ -27,6 +29,7 @@
 #include "engine.h"
 #include "pgx_env.hip.h"
 #include "pgx_guided.hip.h"
+#include "pgx_gumbel.hip.h"
 #include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
 #include "pgx_search.hip.h"
@@ -39,6 +42,7 @@ constexpr int kBlock = 256;
 constexpr unsigned kErrState = 1;   // set_state words that are no position of the game
 constexpr unsigned kErrSearch = 2;  // a search met a running position without a legal action, or a path past the cap
 constexpr unsigned kErrGuided = 3;  // the same, met by a guided search
+constexpr unsigned kErrGumbel = 4;  // the same, or a root without an action of the considered visit count (Gumbel)
 
 // key K's section of rows [row0, row0 + nrows) of the launch, written by the whole block
 template <int G, int K>
@@ -410,9 +414,8 @@ __device__ __forceinline__ void GuidedEmitRow(unsigned char* base, int total, in
 }
 
 // row `row` of the three leaf arrays: the position `s` for status 0, zeros otherwise
-template <int G>
-__device__ __forceinline__ void GuidedEmitLeaf(const GuidedArgs& a, int row, int lane, int status,
-                                               const pgx::State& s) {
+template <int G, class Args>
+__device__ __forceinline__ void GuidedEmitLeaf(const Args& a, int row, int lane, int status, const pgx::State& s) {
   constexpr int A = pgx::Dims<G>::A, OB = pgx::GuidedObsElems<G>();
   pgx::View view{};
   view.s = s;
@@ -601,6 +604,358 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   if (lane == 0) a.action[row] = best;
 }
 
+// Gumbel search (pgx_gumbel.hip.h): the session, lane ownership, hand-offs and leaves of the guided kernels above with
+// another pick.  Where PUCT needs one integer sum and one arg-max per node, a node here costs these wave reductions,
+// all register butterflies (no LDS), every result wave-uniform:
+//   GumbelEval      N (int sum) and vmax (int max); SUM p q and SUM p over the visited edges (float, in the header's
+//                   order: the lane's two terms added first, then the butterfly); min and max of the completed Q
+//   GumbelImproved  max of logit + sigma, SUM of the exponentials
+//   the pick        an arg-max (interior); at the root the legal count (int sum), the largest logit and an arg-max
+// and the leaf whose logits arrive costs a max and a float SUM for its p.  The table of considered visits is walked
+// per root by every lane on wave-uniform integers (scalar work), not read from memory.
+__device__ __forceinline__ float WaveSumF(float x) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x = x + __shfl_xor(x, m, kSearchBlock);
+  return x;
+}
+__device__ __forceinline__ float WaveMaxF(float x) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
+    const float o = __shfl_xor(x, m, kSearchBlock);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ float WaveMinF(float x) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
+    const float o = __shfl_xor(x, m, kSearchBlock);
+    x = o < x ? o : x;
+  }
+  return x;
+}
+__device__ __forceinline__ int WaveMaxI(int x) {
+#pragma unroll
+  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x = std::max(x, __shfl_xor(x, m, kSearchBlock));
+  return x;
+}
+
+// a lane's edges of one node (slot j: action lane + 64 j) with what the picks need of the whole node
+template <int G>
+struct GumbelEdges {
+  static constexpr int SL = pgx::SearchSlotsPerLane<G>();
+  bool legal[SL];
+  int child[SL], v[SL];
+  float w0[SL], logit[SL], sigma[SL];
+  int total, vmax;  // N and the largest v of the node
+};
+
+template <int G>
+__device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const pgx::State& s, int lane, float c_visit,
+                                           float c_scale, GumbelEdges<G>& e) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  const int sign = pgx::SearchSign<G>(s);
+  float p[SL], q[SL];
+  int own = 0, top = 0;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    e.legal[j] = act < A && pgx::Has(s.m, act);
+    e.child[j] = -1;
+    e.v[j] = 0;
+    e.w0[j] = e.logit[j] = p[j] = 0.0f;
+    if (act < A) {
+      e.child[j] = nd.child[act];
+      e.v[j] = nd.v[act];
+      e.w0[j] = nd.w0[act];
+      e.logit[j] = nd.logit[act];
+      p[j] = nd.p[act];
+    }
+    if (e.legal[j]) {
+      own += e.v[j];
+      top = std::max(top, e.v[j]);
+    }
+  }
+  e.total = WaveSum(own);
+  e.vmax = WaveMaxI(top);
+  float pq[2] = {0.0f, 0.0f}, pp[2] = {0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const bool on = e.legal[j] && e.v[j] > 0;
+    q[j] = on ? pgx::GumbelQ(e.v[j], e.w0[j], sign) : 0.0f;
+    if (on) {
+      pq[j] = p[j] * q[j];
+      pp[j] = p[j];
+    }
+  }
+  const float sum_pq = WaveSumF(pq[0] + pq[1]);
+  const float sum_p = WaveSumF(pp[0] + pp[1]);
+  const float mix = pgx::GumbelMix(nd.raw, sign, e.total, sum_pq, sum_p);
+  float cq[SL], lo = FLT_MAX, hi = -FLT_MAX;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    cq[j] = e.v[j] > 0 ? q[j] : mix;
+    if (e.legal[j]) {
+      lo = cq[j] < lo ? cq[j] : lo;
+      hi = cq[j] > hi ? cq[j] : hi;
+    }
+  }
+  lo = WaveMinF(lo);
+  hi = WaveMaxF(hi);
+  const float scale = pgx::GumbelScale(c_visit, c_scale, e.vmax);
+#pragma unroll
+  for (int j = 0; j < SL; ++j) e.sigma[j] = e.legal[j] ? pgx::GumbelSigma(scale, cq[j], lo, hi) : 0.0f;
+}
+
+// pi'(a) of the lane's edges: 0 on illegal actions
+template <int G>
+__device__ __forceinline__ void GumbelImproved(const GumbelEdges<G>& e, float* pi) {
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
+  float x[SL], top = -FLT_MAX;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    x[j] = e.logit[j] + e.sigma[j];
+    if (e.legal[j]) top = x[j] > top ? x[j] : top;
+  }
+  top = WaveMaxF(top);
+  float ex[2] = {0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    if (e.legal[j]) ex[j] = pgx::GumbelExp(x[j] - top);
+  }
+  const float sum = WaveSumF(ex[0] + ex[1]);
+#pragma unroll
+  for (int j = 0; j < SL; ++j) pi[j] = e.legal[j] ? ex[j] / sum : 0.0f;
+}
+
+// the root pick: `final` picks among the most visited actions (the result), otherwise among those of the considered
+// visit count of simulation N(root); -1 without such an action
+template <int G>
+__device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx::GumbelRoot<G>& rec, int lane,
+                                              int considered, int simulations, bool final) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  int legal = 0;
+  float top = -FLT_MAX;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    if (e.legal[j]) {
+      ++legal;
+      top = e.logit[j] > top ? e.logit[j] : top;
+    }
+  }
+  legal = WaveSum(legal);
+  top = WaveMaxF(top);
+  const int cv =
+      final ? e.vmax : pgx::GumbelConsideredVisit(std::min(considered, legal), simulations, e.total);
+  pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    if (act < A && e.legal[j] && e.v[j] == cv) {
+      mine = pgx::SearchBetter(
+          mine, pgx::SearchPick{pgx::GumbelRootScore(rec.gumbel[act], e.logit[j], top, e.sigma[j]), act, 1});
+    }
+  }
+  return WaveBest(mine).action;
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGumbelBegin(CommonDev cm, const pgx::State* st,
+                                                               const int* __restrict__ ids, GumbelArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GumbelNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int e = ids[row];
+  const bool over = cm.done[e] != 0;  // (an env before its first reset is)
+  const pgx::State root = st[e];
+  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  pgx::GumbelRoot<G>& rec = static_cast<pgx::GumbelRoot<G>*>(a.roots)[row];
+  if (lane == 0) {
+    n0.s = root;
+    n0.term0 = 0;
+    n0.raw = 0.0f;
+    pgx::GuidedClearRoot(rec.r, over);
+  }
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    if (act < A) {
+      pgx::GumbelClearEdge<G>(n0, act);
+      rec.gumbel[act] = pgx::GumbelCleanNoise(a.gumbel[(size_t)row * A + act]);
+    }
+  }
+  WaveRelease();
+  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, unsigned* err) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GumbelNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int S = a.simulations;
+  pgx::GumbelRoot<G>& rec = static_cast<pgx::GumbelRoot<G>*>(a.roots)[row];
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)(S + 1);
+  WaveAcquire();
+  int status = rec.r.status;
+  pgx::State s{};  // the pending leaf's position when the launch ends
+  if (status != pgx::kGuidedIdle) {
+    Node& leaf = nodes[rec.r.pending];
+    float val0;
+    if (status == pgx::kGuidedEvaluate) {
+      // the leaf's logits arrive: logit and p of its legal actions (illegal entries are not read), and its raw
+      const pgx::State ls = leaf.s;
+      float lg[SL], top = -FLT_MAX;
+      bool legal[SL];
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        const int act = lane + kSearchBlock * j;
+        legal[j] = act < A && pgx::Has(ls.m, act);
+        lg[j] = legal[j] ? pgx::GumbelCleanLogit(a.logits[(size_t)row * A + act]) : 0.0f;
+        if (legal[j]) top = lg[j] > top ? lg[j] : top;
+      }
+      top = WaveMaxF(top);
+      float ex[2] = {0.0f, 0.0f};
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        if (legal[j]) ex[j] = pgx::GumbelExp(lg[j] - top);
+      }
+      const float sum = WaveSumF(ex[0] + ex[1]);
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        const int act = lane + kSearchBlock * j;
+        if (act < A) {
+          leaf.logit[act] = lg[j];
+          leaf.p[act] = legal[j] ? pgx::GumbelPrior(ex[j], sum) : 0.0f;
+        }
+      }
+      val0 = (float)pgx::SearchSign<G>(ls) * pgx::GuidedCleanV(a.values[row]);
+      if (lane == 0) leaf.raw = val0;
+    } else {
+      val0 = (float)leaf.term0;
+    }
+    const int backed = rec.r.depth;
+    for (int d = 0; d < backed; ++d) {
+      const int p = rec.r.path[d];
+      const int act = p & 255;
+      if ((act & (kSearchBlock - 1)) == lane) {
+        Node& nd = nodes[p >> 8];
+        nd.v[act] += 1;
+        nd.w0[act] += val0;
+      }
+    }
+    WaveRelease();
+    if (a.call >= S) {
+      status = pgx::kGuidedIdle;
+      if (lane == 0) rec.r.status = status;
+    } else {
+      int node = 0, depth = 0, count = rec.r.count;
+      bool broken = false;
+      WaveAcquire();
+      s = nodes[0].s;
+      for (;;) {
+        Node& nd = nodes[node];
+        GumbelEdges<G> e;
+        GumbelEval<G>(nd, s, lane, a.c_visit, a.c_scale, e);
+        int act;
+        if (node == 0) {
+          act = GumbelRootPick<G>(e, rec, lane, a.considered, S, false);
+        } else {
+          float pi[SL];
+          GumbelImproved<G>(e, pi);
+          pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+          for (int j = 0; j < SL; ++j) {
+            if (e.legal[j]) {
+              mine = pgx::SearchBetter(mine, pgx::SearchPick{pgx::GumbelInteriorScore(pi[j], e.v[j], e.total),
+                                                             lane + kSearchBlock * j, 1});
+            }
+          }
+          act = WaveBest(mine).action;
+        }
+        // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
+        if (act < 0 || depth >= pgx::kSearchMaxPath) {
+          broken = true;
+          break;
+        }
+        if (lane == 0) rec.r.path[depth] = node << 8 | act;
+        ++depth;
+        const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
+        int c = __shfl(e.child[0], owner, kSearchBlock);
+        if (SL > 1) {
+          const int c1 = __shfl(e.child[SL - 1], owner, kSearchBlock);
+          c = slot == 1 ? c1 : c;
+        }
+        if (c < 0) {
+          if (count > S) {  // (one node per call: never; the session's memory ends here)
+            broken = true;
+            break;
+          }
+          c = count++;
+          if (lane == owner) nd.child[act] = c;
+          Node& nn = nodes[c];
+          pgx::State s2;
+          const int term0 = pgx::SearchExpand<G>(s, act, s2);
+          if (lane == 0) {
+            nn.s = s2;
+            nn.term0 = term0;
+            nn.raw = pgx::GumbelFreshRaw(s2, term0);
+          }
+#pragma unroll
+          for (int j = 0; j < SL; ++j) {
+            if (lane + kSearchBlock * j < A) pgx::GumbelClearEdge<G>(nn, lane + kSearchBlock * j);
+          }
+          node = c;
+          s = s2;
+          break;
+        }
+        node = c;
+        WaveAcquire();
+        s = nodes[node].s;
+        if (s.done) break;
+      }
+      status = broken ? pgx::kGuidedIdle : s.done ? pgx::kGuidedTerminal : pgx::kGuidedEvaluate;
+      if (lane == 0) {
+        rec.r.count = count;
+        rec.r.pending = node;
+        rec.r.status = status;
+        rec.r.depth = broken ? 0 : depth;
+        if (broken) *err = kErrGumbel;
+      }
+    }
+    WaveRelease();
+  }
+  GuidedEmitLeaf<G>(a, row, lane, status, s);
+}
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGumbelResult(GumbelArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GumbelNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const pgx::GumbelRoot<G>& rec = static_cast<const pgx::GumbelRoot<G>*>(a.roots)[row];
+  const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  WaveAcquire();
+  const bool over = rec.r.over != 0;
+  const pgx::State root = n0.s;
+  const float sign = (float)pgx::SearchSign<G>(root);
+  GumbelEdges<G> e;
+  GumbelEval<G>(n0, root, lane, a.c_visit, a.c_scale, e);
+  float pi[SL];
+  GumbelImproved<G>(e, pi);
+  const int best = GumbelRootPick<G>(e, rec, lane, a.considered, a.simulations, true);
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    const int act = lane + kSearchBlock * j;
+    if (act < A) {
+      a.visits[(size_t)row * A + act] = over ? 0 : e.v[j];
+      a.vals[(size_t)row * A + act] = over ? 0.0f : sign * e.w0[j];
+      a.weights[(size_t)row * A + act] = over ? 0.0f : pi[j];
+    }
+  }
+  if (lane == 0) a.action[row] = over ? -1 : best;
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -682,8 +1037,21 @@ class PgxPool : public Pool {
   void GuidedResult(const GuidedArgs& a) override {
     hipLaunchKernelGGL(PgxGuidedResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
   }
+  size_t GumbelNodeBytes() const override { return sizeof(pgx::GumbelNode<G>); }
+  size_t GumbelRootBytes() const override { return sizeof(pgx::GumbelRoot<G>); }
+  void GumbelBegin(const int* d_ids, const GumbelArgs& a) override {
+    hipLaunchKernelGGL(PgxGumbelBegin<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
+                       a);
+  }
+  void GumbelAdvance(const GumbelArgs& a) override {
+    hipLaunchKernelGGL(PgxGumbelAdvance<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a, err_dev_);
+  }
+  void GumbelResult(const GumbelArgs& a) override {
+    hipLaunchKernelGGL(PgxGumbelResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+  }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
+    if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";
     if (code == kErrSearch) return "PGX: search met a position that is no position of the game";
     return Pool::ErrorText(code);

@@ -89,6 +89,61 @@ class GuidedSearch:
             pool.guided_end()
 
 
+class GumbelResult(NamedTuple):
+    """What a Gumbel search returns: numpy arrays over [k listed envs, A actions]."""
+
+    visits: np.ndarray   # int32 [k, A]: simulations through each root action
+    values: np.ndarray   # float32 [k, A]: summed leaf values through it, seen from the root's mover
+    action: np.ndarray   # int32 [k]: the recommended move (the best of the most visited); -1: the env was over
+    weights: np.ndarray  # float32 [k, A]: the improved policy softmax(logits + sigma(completed q)): the training target
+
+
+class GumbelSearch:
+    """A pool's Gumbel-search session (`env.gumbel_search`): Gumbel top-m sampling with sequential halving at the root
+    of every listed env, the tree on the device, stopping at every new leaf for the caller's logits and value.
+
+        gs = env.gumbel_search(ids, simulations=32, max_considered=16, seed=0)
+        result = gs.run(lambda obs, mask, status: model(obs, mask))     # S + 1 evaluations, then closes
+
+    or step by step, as `GuidedSearch`: `leaves`, `advance(logits [k, A], values [k])`, `result()`, `close()`."""
+
+    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, max_considered: int, gumbel: np.ndarray,
+                 c_visit: float, c_scale: float):
+        self._pool = pool
+        self.simulations = int(simulations)
+        self.calls = 0
+        self.leaves = pool.gumbel_begin(gumbel, ids, int(simulations), int(max_considered), float(c_visit),
+                                        float(c_scale))
+
+    def advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        if self._pool is None:
+            raise ValueError("gumbel search: the session is closed")
+        if self.calls > self.simulations:
+            raise ValueError(f"gumbel_advance: call number {self.calls} is above simulations = {self.simulations}")
+        self.leaves = self._pool.gumbel_advance(logits, values)
+        self.calls += 1
+        return self.leaves
+
+    def result(self) -> GumbelResult:
+        if self._pool is None:
+            raise ValueError("gumbel search: the session is closed")
+        return GumbelResult(*self._pool.gumbel_result())
+
+    def run(self, evaluate: Any) -> GumbelResult:
+        """Calls `evaluate(obs, mask, status) -> (logits, values)` until simulations + 1 advances are made, returns
+        the result and closes the session."""
+        while self.calls <= self.simulations:
+            self.advance(*evaluate(*self.leaves))
+        out = self.result()
+        self.close()
+        return out
+
+    def close(self) -> None:
+        if self._pool is not None:
+            pool, self._pool = self._pool, None
+            pool.guided_end()
+
+
 def _normalize_env_id(env_id: Any) -> Any:
     """env ids as an int32 array of at least one dimension (envpool.py:38-48).  Array-likes with their own `astype`
     (device arrays) keep their type; everything else goes through numpy."""
@@ -255,15 +310,42 @@ class EnvPoolMixin(ABC):
         return Search(*self._search(ids, int(simulations), int(leaf_playouts), float(c_puct), int(max_plies),
                                     int(seed)))
 
-    def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25) -> GuidedSearch:
+    def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
+                      **gumbel: Any) -> Any:
         """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
         (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
         pool has one at a time, and a new one replaces it.  Nothing of the pool changes.  The arguments are checked
-        before any native call."""
+        before any native call.  `policy="gumbel"` is `gumbel_search(env_ids, simulations, **gumbel)` instead (c_puct
+        is not used) and returns a `GumbelSearch`."""
+        if policy == "gumbel":
+            return self.gumbel_search(env_ids, simulations, **gumbel)
+        if policy != "puct":
+            raise ValueError(f"guided_search: policy = {policy!r} must be 'puct' or 'gumbel'")
+        if gumbel:
+            raise ValueError(f"guided_search: {sorted(gumbel)} are arguments of policy='gumbel'")
         ids = native.check_guided(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, c_puct)
         return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct))
+
+    def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
+                      seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1) -> GumbelSearch:
+        """Extension (the PGX board games): opens a Gumbel search (Danihelka et al., ICLR 2022) from the current
+        position of every listed env (global ids; None: all): Gumbel top-`max_considered` sampling without replacement
+        at the root, sequential halving of the `simulations` over those actions, a deterministic rule inside the tree;
+        the caller supplies logits and values at every new leaf.  The result's `action` is the move to play and its
+        `weights` the policy training target.  `gumbel` float32 [k, A] is the root noise (zeros: no noise, for
+        evaluation); None draws it on the host from numpy.random.Generator(PCG64(seed)), seed=None unseeded.  Returns
+        the `GumbelSearch` session; it is the pool's one guided-search session.  Nothing of the pool changes.  The
+        arguments are checked before any native call."""
+        ids = native.check_gumbel(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
+                                  simulations, max_considered, c_visit, c_scale)
+        pool = self._gumbel()
+        actions = pool.gumbel_actions()
+        if gumbel is None:
+            gumbel = np.random.Generator(np.random.PCG64(seed)).gumbel(size=(len(ids), actions)).astype(np.float32)
+        gumbel = native.check_gumbel_noise(gumbel, len(ids), actions)
+        return GumbelSearch(pool, ids, int(simulations), int(max_considered), gumbel, float(c_visit), float(c_scale))
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

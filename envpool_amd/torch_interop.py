@@ -271,3 +271,55 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
                                                                   action.data_ptr()))
     pool.guided_end()
     return visits, vals, action
+
+
+def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
+                         gumbel: Any = None, seed: Any = None, c_visit: float = 50.0,
+                         c_scale: float = 0.1) -> tuple[Any, Any, Any, Any]:
+    """A whole Gumbel search (`pool.gumbel_begin` ..) with the evaluator on the device, as `guided_search_device`:
+    `evaluate(obs, mask, status)` gets torch tensors on the pool's device and returns (logits float32 [k, A], values
+    float32 [k]) there; nothing crosses PCIe and the host never waits.  `gumbel` is a float32 [k, A] tensor on the
+    pool's device, or None: torch draws Gumbel(0, 1) noise there (from a generator seeded with `seed`, or torch's
+    default one).  Returns (visits int32 [k, A], values float32 [k, A], action int32 [k], weights float32 [k, A]) on
+    the device and closes the session."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_gumbel(env_ids, simulations, max_considered, c_visit, c_scale)
+    a = pool.gumbel_actions()
+    h, w, c, _ = pool.guided_shape()
+    k = len(ids)
+    dev = torch.device("cuda", pool.device)
+    if gumbel is None:
+        gen = None if seed is None else torch.Generator(device=dev).manual_seed(int(seed))
+        u = torch.rand((k, a), dtype=torch.float32, device=dev, generator=gen).clamp_(1e-20, 1.0 - 1e-7)
+        gumbel = -torch.log(-torch.log(u))
+    gumbel = gumbel.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(gumbel.shape) != (k, a):
+        raise ValueError(f"gumbel_begin: gumbel of shape {tuple(gumbel.shape)} for a session of [{k}, {a}]")
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.gumbel_begin_device(gumbel.data_ptr(), obs.data_ptr(), mask.data_ptr(),
+                                                                 status.data_ptr(), ids, simulations, max_considered,
+                                                                 c_visit, c_scale))
+    for _ in range(int(simulations) + 1):
+        logits, values = evaluate(obs, mask, status)
+        logits = logits.to(device=dev, dtype=torch.float32).contiguous()
+        values = values.to(device=dev, dtype=torch.float32).contiguous().view(-1)
+        if tuple(logits.shape) != (k, a) or tuple(values.shape) != (k,):
+            pool.guided_end()
+            raise ValueError(f"gumbel_search_device: evaluate returned logits {tuple(logits.shape)} and values "
+                             f"{tuple(values.shape)} for a session of [{k}, {a}]")
+        _order_both_ways(pool, dev, lambda: pool.gumbel_advance_device(logits.data_ptr(), values.data_ptr(), k,
+                                                                       obs.data_ptr(), mask.data_ptr(),
+                                                                       status.data_ptr()))
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    weights = torch.empty((k, a), dtype=torch.float32, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.gumbel_result_device(visits.data_ptr(), vals.data_ptr(),
+                                                                  action.data_ptr(), weights.data_ptr()))
+    pool.guided_end()
+    return visits, vals, action, weights

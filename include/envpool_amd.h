@@ -564,6 +564,58 @@ int epa_guided_result(epa_pool* pool, int32_t* visits, float* values, int32_t* a
 int epa_guided_result_device(epa_pool* pool, void* device_visits, void* device_values, void* device_action);
 int epa_guided_end(epa_pool* pool);
 
+/* Gumbel search (no reference analogue; the four PGX board games): the guided-search session above with a second
+ * selection policy -- Gumbel top-m sampling without replacement at the root, sequential halving of the simulations
+ * over those m actions, a deterministic rule inside the tree, and the improved policy softmax(logits + sigma(completed
+ * Q)) as the training target (Danihelka et al., "Policy improvement by planning with Gumbel", ICLR 2022).  It needs
+ * far fewer simulations per move than PUCT.  The session, its statuses, the emitted leaves, expansion, terminal
+ * leaves, the backup and the session rules are those of epa_guided_begin; what differs (csrc/pgx_gumbel.hip.h is the
+ * authority; nothing is pinned to another implementation's floating point):
+ *   begin(ids, S, m, c_visit, c_scale, gumbel[k, A]):  m = the most root actions considered, 1 .. A (a larger one
+ *     counts as A: a root considers min(m, its legal actions), so 16 serves every game);  c_visit, c_scale
+ *     finite and >= 0 (the paper: 50 and 0.1);  gumbel: the caller's Gumbel(0, 1) noise per root action, float; a
+ *     non-finite entry counts as 0; all zeros is the noise-free evaluation mode.  The library draws no random numbers.
+ *   advance(logits[k, A], values[k]) -- call number t = 0 .. S:  logits are the policy's raw scores (any sign; a
+ *     non-finite entry or one above 1e30 in magnitude counts as 0), values as for epa_guided_advance.  Entries of
+ *     illegal actions are never read.  The host forms refuse such rows with EPA_ERR_INVALID before any launch.
+ *   A node also holds raw (the caller's value of the node, as seat 0's; (float) term0 for a finished node) and per
+ *   action logit[a] and p[a] = the softmax of the node's logits over its legal actions, floored at FLT_MIN.
+ *   Per node, over its legal actions, sign as above, all float, in this order, nothing fused:
+ *     N = sum of v[a];  vmax = max of v[a];  sraw = sign * raw;  q(a) = (sign * w0[a]) / v[a]   (where v[a] > 0)
+ *     v_mix = N == 0 ? sraw : (sraw + N * (SUM_{v>0}(p[a] * q(a)) / SUM_{v>0}(p[a]))) / (1 + N)
+ *     cq(a) = v[a] > 0 ? q(a) : v_mix;  scale = min((c_visit + vmax) * c_scale, 1e30)
+ *     sg(a) = (scale * (cq(a) - min cq)) / max(max cq - min cq, 1e-8)
+ *     pi'(a) = softmax over the legal actions of logit[a] + sg(a)
+ *   interior pick:  argmax of pi'(a) - v[a] / (1 + N); ties: the lowest a
+ *   root pick at simulation t = N(root):  m_eff = min(m, legal root actions);  cv = the t-th entry of the sequence
+ *     of considered visits of sequential halving for (m_eff, S);  argmax over the legal a with v[a] == cv of
+ *     (gumbel[a] + (logit[a] - max legal logit)) + sg(a); ties: the lowest a.  No such action ends the root with
+ *     status 2 and sets the pool's error word.
+ *   The exponential is the header's own (float + - * only, the argument clamped to [-87, 0]) and every float sum
+ *   over actions has one stated order, so the kernels and the header's host build agree bit for bit.
+ * epa_gumbel_result is valid any time after begin and complete after S + 1 advances:
+ *   visits, values   as epa_guided_result
+ *   action  [k]    int32   the root pick with cv = vmax: the recommended move; -1 for a root that was over
+ *   weights [k, A] float   pi' of the root: 0 on illegal actions, sums to 1; the training target (zeros: root over)
+ * A pool's one session has one policy.  epa_gumbel_begin replaces an open session of either policy, as
+ * epa_guided_begin does; epa_guided_end ends a session of either policy.  EPA_ERR_INVALID: epa_guided_advance or
+ * epa_guided_result on a Gumbel session, epa_gumbel_advance or epa_gumbel_result on a PUCT session; and the checks of
+ * the guided calls, with m below 1 and c_visit / c_scale negative or not finite beside them.  Every family
+ * without guided search fails with EPA_ERR_RUNTIME "gumbel search not implemented for this environment".
+ * The _device forms take device pointers (float and int32 arrays 4-byte aligned) and only enqueue. */
+int epa_gumbel_begin(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t max_considered,
+                     float c_visit, float c_scale, const float* gumbel, uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_gumbel_begin_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                            int32_t max_considered, float c_visit, float c_scale, const void* device_gumbel,
+                            void* device_obs, void* device_mask, void* device_status);
+int epa_gumbel_advance(epa_pool* pool, const float* logits, const float* values, int32_t k, uint8_t* obs,
+                       uint8_t* mask, uint8_t* status);
+int epa_gumbel_advance_device(epa_pool* pool, const void* device_logits, const void* device_values, int32_t k,
+                              void* device_obs, void* device_mask, void* device_status);
+int epa_gumbel_result(epa_pool* pool, int32_t* visits, float* values, int32_t* action, float* weights);
+int epa_gumbel_result_device(epa_pool* pool, void* device_visits, void* device_values, void* device_action,
+                             void* device_weights);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
