@@ -22,7 +22,13 @@
 //   shift 0 on both sides  one thread = one word.  Thread t: row t % k, word t / k: lanes run along the rows, so a
 //                          wave reads / writes 64 consecutive 4-byte columns of one word row in the blob, and of the
 //                          pool's row too when the ids are consecutive.
-//   mixed (a blob restored into a pool built with another "mt_tile")  the word mapping with each side's own index.
+//   mixed (a blob restored into a pool built with another "mt_tile")  the word mapping with each side's own index,
+//                          then one thread per env converts the ONE partly consumed tile on the pool side
+//                          (MtConvertTile below): the two layouts regenerate lazily at different grains -- [624][N]
+//                          twists word i when it is consumed, the tiled layout twists a whole tile when its first
+//                          word is reached -- so with mti % 16 != 0 the words mti .. mti | 15 are still the old
+//                          block's in a shift-0 generator and already the new block's in a shift-4 one.  Every other
+//                          word, and every word when mti % 16 == 0, means the same in both and is copied verbatim.
 // The thread of word 0 / quarter 0 of tile 0 of a row also moves that row's mti.
 // The stack ring moves as double2 (thread = one pair of a row) when S * nobs is even, so that every env's row starts on
 // a 16-byte boundary on both sides; for an odd S * nobs the same thread moves its two doubles one by one.  The thread
@@ -190,6 +196,46 @@ EPA_SNAP_HD inline void StackThread(size_t t, int len, int* row, int* pair) {
 }
 EPA_SNAP_HD inline size_t StackIndex(int row, int len, int pair) { return (size_t)row * (size_t)len + 2u * (size_t)pair; }
 
+// ---- the partly consumed tile of a generator that changes layout (host and device) ------------
+// Mt19937::Twist1 (device_common.hip.h): word j of the next block out of words j, j + 1 and the partner j + 397
+EPA_SNAP_HD inline uint32_t MtTwist1(uint32_t cur, uint32_t nxt, uint32_t partner) {
+  const uint32_t y = (cur & 0x80000000u) | (nxt & 0x7fffffffu);
+  return partner ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+EPA_SNAP_HD inline int MtPartner(int j) { return j >= 227 ? j - 227 : j + 397; }
+// Column `col` of a generator of `cols` envs in layout `to_sh` holds the words of a generator of layout `from_sh`
+// at position p = mti (a verbatim copy): make them the words a generator of layout `to_sh` holds at that position.
+// Nothing to do when the layouts agree or p starts a tile.  Words p .. p | 15 change, nothing else is written; the
+// partner words (227 away) and word 0 behind word 623 lie outside that range and mean the same in both layouts.
+//   0 -> 4  the tile is expected regenerated: twist its remaining words in ascending order, exactly as Next() of the
+//           [624][N] layout would when it consumes them (word j + 1 still old, word 0 behind 623 already new)
+//   4 -> 0  the tile is expected old from p on: z = new[j] ^ partner = (y >> 1) ^ (y & 1 ? 0x9908b0df : 0) with
+//           y = (old[j] & 0x80000000) | (old[j + 1] & 0x7fffffff); y >> 1 has a clear top bit and the constant a set
+//           one, so the top bit of z is y & 1 and y is recovered whole.  old[j] is the top bit of y_j and the low
+//           31 bits of y_{j - 1}; p - 1 is in the same tile (p % 16 != 0) and new in both layouts.
+EPA_SNAP_HD inline void MtConvertTile(uint32_t* mt, int col, int cols, int to_sh, int from_sh, int p) {
+  if (to_sh == from_sh || (p & 15) == 0 || p < 0 || p >= kMtWords) return;
+  const int last = p | 15;
+  if (from_sh == 0) {
+    for (int j = p; j <= last; ++j) {
+      uint32_t& w = mt[MtWordIndex(j, col, cols, to_sh)];
+      w = MtTwist1(w, mt[MtWordIndex(j == kMtWords - 1 ? 0 : j + 1, col, cols, to_sh)],
+                   mt[MtWordIndex(MtPartner(j), col, cols, to_sh)]);
+    }
+  } else {
+    uint32_t prev = 0;  // y of word j - 1
+    for (int j = p - 1; j <= last; ++j) {
+      uint32_t& w = mt[MtWordIndex(j, col, cols, to_sh)];
+      uint32_t z = w ^ mt[MtWordIndex(MtPartner(j), col, cols, to_sh)];
+      const uint32_t bit = z >> 31;
+      if (bit) z ^= 0x9908b0dfu;
+      const uint32_t y = (z << 1) | bit;
+      if (j >= p) w = (y & 0x80000000u) | (prev & 0x7fffffffu);
+      prev = y;
+    }
+  }
+}
+
 #if defined(__HIPCC__)
 // ---- kernels ----------------------------------------------------------------------------------
 struct HeaderWords {
@@ -250,6 +296,17 @@ __global__ __launch_bounds__(256) void MtWordKernel(uint32_t* __restrict__ pool_
       blob_mti[row] = pool_mti[e];
     }
   }
+}
+
+// behind MtWordKernel<true> with sides of different layouts: one thread per restored env converts its partly consumed
+// tile in the pool (restore ids are unique: no two threads share a column)
+__global__ __launch_bounds__(256) void MtConvertKernel(uint32_t* __restrict__ pool_mt, const int* __restrict__ pool_mti,
+                                                       int n, int pool_sh, const int* __restrict__ ids, int k,
+                                                       int blob_sh) {
+  const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (row >= k) return;
+  const int e = ids[row];
+  MtConvertTile(pool_mt, e, n, pool_sh, blob_sh, pool_mti[e]);
 }
 
 // the observation ring [N][len] <-> [k][len] and its heads.  WIDE: len is even, every row 16-byte aligned.

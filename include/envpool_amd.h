@@ -115,6 +115,14 @@ typedef struct epa_pool epa_pool;
  *   "classic_early" classic_control: 1 = the step kernel reads state, action and generator position together with
  *                 `done`, in front of the reset branch (default: CartPole only, where every wave holds a reset row:
  *                 -6 % kernel time at num_envs = 65536); never changes results
+ *   "mt_tile"     every family with generators: consecutive words of ONE env's mt19937 that are kept contiguous in device
+ *                 memory -- 1 = the plain [624][N] structure of arrays (every env draws the same word in the same
+ *                 launch: a draw is one coalesced column), 16 = tiles of 16 words per env, [39][N][16] (envs that reset
+ *                 at their own times: a reset's 8 .. 60 draws stay inside 1 .. 4 64-byte sectors).  Default by family:
+ *                 16 where episodes end at their own times (CartPole, Acrobot, FrozenLake, Taxi, Blackjack, Walker2d,
+ *                 the Ant, Humanoid, the inverted pendulums, Jumanji, MiniGrid, PGX), 1 elsewhere; any other value is
+ *                 refused.  Never changes results: both layouts produce std::mt19937's sequence, and a snapshot taken
+ *                 in one restores into a pool built with the other.
  *   "recv_timeout_ms" every family: how long epa_recv* waits for rows that have not been sent yet (see epa_recv):
  *                 < 0 forever (default, the reference's behaviour), 0 not at all, > 0 milliseconds
  *   "compute_streams" async mode (batch_size < num_envs): successive batches run on this many

@@ -13,9 +13,11 @@ using namespace epa::snap;
 namespace {
 // one pass of the generator kernel's mapping; `tiled`: MtTileKernel, otherwise MtWordKernel with the two shifts.
 // Returns 0, or a negative code: -1 pool index out of range, -2 blob index out of range, -3 a blob word touched
-// twice, -4 a blob word never touched.
+// twice, -4 a blob word never touched.  With the two position arrays (both or neither) the positions move as the
+// kernels' thread of word 0 / quarter 0 of tile 0 moves them, and an unpack between different layouts ends like
+// Pool::SnapUnpack: MtConvertKernel's one thread per row over the pool image.
 int MtPass(bool tiled, bool unpack, uint32_t* pool, int n, int pool_sh, const int* ids, int k, uint32_t* blob,
-           int blob_sh) {
+           int blob_sh, int* pool_mti, int* blob_mti) {
   const size_t pool_words = (size_t)kMtWords * n, blob_words = (size_t)kMtWords * k;
   std::vector<unsigned char> hit(blob_words, 0);
   auto move = [&](size_t p, size_t b, int words) -> int {
@@ -49,16 +51,29 @@ int MtPass(bool tiled, bool unpack, uint32_t* pool, int n, int pool_sh, const in
   for (unsigned char h : hit) {
     if (h != 1) return -4;
   }
+  if (pool_mti != nullptr && blob_mti != nullptr) {
+    for (int row = 0; row < k; ++row) {
+      if (unpack) {
+        pool_mti[ids[row]] = blob_mti[row];
+      } else {
+        blob_mti[row] = pool_mti[ids[row]];
+      }
+    }
+    if (unpack && !tiled && pool_sh != blob_sh) {
+      for (int row = 0; row < k; ++row) MtConvertTile(pool, ids[row], n, pool_sh, blob_sh, pool_mti[ids[row]]);
+    }
+  }
   return 0;
 }
 }  // namespace
 
 extern "C" {
 
-// pack the listed columns of `pool` into `blob`, or unpack them; see MtPass for the result
+// pack the listed columns of `pool` into `blob`, or unpack them; see MtPass for the result.  pool_mti [n] and
+// blob_mti [k] may both be null: the words alone move then.
 int snap_mt_pass(int tiled, int unpack, uint32_t* pool, int n, int pool_sh, const int* ids, int k, uint32_t* blob,
-                 int blob_sh) {
-  return MtPass(tiled != 0, unpack != 0, pool, n, pool_sh, ids, k, blob, blob_sh);
+                 int blob_sh, int* pool_mti, int* blob_mti) {
+  return MtPass(tiled != 0, unpack != 0, pool, n, pool_sh, ids, k, blob, blob_sh, pool_mti, blob_mti);
 }
 
 // where word j of env e lives in a pool image (the layout the step kernels use)

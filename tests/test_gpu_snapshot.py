@@ -34,20 +34,28 @@ DRAWS_EVERY_STEP = {"Game2048-v1"}
 class Handle:
     """A pool under test: the gymnasium env (whose snapshot / restore / fork are the calls under test) and its
     DevicePool (through which every state key of every row is recorded).  A case with an engine key
-    ("Hopper-v4/planar_layout=1") has no env: engine keys do not pass through `make`, the DevicePool is the handle."""
+    ("Hopper-v4/planar_layout=1"), or with `engine_keys`, has no env: engine keys do not pass through `make`, the
+    DevicePool is the handle."""
 
-    def __init__(self, case, seed, n=N, **kw):
+    def __init__(self, case, seed, n=N, engine_keys=None, **kw):
+        from mj_util import GYM_VARIANTS, native_variant
+
         task, _, key = case.partition("/")
-        kw.setdefault("max_episode_steps", TASKS[case])
+        if "max_episode_steps" not in kw:
+            kw["max_episode_steps"] = TASKS[case] if case in TASKS else TASKS[task]
         self.space = envpool.make_spec(task).action_space
-        if key:
-            from mj_util import native_variant
-
-            family, _, params = native_variant(task)
-            name, value = key.split("=")
+        keys = dict([key.split("=")] if key else [], **(engine_keys or {}))
+        keys = {name: float(value) for name, value in keys.items()}
+        if keys:
             self.env = None
-            self.pool = DevicePool(family, n, seed=seed, max_episode_steps=kw.pop("max_episode_steps"),
-                                   params={**params, name: float(value), **kw})
+            if task in GYM_VARIANTS:
+                family, _, params = native_variant(task)
+                self.pool = DevicePool(family, n, seed=seed, max_episode_steps=kw.pop("max_episode_steps"),
+                                       params={**params, **keys, **kw})
+            else:
+                from hip_util import registered_pool
+
+                self.pool = registered_pool(task, n, seed, keys, **kw)
             self.api = self.pool
         else:
             self.env = envpool.make(task, env_type="gymnasium", num_envs=n, seed=seed, **kw)
@@ -147,13 +155,21 @@ def test_whole_pool_continues_bit_for_bit(case):
     h.close()
 
 
-def into_another_pool(a, a_ids, b, twin, tag):
+def into_another_pool(a, a_ids, b, twin, tag, device_blob=False):
     """Test 2's comparison: b.restore(a.snapshot(a_ids), IDS2); then b's rows IDS2 are a's rows a_ids in every key
-    but the env ids, and b's other rows are those of its untouched twin."""
+    but the env ids, and b's other rows are those of its untouched twin.  `device_blob`: the blob stays on the device
+    (snapshot_device / restore_device)."""
     rng = np.random.default_rng(5)
-    blob = a.api.snapshot(a_ids)
-    assert blob.nbytes == a.pool.snapshot_bytes(len(a_ids))
-    b.api.restore(blob, IDS2 + b.pool.env_id_offset)
+    if device_blob:
+        from envpool_amd import torch_interop as ti
+
+        dblob = ti.snapshot_device(a.pool, a_ids)
+        assert dblob.numel() == a.pool.snapshot_bytes(len(a_ids))
+        ti.restore_device(b.pool, dblob, IDS2 + b.pool.env_id_offset)
+    else:
+        blob = a.api.snapshot(a_ids)
+        assert blob.nbytes == a.pool.snapshot_bytes(len(a_ids))
+        b.api.restore(blob, IDS2 + b.pool.env_id_offset)
     others = np.setdiff1d(np.arange(b.n), IDS2)
     ra, rb, rt = [], [], []
     for _ in range(STEPS):
@@ -181,6 +197,62 @@ def test_subset_continues_in_another_pool(case):
     into_another_pool(a, IDS, b, twin, case)
     for h in (a, b, twin):
         h.close()
+
+
+# one id per way of drawing from the generator: CartPole NextWords bursts, Blackjack UniformInt, Pendulum UniformReal,
+# HalfCheetah Normal, the Ant (its own kernel), Game2048 UniformInt + Canonical, Minesweeper a shuffle, the MiniGrid
+# and PGX reset kernels
+MIXED_LAYOUT_TASKS = ["CartPole-v1", "Blackjack-v1", "Pendulum-v1", "HalfCheetah-v4", "Ant-v4", "Game2048-v1",
+                      "Minesweeper-v0", "MiniGrid-Dynamic-Obstacles-6x6-v0", "Othello-v1"]
+
+
+def blob_generators(blob):
+    """(generator layout, positions [k]) of a generator-carrying blob of a pool without a frame stack: the header
+    fields and section offsets of envpool_amd/csrc/snapshot.hip.h (`struct Header`, `LayoutOf`)."""
+    assert int(blob[:8].view("<u4")[1]) == 1, "snapshot.hip.h: kVersion has changed, and with it maybe the layout"
+    dim, k, flags, shift, stack_s = (int(x) for x in blob[16:36].view("<i4"))
+    assert flags & 1 and stack_s == 1
+    off = (64 + 8 * k * dim + 63) // 64 * 64 + 4 * 624 * k
+    return shift, blob[off:off + 4 * k].view("<i4").copy()
+
+
+# CartPole draws 8 words per reset and no env falls within 6 steps: after warm_up's 12 steps every env has reset twice
+# and stands at word 16, a tile start.  Three more steps bring the third reset (word 24).
+MIXED_WARM_UP = {"CartPole-v1": STEPS + 3}
+
+
+def mixed_layouts(task, tiles, device_blob):
+    a = Handle(task, seed=7, engine_keys={"mt_tile": tiles[0]})
+    b, twin = (Handle(task, seed=1007, engine_keys={"mt_tile": tiles[1]}) for _ in range(2))
+    rng = np.random.default_rng(4)
+    warm_up(a, rng, MIXED_WARM_UP.get(task, STEPS))
+    b.reset(), twin.reset()
+    for _ in range(5):
+        act = b.actions(rng)
+        b.step(act), twin.step(act)
+    shift, mti = blob_generators(a.api.snapshot(IDS))
+    assert shift == {1: 0, 16: 4}[tiles[0]]
+    assert blob_generators(b.api.snapshot(IDS2))[0] == {1: 0, 16: 4}[tiles[1]]
+    assert ((0 <= mti) & (mti < 624)).all()
+    # inside a tile the two layouts hold different words: a blob whose positions all start a tile would restore
+    # correctly as a verbatim copy, and the case would prove nothing
+    assert (mti % 16 != 0).any(), mti
+    into_another_pool(a, IDS, b, twin, (task, tiles), device_blob)
+    for h in (a, b, twin):
+        h.close()
+
+
+@pytest.mark.parametrize("tiles", [(1, 16), (16, 1)])
+@pytest.mark.parametrize("task", MIXED_LAYOUT_TASKS)
+def test_subset_continues_in_a_pool_of_the_other_generator_layout(task, tiles):
+    """A's generators are [624][N] and B's tiled, or the reverse ("mt_tile"): the restore converts the partly
+    consumed tile of every env, so B's rows IDS2 continue as A's rows IDS do, resets and their draws included."""
+    mixed_layouts(task, tiles, False)
+
+
+@pytest.mark.parametrize("tiles", [(1, 16), (16, 1)])
+def test_device_blob_moves_between_generator_layouts(tiles):
+    mixed_layouts("Blackjack-v1", tiles, True)
 
 
 @pytest.mark.parametrize("task", ["HalfCheetah-v4", "Ant-v4"])

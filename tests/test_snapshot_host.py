@@ -57,14 +57,14 @@ def test_generator_pack_then_unpack_is_the_identity(lib, n, shift):
         ids_a = np.asarray(ids, np.int32)
         blob = np.zeros(MT_WORDS * k, np.uint32)
         src = pool.copy()
-        assert lib.snap_mt_pass(tiled, 0, _ptr(src), n, shift, _ptr(ids_a), k, _ptr(blob), shift) == 0
+        assert lib.snap_mt_pass(tiled, 0, _ptr(src), n, shift, _ptr(ids_a), k, _ptr(blob), shift, None, None) == 0
         assert np.array_equal(src, pool)  # packing reads the pool only
         # the blob is the generator of a k-env pool whose env i is env ids[i]
         for i, e in enumerate(ids):
             for j in (0, 1, 15, 16, 17, 226, 227, 396, 397, 623):
                 assert blob[lib.snap_mt_word_index(j, i, k, shift)] == pool[lib.snap_mt_word_index(j, e, n, shift)]
         back = np.zeros_like(pool)
-        assert lib.snap_mt_pass(tiled, 1, _ptr(back), n, shift, _ptr(ids_a), k, _ptr(blob), shift) == 0
+        assert lib.snap_mt_pass(tiled, 1, _ptr(back), n, shift, _ptr(ids_a), k, _ptr(blob), shift, None, None) == 0
         cols = np.zeros(n, bool)
         cols[ids] = True
         want = np.zeros_like(pool)
@@ -75,21 +75,172 @@ def test_generator_pack_then_unpack_is_the_identity(lib, n, shift):
         assert np.array_equal(back, want)  # the listed envs restored, every other word untouched
 
 
-@pytest.mark.parametrize("pool_shift,blob_shift", [(0, 4), (4, 0)])
-def test_generator_moves_between_layouts(lib, pool_shift, blob_shift):
-    """A blob restored into a pool built with the other generator layout (the word mapping)."""
-    n, ids = 40, [39, 0, 17, 16, 15, 3]
+# A plain restatement of Mt19937 (envpool_amd/csrc/device_common.hip.h): the seeding of InitCommonKernel and the two
+# lazy Next() rules, one generator = 624 words in word order + the position of the next word.
+MASK32 = 0xFFFFFFFF
+
+
+def mt_seeded(seed):
+    w = np.empty(MT_WORDS, np.uint32)
+    x = seed & MASK32
+    w[0] = x
+    for i in range(1, MT_WORDS):
+        x = (1812433253 * (x ^ (x >> 30)) + i) & MASK32
+        w[i] = x
+    return w
+
+
+def mt_twist1(cur, nxt, partner):
+    y = (cur & 0x80000000) | (nxt & 0x7FFFFFFF)
+    return partner ^ (y >> 1) ^ (0x9908B0DF if y & 1 else 0)
+
+
+def mt_partner(j):
+    return j - 227 if j >= 227 else j + 397
+
+
+class MtModel:
+    """shift 0: word i is twisted when it is consumed; shift 4: the 16 words of a tile when its first word is."""
+
+    def __init__(self, words, pos, shift):
+        self.w, self.pos, self.shift = [int(x) for x in words], int(pos), shift
+
+    def _twist(self, j):
+        w = self.w
+        w[j] = mt_twist1(w[j], w[0 if j == MT_WORDS - 1 else j + 1], w[mt_partner(j)])
+
+    def next(self):
+        i = self.pos
+        if self.shift == 0:
+            self._twist(i)
+        elif i % 16 == 0:
+            for j in range(i, i + 16):
+                self._twist(j)
+        y = self.w[i]
+        self.pos = 0 if i == MT_WORDS - 1 else i + 1
+        y ^= y >> 11
+        y ^= (y << 7) & 0x9D2C5680
+        y ^= (y << 15) & 0xEFC60000
+        y ^= y >> 18
+        return y
+
+    def words(self):
+        return np.array(self.w, np.uint32)
+
+
+def numpy_draws(seed, count):
+    """The first `count` 32-bit outputs of std::mt19937(seed): numpy's RandomState seeds and tempers alike."""
+    return np.random.RandomState(seed).randint(0, 2**32, count, dtype=np.uint64).astype(np.uint32)
+
+
+def test_the_restated_generators_are_mt19937():
+    for shift in (0, 4):
+        g = MtModel(mt_seeded(5), 0, shift)
+        assert np.array_equal(np.array([g.next() for _ in range(3000)], np.uint32), numpy_draws(5, 3000))
+
+
+# draws made before the snapshot: the position is draws % 624.  Tile starts, their neighbours, the tiles around the
+# partner boundary (word 227) and the last tile (whose word 623 has the regenerated word 0 as its neighbour), and the
+# same after one and after three wraps.
+MIXED_DRAWS = ([0, 1, 15, 16, 17] + list(range(223, 241)) + list(range(607, 624))
+               + [624 + d for d in (0, 1, 5, 15, 16, 229, 600, 623)] + [3 * 624 + d for d in (0, 8, 226, 227, 376, 623)])
+MIXED_AFTER = 700
+
+
+@pytest.fixture(scope="module")
+def mixed_pools():
+    """Per layout: the generators of a pool whose env e was seeded with 100 + e and has made MIXED_DRAWS[e] draws,
+    as (words [n][624] in word order, positions [n])."""
+    out = {}
+    for shift in (0, 4):
+        words, pos = [], []
+        for e, draws in enumerate(MIXED_DRAWS):
+            g = MtModel(mt_seeded(100 + e), 0, shift)
+            for _ in range(draws):
+                g.next()
+            words.append(g.words())
+            pos.append(g.pos)
+        out[shift] = (np.stack(words), np.array(pos, np.int32))
+    return out
+
+
+def pool_image(lib, words, shift):
+    """[n][624] words in word order -> the flat pool image of that layout."""
+    n = words.shape[0]
+    img = np.zeros(MT_WORDS * n, np.uint32)
+    for e in range(n):
+        for j in range(MT_WORDS):
+            img[lib.snap_mt_word_index(j, e, n, shift)] = words[e, j]
+    return img
+
+
+def pool_words(lib, img, n, shift):
+    idx = np.array([[lib.snap_mt_word_index(j, e, n, shift) for j in range(MT_WORDS)] for e in range(n)])
+    return img[idx]
+
+
+def move_through_a_blob(lib, src_img, src_mti, n, blob_shift, pool_shift, ids, dst_img, dst_mti):
+    """Snapshot (the source pool's layout) and restore into a pool image of `pool_shift`, as the engine picks the
+    kernels: the tile mapping when both sides are tiled, the word mapping otherwise."""
     k = len(ids)
     ids_a = np.asarray(ids, np.int32)
+    blob, blob_mti = np.zeros(MT_WORDS * k, np.uint32), np.zeros(k, np.int32)
+    assert lib.snap_mt_pass(1 if blob_shift == 4 else 0, 0, _ptr(src_img), n, blob_shift, _ptr(ids_a), k, _ptr(blob),
+                            blob_shift, _ptr(src_mti), _ptr(blob_mti)) == 0
+    assert np.array_equal(blob_mti, src_mti[ids_a])
+    assert lib.snap_mt_pass(1 if blob_shift == pool_shift == 4 else 0, 1, _ptr(dst_img), n, pool_shift, _ptr(ids_a), k,
+                            _ptr(blob), blob_shift, _ptr(dst_mti), _ptr(blob_mti)) == 0
+
+
+@pytest.mark.parametrize("pool_shift,blob_shift", [(0, 4), (4, 0), (0, 0), (4, 4)])
+def test_generator_continues_in_the_other_layout(lib, mixed_pools, pool_shift, blob_shift):
+    """A generator restored into a pool of the other layout holds, word for word, what a generator of THAT layout
+    holds at the same position, and its next 700 outputs are std::mt19937's.  (Same-layout restores ride along: they
+    are plain copies and must stay so.)"""
+    n = len(MIXED_DRAWS)
+    src_words, src_mti = mixed_pools[blob_shift]
+    want_words, want_mti = mixed_pools[pool_shift]
+    assert any(p % 16 for p in src_mti) and 0 in src_mti and 623 in src_mti
+    src = pool_image(lib, src_words, blob_shift)
+    dst, dst_mti = np.zeros(MT_WORDS * n, np.uint32), np.full(n, -1, np.int32)
+    move_through_a_blob(lib, src, src_mti.copy(), n, blob_shift, pool_shift, list(range(n))[::-1], dst, dst_mti)
+    assert np.array_equal(dst_mti, want_mti)
+    got = pool_words(lib, dst, n, pool_shift)
+    bad = np.argwhere(got != want_words)
+    assert bad.size == 0, [(MIXED_DRAWS[e], j) for e, j in bad[:8]]
+    for e, draws in enumerate(MIXED_DRAWS):
+        g = MtModel(got[e], dst_mti[e], pool_shift)
+        out = np.array([g.next() for _ in range(MIXED_AFTER)], np.uint32)
+        assert np.array_equal(out, numpy_draws(100 + e, draws + MIXED_AFTER)[draws:]), draws
+
+
+@pytest.mark.parametrize("pool_shift,blob_shift", [(0, 4), (4, 0)])
+def test_generator_moves_between_layouts(lib, pool_shift, blob_shift):
+    """A blob restored into a pool built with the other generator layout: the word mapping moves every word outside
+    the tile that holds the position verbatim -- and all words of an env whose position starts a tile -- into the
+    listed columns only, and the positions with them.  The words of the partly consumed tile in front of the
+    position stay too (they are the new block's in both layouts); what the rest of that tile becomes is
+    test_generator_continues_in_the_other_layout's subject."""
+    n, ids = 40, [39, 0, 17, 16, 15, 3]
+    k = len(ids)
     src = np.arange(1, MT_WORDS * n + 1, dtype=np.uint32)  # in the blob's layout
-    blob = np.zeros(MT_WORDS * k, np.uint32)
-    assert lib.snap_mt_pass(1 if blob_shift == 4 else 0, 0, _ptr(src), n, blob_shift, _ptr(ids_a), k, _ptr(blob),
-                            blob_shift) == 0
-    dst = np.zeros(MT_WORDS * n, np.uint32)
-    assert lib.snap_mt_pass(0, 1, _ptr(dst), n, pool_shift, _ptr(ids_a), k, _ptr(blob), blob_shift) == 0
+    src_mti = ((np.arange(n) * 37 + 6) % MT_WORDS).astype(np.int32)
+    src_mti[[0, 16]] = [0, 608]  # two of the listed envs are at a tile start
+    assert sum(src_mti[e] % 16 != 0 for e in ids) == k - 2
+    dst, dst_mti = np.zeros(MT_WORDS * n, np.uint32), np.full(n, -1, np.int32)
+    move_through_a_blob(lib, src, src_mti.copy(), n, blob_shift, pool_shift, ids, dst, dst_mti)
+    touched = np.zeros(MT_WORDS * n, bool)
     for e in ids:
+        p = int(src_mti[e])
+        assert dst_mti[e] == p
         for j in range(MT_WORDS):
-            assert dst[lib.snap_mt_word_index(j, e, n, pool_shift)] == src[lib.snap_mt_word_index(j, e, n, blob_shift)]
+            w = lib.snap_mt_word_index(j, e, n, pool_shift)
+            touched[w] = True
+            if p % 16 == 0 or not p <= j <= (p | 15):
+                assert dst[w] == src[lib.snap_mt_word_index(j, e, n, blob_shift)], (e, j)
+    assert not dst[~touched].any()  # no other env's word is written
+    others = np.setdiff1d(np.arange(n), ids)
+    assert (dst_mti[others] == -1).all()
 
 
 def test_word_index_is_the_step_kernels_layout(lib):
