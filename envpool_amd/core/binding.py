@@ -329,13 +329,14 @@ class _ShardedPools:
     def guided_shape(self) -> tuple[int, int, int, int]:
         return self.pools[0].guided_shape()
 
-    def guided_begin(self, env_ids: Any = None, simulations: int = 64,
-                     c_puct: float = 1.25) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
+                     nodes: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A session in every shard that owns listed envs, all shards at once.  The search has no random numbers and
         no dependence on the env id, so the rows are those of the unsharded pool."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
         ids = native.check_guided(env_ids, simulations, c_puct)
+        cap = native.check_guided_nodes(simulations, nodes)
         h, w, c, a = self.guided_shape()
         shard = (ids - self.offset) // self.per
         bad = ids[(shard < 0) | (shard >= len(self.pools))]
@@ -347,11 +348,29 @@ class _ShardedPools:
                   np.empty(k, dtype=np.uint8))
 
         def begin(s: int, p: DevicePool, idx: Any) -> None:
-            for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct)):
+            for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct, *((nodes,) if nodes else ()))):
                 o[idx] = part
 
         self._each(begin, parts)
         self._guided = (k, a, parts)
+        self._guided_nodes = cap
+        return leaves
+
+    def guided_reroot(self, actions: Any, simulations: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`guided_reroot` of every shard's session, all shards at once; row i of `actions` goes with root i."""
+        k, a, parts = self._guided_session("guided_reroot")
+        if getattr(self, "_guided_nodes", None) is None:
+            raise ValueError("guided_reroot: reroot not implemented for gumbel sessions")
+        actions = native.check_guided_reroot(actions, k, a, simulations, self._guided_nodes)
+        h, w, c, _ = self.guided_shape()
+        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
+                  np.empty(k, dtype=np.uint8))
+
+        def reroot(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(leaves, p.guided_reroot(actions[idx], simulations)):
+                o[idx] = part
+
+        self._each(reroot, parts)
         return leaves
 
     def _guided_session(self, what: str) -> tuple:
@@ -421,6 +440,7 @@ class _ShardedPools:
 
         self._each(begin, parts)
         self._guided = (k, a, parts)
+        self._guided_nodes = None  # (no reroot of a Gumbel session)
         return leaves
 
     def gumbel_advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -504,21 +504,45 @@ class DevicePool:
         h, w, c, a = self.guided_shape()
         return np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_), np.empty(k, dtype=np.uint8)
 
-    def guided_begin(self, env_ids: Any = None, simulations: int = 64,
-                     c_puct: float = 1.25) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
+                     nodes: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Opens the pool's guided-search session (the PGX board games; RuntimeError("guided search not implemented
         for this environment") elsewhere) on the current positions of the listed envs (global ids; None: the whole
         pool), replacing any earlier one: a PUCT search whose tree stays on the device and that stops at every new
         leaf for the caller's priors and value (include/envpool_amd.h: epa_guided_begin has the contract).  Returns
         the first leaves (obs bool [k, H, W, C] of the seat to move, mask bool [k, A], status uint8 [k]: 0 evaluate,
         1 a finished game, 2 nothing pending).  Nothing of the pool changes, and later steps of the pool change
-        nothing in the session."""
+        nothing in the session.  `nodes`: the node capacity per root, simulations + 1 .. 8192 (0: simulations + 1),
+        the room `guided_reroot` needs to keep a subtree and grow it."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
+        cap = native.check_guided_nodes(simulations, nodes)
         self.guided_shape()
         obs, mask, status = self._guided_leaves(len(ids))
-        native.check(self._lib.epa_guided_begin(self._h, ids.ctypes.data, len(ids), int(simulations), float(c_puct),
-                                                obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
-        self._guided_k, self._guided_policy = len(ids), "puct"
+        if nodes:
+            native.check(self._lib.epa_guided_begin_nodes(self._h, ids.ctypes.data, len(ids), int(simulations), cap,
+                                                          float(c_puct), obs.ctypes.data, mask.ctypes.data,
+                                                          status.ctypes.data))
+        else:
+            native.check(self._lib.epa_guided_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                    float(c_puct), obs.ctypes.data, mask.ctypes.data,
+                                                    status.ctypes.data))
+        self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
+        return obs, mask, status
+
+    def guided_reroot(self, actions: Any, simulations: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Tree reuse, after the round's last advance: root i's tree becomes the subtree under `actions[i]` (int32
+        [k], the move played), compacted in place on the device; a move the search never tried gives a fresh tree on
+        the position behind it, and a root whose game that move ends is over from then on.  The next round has
+        `simulations` simulations (simulations + 1 <= the session's nodes) and starts with the new roots as its
+        leaves, which are returned as `guided_begin` returns its own; the kept visits count in `guided_result`.
+        ValueError before any launch: no session, a Gumbel session, a round that is not complete, another number of
+        rows, an action outside 0 .. A-1."""
+        k = self._guided_open("guided_reroot", "puct")
+        actions = native.check_guided_reroot(actions, k, self.guided_shape()[3], simulations,
+                                             getattr(self, "_guided_nodes", native.GUIDED_MAX_NODES))
+        obs, mask, status = self._guided_leaves(k)
+        native.check(self._lib.epa_guided_reroot(self._h, actions.ctypes.data, k, int(simulations), obs.ctypes.data,
+                                                 mask.ctypes.data, status.ctypes.data))
         return obs, mask, status
 
     def _guided_open(self, what: str, policy: str) -> int:
@@ -563,15 +587,33 @@ class DevicePool:
         self._guided_k = None
 
     def guided_begin_device(self, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None, simulations: int = 64,
-                            c_puct: float = 1.25) -> int:
+                            c_puct: float = 1.25, nodes: int = 0) -> int:
         """`guided_begin` with the leaves written to device memory at the raw addresses `d_obs` (k H W C bytes),
         `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
-        native.check(self._lib.epa_guided_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                       float(c_puct), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
-                                                       ctypes.c_void_p(d_status)))
-        self._guided_k, self._guided_policy = len(ids), "puct"
+        cap = native.check_guided_nodes(simulations, nodes)
+        if nodes:
+            native.check(self._lib.epa_guided_begin_nodes_device(
+                self._h, ids.ctypes.data, len(ids), int(simulations), cap, float(c_puct), ctypes.c_void_p(d_obs),
+                ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        else:
+            native.check(self._lib.epa_guided_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                           float(c_puct), ctypes.c_void_p(d_obs),
+                                                           ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
         return len(ids)
+
+    def guided_reroot_device(self, d_actions: int, k: int, simulations: int, d_obs: int, d_mask: int,
+                             d_status: int) -> None:
+        """`guided_reroot` on device memory: `d_actions` (int32 [k], 4-byte aligned) is read by the kernel, which
+        ends a root whose action is outside 0 .. A-1; the leaves are written at `d_obs`, `d_mask`, `d_status`; only
+        enqueued."""
+        self._guided_open("guided_reroot", "puct")
+        native.check_guided_reroot(None, k, 0, simulations, getattr(self, "_guided_nodes", native.GUIDED_MAX_NODES),
+                                   device=True)
+        native.check(self._lib.epa_guided_reroot_device(self._h, ctypes.c_void_p(d_actions), int(k), int(simulations),
+                                                        ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                        ctypes.c_void_p(d_status)))
 
     def guided_advance_device(self, d_priors: int, d_values: int, k: int, d_obs: int, d_mask: int,
                               d_status: int) -> None:

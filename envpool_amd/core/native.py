@@ -28,6 +28,7 @@ EPA_PLAYOUT_COMMIT = 1
 PLAYOUT_MAX_PLIES = 256
 PLAYOUT_MAX_REPEATS = 4096
 SEARCH_MAX_SIMULATIONS = 4096
+GUIDED_MAX_NODES = 8192  # EPA_GUIDED_MAX_NODES: the largest node capacity of a guided-search root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
@@ -134,6 +135,10 @@ def lib() -> ctypes.CDLL:
         "epa_guided_result": (i32, [vp, vp, vp, vp]),
         "epa_guided_result_device": (i32, [vp, vp, vp, vp]),
         "epa_guided_end": (i32, [vp]),
+        "epa_guided_begin_nodes": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_begin_nodes_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_reroot": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "epa_guided_reroot_device": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_begin_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_advance": (i32, [vp, vp, vp, i32, vp, vp, vp]),
@@ -176,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "epa_playout", "epa_playout_device", "epa_search_actions", "epa_search", "epa_search_device",
     "epa_guided_shape", "epa_guided_begin", "epa_guided_begin_device", "epa_guided_advance",
     "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
+    "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device",
     "epa_atari_post_create",
@@ -270,6 +276,38 @@ def check_guided(env_ids: Any, simulations: int, c_puct: float) -> np.ndarray:
     if len(ids) == 0:
         raise ValueError("guided_begin env_ids must not be empty")
     return ids
+
+
+def check_guided_nodes(simulations: int, nodes: Any) -> int:
+    """The node capacity per root of a guided_begin call: `nodes` (None or 0: simulations + 1) after its check:
+    ValueError outside simulations + 1 .. 8192."""
+    if nodes is None or int(nodes) == 0:
+        return int(simulations) + 1
+    if not int(simulations) + 1 <= int(nodes) <= GUIDED_MAX_NODES:
+        raise ValueError(f"guided_begin: nodes = {nodes} must be simulations + 1 = {int(simulations) + 1} .. "
+                         f"{GUIDED_MAX_NODES}")
+    return int(nodes)
+
+
+def check_guided_reroot(actions: Any, k: int, n_actions: int, simulations: int, nodes: int,
+                        device: bool = False) -> np.ndarray:
+    """The checks of a guided_reroot call that every layer makes before the native call: ValueError for simulations
+    outside 1 .. 4096 or above nodes - 1, and, in the host form, for another number of rows than the session's and an
+    action outside 0 .. A-1; returns the actions as a contiguous int32 array [k].  (The device form cannot look at its
+    rows -- `actions` is returned as it is; there the kernel ends such a root.)"""
+    if not 1 <= int(simulations) <= SEARCH_MAX_SIMULATIONS:
+        raise ValueError(f"guided_reroot: simulations = {simulations} must be 1 .. {SEARCH_MAX_SIMULATIONS}")
+    if int(simulations) + 1 > int(nodes):
+        raise ValueError(f"guided_reroot: simulations = {simulations} need {int(simulations) + 1} nodes, the session "
+                         f"has {nodes} per root")
+    if device:
+        return actions
+    actions = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1)
+    if actions.shape != (k,):
+        raise ValueError(f"guided_reroot: {len(actions)} actions for a session of {k} roots")
+    if not ((actions >= 0) & (actions < n_actions)).all():
+        raise ValueError(f"guided_reroot: actions must be 0 .. {n_actions - 1}")
+    return actions
 
 
 def check_guided_rows(priors: Any, values: Any, k: int, actions: int) -> tuple[np.ndarray, np.ndarray]:

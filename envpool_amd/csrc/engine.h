@@ -161,16 +161,19 @@ struct DeviceBlock {
   }
 };
 
-// One launch of a guided-search session (Pool::GuidedBegin / GuidedAdvance / GuidedResult): the session's k roots,
-// its root records and nodes (family types: Pool::GuidedRootBytes / GuidedNodeBytes), and the device arrays the
-// launch reads or writes -- begin and advance the three leaf arrays, advance the caller's rows, result its three.
+// One launch of a guided-search session (Pool::GuidedBegin / GuidedAdvance / GuidedResult / GuidedReroot): the
+// session's k roots, its root records and nodes (family types: Pool::GuidedRootBytes / GuidedNodeBytes), and the device
+// arrays the launch reads or writes -- begin, advance and reroot the three leaf arrays, advance the caller's rows,
+// reroot the played actions, result its three.
 struct GuidedArgs {
   int k;
   int simulations;
   int call;                 // advance: its number t = 0 .. simulations
+  int capacity;             // nodes per root, the stride of a root's node block: simulations + 1 .. EPA_GUIDED_MAX_NODES
   float c_puct;
   void* roots;              // [k], 16-byte aligned
-  void* nodes;              // [k][simulations + 1], 16-byte aligned
+  void* nodes;              // [k][capacity], 16-byte aligned
+  const int32_t* actions;   // reroot: [k]
   const float* priors;      // [k][A]
   const float* values;      // [k]
   unsigned char* obs;       // [k][H][W][C]
@@ -412,9 +415,16 @@ class Pool {
   virtual void GuidedBegin(const int* d_ids, const GuidedArgs& a);
   virtual void GuidedAdvance(const GuidedArgs& a);
   virtual void GuidedResult(const GuidedArgs& a);
-  // obs / mask / status: host arrays (device == false) or device pointers
-  void GuidedBeginCall(const int32_t* ids, int k, int simulations, float c_puct, void* obs, void* mask, void* status,
-                       bool device);
+  virtual void GuidedReroot(const GuidedArgs& a);
+  // obs / mask / status: host arrays (device == false) or device pointers.  nodes: the capacity per root, 0 for
+  // simulations + 1.
+  void GuidedBeginCall(const int32_t* ids, int k, int simulations, int nodes, float c_puct, void* obs, void* mask,
+                       void* status, bool device);
+  // Tree reuse (pgx_guided.hip.h "Tree reuse"): after the round's last advance, the subtree under actions[i] becomes
+  // root i's tree, `simulations` the length of the next round, and the new roots are emitted as begin emits its own.
+  // actions: a host array (checked against 0 .. A-1 here) or a device pointer (the kernel ends such a root).  PUCT
+  // sessions only.
+  void GuidedRerootCall(const void* actions, int k, int simulations, void* obs, void* mask, void* status, bool device);
   void GuidedAdvanceCall(const void* priors, const void* values, int k, void* obs, void* mask, void* status,
                          bool device);
   void GuidedResultCall(void* visits, void* values, void* action, bool device);
@@ -633,6 +643,7 @@ class Pool {
     char* pinned{nullptr};  // the host forms' pinned block, laid out like the staging
     bool gumbel{false};     // the session's policy: PUCT or Gumbel
     int k{0}, simulations{0}, calls{0};
+    int capacity{0};        // nodes per root (PUCT: simulations + 1 .. EPA_GUIDED_MAX_NODES; Gumbel: simulations + 1)
     float c_puct{0.0f};
     int considered{0};      // Gumbel: m, c_visit, c_scale
     float c_visit{0.0f}, c_scale{0.0f};

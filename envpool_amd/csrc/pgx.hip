@@ -19,7 +19,8 @@
 // Playout: pgx_playout.hip.h, one (env, repeat) per lane, the whole game in registers (PgxPlayoutKernel).
 // Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
 // Guided search: pgx_guided.hip.h, one wave per root and one launch per simulation, the tree in the session's own
-// memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult).
+// memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult), and PgxGuidedReroot, which keeps the
+// played move's subtree for the next move by compacting it in place.
 // Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
 // policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
 #include <algorithm>
@@ -216,7 +217,8 @@ __global__ __launch_bounds__(kPlayoutBlock) void PgxPlayoutKernel(CommonDev cm, 
 // of a descent (the same pair brackets the path in LDS), so neither the compiler nor the memory pipeline reorders them.
 constexpr int kSearchBlock = pgx::kSearchWave;
 static_assert(pgx::kSearchMaxSimulations == EPA_SEARCH_MAX_SIMULATIONS &&
-                  pgx::kSearchMaxLeafPlayouts == EPA_SEARCH_MAX_LEAF_PLAYOUTS,
+                  pgx::kSearchMaxLeafPlayouts == EPA_SEARCH_MAX_LEAF_PLAYOUTS &&
+                  pgx::kGuidedMaxNodes == EPA_GUIDED_MAX_NODES,
               "the C ABI states the header's limits");
 
 __device__ __forceinline__ void WaveRelease() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); }
@@ -436,7 +438,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedBegin(CommonDev cm, con
   const int e = ids[row];
   const bool over = cm.done[e] != 0;  // (an env before its first reset is)
   const pgx::State root = st[e];
-  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
   if (lane == 0) {
     n0.s = root;
     n0.term0 = 0;
@@ -457,7 +459,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
   const int row = blockIdx.x, lane = threadIdx.x;
   const int S = a.simulations;
   pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[row];
-  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)(S + 1);
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
   WaveAcquire();
   int status = rec.status;
   pgx::State s{};  // the pending leaf's position when the launch ends
@@ -485,11 +487,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
       }
     }
     WaveRelease();
-    if (a.call >= S) {
+    int count = rec.count;
+    // the round's last call -- or the root's memory is used up (a rerooted tree may come to that): a normal end
+    if (a.call >= S || count >= a.capacity) {
       status = pgx::kGuidedIdle;
       if (lane == 0) rec.status = status;
     } else {
-      int node = 0, depth = 0, count = rec.count;
+      int node = 0, depth = 0;
       bool broken = false;
       WaveAcquire();
       s = nodes[0].s;
@@ -538,11 +542,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
           c = slot == 1 ? c1 : c;
         }
         if (c < 0) {
-          if (count > S) {  // (one node per call: never; the session's memory ends here)
-            broken = true;
-            break;
-          }
-          c = count++;
+          c = count++;  // (count < capacity: checked before the descent, which makes one node at the most)
           if (lane == owner) nd.child[act] = c;
           Node& nn = nodes[c];
           pgx::State s2;
@@ -570,7 +570,10 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
         rec.pending = node;
         rec.status = status;
         rec.depth = broken ? 0 : depth;
-        if (broken) *err = kErrGuided;
+        if (broken) {
+          rec.broken = 1;
+          *err = kErrGuided;
+        }
       }
     }
     WaveRelease();
@@ -584,7 +587,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   using Node = pgx::GuidedNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
   const pgx::GuidedRoot& rec = static_cast<const pgx::GuidedRoot*>(a.roots)[row];
-  const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
+  const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
   WaveAcquire();
   const bool over = rec.over != 0;
   const pgx::State root = n0.s;
@@ -602,6 +605,125 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   }
   const int best = WaveBest(mine).action;  // (-1 without a legal action)
   if (lane == 0) a.action[row] = best;
+}
+
+// reroot (pgx_guided.hip.h "Tree reuse"): the subtree under the played move becomes the tree, compacted in place.  One
+// wave per root, one block per wave, the lane ownership of PgxGuidedAdvance: lane j is the only lane that reads or
+// writes child / v / w0 / p of actions j and j + 64, in the source node and in the destination node; lane 0 moves
+// State and term0 and writes the root record.
+//   table          int32[capacity] in LDS, first the marks, then the ranks.  The array is static, in three sizes of
+//                  512, 2048 and 8192 entries (2, 8 and 32 KiB; the launch takes the smallest that holds the session's
+//                  capacity): with a dynamic array the backend keeps the per-lane homes of `Step`'s seat-indexed
+//                  reward pairs in scratch instead of LDS
+//   mark           the nodes in index order; whether node i is kept is one LDS word, so the branch is wave-uniform; the
+//                  lanes of a kept node mark its children, whose indices are all above i
+//   rank           64 nodes a trip: a lane's mark, an inclusive wave scan by register shifts, the carry of the trips
+//                  before; the rank replaces the mark
+//   copy           the nodes in index order again, kept ones only (wave-uniform); new index < old index, so a store
+//                  lands on a slot that no later trip loads
+// The table's hand-offs between lanes sit between wavefront-scope release and acquire fences with the block's barrier
+// between them, as the path of PgxSearchKernel; so do the loads of what earlier launches stored and the stores that
+// later launches load.
+__device__ __forceinline__ int WaveScan(int x, int lane) {  // the inclusive prefix sum over the wave's lanes
+#pragma unroll
+  for (int m = 1; m < kSearchBlock; m <<= 1) {
+    const int y = __shfl_up(x, m, kSearchBlock);
+    if (lane >= m) x += y;
+  }
+  return x;
+}
+
+constexpr int kRerootTables[3] = {512, 2048, pgx::kGuidedMaxNodes};
+
+template <int G, int CAP>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  __shared__ int32_t table[CAP];  // (a.capacity <= CAP)
+  const int row = blockIdx.x, lane = threadIdx.x;
+  pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[row];
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
+  WaveAcquire();
+  const int act = a.actions[row];
+  const int old_count = std::min(std::max(rec.count, 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
+  bool over = rec.over != 0 || rec.broken != 0 || act < 0 || act >= A;
+  int count = old_count;
+  pgx::State s = nodes[0].s;
+  if (!over) {
+    const int c = nodes[0].child[act];  // one address: wave-uniform
+    if (c < 0 || c >= old_count) {      // (never >= count) a move the search did not try: a fresh tree on its position
+      pgx::State s2;
+      const int term0 = pgx::SearchExpand<G>(s, act, s2);
+      if (lane == 0) {
+        nodes[0].s = s2;
+        nodes[0].term0 = term0;
+      }
+#pragma unroll
+      for (int j = 0; j < SL; ++j) {
+        if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(nodes[0], lane + kSearchBlock * j);
+      }
+      s = s2;
+      count = 1;
+    } else {
+      s = nodes[c].s;  // (read before the copy below reuses the slot)
+      for (int i = lane; i < old_count; i += kSearchBlock) table[i] = i == c ? 1 : 0;
+      WaveRelease();
+      __syncthreads();
+      WaveAcquire();
+      for (int i = c; i < old_count; ++i) {
+        if (table[i] != 0) {
+#pragma unroll
+          for (int j = 0; j < SL; ++j) {
+            if (lane + kSearchBlock * j < A) {
+              const int ch = nodes[i].child[lane + kSearchBlock * j];
+              if (ch < old_count) pgx::GuidedRerootReach(table, ch);  // (never >= count)
+            }
+          }
+          WaveRelease();
+          __syncthreads();
+          WaveAcquire();
+        }
+      }
+      int kept = 0;
+      for (int base = 0; base < old_count; base += kSearchBlock) {
+        const int i = base + lane;
+        const int m = i < old_count && table[i] != 0 ? 1 : 0;
+        const int upto = WaveScan(m, lane);
+        if (i < old_count) table[i] = pgx::GuidedRerootRank(kept + upto - m, m != 0);
+        kept += __shfl(upto, kSearchBlock - 1, kSearchBlock);
+      }
+      WaveRelease();
+      __syncthreads();
+      WaveAcquire();
+      for (int i = c; i < old_count; ++i) {
+        const int dst = table[i];
+        if (dst >= 0 && dst != i) {  // (dst < i: node 0 is never kept)
+          const Node& from = nodes[i];
+          Node& to = nodes[dst];
+          if (lane == 0) {
+            to.s = from.s;
+            to.term0 = from.term0;
+          }
+#pragma unroll
+          for (int j = 0; j < SL; ++j) {
+            const int e = lane + kSearchBlock * j;
+            if (e < A) {
+              const int ch = from.child[e];
+              to.child[e] = pgx::GuidedRerootEdge(table, ch < old_count ? ch : -1);
+              to.v[e] = from.v[e];
+              to.w0[e] = from.w0[e];
+              to.p[e] = from.p[e];
+            }
+          }
+        }
+      }
+      count = kept;
+    }
+    over = s.done != 0;
+  }
+  if (lane == 0) pgx::GuidedRerootRoot(rec, count, over);
+  WaveRelease();
+  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
 }
 
 // Gumbel search (pgx_gumbel.hip.h): the session, lane ownership, hand-offs and leaves of the guided kernels above with
@@ -1036,6 +1158,15 @@ class PgxPool : public Pool {
   }
   void GuidedResult(const GuidedArgs& a) override {
     hipLaunchKernelGGL(PgxGuidedResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+  }
+  void GuidedReroot(const GuidedArgs& a) override {
+    if (a.capacity <= kRerootTables[0]) {
+      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[0]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+    } else if (a.capacity <= kRerootTables[1]) {
+      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[1]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+    } else {
+      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[2]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+    }
   }
   size_t GumbelNodeBytes() const override { return sizeof(pgx::GumbelNode<G>); }
   size_t GumbelRootBytes() const override { return sizeof(pgx::GumbelRoot<G>); }

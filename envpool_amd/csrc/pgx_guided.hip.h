@@ -47,6 +47,32 @@
 // A running position without a legal action, or a path past kSearchMaxPath, is no position of the game: that root
 // ends with status 2 (the kernel also sets the pool's error word, the harness returns -3).
 //
+// Tree reuse (DESIGN.md "PGX guided search: tree reuse").  A session has a node CAPACITY per root, C: S + 1 unless
+// begin is given `nodes = C` with S + 1 <= C <= kGuidedMaxNodes.  A root's node block has C nodes (its stride), and
+// advance has one more rule: a root begins a descent only if count < C; otherwise it goes to status 2 for the rest of
+// the round, a normal end ("memory used up") that sets no error.  With C = S + 1 and no reroot it never triggers
+// (count <= t + 1 <= S at call t < S), so such a session is, byte for byte, the one described above.
+//   reroot(actions[k], S2) -- only when the round is complete (simulations + 1 advances made); per root, a = actions[i]:
+//     idle root (over != 0, or broken):  stays over (over = 1, status 2); a is ignored
+//     a outside 0 .. A-1:                over = 1, status 2  (the host forms refuse such a row before any launch)
+//     c = node0.child[a] >= 0:  the subtree of c is kept.  A node is kept if it is c or the child of a kept node
+//         (GuidedRerootReach; a child's index is above its parent's, so one pass in index order finds them all).  The
+//         new index of a kept node is its rank among the kept nodes in increasing old index (GuidedRerootRank), so
+//         order is preserved and c becomes 0.  Each kept node is copied to its new slot with child[] remapped
+//         (GuidedRerootEdge); State, term0, v, w0 and p stay bit for bit.  count = the number kept.  As new index <=
+//         old index and the nodes are processed in increasing order, a copy only ever lands on a slot whose node was
+//         dropped or has moved already, and no later copy reads it: the compaction is in place.
+//     c < 0:  node 0 = Step<G>(root position, a), made as SearchExpand makes it; its edges are cleared; count = 1
+//     then:   the new root's State.done set (also: an illegal played move, which Step turns into a finished game):
+//             over = 1, status 2 -- result() gives -1 and zero rows as for a root that was over at begin;
+//             otherwise pending = 0, depth = 0, status 0.
+//     the session's simulations become S2 (1 .. 4096, S2 + 1 <= C) and the call number restarts at 0
+//     emit leaves.
+// The new root is ALWAYS handed out for evaluation, as begin hands out the root: advance 0 of the new round writes the
+// caller's priors into it (replacing the stored ones: fresh root noise) and backs up nothing, the statistics below the
+// root stay, and result() counts the kept visits.  So a round after reroot is again S2 + 1 advances in lockstep for
+// all roots.  reroot has no floating-point arithmetic.
+//
 // There are no random numbers.  Only seat 0's value is stored, as in pgx_search.hip.h: the games are zero-sum.  Build
 // without fast-math and with -ffp-contract=off.
 #ifndef ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
@@ -61,6 +87,8 @@ namespace epa {
 namespace pgx {
 
 enum GuidedStatus : int { kGuidedEvaluate = 0, kGuidedTerminal = 1, kGuidedIdle = 2 };
+// the largest node capacity of a root: reroot's mark / remap table, one int32 per node, is at most 32 KiB of LDS
+constexpr int kGuidedMaxNodes = 8192;
 
 // One node in the session's memory.  The per-action arrays are action-major, so the loads of a wave's lanes (lane j:
 // entries j and j + 64) are contiguous.  The State is written by one lane when the node is made and read by every
@@ -82,8 +110,9 @@ struct alignas(16) GuidedRoot {
   int32_t pending;  // the pending leaf
   int32_t status;   // GuidedStatus
   int32_t depth;    // entries of `path`
-  int32_t over;     // the env was over at begin
-  int32_t pad[3];
+  int32_t over;     // the env was over at begin, or the root became over at a reroot
+  int32_t broken;   // advance met a position that is no position of the game
+  int32_t pad[2];
   int32_t path[kSearchMaxPath];
 };
 
@@ -113,6 +142,25 @@ PGX_HD inline void GuidedClearRoot(GuidedRoot& r, bool over) {
   r.status = over ? kGuidedIdle : kGuidedEvaluate;
   r.depth = 0;
   r.over = over ? 1 : 0;
+  r.broken = 0;
+}
+
+// reroot, the reachability rule: a kept node's edge keeps its child.  `mark` has one entry per node, nonzero: kept.
+PGX_HD inline void GuidedRerootReach(int32_t* mark, int child) {
+  if (child >= 0) mark[child] = 1;
+}
+// reroot, the rank: the new index of a node, given how many nodes of a lower index are kept; -1 for a dropped node
+PGX_HD inline int GuidedRerootRank(int kept_below, bool kept) { return kept ? kept_below : -1; }
+// reroot, one edge of a kept node: its child's new index out of the table of ranks
+PGX_HD inline int GuidedRerootEdge(const int32_t* rank, int child) { return child >= 0 ? rank[child] : -1; }
+// the root record after a reroot; `over`: the root is idle from now on
+PGX_HD inline void GuidedRerootRoot(GuidedRoot& r, int count, bool over) {
+  r.count = count;
+  r.pending = 0;
+  r.status = over ? kGuidedIdle : kGuidedEvaluate;
+  r.depth = 0;
+  r.over = over ? 1 : 0;
+  r.broken = 0;
 }
 
 // bytes of one emitted obs row: the mover's [H, W, C] block of the kObs key

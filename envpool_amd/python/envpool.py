@@ -52,13 +52,26 @@ class GuidedSearch:
 
     or step by step: `leaves` -> (obs bool [k, H, W, C] of the seat to move, mask bool [k, A], status uint8 [k]:
     0 evaluate, 1 a finished game (the row is ignored), 2 nothing pending); `advance(priors [k, A], values [k])`
-    answers them and fetches the next; `result()` at any time; `close()` releases the device memory."""
+    answers them and fetches the next; `result()` at any time; `close()` releases the device memory.
 
-    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float):
+    Tree reuse over a game: open the session with `nodes=` (room per root, simulations + 1 .. 8192), keep it open with
+    `run(evaluate, close=False)`, play the move, and `reroot(actions)` makes the subtree under the played move the tree
+    of the next round -- the simulations already evaluated below it are kept:
+
+        gs = env.guided_search(ids, simulations=64, nodes=129)
+        while playing:
+            result = gs.run(evaluate, close=False)
+            env.step(result.action, ids)
+            gs.reroot(result.action)"""
+
+    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float, nodes: Any = None):
         self._pool = pool
         self.simulations = int(simulations)
         self.calls = 0
-        self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct))
+        if nodes is None:
+            self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct))
+        else:
+            self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes))
 
     def advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         if self._pool is None:
@@ -74,13 +87,29 @@ class GuidedSearch:
             raise ValueError("guided search: the session is closed")
         return GuidedResult(*self._pool.guided_result())
 
-    def run(self, evaluate: Any) -> GuidedResult:
+    def reroot(self, actions: Any, simulations: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """After the round's last advance: the subtree under `actions[i]` (the move played at root i) becomes root
+        i's tree, and a new round of `simulations` (None: as the last one) begins with the new roots as `leaves`,
+        which are returned.  A move the search never tried gives a fresh tree; a root whose game the move ends is over
+        from then on (status 2, result -1 and zeros).  The kept visits count in `result()`."""
+        if self._pool is None:
+            raise ValueError("guided search: the session is closed")
+        if self.calls != self.simulations + 1:
+            raise ValueError(f"guided_reroot: the round is not complete: {self.calls} of {self.simulations + 1} "
+                             f"advances made")
+        s2 = self.simulations if simulations is None else int(simulations)
+        self.leaves = self._pool.guided_reroot(actions, s2)
+        self.simulations, self.calls = s2, 0
+        return self.leaves
+
+    def run(self, evaluate: Any, close: bool = True) -> GuidedResult:
         """Calls `evaluate(obs, mask, status) -> (priors, values)` until simulations + 1 advances are made, returns
-        the result and closes the session."""
+        the result and closes the session (`close=False`: leaves it open, for `reroot`)."""
         while self.calls <= self.simulations:
             self.advance(*evaluate(*self.leaves))
         out = self.result()
-        self.close()
+        if close:
+            self.close()
         return out
 
     def close(self) -> None:
@@ -311,14 +340,18 @@ class EnvPoolMixin(ABC):
                                     int(seed)))
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
-                      **gumbel: Any) -> Any:
+                      nodes: Any = None, **gumbel: Any) -> Any:
         """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
         (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
         pool has one at a time, and a new one replaces it.  Nothing of the pool changes.  The arguments are checked
         before any native call.  `policy="gumbel"` is `gumbel_search(env_ids, simulations, **gumbel)` instead (c_puct
-        is not used) and returns a `GumbelSearch`."""
+        is not used) and returns a `GumbelSearch`.  `nodes` (PUCT only): the node capacity per root, simulations + 1 ..
+        8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree."""
         if policy == "gumbel":
+            if nodes is not None:
+                raise ValueError("guided_search: nodes is an argument of policy='puct' (reroot not implemented for "
+                                 "gumbel sessions)")
             return self.gumbel_search(env_ids, simulations, **gumbel)
         if policy != "puct":
             raise ValueError(f"guided_search: policy = {policy!r} must be 'puct' or 'gumbel'")
@@ -326,7 +359,9 @@ class EnvPoolMixin(ABC):
             raise ValueError(f"guided_search: {sorted(gumbel)} are arguments of policy='gumbel'")
         ids = native.check_guided(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, c_puct)
-        return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct))
+        if nodes is not None:
+            native.check_guided_nodes(simulations, nodes)
+        return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes)
 
     def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
                       seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1) -> GumbelSearch:

@@ -232,34 +232,20 @@ def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_pl
     return visits, returns, action
 
 
-def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
-                         c_puct: float = 1.25) -> tuple[Any, Any, Any]:
-    """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
-    gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
-    and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
-    Every launch is ordered against torch's current stream like `search_device`: the kernel behind what torch has
-    enqueued (the evaluator), the current stream behind the kernel.  Returns (visits int32 [k, A], values float32
-    [k, A], action int32 [k]) on the device and closes the session."""
+def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations: int, leaves: tuple,
+                         what: str) -> tuple[Any, Any, Any]:
+    """simulations + 1 advances from the emitted `leaves` and the result, every launch ordered both ways."""
     import torch
 
-    if env_ids is None:
-        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
-    ids = native.check_guided(env_ids, simulations, c_puct)
-    h, w, c, a = pool.guided_shape()
-    k = len(ids)
-    dev = torch.device("cuda", pool.device)
-    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
-    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
-    status = torch.empty((k,), dtype=torch.uint8, device=dev)
-    _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(),
-                                                                 ids, simulations, c_puct))
+    obs, mask, status = leaves
+    a = mask.shape[1]
     for _ in range(int(simulations) + 1):
         priors, values = evaluate(obs, mask, status)
         priors = priors.to(device=dev, dtype=torch.float32).contiguous()
         values = values.to(device=dev, dtype=torch.float32).contiguous().view(-1)
         if tuple(priors.shape) != (k, a) or tuple(values.shape) != (k,):
             pool.guided_end()
-            raise ValueError(f"guided_search_device: evaluate returned priors {tuple(priors.shape)} and values "
+            raise ValueError(f"{what}: evaluate returned priors {tuple(priors.shape)} and values "
                              f"{tuple(values.shape)} for a session of [{k}, {a}]")
         _order_both_ways(pool, dev, lambda: pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k,
                                                                        obs.data_ptr(), mask.data_ptr(),
@@ -269,8 +255,57 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     action = torch.empty((k,), dtype=torch.int32, device=dev)
     _order_both_ways(pool, dev, lambda: pool.guided_result_device(visits.data_ptr(), vals.data_ptr(),
                                                                   action.data_ptr()))
-    pool.guided_end()
     return visits, vals, action
+
+
+def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
+                         c_puct: float = 1.25, nodes: Any = None, keep_open: bool = False) -> tuple[Any, Any, Any]:
+    """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
+    gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
+    and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
+    Every launch is ordered against torch's current stream like `search_device`: the kernel behind what torch has
+    enqueued (the evaluator), the current stream behind the kernel.  Returns (visits int32 [k, A], values float32
+    [k, A], action int32 [k]) on the device and closes the session -- or, with `keep_open`, leaves it open for
+    `guided_reroot_device`; `nodes` is the node capacity per root (`DevicePool.guided_begin`)."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_guided(env_ids, simulations, c_puct)
+    native.check_guided_nodes(simulations, nodes)
+    h, w, c, a = pool.guided_shape()
+    k = len(ids)
+    dev = torch.device("cuda", pool.device)
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(),
+                                                                 ids, simulations, c_puct, int(nodes or 0)))
+    out = _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_search_device")
+    if not keep_open:
+        pool.guided_end()
+    return out
+
+
+def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: int) -> tuple[Any, Any, Any]:
+    """The next round of the pool's open PUCT session (`guided_search_device(..., keep_open=True)`) with tree reuse:
+    `actions` is an int32 tensor [k] on the pool's device, the moves played -- `pool.guided_reroot_device` keeps their
+    subtrees --, then `simulations` + 1 advances with `evaluate` and the result, every launch ordered both ways against
+    torch's current stream as in `guided_search_device`.  Returns (visits, values, action) on the device and leaves the
+    session open."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    h, w, c, a = pool.guided_shape()
+    if actions.dtype != torch.int32 or actions.device != dev or actions.dim() != 1 or not actions.is_contiguous():
+        raise ValueError(f"guided_reroot_device: actions must be a contiguous one-dimensional int32 tensor on {dev}")
+    k = int(actions.shape[0])
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_reroot_device(actions.data_ptr(), k, simulations, obs.data_ptr(),
+                                                                  mask.data_ptr(), status.data_ptr()))
+    return _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_reroot_device")
 
 
 def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,

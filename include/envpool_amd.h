@@ -572,6 +572,45 @@ int epa_guided_result(epa_pool* pool, int32_t* visits, float* values, int32_t* a
 int epa_guided_result_device(epa_pool* pool, void* device_visits, void* device_values, void* device_action);
 int epa_guided_end(epa_pool* pool);
 
+/* Guided search, tree reuse (PUCT sessions; csrc/pgx_guided.hip.h "Tree reuse" is the authority): after a move is
+ * played, the subtree under it becomes the tree of the next search, so the simulations already evaluated below it are
+ * not paid for again.
+ *   CAPACITY.  A session has C nodes per root.  epa_guided_begin keeps C = S + 1, and a session that is never rerooted
+ *   is byte for byte what it always was.  epa_guided_begin_nodes is epa_guided_begin with `nodes` = C,
+ *   S + 1 <= C <= EPA_GUIDED_MAX_NODES; the trees are k * C nodes.  advance has one more rule: a root begins a descent
+ *   only if its node count is below C; otherwise it goes to status 2 for the rest of the round -- a normal end, "memory
+ *   used up", which sets no error.  With C = S + 1 and no reroot it never triggers.
+ *   epa_guided_reroot(actions[k], S2) is allowed once the round is complete (S + 1 advances made).  Per root, a =
+ *   actions[i]:
+ *     a root that was over (or broken)  stays over; a is ignored
+ *     a outside 0 .. A-1                the root is over (the host form refuses the row instead)
+ *     node0.child[a] = c >= 0           the nodes reachable from c are kept and compacted in place: a kept node's new
+ *                                       index is its rank among the kept ones in increasing old index (c becomes 0),
+ *                                       child[] is remapped, every other field stays bit for bit; count = the number kept
+ *     node0.child[a] < 0                node 0 = the root position stepped by a, no edges, count = 1
+ *     then                              the new root's game is over (an illegal a ends the game, too): the root is over,
+ *                                       status 2, and the result is -1 and zero rows; otherwise pending = node 0, status 0
+ *   The session's simulations become S2 (1 .. EPA_SEARCH_MAX_SIMULATIONS, S2 + 1 <= C), the call number restarts at 0,
+ *   and the leaves are emitted as begin emits them.  The new root is always handed out for evaluation: advance 0 of the
+ *   new round stores the caller's priors into it (replacing the old ones) and backs up nothing; the statistics below it
+ *   stay, and epa_guided_result counts the kept visits.  A round after reroot is again S2 + 1 advances for all roots.
+ *   EPA_ERR_INVALID, before any launch: reroot without a session, on a Gumbel session ("reroot not implemented for
+ *     gumbel sessions") or before the round's last advance; k != the session's rows; in the host form an action outside
+ *     0 .. A-1; S2 outside 1 .. EPA_SEARCH_MAX_SIMULATIONS or S2 + 1 > C; nodes outside S + 1 .. EPA_GUIDED_MAX_NODES;
+ *     trees above EPA_SEARCH_MAX_TREE_BYTES (the message names the largest k that fits).
+ *   Every other family fails with EPA_ERR_RUNTIME "guided search not implemented for this environment".
+ * The _device forms take device pointers (actions: int32 [k], 4-byte aligned) and only enqueue. */
+#define EPA_GUIDED_MAX_NODES 8192
+int epa_guided_begin_nodes(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t nodes,
+                           float c_puct, uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_guided_begin_nodes_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                                  int32_t nodes, float c_puct, void* device_obs, void* device_mask,
+                                  void* device_status);
+int epa_guided_reroot(epa_pool* pool, const int32_t* actions, int32_t k, int32_t simulations, uint8_t* obs,
+                      uint8_t* mask, uint8_t* status);
+int epa_guided_reroot_device(epa_pool* pool, const void* device_actions, int32_t k, int32_t simulations,
+                             void* device_obs, void* device_mask, void* device_status);
+
 /* Gumbel search (no reference analogue; the four PGX board games): the guided-search session above with a second
  * selection policy -- Gumbel top-m sampling without replacement at the root, sequential halving of the simulations
  * over those m actions, a deterministic rule inside the tree, and the improved policy softmax(logits + sigma(completed

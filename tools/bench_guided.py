@@ -13,6 +13,18 @@ Per game and k freshly reset roots, S = 64 simulations, one JSON line:
             roots x simulations per second = k * S / median
   search    `torch_interop.search_device(simulations=S, leaf_playouts=1)` on the same pool: 2 warm-up launches, then
             `reps` launches (a new seed each) each between its own pair of events; the median
+
+    python tools/bench_guided.py --reroot [--games Othello,Hex] [--sizes 4096] [--reps 5] [--warmup 1] [--out FILE]
+
+Tree reuse instead: per game and k freshly reset roots, S = 64 and nodes = 2 S + 1 = 129, one JSON line.  After `warmup`
+whole sessions, `reps` sessions of 3 moves each: a full round of S + 1 advances, the result, and `guided_reroot_device`
+by the most visited action (the result's action tensor, on the device), every launch between its own pair of events on
+the pool's stream.
+  reroot    the median over the reps x 3 reroot launches; beside it the median begin launch and the median advance
+            launch of the same run
+  kept      the share of a root's nodes that a reroot keeps, per move, averaged over the roots: (1 + the root's visits
+            after the reroot) / (1 + its visits before) -- every simulation that did not end in a finished game made
+            one node, so early in a game this is the node count itself
 """
 import argparse
 import json
@@ -87,6 +99,69 @@ def measure(torch, ti, DevicePool, fam, k, args):
             "search_r1_roots_simulations_per_s": float(k * S / (float(np.median(search)) * 1e-3))}
 
 
+def measure_reroot(torch, ti, DevicePool, fam, k, args):
+    moves, nodes = 3, 2 * S + 1
+    pool = DevicePool(fam, k, seed=0)
+    dev = torch.device("cuda", pool.device)
+    stream = torch.cuda.ExternalStream(pool.stream, device=dev)
+    ids = torch.arange(k, dtype=torch.int32, device=dev)
+    ti.send_device_tensors(pool, None, ids)  # reset: every env at the start of a game
+    ti.recv_device_tensors(pool)
+    h, w, c, a = pool.guided_shape()
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    priors = torch.full((k, a), 1.0 / a, dtype=torch.float32, device=dev)
+    values = torch.zeros((k,), dtype=torch.float32, device=dev)
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    kept_visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    scratch = torch.empty((k,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    begins, advances, reroots, kept = [], [], [], [[] for _ in range(moves)]
+
+    def event():
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(stream)
+        return ev
+
+    for rep in range(args.warmup + args.reps):
+        timed = {"begin": [], "advance": [], "reroot": []}
+        shares = []
+        e0 = event()
+        pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, S, C_PUCT, nodes)
+        timed["begin"].append((e0, event()))
+        for move in range(moves):
+            for t in range(S + 1):
+                e0 = event()
+                pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k, obs.data_ptr(), mask.data_ptr(),
+                                           status.data_ptr())
+                timed["advance"].append((e0, event()))
+            pool.guided_result_device(visits.data_ptr(), vals.data_ptr(), action.data_ptr())
+            e0 = event()
+            pool.guided_reroot_device(action.data_ptr(), k, S, obs.data_ptr(), mask.data_ptr(), status.data_ptr())
+            timed["reroot"].append((e0, event()))
+            pool.guided_result_device(kept_visits.data_ptr(), vals.data_ptr(), scratch.data_ptr())
+            torch.cuda.synchronize(dev)
+            assert bool((visits.sum(1) >= S).all()) and bool((status == 0).all())
+            shares.append(float(((1 + kept_visits.sum(1)).double() / (1 + visits.sum(1)).double()).mean()))
+        if rep >= args.warmup:
+            begins += [x.elapsed_time(y) for x, y in timed["begin"]]
+            advances += [x.elapsed_time(y) for x, y in timed["advance"]]
+            reroots += [x.elapsed_time(y) for x, y in timed["reroot"]]
+            for move in range(moves):
+                kept[move].append(shares[move])
+        pool.guided_end()
+    pool.close()
+    return {"game": fam, "roots": k, "simulations": S, "nodes": nodes, "moves": moves,
+            "reroot_us_per_launch": round(float(np.median(reroots)) * 1e3, 2),
+            "reroot_us_min_max": [round(min(reroots) * 1e3, 2), round(max(reroots) * 1e3, 2)],
+            "begin_us_per_launch": round(float(np.median(begins)) * 1e3, 2),
+            "advance_us_per_launch": round(float(np.median(advances)) * 1e3, 2),
+            "nodes_kept_share_per_move": [round(float(np.mean(x)), 4) for x in kept]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="Othello,Hex")
@@ -94,6 +169,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--reroot", action="store_true", help="time guided_reroot_device instead (tree reuse)")
     args = ap.parse_args()
     import torch
 
@@ -103,7 +179,7 @@ def main():
     sink = open(args.out, "w") if args.out else None
     for fam in args.games.split(","):
         for k in [int(x) for x in args.sizes.split(",")]:
-            text = json.dumps(measure(torch, ti, DevicePool, fam, k, args))
+            text = json.dumps((measure_reroot if args.reroot else measure)(torch, ti, DevicePool, fam, k, args))
             print(text, flush=True)
             if sink:
                 sink.write(text + "\n")
