@@ -329,14 +329,22 @@ class _ShardedPools:
     def guided_shape(self) -> tuple[int, int, int, int]:
         return self.pools[0].guided_shape()
 
+    def _guided_empty(self, k: int, width: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        h, w, c, a = self.guided_shape()
+        lead = (k, width) if width else (k,)  # (a wide session's leaves carry the slot axis)
+        return (np.empty(lead + (h, w, c), dtype=np.bool_), np.empty(lead + (a,), dtype=np.bool_),
+                np.empty(lead, dtype=np.uint8))
+
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
-                     nodes: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     nodes: int = 0, width: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A session in every shard that owns listed envs, all shards at once.  The search has no random numbers and
-        no dependence on the env id, so the rows are those of the unsharded pool."""
+        no dependence on the env id, so the rows are those of the unsharded pool.  `width`: a wide session in every
+        shard (`DevicePool.guided_begin`)."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
         ids = native.check_guided(env_ids, simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
+        width = native.check_guided_width(width)
         h, w, c, a = self.guided_shape()
         shard = (ids - self.offset) // self.per
         bad = ids[(shard < 0) | (shard >= len(self.pools))]
@@ -344,16 +352,17 @@ class _ShardedPools:
             raise ValueError(f"env_id {int(bad[0])} out of range")
         parts = [np.flatnonzero(shard == s) for s in range(len(self.pools))]
         k = len(ids)
-        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
-                  np.empty(k, dtype=np.uint8))
+        leaves = self._guided_empty(k, width)
+        extra = (int(nodes or 0), width) if width else ((nodes,) if nodes else ())
 
         def begin(s: int, p: DevicePool, idx: Any) -> None:
-            for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct, *((nodes,) if nodes else ()))):
+            for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct, *extra)):
                 o[idx] = part
 
         self._each(begin, parts)
         self._guided = (k, a, parts)
         self._guided_nodes = cap
+        self._guided_width = width
         return leaves
 
     def guided_reroot(self, actions: Any, simulations: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -362,9 +371,7 @@ class _ShardedPools:
         if getattr(self, "_guided_nodes", None) is None:
             raise ValueError("guided_reroot: reroot not implemented for gumbel sessions")
         actions = native.check_guided_reroot(actions, k, a, simulations, self._guided_nodes)
-        h, w, c, _ = self.guided_shape()
-        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
-                  np.empty(k, dtype=np.uint8))
+        leaves = self._guided_empty(k, getattr(self, "_guided_width", 0))
 
         def reroot(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.guided_reroot(actions[idx], simulations)):
@@ -381,10 +388,13 @@ class _ShardedPools:
 
     def guided_advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         k, a, parts = self._guided_session("guided_advance")
-        priors, values = native.check_guided_rows(priors, values, k, a)
-        h, w, c, _ = self.guided_shape()
-        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
-                  np.empty(k, dtype=np.uint8))
+        width = getattr(self, "_guided_width", 0)
+        if width:  # the rows of root i are rows i W .. i W + W - 1: split by root
+            priors, values = native.check_guided_wide_rows(priors, values, k, width, a)
+            priors, values = priors.reshape(k, width, a), values.reshape(k, width)
+        else:
+            priors, values = native.check_guided_rows(priors, values, k, a)
+        leaves = self._guided_empty(k, width)
 
         def advance(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.guided_advance(priors[idx], values[idx])):

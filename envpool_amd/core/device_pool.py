@@ -500,12 +500,14 @@ class DevicePool:
             raise RuntimeError("guided search not implemented for this environment")
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
-    def _guided_leaves(self, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def _guided_leaves(self, k: int, width: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         h, w, c, a = self.guided_shape()
-        return np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_), np.empty(k, dtype=np.uint8)
+        lead = (k, width) if width else (k,)  # (a wide session's leaves carry the slot axis)
+        return (np.empty(lead + (h, w, c), dtype=np.bool_), np.empty(lead + (a,), dtype=np.bool_),
+                np.empty(lead, dtype=np.uint8))
 
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
-                     nodes: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     nodes: int = 0, width: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Opens the pool's guided-search session (the PGX board games; RuntimeError("guided search not implemented
         for this environment") elsewhere) on the current positions of the listed envs (global ids; None: the whole
         pool), replacing any earlier one: a PUCT search whose tree stays on the device and that stops at every new
@@ -513,12 +515,20 @@ class DevicePool:
         the first leaves (obs bool [k, H, W, C] of the seat to move, mask bool [k, A], status uint8 [k]: 0 evaluate,
         1 a finished game, 2 nothing pending).  Nothing of the pool changes, and later steps of the pool change
         nothing in the session.  `nodes`: the node capacity per root, simulations + 1 .. 8192 (0: simulations + 1),
-        the room `guided_reroot` needs to keep a subtree and grow it."""
+        the room `guided_reroot` needs to keep a subtree and grow it.  `width` = W, 1 .. 32, opens a WIDE session
+        (epa_guided_begin_wide): W slots per root, up to W leaves per root and advance, steered apart by virtual
+        losses; every leaf array and the rows of `guided_advance` then carry a slot axis ([k, W, ...]), a slot of
+        status 2 has nothing pending, and the round is complete when all statuses are 2.  None: a plain session."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
+        width = native.check_guided_width(width)
         self.guided_shape()
-        obs, mask, status = self._guided_leaves(len(ids))
-        if nodes:
+        obs, mask, status = self._guided_leaves(len(ids), width)
+        if width:
+            native.check(self._lib.epa_guided_begin_wide(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                         int(nodes or 0), width, float(c_puct), obs.ctypes.data,
+                                                         mask.ctypes.data, status.ctypes.data))
+        elif nodes:
             native.check(self._lib.epa_guided_begin_nodes(self._h, ids.ctypes.data, len(ids), int(simulations), cap,
                                                           float(c_puct), obs.ctypes.data, mask.ctypes.data,
                                                           status.ctypes.data))
@@ -527,6 +537,7 @@ class DevicePool:
                                                     float(c_puct), obs.ctypes.data, mask.ctypes.data,
                                                     status.ctypes.data))
         self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
+        self._guided_width = width
         return obs, mask, status
 
     def guided_reroot(self, actions: Any, simulations: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -535,12 +546,13 @@ class DevicePool:
         the position behind it, and a root whose game that move ends is over from then on.  The next round has
         `simulations` simulations (simulations + 1 <= the session's nodes) and starts with the new roots as its
         leaves, which are returned as `guided_begin` returns its own; the kept visits count in `guided_result`.
-        ValueError before any launch: no session, a Gumbel session, a round that is not complete, another number of
-        rows, an action outside 0 .. A-1."""
+        ValueError before any launch: no session, a Gumbel session, a round that is not complete (a wide session: a
+        slot that is still pending), another number of rows, an action outside 0 .. A-1.  A wide session takes one
+        action per root, too; afterwards slot 0 holds the new root and the other slots are idle."""
         k = self._guided_open("guided_reroot", "puct")
         actions = native.check_guided_reroot(actions, k, self.guided_shape()[3], simulations,
                                              getattr(self, "_guided_nodes", native.GUIDED_MAX_NODES))
-        obs, mask, status = self._guided_leaves(k)
+        obs, mask, status = self._guided_leaves(k, getattr(self, "_guided_width", 0))
         native.check(self._lib.epa_guided_reroot(self._h, actions.ctypes.data, k, int(simulations), obs.ctypes.data,
                                                  mask.ctypes.data, status.ctypes.data))
         return obs, mask, status
@@ -563,10 +575,14 @@ class DevicePool:
         simulations + 1 times.  Rows that are not finite, negative priors and values outside -1 .. 1 raise ValueError
         before any launch."""
         k = self._guided_open("guided_advance", "puct")
-        priors, values = native.check_guided_rows(priors, values, k, self.guided_shape()[3])
-        obs, mask, status = self._guided_leaves(k)
-        native.check(self._lib.epa_guided_advance(self._h, priors.ctypes.data, values.ctypes.data, k, obs.ctypes.data,
-                                                  mask.ctypes.data, status.ctypes.data))
+        width = getattr(self, "_guided_width", 0)
+        if width:  # a wide session: rows [k, W, ..] or flattened, the leaves with the slot axis
+            priors, values = native.check_guided_wide_rows(priors, values, k, width, self.guided_shape()[3])
+        else:
+            priors, values = native.check_guided_rows(priors, values, k, self.guided_shape()[3])
+        obs, mask, status = self._guided_leaves(k, width)
+        native.check(self._lib.epa_guided_advance(self._h, priors.ctypes.data, values.ctypes.data, len(values),
+                                                  obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
         return obs, mask, status
 
     def guided_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -587,12 +603,19 @@ class DevicePool:
         self._guided_k = None
 
     def guided_begin_device(self, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None, simulations: int = 64,
-                            c_puct: float = 1.25, nodes: int = 0) -> int:
+                            c_puct: float = 1.25, nodes: int = 0, width: Any = None) -> int:
         """`guided_begin` with the leaves written to device memory at the raw addresses `d_obs` (k H W C bytes),
-        `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k."""
+        `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k.  With `width`
+        = W the arrays have k W rows, and so have those of `guided_advance_device` (its `k` is k W) and of
+        `guided_reroot_device` (whose `k` stays the number of roots)."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
-        if nodes:
+        width = native.check_guided_width(width)
+        if width:
+            native.check(self._lib.epa_guided_begin_wide_device(
+                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct),
+                ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        elif nodes:
             native.check(self._lib.epa_guided_begin_nodes_device(
                 self._h, ids.ctypes.data, len(ids), int(simulations), cap, float(c_puct), ctypes.c_void_p(d_obs),
                 ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
@@ -601,6 +624,7 @@ class DevicePool:
                                                            float(c_puct), ctypes.c_void_p(d_obs),
                                                            ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
         self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
+        self._guided_width = width
         return len(ids)
 
     def guided_reroot_device(self, d_actions: int, k: int, simulations: int, d_obs: int, d_mask: int,

@@ -29,6 +29,7 @@ PLAYOUT_MAX_PLIES = 256
 PLAYOUT_MAX_REPEATS = 4096
 SEARCH_MAX_SIMULATIONS = 4096
 GUIDED_MAX_NODES = 8192  # EPA_GUIDED_MAX_NODES: the largest node capacity of a guided-search root
+GUIDED_MAX_WIDTH = 32    # EPA_GUIDED_MAX_WIDTH: the most slots (leaves per launch) of a wide guided-search root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
@@ -139,6 +140,8 @@ def lib() -> ctypes.CDLL:
         "epa_guided_begin_nodes_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "epa_guided_reroot": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "epa_guided_reroot_device": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "epa_guided_begin_wide": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_begin_wide_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_begin_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_advance": (i32, [vp, vp, vp, i32, vp, vp, vp]),
@@ -182,6 +185,7 @@ EXPORTED_SYMBOLS = [
     "epa_guided_shape", "epa_guided_begin", "epa_guided_begin_device", "epa_guided_advance",
     "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
     "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
+    "epa_guided_begin_wide", "epa_guided_begin_wide_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device",
     "epa_atari_post_create",
@@ -287,6 +291,29 @@ def check_guided_nodes(simulations: int, nodes: Any) -> int:
         raise ValueError(f"guided_begin: nodes = {nodes} must be simulations + 1 = {int(simulations) + 1} .. "
                          f"{GUIDED_MAX_NODES}")
     return int(nodes)
+
+
+def check_guided_width(width: Any) -> int:
+    """The width (slots per root) of a guided_begin call after its check: ValueError outside 1 .. 32.  None: 0, a plain
+    session."""
+    if width is None:
+        return 0
+    if isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= GUIDED_MAX_WIDTH:
+        raise ValueError(f"guided_begin: width = {width} must be 1 .. {GUIDED_MAX_WIDTH}")
+    return int(width)
+
+
+def check_guided_wide_rows(priors: Any, values: Any, k: int, width: int, actions: int) -> tuple[np.ndarray, np.ndarray]:
+    """The rows of a host-form guided_advance of a wide session, given with the slot axis ([k, W, A] and [k, W]) or
+    flattened ([k W, A] and [k W]), as contiguous float32 arrays [k W, A] and [k W] after the checks of
+    `check_guided_rows`."""
+    priors = np.ascontiguousarray(priors, dtype=np.float32)
+    if priors.shape not in ((k, width, actions), (k * width, actions)):
+        raise ValueError(f"guided_advance: priors of shape {priors.shape} for a session of [{k}, {width}, {actions}]")
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    if values.shape not in ((k, width), (k * width,)):
+        raise ValueError(f"guided_advance: values of shape {values.shape} for a session of [{k}, {width}]")
+    return check_guided_rows(priors.reshape(k * width, actions), values.reshape(-1), k * width, actions)
 
 
 def check_guided_reroot(actions: Any, k: int, n_actions: int, simulations: int, nodes: int,

@@ -171,6 +171,8 @@ struct GuidedArgs {
   int call;                 // advance: its number t = 0 .. simulations
   int capacity;             // nodes per root, the stride of a root's node block: simulations + 1 .. EPA_GUIDED_MAX_NODES
   float c_puct;
+  int width;                // 0: a plain session (the plain kernels ignore it); 1 .. EPA_GUIDED_MAX_WIDTH: a wide one,
+                            // whose priors, values, obs, mask and status below have k * width rows
   void* roots;              // [k], 16-byte aligned
   void* nodes;              // [k][capacity], 16-byte aligned
   const int32_t* actions;   // reroot: [k]
@@ -416,10 +418,19 @@ class Pool {
   virtual void GuidedAdvance(const GuidedArgs& a);
   virtual void GuidedResult(const GuidedArgs& a);
   virtual void GuidedReroot(const GuidedArgs& a);
+  // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; GuidedResult and GuidedReroot
+  // serve them too (a.width != 0)
+  virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
+  virtual size_t GuidedWideLiveOffset() const { return 0; }  // of a record's int32 count of pending slots
+  virtual void GuidedBeginWide(const int* d_ids, const GuidedArgs& a);
+  virtual void GuidedAdvanceWide(const GuidedArgs& a);
   // obs / mask / status: host arrays (device == false) or device pointers.  nodes: the capacity per root, 0 for
   // simulations + 1.
   void GuidedBeginCall(const int32_t* ids, int k, int simulations, int nodes, float c_puct, void* obs, void* mask,
                        void* status, bool device);
+  // ... with `width` slots per root (0: a plain session): the leaf arrays have k * width rows from then on
+  void GuidedBeginWideCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct, void* obs,
+                           void* mask, void* status, bool device);
   // Tree reuse (pgx_guided.hip.h "Tree reuse"): after the round's last advance, the subtree under actions[i] becomes
   // root i's tree, `simulations` the length of the next round, and the new roots are emitted as begin emits its own.
   // actions: a host array (checked against 0 .. A-1 here) or a device pointer (the kernel ends such a root).  PUCT
@@ -643,6 +654,7 @@ class Pool {
     char* pinned{nullptr};  // the host forms' pinned block, laid out like the staging
     bool gumbel{false};     // the session's policy: PUCT or Gumbel
     int k{0}, simulations{0}, calls{0};
+    int width{0};           // slots per root of a wide PUCT session; 0: a plain session
     int capacity{0};        // nodes per root (PUCT: simulations + 1 .. EPA_GUIDED_MAX_NODES; Gumbel: simulations + 1)
     float c_puct{0.0f};
     int considered{0};      // Gumbel: m, c_visit, c_scale

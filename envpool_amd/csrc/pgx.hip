@@ -20,7 +20,8 @@
 // Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
 // Guided search: pgx_guided.hip.h, one wave per root and one launch per simulation, the tree in the session's own
 // memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult), and PgxGuidedReroot, which keeps the
-// played move's subtree for the next move by compacting it in place.
+// played move's subtree for the next move by compacting it in place.  Wide sessions (PgxGuidedBeginWide /
+// PgxGuidedAdvanceWide) keep W slots per root and descend up to W times per launch, steered apart by virtual losses.
 // Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
 // policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
 #include <algorithm>
@@ -429,6 +430,16 @@ __device__ __forceinline__ void GuidedEmitLeaf(const Args& a, int row, int lane,
   if (lane == 0) a.status[row] = (unsigned char)status;
 }
 
+// rows `row` .. `row + n - 1` of the three leaf arrays, which are contiguous: idle slots of a wide session
+template <int G, class Args>
+__device__ __forceinline__ void GuidedEmitIdle(const Args& a, int row, int n, int lane) {
+  constexpr int A = pgx::Dims<G>::A, OB = pgx::GuidedObsElems<G>();
+  if (n <= 0) return;
+  GuidedEmitRow(a.obs + (size_t)row * OB, n * OB, lane, [](int) { return 0u; });
+  GuidedEmitRow(a.mask + (size_t)row * A, n * A, lane, [](int) { return 0u; });
+  if (lane < n) a.status[row + lane] = (unsigned char)pgx::kGuidedIdle;
+}
+
 template <int G>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedBegin(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, GuidedArgs a) {
@@ -581,15 +592,16 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
   GuidedEmitLeaf<G>(a, row, lane, status, s);
 }
 
-template <int G>
+// (WIDE: the root record of a wide session, pgx::GuidedWideRoot with its stride; one row per root either way)
+template <int G, bool WIDE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
-  const pgx::GuidedRoot& rec = static_cast<const pgx::GuidedRoot*>(a.roots)[row];
   const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
   WaveAcquire();
-  const bool over = rec.over != 0;
+  const bool over = WIDE ? pgx::GuidedWideRootAt(a.roots, row, a.width).over != 0
+                         : static_cast<const pgx::GuidedRoot*>(a.roots)[row].over != 0;
   const pgx::State root = n0.s;
   const float sign = (float)pgx::SearchSign<G>(root);
   pgx::SearchPick mine = pgx::SearchNone();
@@ -635,18 +647,23 @@ __device__ __forceinline__ int WaveScan(int x, int lane) {  // the inclusive pre
 
 constexpr int kRerootTables[3] = {512, 2048, pgx::kGuidedMaxNodes};
 
-template <int G, int CAP>
+// WIDE: a wide session (pgx_guided.hip.h "Several leaves per launch"): the record is pgx::GuidedWideRoot, the new root goes
+// to slot 0 (leaf row i * W), the other slots become idle whatever they held, and their rows are zeros.
+template <int G, int CAP, bool WIDE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
   constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
   __shared__ int32_t table[CAP];  // (a.capacity <= CAP)
   const int row = blockIdx.x, lane = threadIdx.x;
-  pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[row];
+  pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[WIDE ? 0 : row];  // (not touched when WIDE)
+  pgx::GuidedWideRoot& wrec = pgx::GuidedWideRootAt(a.roots, WIDE ? row : 0, WIDE ? a.width : 1);  // (only WIDE)
   Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
   WaveAcquire();
   const int act = a.actions[row];
-  const int old_count = std::min(std::max(rec.count, 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
-  bool over = rec.over != 0 || rec.broken != 0 || act < 0 || act >= A;
+  const int rec_count = WIDE ? wrec.count : rec.count;
+  const bool rec_idle = WIDE ? (wrec.over != 0 || wrec.broken != 0) : (rec.over != 0 || rec.broken != 0);
+  const int old_count = std::min(std::max(rec_count, 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
+  bool over = rec_idle || act < 0 || act >= A;
   int count = old_count;
   pgx::State s = nodes[0].s;
   if (!over) {
@@ -721,9 +738,238 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
     }
     over = s.done != 0;
   }
+  if (WIDE) {
+    if (lane == 0) pgx::GuidedWideClearRoot(wrec, a.width, count, over);
+    WaveRelease();
+    GuidedEmitLeaf<G>(a, row * a.width, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
+    GuidedEmitIdle<G>(a, row * a.width + 1, a.width - 1, lane);
+    return;
+  }
   if (lane == 0) pgx::GuidedRerootRoot(rec, count, over);
   WaveRelease();
   GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
+}
+
+// Several leaves per launch (pgx_guided.hip.h "Several leaves per launch"): PgxGuidedBegin / PgxGuidedAdvance for a
+// session whose roots have W slots.  One wave per root, one block per wave, the lane ownership and the fences of
+// PgxGuidedAdvance.
+//   phase A    the slots in order: the owner lanes store the slot's priors row (row i * W + j) and add along its path,
+//              read from the root record (one address a load: wave-uniform), in slot order, then path order
+//   phase B    up to W descents.  Lane i holds depth and pending leaf of slot i of THIS launch in registers, and the
+//              slot's path is column i of `lpath` in LDS ([depth][WB], so the lanes' loads of one depth are contiguous);
+//              lane 0 writes a path entry to LDS and to the record, and a release / barrier / acquire separates two
+//              descents, as around `path` in PgxSearchKernel.  At depth d lane i < j loads path_i[d] -- one LDS load
+//              for the wave -- and compares it with the wave-uniform node; the matches are a ballot, whose population
+//              is the sum of o, and the owner lane of each matched action bumps its o from a register broadcast.  The
+//              collision test is a ballot over the lanes' pending leaves.
+//   nodes      a node made by an earlier descent of the launch can be reached by a later one (a finished game: status
+//              1; a running one is the collision): its State goes from lane 0 to the wave through memory inside the
+//              launch, between the same release and acquire fences as in PgxSearchKernel.
+//   leaves     slot j's State is in registers when its descent ends: its rows are emitted then; the idle slots' rows
+//              are zeroed in one sweep at the end.
+// `lpath` is static, in three width buckets (WB = 4, 16, 32: 4, 16 and 32 KiB), for the reason given at kRerootTables.
+constexpr int kWideBuckets[3] = {4, 16, pgx::kGuidedMaxWidth};
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedBeginWide(CommonDev cm, const pgx::State* st,
+                                                                   const int* __restrict__ ids, GuidedArgs a) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x, W = a.width;
+  const int e = ids[row];
+  const bool over = cm.done[e] != 0;  // (an env before its first reset is)
+  const pgx::State root = st[e];
+  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
+  if (lane == 0) {
+    n0.s = root;
+    n0.term0 = 0;
+    pgx::GuidedWideClearRoot(pgx::GuidedWideRootAt(a.roots, row, W), W, 1, over);
+  }
+#pragma unroll
+  for (int j = 0; j < SL; ++j) {
+    if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(n0, lane + kSearchBlock * j);
+  }
+  WaveRelease();
+  GuidedEmitLeaf<G>(a, row * W, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+  GuidedEmitIdle<G>(a, row * W + 1, W - 1, lane);
+}
+
+template <int G, int WB>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs a, unsigned* err) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  __shared__ int32_t lpath[pgx::kSearchMaxPath * WB];  // [depth][slot]: node << 8 | action  (a.width <= WB)
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int S = a.simulations, W = std::min(a.width, WB);
+  pgx::GuidedWideRoot& rec = pgx::GuidedWideRootAt(a.roots, row, a.width);
+  pgx::GuidedWideSlot* slots = pgx::GuidedWideSlots(rec);
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
+  WaveAcquire();
+  int done = rec.done;
+  // A. the answers
+  for (int j = 0; j < W; ++j) {
+    const int status = slots[j].status;
+    if (status == pgx::kGuidedIdle) continue;
+    Node& leaf = nodes[slots[j].pending];
+    const size_t lrow = (size_t)row * W + j;
+    float val0;
+    if (status == pgx::kGuidedEvaluate) {
+#pragma unroll
+      for (int q = 0; q < SL; ++q) {
+        const int act = lane + kSearchBlock * q;
+        if (act < A) leaf.p[act] = pgx::GuidedClean(a.priors[lrow * A + act]);
+      }
+      val0 = (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[lrow]);
+    } else {
+      val0 = (float)leaf.term0;
+    }
+    const int backed = std::min(slots[j].depth, pgx::kSearchMaxPath);
+    for (int d = 0; d < backed; ++d) {
+      const int p = slots[j].path[d];
+      const int act = p & 255;
+      if ((act & (kSearchBlock - 1)) == lane) {
+        Node& nd = nodes[p >> 8];
+        nd.v[act] += 1;
+        nd.w0[act] += val0;
+      }
+    }
+    if (backed > 0) ++done;
+  }
+  WaveRelease();
+  // B. the descents
+  int count = rec.count;
+  const bool idle = rec.over != 0 || rec.broken != 0;
+  int my_depth = 0, my_pend = -1;  // lane i: slot i of this launch; the pending leaf only with status 0
+  int j = 0;
+  bool broken = false;
+  WaveAcquire();
+  const pgx::State root = nodes[0].s;
+  for (; j < W && !idle; ++j) {
+    if (!(done + j < S && count < a.capacity)) break;
+    int node = 0, depth = 0;
+    bool collided = false;
+    pgx::State s = root;
+    for (;;) {
+      Node& nd = nodes[node];
+      int child[SL], v[SL], o[SL];
+      float w0[SL], pr[SL];
+      int own = 0;
+#pragma unroll
+      for (int q = 0; q < SL; ++q) {
+        const int act = lane + kSearchBlock * q;
+        child[q] = -1;
+        v[q] = o[q] = 0;
+        w0[q] = pr[q] = 0.0f;
+        if (act < A) {
+          child[q] = nd.child[act];
+          v[q] = nd.v[act];
+          w0[q] = nd.w0[act];
+          pr[q] = nd.p[act];
+        }
+        own += v[q];
+      }
+      // the virtual losses: the earlier slots of this launch whose path runs through `node`
+      int mine_e = -1;
+      if (lane < j && depth < my_depth) mine_e = lpath[depth * WB + lane];
+      const bool on = lane < j && pgx::GuidedWideOn(mine_e, my_depth, depth, node);
+      unsigned long long mb = __ballot(on);
+      const int osum = __popcll(mb);
+      while (mb != 0) {
+        const int i = __ffsll((long long)mb) - 1;
+        mb &= mb - 1;
+        const int ai = __shfl(mine_e, i, kSearchBlock) & 255;
+#pragma unroll
+        for (int q = 0; q < SL; ++q) {
+          if (ai == lane + kSearchBlock * q) o[q] += 1;
+        }
+      }
+      const int total = WaveSum(own) + osum;
+      const int sign = pgx::SearchSign<G>(s);
+      pgx::SearchPick mine = pgx::SearchNone();
+#pragma unroll
+      for (int q = 0; q < SL; ++q) {
+        const int act = lane + kSearchBlock * q;
+        if (act < A && pgx::Has(s.m, act)) {
+          mine = pgx::SearchBetter(
+              mine, pgx::SearchPick{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), act, 1});
+        }
+      }
+      const int act = WaveBest(mine).action;
+      if (act < 0 || depth >= pgx::kSearchMaxPath) {  // unreachable from a position of the game (PgxGuidedAdvance)
+        broken = true;
+        break;
+      }
+      if (lane == 0) {
+        lpath[depth * WB + j] = node << 8 | act;
+        slots[j].path[depth] = node << 8 | act;
+      }
+      ++depth;
+      const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
+      int c = __shfl(child[0], owner, kSearchBlock);
+      if (SL > 1) {
+        const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
+        c = slot == 1 ? c1 : c;
+      }
+      if (c < 0) {
+        c = count++;  // (count < capacity: checked before the descent, which makes one node at the most)
+        if (lane == owner) nd.child[act] = c;
+        Node& nn = nodes[c];
+        pgx::State s2;
+        const int term0 = pgx::SearchExpand<G>(s, act, s2);
+        if (lane == 0) {
+          nn.s = s2;
+          nn.term0 = term0;
+        }
+#pragma unroll
+        for (int q = 0; q < SL; ++q) {
+          if (lane + kSearchBlock * q < A) pgx::GuidedClearEdge<G>(nn, lane + kSearchBlock * q);
+        }
+        node = c;
+        s = s2;
+        break;
+      }
+      node = c;
+      WaveAcquire();
+      s = nodes[node].s;
+      if (s.done) break;
+      if (__ballot(lane < j && my_pend == node) != 0) {
+        collided = true;
+        break;
+      }
+    }
+    if (broken || collided) break;
+    const int status = s.done ? pgx::kGuidedTerminal : pgx::kGuidedEvaluate;
+    if (lane == 0) {
+      slots[j].pending = node;
+      slots[j].status = status;
+      slots[j].depth = depth;
+    }
+    if (lane == j) {
+      my_depth = depth;
+      my_pend = status == pgx::kGuidedEvaluate ? node : -1;
+    }
+    GuidedEmitLeaf<G>(a, row * W + j, lane, status, s);
+    WaveRelease();
+    __syncthreads();
+    WaveAcquire();
+  }
+  if (broken) j = 0;  // a broken position ends all slots of the root
+  // the record: the answered slots and the slots without a descent are idle
+  if (lane >= j && lane < W) {
+    slots[lane].status = pgx::kGuidedIdle;
+    slots[lane].depth = 0;
+  }
+  if (lane == 0) {
+    rec.count = count;
+    rec.done = done;
+    rec.live = j;
+    if (broken) {
+      rec.broken = 1;
+      *err = kErrGuided;
+    }
+  }
+  WaveRelease();
+  GuidedEmitIdle<G>(a, row * W + j, W - j, lane);
 }
 
 // Gumbel search (pgx_gumbel.hip.h): the session, lane ownership, hand-offs and leaves of the guided kernels above with
@@ -1149,6 +1395,24 @@ class PgxPool : public Pool {
   }
   size_t GuidedNodeBytes() const override { return sizeof(pgx::GuidedNode<G>); }
   size_t GuidedRootBytes() const override { return sizeof(pgx::GuidedRoot); }
+  size_t GuidedWideRootBytes(int width) const override { return pgx::GuidedWideRootBytes(width); }
+  size_t GuidedWideLiveOffset() const override { return offsetof(pgx::GuidedWideRoot, live); }
+  void GuidedBeginWide(const int* d_ids, const GuidedArgs& a) override {
+    hipLaunchKernelGGL(PgxGuidedBeginWide<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_,
+                       d_ids, a);
+  }
+  void GuidedAdvanceWide(const GuidedArgs& a) override {
+    if (a.width <= kWideBuckets[0]) {
+      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[0]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                         stream_, a, err_dev_);
+    } else if (a.width <= kWideBuckets[1]) {
+      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[1]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                         stream_, a, err_dev_);
+    } else {
+      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[2]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                         stream_, a, err_dev_);
+    }
+  }
   void GuidedBegin(const int* d_ids, const GuidedArgs& a) override {
     hipLaunchKernelGGL(PgxGuidedBegin<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
                        a);
@@ -1157,9 +1421,26 @@ class PgxPool : public Pool {
     hipLaunchKernelGGL(PgxGuidedAdvance<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a, err_dev_);
   }
   void GuidedResult(const GuidedArgs& a) override {
+    if (a.width != 0) {
+      hipLaunchKernelGGL((PgxGuidedResult<G, true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
+      return;
+    }
     hipLaunchKernelGGL(PgxGuidedResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
   }
   void GuidedReroot(const GuidedArgs& a) override {
+    if (a.width != 0) {
+      if (a.capacity <= kRerootTables[0]) {
+        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[0], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                           stream_, a);
+      } else if (a.capacity <= kRerootTables[1]) {
+        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[1], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                           stream_, a);
+      } else {
+        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[2], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
+                           stream_, a);
+      }
+      return;
+    }
     if (a.capacity <= kRerootTables[0]) {
       hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[0]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
     } else if (a.capacity <= kRerootTables[1]) {

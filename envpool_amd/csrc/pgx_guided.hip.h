@@ -73,6 +73,57 @@
 // root stay, and result() counts the kept visits.  So a round after reroot is again S2 + 1 advances in lockstep for
 // all roots.  reroot has no floating-point arithmetic.
 //
+// Several leaves per launch (DESIGN.md "PGX guided search: several leaves per launch").  A WIDE session has a width W,
+// 1 .. kGuidedMaxWidth: every root has W SLOTS, each what a plain session keeps once per root -- a pending leaf, a
+// status and a path -- and an advance answers all pending slots and then descends up to W times, steering the descents
+// apart with virtual losses: an edge on the path of an earlier descent of the same launch counts as one more visit
+// that lost.  Nodes are GuidedNode<G>, unchanged; there is no per-edge virtual-loss array (the o[] below are
+// recomputed from the launch's own paths).  The leaf arrays and the caller's rows have k * W rows, row i * W + j for
+// slot j of root i.  The root record is GuidedWideRoot followed by W GuidedWideSlot.  `done` counts the root's
+// completed simulations, C is the node capacity.
+//   begin_wide(ids, S, C, W, c_puct):
+//     as begin; slot 0 = {pending 0, path [], status: the env is over ? 2 : 0}; slots 1..W-1 status 2; done = 0
+//   advance(priors[k, W, A], values[k, W]) -- call number t = 0 .. S:
+//     A. answers, slots j = 0..W-1 in this order, status_j != 2, L = pending_j:
+//          status 0: L.p[a] = clean(priors[i, j, a]) for every a;  val0 = sign(L) * cleanv(values[i, j])
+//          status 1: val0 = (float) L.term0
+//          for (n, a) in path_j in path order:  n.v[a] += 1;  n.w0[a] += val0        (float32 add)
+//          if path_j is not empty: done += 1          (the root's own evaluation is no simulation)
+//          status_j = 2; path_j = []
+//     B. descents, slots j = 0, 1, ..: begin descent j only while  done + j < S  and  count < C  (and the root is
+//        neither over nor broken);  node = 0, path = []:
+//          loop:  d = len(path)
+//            o[a] = number of slots i < j of THIS launch with len(path_i) > d and path_i[d] == (node, a)
+//            pick the legal a of the largest wscore(node, a), ties: the lowest a;  path += (node, a)
+//            if node.child[a] < 0:  expand as the plain advance does (SearchExpand); node = the new node; break
+//            node = node.child[a]
+//            if node.state.done: break
+//            if node == pending_i for a slot i < j of this launch with status_i == 0:  COLLISION
+//          COLLISION: the descent is dropped (it made no node, stores no path), and this root begins no further
+//                     descent in this launch; slots j.. keep status 2
+//          else: path_j = path; pending_j = node; status_j = node.state.done ? 1 : 0
+//     emit leaves: every slot's row; rows of status 1 or 2 are zeros.
+//   wscore(node, a), float32, each operation correctly rounded, nothing fused:
+//     n = v[a] + o[a] (int);  V = sum_b v[b] + sum_b o[b] (int)
+//     q = n > 0 ? (sign * w0[a] - (float) o[a]) / (float) n : 0.0f
+//     wscore = q + ((c_puct * p[a]) * sqrtf((float)(V + 1))) / (float)(1 + n)
+// Consequences:
+//   - with every o zero, wscore is score (GuidedScore) bit for bit (x - 0.0f == x), and descent 0 of a launch has no
+//     earlier slot: a wide session of W = 1 is the plain session, call for call
+//   - slot 0 never collides; while done < S and count < C every advance completes at least one simulation, so a round
+//     is complete -- all k * W statuses are 2 -- after at most S + 1 advances
+//   - two slots of one launch may reach the same finished game: both have status 1 and both back up term0; this is no
+//     collision.  No two status-0 slots of one launch share a node
+//   - later advances on a complete round, up to call number S, change nothing; a call number above S is refused
+//   - the root's visits sum to S after a round whose capacity sufficed; after a reroot the kept visits add to that
+//   - a descent makes at most one node and begins only with count < C, so count <= C always
+//   - a broken position (as above) ends ALL slots of that root: every status 2, the paths dropped, no later descent
+//   - a tree is a tree: a node sits at one depth, so path_i[d] names `node` exactly when path i ran through it
+// reroot of a wide session: the rule and the compaction above; afterwards slot 0 is the new root (status 0, or the root
+// is over), the other slots are idle, done = 0 and the session's simulations become S2.  The host forms refuse a reroot
+// while any status is not 2.  The device form cannot look: slots still pending there are dropped, their paths
+// discarded and nothing backed up; their nodes stay unevaluated (priors 0) -- the caller finishes the round first.
+//
 // There are no random numbers.  Only seat 0's value is stored, as in pgx_search.hip.h: the games are zero-sum.  Build
 // without fast-math and with -ffp-contract=off.
 #ifndef ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
@@ -161,6 +212,59 @@ PGX_HD inline void GuidedRerootRoot(GuidedRoot& r, int count, bool over) {
   r.depth = 0;
   r.over = over ? 1 : 0;
   r.broken = 0;
+}
+
+// ---- wide sessions: several leaves per root per launch ----
+constexpr int kGuidedMaxWidth = 32;
+
+// One slot of a wide root: what GuidedRoot keeps once.  A path entry is node << 8 | action.
+struct alignas(16) GuidedWideSlot {
+  int32_t pending;
+  int32_t status;  // GuidedStatus
+  int32_t depth;   // entries of `path`
+  int32_t pad;
+  int32_t path[kSearchMaxPath];
+};
+// What a wide session keeps per root beside its nodes: this header, then its W slots.
+struct alignas(16) GuidedWideRoot {
+  int32_t count;   // nodes made
+  int32_t done;    // simulations completed in this round
+  int32_t over;    // the env was over at begin, or the root became over at a reroot
+  int32_t broken;  // advance met a position that is no position of the game
+  int32_t live;    // slots whose status is not 2 (for the host forms' reroot check)
+  int32_t pad[3];
+};
+PGX_HD inline size_t GuidedWideRootBytes(int width) {
+  return sizeof(GuidedWideRoot) + (size_t)width * sizeof(GuidedWideSlot);
+}
+PGX_HD inline GuidedWideRoot& GuidedWideRootAt(void* roots, int row, int width) {
+  return *reinterpret_cast<GuidedWideRoot*>(static_cast<char*>(roots) + (size_t)row * GuidedWideRootBytes(width));
+}
+PGX_HD inline GuidedWideSlot* GuidedWideSlots(GuidedWideRoot& r) { return reinterpret_cast<GuidedWideSlot*>(&r + 1); }
+
+// wscore(node, a): `v`, `w0`, `p` the edge's, `o` its virtual losses, `total` = V (visits and virtual losses)
+PGX_HD inline float GuidedWideScore(int v, float w0, float p, int o, int total, int sign, float c_puct) {
+  const int n = v + o;
+  const float q = n > 0 ? ((float)sign * w0 - (float)o) / (float)n : 0.0f;
+  const float u = (c_puct * p) * sqrtf((float)(total + 1));
+  return q + u / (float)(1 + n);
+}
+// whether path entry `e` of an earlier slot with `depth` entries, read at depth d, runs through `node`
+PGX_HD inline bool GuidedWideOn(int e, int depth, int d, int node) { return d < depth && (e >> 8) == node; }
+
+// a wide root record at begin and after a reroot: slot 0 holds the root, the others are idle
+PGX_HD inline void GuidedWideClearRoot(GuidedWideRoot& r, int width, int count, bool over) {
+  r.count = count;
+  r.done = 0;
+  r.over = over ? 1 : 0;
+  r.broken = 0;
+  r.live = over ? 0 : 1;
+  GuidedWideSlot* sl = GuidedWideSlots(r);
+  for (int j = 0; j < width; ++j) {
+    sl[j].pending = 0;
+    sl[j].status = (j == 0 && !over) ? kGuidedEvaluate : kGuidedIdle;
+    sl[j].depth = 0;
+  }
 }
 
 // bytes of one emitted obs row: the mover's [H, W, C] block of the kObs key

@@ -62,16 +62,38 @@ class GuidedSearch:
         while playing:
             result = gs.run(evaluate, close=False)
             env.step(result.action, ids)
+            gs.reroot(result.action)
+
+    Several leaves per launch: `width=W` (2 .. 32) gives every root W slots; one advance answers all pending slots and
+    descends up to W times per root, the descents steered apart by virtual losses, so a move costs about S / W + 1
+    model calls of k W rows instead of S + 1 calls of k rows.  `leaves` then carry a slot axis (obs [k, W, H, Wd, C],
+    mask [k, W, A], status [k, W]; a slot of status 2 has nothing pending) and `advance` takes priors [k, W, A] and
+    values [k, W], or the same flattened to k W rows.  The round is over when `done` is true; `run` flattens the rows
+    for `evaluate` -- which therefore is the function written for the plain session -- and loops until then:
+
+        gs = env.guided_search(ids, simulations=64, nodes=129, width=8)
+        while playing:
+            result = gs.run(evaluate, close=False)      # about 9 model calls of 8 k rows, not 65 of k
+            env.step(result.action, ids)
             gs.reroot(result.action)"""
 
-    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float, nodes: Any = None):
+    def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float, nodes: Any = None,
+                 width: int = 1):
         self._pool = pool
         self.simulations = int(simulations)
         self.calls = 0
-        if nodes is None:
+        self.width = int(width)
+        if self.width > 1:
+            self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes or 0), self.width)
+        elif nodes is None:
             self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct))
         else:
             self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes))
+
+    @property
+    def done(self) -> bool:
+        """Whether the round is complete: nothing is pending, all statuses are 2."""
+        return bool((np.asarray(self.leaves[2]) == 2).all())
 
     def advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         if self._pool is None:
@@ -94,7 +116,11 @@ class GuidedSearch:
         from then on (status 2, result -1 and zeros).  The kept visits count in `result()`."""
         if self._pool is None:
             raise ValueError("guided search: the session is closed")
-        if self.calls != self.simulations + 1:
+        if self.width > 1:
+            if not self.done:
+                raise ValueError(f"guided_reroot: the round is not complete: "
+                                 f"{int((np.asarray(self.leaves[2]) != 2).sum())} slots are pending")
+        elif self.calls != self.simulations + 1:
             raise ValueError(f"guided_reroot: the round is not complete: {self.calls} of {self.simulations + 1} "
                              f"advances made")
         s2 = self.simulations if simulations is None else int(simulations)
@@ -104,8 +130,13 @@ class GuidedSearch:
 
     def run(self, evaluate: Any, close: bool = True) -> GuidedResult:
         """Calls `evaluate(obs, mask, status) -> (priors, values)` until simulations + 1 advances are made, returns
-        the result and closes the session (`close=False`: leaves it open, for `reroot`)."""
-        while self.calls <= self.simulations:
+        the result and closes the session (`close=False`: leaves it open, for `reroot`).  A wide session calls it
+        with the rows flattened to [k W, ...] until the round is `done`, at most simulations + 1 times."""
+        while self.width > 1 and not self.done and self.calls <= self.simulations:
+            obs, mask, status = self.leaves
+            self.advance(*evaluate(obs.reshape((-1,) + obs.shape[2:]), mask.reshape(-1, mask.shape[-1]),
+                                   status.reshape(-1)))
+        while self.width == 1 and self.calls <= self.simulations:
             self.advance(*evaluate(*self.leaves))
         out = self.result()
         if close:
@@ -340,15 +371,21 @@ class EnvPoolMixin(ABC):
                                     int(seed)))
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
-                      nodes: Any = None, **gumbel: Any) -> Any:
+                      nodes: Any = None, width: int = 1, **gumbel: Any) -> Any:
         """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
         (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
         pool has one at a time, and a new one replaces it.  Nothing of the pool changes.  The arguments are checked
         before any native call.  `policy="gumbel"` is `gumbel_search(env_ids, simulations, **gumbel)` instead (c_puct
         is not used) and returns a `GumbelSearch`.  `nodes` (PUCT only): the node capacity per root, simulations + 1 ..
-        8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree."""
+        8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree.  `width`
+        (PUCT only), 1 .. 32: the leaves per root and launch (`GuidedSearch`: "Several leaves per launch"); 1 is the
+        plain session."""
+        native.check_guided_width(width)
         if policy == "gumbel":
+            if width != 1:
+                raise ValueError("guided_search: width is an argument of policy='puct' (several leaves per launch not "
+                                 "implemented for gumbel sessions)")
             if nodes is not None:
                 raise ValueError("guided_search: nodes is an argument of policy='puct' (reroot not implemented for "
                                  "gumbel sessions)")
@@ -361,10 +398,11 @@ class EnvPoolMixin(ABC):
                                   simulations, c_puct)
         if nodes is not None:
             native.check_guided_nodes(simulations, nodes)
-        return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes)
+        return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes, int(width))
 
     def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
-                      seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1) -> GumbelSearch:
+                      seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1,
+                      width: int = 1) -> GumbelSearch:
         """Extension (the PGX board games): opens a Gumbel search (Danihelka et al., ICLR 2022) from the current
         position of every listed env (global ids; None: all): Gumbel top-`max_considered` sampling without replacement
         at the root, sequential halving of the `simulations` over those actions, a deterministic rule inside the tree;
@@ -372,7 +410,11 @@ class EnvPoolMixin(ABC):
         `weights` the policy training target.  `gumbel` float32 [k, A] is the root noise (zeros: no noise, for
         evaluation); None draws it on the host from numpy.random.Generator(PCG64(seed)), seed=None unseeded.  Returns
         the `GumbelSearch` session; it is the pool's one guided-search session.  Nothing of the pool changes.  The
-        arguments are checked before any native call."""
+        arguments are checked before any native call.  `width` other than 1 raises: sequential halving has its own
+        schedule, and several leaves per launch are a feature of the PUCT sessions."""
+        if width != 1:
+            raise ValueError("gumbel_search: width is an argument of policy='puct' (several leaves per launch not "
+                             "implemented for gumbel sessions)")
         ids = native.check_gumbel(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, max_considered, c_visit, c_scale)
         pool = self._gumbel()

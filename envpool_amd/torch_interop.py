@@ -233,21 +233,32 @@ def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_pl
 
 
 def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations: int, leaves: tuple,
-                         what: str) -> tuple[Any, Any, Any]:
-    """simulations + 1 advances from the emitted `leaves` and the result, every launch ordered both ways."""
+                         what: str, width: int = 0, advances: Any = None) -> tuple[Any, Any, Any]:
+    """simulations + 1 advances from the emitted `leaves` and the result, every launch ordered both ways.  A wide
+    session (`width` slots per root; the leaves have k * width rows): `advances` launches without a host wait, or
+    (None) as many as the round needs, found by reading one reduced status byte per launch."""
     import torch
 
     obs, mask, status = leaves
     a = mask.shape[1]
-    for _ in range(int(simulations) + 1):
+    rows = k * width if width else k
+    most = int(simulations) + 1
+    if width and advances is not None:
+        if isinstance(advances, bool) or int(advances) != advances or not 1 <= int(advances) <= most:
+            pool.guided_end()
+            raise ValueError(f"{what}: advances = {advances} must be 1 .. simulations + 1 = {most}")
+        most = int(advances)
+    for _ in range(most):
+        if width and advances is None and not bool((status != 2).any().item()):
+            break  # the round is complete: nothing is pending
         priors, values = evaluate(obs, mask, status)
         priors = priors.to(device=dev, dtype=torch.float32).contiguous()
         values = values.to(device=dev, dtype=torch.float32).contiguous().view(-1)
-        if tuple(priors.shape) != (k, a) or tuple(values.shape) != (k,):
+        if tuple(priors.shape) != (rows, a) or tuple(values.shape) != (rows,):
             pool.guided_end()
             raise ValueError(f"{what}: evaluate returned priors {tuple(priors.shape)} and values "
-                             f"{tuple(values.shape)} for a session of [{k}, {a}]")
-        _order_both_ways(pool, dev, lambda: pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k,
+                             f"{tuple(values.shape)} for a session of [{rows}, {a}]")
+        _order_both_ways(pool, dev, lambda: pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), rows,
                                                                        obs.data_ptr(), mask.data_ptr(),
                                                                        status.data_ptr()))
     visits = torch.empty((k, a), dtype=torch.int32, device=dev)
@@ -259,40 +270,60 @@ def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations
 
 
 def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
-                         c_puct: float = 1.25, nodes: Any = None, keep_open: bool = False) -> tuple[Any, Any, Any]:
+                         c_puct: float = 1.25, nodes: Any = None, keep_open: bool = False, width: Any = None,
+                         advances: Any = None) -> tuple[Any, Any, Any]:
     """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
     gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
     and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
     Every launch is ordered against torch's current stream like `search_device`: the kernel behind what torch has
     enqueued (the evaluator), the current stream behind the kernel.  Returns (visits int32 [k, A], values float32
     [k, A], action int32 [k]) on the device and closes the session -- or, with `keep_open`, leaves it open for
-    `guided_reroot_device`; `nodes` is the node capacity per root (`DevicePool.guided_begin`)."""
+    `guided_reroot_device`; `nodes` is the node capacity per root (`DevicePool.guided_begin`).
+    `width` = W (1 .. 32) opens a wide session: `evaluate` gets and returns k W rows, flattened (row i W + j is slot j
+    of root i; a slot of status 2 has nothing pending), so a model function written for the plain session works
+    unchanged.  `advances=None` reads one reduced status byte per launch -- the one host wait -- and stops when the
+    round is complete; an integer makes exactly that many advances with no host wait: roots that are not finished then
+    simply have fewer visits, which the result shows."""
     import torch
 
     if env_ids is None:
         env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
     ids = native.check_guided(env_ids, simulations, c_puct)
     native.check_guided_nodes(simulations, nodes)
+    width = native.check_guided_width(width)
+    if advances is not None and not width:
+        raise ValueError("guided_search_device: advances is an argument of a wide session (width=)")
     h, w, c, a = pool.guided_shape()
     k = len(ids)
+    rows = k * width if width else k
     dev = torch.device("cuda", pool.device)
-    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
-    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
-    status = torch.empty((k,), dtype=torch.uint8, device=dev)
-    _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(),
-                                                                 ids, simulations, c_puct, int(nodes or 0)))
-    out = _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_search_device")
+    obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
+    status = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    if width:
+        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
+                                                                     status.data_ptr(), ids, simulations, c_puct,
+                                                                     int(nodes or 0), width))
+    else:
+        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
+                                                                     status.data_ptr(), ids, simulations, c_puct,
+                                                                     int(nodes or 0)))
+    out = _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_search_device",
+                               width, advances)
     if not keep_open:
         pool.guided_end()
     return out
 
 
-def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: int) -> tuple[Any, Any, Any]:
+def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: int,
+                         advances: Any = None) -> tuple[Any, Any, Any]:
     """The next round of the pool's open PUCT session (`guided_search_device(..., keep_open=True)`) with tree reuse:
     `actions` is an int32 tensor [k] on the pool's device, the moves played -- `pool.guided_reroot_device` keeps their
     subtrees --, then `simulations` + 1 advances with `evaluate` and the result, every launch ordered both ways against
     torch's current stream as in `guided_search_device`.  Returns (visits, values, action) on the device and leaves the
-    session open."""
+    session open.  A wide session keeps its width; `advances` as in `guided_search_device`.  The reroot kernel cannot
+    know whether slots are still pending: they are dropped and nothing of them is backed up, so finish the round first
+    (`advances=None`, or enough of them)."""
     import torch
 
     dev = torch.device("cuda", pool.device)
@@ -300,12 +331,17 @@ def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: in
     if actions.dtype != torch.int32 or actions.device != dev or actions.dim() != 1 or not actions.is_contiguous():
         raise ValueError(f"guided_reroot_device: actions must be a contiguous one-dimensional int32 tensor on {dev}")
     k = int(actions.shape[0])
-    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
-    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
-    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    width = int(getattr(pool, "_guided_width", 0) or 0)
+    if advances is not None and not width:
+        raise ValueError("guided_reroot_device: advances is an argument of a wide session (width=)")
+    rows = k * width if width else k
+    obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
+    status = torch.empty((rows,), dtype=torch.uint8, device=dev)
     _order_both_ways(pool, dev, lambda: pool.guided_reroot_device(actions.data_ptr(), k, simulations, obs.data_ptr(),
                                                                   mask.data_ptr(), status.data_ptr()))
-    return _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_reroot_device")
+    return _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_reroot_device",
+                                width, advances)
 
 
 def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,

@@ -611,6 +611,33 @@ int epa_guided_reroot(epa_pool* pool, const int32_t* actions, int32_t k, int32_t
 int epa_guided_reroot_device(epa_pool* pool, const void* device_actions, int32_t k, int32_t simulations,
                              void* device_obs, void* device_mask, void* device_status);
 
+/* Guided search, several leaves per launch (PUCT sessions; csrc/pgx_guided.hip.h "Several leaves per launch" is the
+ * authority): a WIDE session of width W, 1 .. EPA_GUIDED_MAX_WIDTH, keeps W slots per root -- each a pending leaf, a
+ * status and a path -- and one advance answers every pending slot and then descends up to W times per root, the
+ * descents steered apart by virtual losses, so that a move of S simulations costs about S / W + 1 model calls of
+ * k * W rows instead of S + 1 calls of k rows.  Through this interface a wide session is a session of k * W rows: obs,
+ * mask and status of begin, advance and reroot, and priors and values of advance, have k * W rows, row i * W + j for
+ * slot j of root i; `k` of epa_guided_advance is k * W.  epa_guided_reroot still takes one action per root (its `k`
+ * is the number of roots), and epa_guided_result gives one row per root, as for a plain session.
+ *   A slot of status 2 has nothing pending and its rows are zeros.  A round is complete when all k * W statuses are 2,
+ *   after at most S + 1 advances (typically about S / W + 1); later advances up to call number S change nothing, and a
+ *   call number above S is refused.  A descent that arrives at a leaf handed out earlier in the same launch is dropped
+ *   (a collision), and that root hands out no further leaf in that launch.  Width 1 is the plain session, call for call.
+ *   `nodes`: the capacity per root, 0 for S + 1, as epa_guided_begin_nodes.
+ *   epa_guided_reroot of a wide session: the host form refuses while any slot is pending; the device form cannot look:
+ *   slots still pending are dropped and nothing of them is backed up -- finish the round first.  After it slot 0 of
+ *   every root holds the new root and the other slots are idle.
+ *   EPA_ERR_INVALID, before any launch, beside the refusals of epa_guided_begin_nodes: a width outside 1 ..
+ *     EPA_GUIDED_MAX_WIDTH; advance with a row count other than k * W; a host reroot with a pending slot.  The tree
+ *     limit EPA_SEARCH_MAX_TREE_BYTES counts the wide root records (about 1 KiB per slot).
+ * The _device form takes device pointers and only enqueues. */
+#define EPA_GUIDED_MAX_WIDTH 32
+int epa_guided_begin_wide(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t nodes,
+                          int32_t width, float c_puct, uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_guided_begin_wide_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                                 int32_t nodes, int32_t width, float c_puct, void* device_obs, void* device_mask,
+                                 void* device_status);
+
 /* Gumbel search (no reference analogue; the four PGX board games): the guided-search session above with a second
  * selection policy -- Gumbel top-m sampling without replacement at the root, sequential halving of the simulations
  * over those m actions, a deterministic rule inside the tree, and the improved policy softmax(logits + sigma(completed

@@ -25,6 +25,22 @@ the pool's stream.
   kept      the share of a root's nodes that a reroot keeps, per move, averaged over the roots: (1 + the root's visits
             after the reroot) / (1 + its visits before) -- every simulation that did not end in a finished game made
             one node, so early in a game this is the node count itself
+
+    python tools/bench_guided.py --width 1,4,8,16 [--evaluators const,hash] [--games Othello,Hex] [--sizes 64,4096] ...
+
+Several leaves per launch instead: per game, k freshly reset roots, width W and evaluator, S = 64 in the device form, one
+JSON line.  W = 1 is the plain session (S + 1 advances of k rows), the others are wide sessions (k W rows).
+  evaluators  const: the two tensors above, nothing runs between the launches;  hash: a device-side evaluator on the
+              pool's stream -- peaked priors softmax(8 cos(obs . P)) over the legal actions and values tanh(obs . v) from
+              fixed random P, v -- so that descents collide as they do under a real policy
+  advances    a first session reads the statuses after every launch and counts the advances until all of them are 2
+              (and the leaves of status 0 handed out); the positions and the evaluator are fixed, so every later session
+              makes exactly that many advances with no host wait
+  advance     the median over all advance launches of `reps` sessions, each between its own pair of events (the
+              evaluator is outside the pair); `vs_plain` = that median over W times the plain advance of the same game,
+              k and evaluator (when W = 1 is in the same run): the cost of one wide launch in plain launches' worth of
+              descents
+  session     one pair of events around begin, all advances (and the evaluator's launches) and the result; the median
 """
 import argparse
 import json
@@ -162,6 +178,94 @@ def measure_reroot(torch, ti, DevicePool, fam, k, args):
             "nodes_kept_share_per_move": [round(float(np.mean(x)), 4) for x in kept]}
 
 
+def measure_wide(torch, ti, DevicePool, fam, k, width, evaluator, args, plain_us):
+    pool = DevicePool(fam, k, seed=0)
+    dev = torch.device("cuda", pool.device)
+    stream = torch.cuda.ExternalStream(pool.stream, device=dev)
+    ids = torch.arange(k, dtype=torch.int32, device=dev)
+    ti.send_device_tensors(pool, None, ids)  # reset: every env at the start of a game
+    ti.recv_device_tensors(pool)
+    h, w, c, a = pool.guided_shape()
+    rows = k * width
+    obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
+    status = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    const = (torch.full((rows, a), 1.0 / a, dtype=torch.float32, device=dev),
+             torch.zeros((rows,), dtype=torch.float32, device=dev))
+    gen = torch.Generator().manual_seed(7)
+    w_p = torch.randn((h * w * c, a), generator=gen).to(dev)
+    w_v = (torch.randn((h * w * c,), generator=gen) * 0.2).to(dev)
+    torch.cuda.synchronize(dev)
+
+    def evaluate():
+        if evaluator == "const":
+            return const
+        x = obs.reshape(rows, -1).to(torch.float32)
+        e = torch.exp(8.0 * torch.cos(x @ w_p)) * mask.to(torch.float32)
+        return (e / e.sum(1, keepdim=True).clamp_min(1e-30)).contiguous(), torch.tanh(x @ w_v).contiguous()
+
+    def begin():
+        if width == 1:
+            pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, S, C_PUCT)
+        else:
+            pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, S, C_PUCT, 0, width)
+
+    def event():
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(stream)
+        return ev
+
+    with torch.cuda.stream(stream):
+        # the session that counts: a host wait after every launch
+        begin()
+        advances, leaves = 0, 0
+        while bool((status != 2).any()):
+            leaves += int((status == 0).sum())
+            priors, values = evaluate()
+            pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), rows, obs.data_ptr(), mask.data_ptr(),
+                                       status.data_ptr())
+            advances += 1
+            assert advances <= S + 1
+        pool.guided_result_device(visits.data_ptr(), vals.data_ptr(), action.data_ptr())
+        torch.cuda.synchronize(dev)
+        assert bool((visits.sum(1) == S).all())
+        launches, sessions = [], []
+        for rep in range(args.warmup + args.reps):
+            timed = []
+            first = event()
+            begin()
+            for t in range(advances):
+                priors, values = evaluate()
+                e0 = event()
+                pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), rows, obs.data_ptr(), mask.data_ptr(),
+                                           status.data_ptr())
+                timed.append((e0, event()))
+            pool.guided_result_device(visits.data_ptr(), vals.data_ptr(), action.data_ptr())
+            last = event()
+            last.synchronize()
+            torch.cuda.synchronize(dev)
+            assert bool((visits.sum(1) == S).all()) and bool((status == 2).all())
+            if rep >= args.warmup:
+                launches += [x.elapsed_time(y) for x, y in timed]
+                sessions.append(first.elapsed_time(last))
+    pool.guided_end()
+    pool.close()
+    us = float(np.median(launches)) * 1e3
+    out = {"game": fam, "roots": k, "simulations": S, "width": width, "evaluator": evaluator,
+           "advances_per_round": advances, "leaves_per_launch_per_root": round(leaves / (advances * k), 3),
+           "advance_us_per_launch": round(us, 2),
+           "advance_us_min_max": [round(min(launches) * 1e3, 2), round(max(launches) * 1e3, 2)],
+           "session_ms": round(float(np.median(sessions)), 3), "session_ms_all": [round(x, 3) for x in sessions]}
+    if width == 1:
+        plain_us[(fam, k, evaluator)] = us
+    elif (fam, k, evaluator) in plain_us:
+        out["vs_plain"] = round(us / (width * plain_us[(fam, k, evaluator)]), 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="Othello,Hex")
@@ -170,6 +274,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--reroot", action="store_true", help="time guided_reroot_device instead (tree reuse)")
+    ap.add_argument("--width", default=None, help="several leaves per launch instead: the widths, e.g. 1,4,8,16")
+    ap.add_argument("--evaluators", default="const,hash", help="with --width: const, hash or both")
     args = ap.parse_args()
     import torch
 
@@ -177,8 +283,19 @@ def main():
     from envpool_amd.core.device_pool import DevicePool
 
     sink = open(args.out, "w") if args.out else None
+    plain_us = {}
     for fam in args.games.split(","):
         for k in [int(x) for x in args.sizes.split(",")]:
+            if args.width:
+                for evaluator in args.evaluators.split(","):
+                    for width in [int(x) for x in args.width.split(",")]:
+                        text = json.dumps(measure_wide(torch, ti, DevicePool, fam, k, width, evaluator, args,
+                                                       plain_us))
+                        print(text, flush=True)
+                        if sink:
+                            sink.write(text + "\n")
+                            sink.flush()
+                continue
             text = json.dumps((measure_reroot if args.reroot else measure)(torch, ti, DevicePool, fam, k, args))
             print(text, flush=True)
             if sink:
