@@ -418,12 +418,10 @@ class Pool {
   virtual void GuidedAdvance(const GuidedArgs& a);
   virtual void GuidedResult(const GuidedArgs& a);
   virtual void GuidedReroot(const GuidedArgs& a);
-  // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; GuidedResult and GuidedReroot
-  // serve them too (a.width != 0)
+  // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; the four hooks above serve
+  // them too (a.width != 0: the family chooses its kernels)
   virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
   virtual size_t GuidedWideLiveOffset() const { return 0; }  // of a record's int32 count of pending slots
-  virtual void GuidedBeginWide(const int* d_ids, const GuidedArgs& a);
-  virtual void GuidedAdvanceWide(const GuidedArgs& a);
   // obs / mask / status: host arrays (device == false) or device pointers.  nodes: the capacity per root, 0 for
   // simulations + 1.
   void GuidedBeginCall(const int32_t* ids, int k, int simulations, int nodes, float c_puct, void* obs, void* mask,

@@ -17,10 +17,15 @@
 // apart.
 // Render: pgx_render.hip.h painted by render_kernel.hip.h, one workgroup per band of a frame.
 // Playout: pgx_playout.hip.h, one (env, repeat) per lane, the whole game in registers (PgxPlayoutKernel).
-// Search: pgx_search.hip.h, one wave per root, the tree in the pool's side scratch (PgxSearchKernel).
-// Guided search: pgx_guided.hip.h, one wave per root and one launch per simulation, the tree in the session's own
-// memory between launches (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult), and PgxGuidedReroot, which keeps the
-// played move's subtree for the next move by compacting it in place.  Wide sessions (PgxGuidedBeginWide /
+// Tree search, one wave per root: the kernels below are made of the building blocks of pgx_tree.hip.h (device only) --
+// the loop over a lane's action slots (ForOwned / ForSlots / ForLegal), the wave butterflies (WaveReduce, WaveBest,
+// WaveSoftmax), the child broadcast (OwnerChild), MakeNode / Expand / Backup, LoadPuctEdges, the result rows
+// (RootResult) and the root record of a plain or a wide session (GuidedRec) -- over the arithmetic of the shared
+// headers:
+// Search: pgx_search.hip.h, the tree in the pool's side scratch (PgxSearchKernel).
+// Guided search: pgx_guided.hip.h, one launch per simulation, the tree in the session's own memory between launches
+// (PgxGuidedBegin / PgxGuidedAdvance / PgxGuidedResult), and PgxGuidedReroot, which keeps the played move's subtree for
+// the next move by compacting it in place.  Wide sessions (PgxGuidedBegin / Result / Reroot with WIDE,
 // PgxGuidedAdvanceWide) keep W slots per root and descend up to W times per launch, steered apart by virtual losses.
 // Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
 // policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
@@ -35,6 +40,7 @@
 #include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
 #include "pgx_search.hip.h"
+#include "pgx_tree.hip.h"
 #include "render_kernel.hip.h"
 
 namespace epa {
@@ -200,45 +206,25 @@ __global__ __launch_bounds__(kPlayoutBlock) void PgxPlayoutKernel(CommonDev cm, 
 }
 
 // Tree search (pgx_search.hip.h): one wave per root, one block per wave; block i searches listed env i in its own
-// S + 1 nodes of the tree scratch.  Everything that steers the control flow -- the node, the picked action, the child,
-// val0 -- is wave-uniform: it comes out of a butterfly reduction or a broadcast, so every lane holds the same value
-// and the loops need no divergence handling.
-//   lane ownership  lane j owns actions j and j + 64 (Hex: two per lane; Othello's pass, action 64, is lane 0's second
-//                   slot) of every node: it loads their child / v / w0 (contiguous over the wave), scores them, and
-//                   is the only lane that writes them -- at the node's making, at expansion (child) and in backup.
-//                   Edge statistics never pass between lanes through memory; the picked edge's child index reaches
-//                   the other lanes by a register broadcast from its owner.
-//   selection       V is a wave integer sum, the pick a wave arg-max of pgx::SearchBetter (lowest action on ties)
-//   expansion       every lane runs the same pgx::Step on its copy of the node's State; lane 0 stores the new node's
-//                   State and term0, every lane clears its own edges of it
+// S + 1 nodes of the tree scratch.  The lane ownership, the wave-uniform control flow and the fences are those of
+// pgx_tree.hip.h, whose helpers the kernel is made of:
+//   selection       V is a wave integer sum (WaveSum), the pick a wave arg-max of pgx::SearchBetter (WaveBest), the
+//                   child a register broadcast from the edge's owner (OwnerChild)
+//   expansion       Expand: every lane runs the same pgx::Step on its copy of the node's State; lane 0 stores the new
+//                   node's State and term0, every lane clears its own edges of it
 //   leaf            lane r < R plays leaf playout r (the other 64 - R lanes idle); val0 is a wave integer sum
-//   backup          the path's (node, action) pairs are kept in LDS by lane 0; each pair's owner lane adds to v, w0
-// A node's State is written by lane 0 and read by all lanes on later simulations: a hand-off between lanes through
-// memory.  A wavefront-scope release fence follows the stores of an expansion and an acquire fence precedes the loads
-// of a descent (the same pair brackets the path in LDS), so neither the compiler nor the memory pipeline reorders them.
-constexpr int kSearchBlock = pgx::kSearchWave;
+//   backup          the path's (node, action) pairs are kept in LDS by lane 0; Backup: each pair's owner lane adds to
+//                   v, w0
+// A wavefront-scope release fence follows the stores of an expansion and an acquire fence precedes the loads of a
+// descent (the same pair brackets the path in LDS).
+namespace tree = pgx::tree;
+using tree::WaveAcquire;
+using tree::WaveRelease;
+constexpr int kSearchBlock = tree::kWave;
 static_assert(pgx::kSearchMaxSimulations == EPA_SEARCH_MAX_SIMULATIONS &&
                   pgx::kSearchMaxLeafPlayouts == EPA_SEARCH_MAX_LEAF_PLAYOUTS &&
                   pgx::kGuidedMaxNodes == EPA_GUIDED_MAX_NODES,
               "the C ABI states the header's limits");
-
-__device__ __forceinline__ void WaveRelease() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); }
-__device__ __forceinline__ void WaveAcquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-
-__device__ __forceinline__ int WaveSum(int x) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kSearchBlock);
-  return x;
-}
-__device__ __forceinline__ pgx::SearchPick WaveBest(pgx::SearchPick p) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
-    const pgx::SearchPick o{__shfl_xor(p.key, m, kSearchBlock), __shfl_xor(p.action, m, kSearchBlock),
-                            __shfl_xor(p.ok, m, kSearchBlock)};
-    p = pgx::SearchBetter(p, o);
-  }
-  return p;
-}
 
 template <int G>
 __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, const pgx::State* st,
@@ -255,23 +241,12 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
   int32_t* visits = a.visits + (size_t)row * A;
   int32_t* returns = a.returns + (size_t)row * A;
   if (cm.done[e] != 0) {  // over at the call (an env before its first reset is)
-#pragma unroll
-    for (int j = 0; j < SL; ++j) {
-      const int act = lane + kSearchBlock * j;
-      if (act < A) visits[act] = returns[act] = 0;
-    }
+    tree::ForOwned<G>(lane, [&](int, int act) { visits[act] = returns[act] = 0; });
     if (lane == 0) a.action[row] = -1;
     return;
   }
   const pgx::State root = st[e];
-  if (lane == 0) {
-    nodes[0].s = root;
-    nodes[0].term0 = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    if (lane + kSearchBlock * j < A) pgx::SearchClearEdge<G>(nodes[0], lane + kSearchBlock * j);
-  }
+  tree::MakeNode<G>(nodes[0], root, 0, lane);
   WaveRelease();
   int count = 1;
   bool broken = false;
@@ -280,28 +255,28 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
     for (;;) {
       WaveAcquire();
       Node& nd = nodes[node];
-      const pgx::State s = nd.s;
+      pgx::State s = nd.s;
       if (s.done) {
         val0 = R * nd.term0;
         break;
       }
       int child[SL], v[SL], w0[SL];
       int own = 0;
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        const int act = lane + kSearchBlock * j;
+      tree::ForSlots<G>(lane, [&](int j, int act, bool owned) {
         child[j] = -1;
         v[j] = w0[j] = 0;
-        if (act < A) {
+        if (owned) {
           child[j] = nd.child[act];
           v[j] = nd.v[act];
           w0[j] = nd.w0[act];
         }
         own += v[j];
-      }
-      const int total = WaveSum(own);
+      });
+      const int total = tree::WaveSum(own);
       const int sign = pgx::SearchSign<G>(s);
       pgx::SearchPick mine = pgx::SearchNone();
+      // (tree::ForLegal written out: through the helper the backend lays this kernel's code out differently, and
+      // Othello at one wave per SIMD, where nothing hides latency, measured 2.6 % slower)
 #pragma unroll
       for (int j = 0; j < SL; ++j) {
         const int act = lane + kSearchBlock * j;
@@ -310,7 +285,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
               mine, pgx::SearchPick{pgx::SearchScore(v[j], w0[j], total, sign, R, a.c_puct), act, 1});
         }
       }
-      const int act = WaveBest(mine).action;
+      const int act = tree::WaveBest(mine).action;
       // A running game has a legal action and a path is a line of play, far shorter than the LDS array: this is
       // unreachable from a position of the game.  A broken one is reported through the pool's error word, like
       // set_state's, and the root gives the rows of an env that is over (the host harness returns -3 here).
@@ -320,31 +295,14 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
       }
       if (lane == 0) path[depth] = node << 8 | act;
       ++depth;
-      const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
-      int c = __shfl(child[0], owner, kSearchBlock);
-      if (SL > 1) {
-        const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
-        c = slot == 1 ? c1 : c;
-      }
+      const int c = tree::OwnerChild<SL>(child, act);
       if (c < 0) {
-        c = count++;
-        if (lane == owner) nd.child[act] = c;
-        Node& nn = nodes[c];
-        pgx::State s2;
-        const int term0 = pgx::SearchExpand<G>(s, act, s2);
-        if (lane == 0) {
-          nn.s = s2;
-          nn.term0 = term0;
-        }
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-          if (lane + kSearchBlock * j < A) pgx::SearchClearEdge<G>(nn, lane + kSearchBlock * j);
-        }
+        const int term0 = tree::Expand<G>(nodes, node, s, act, count, lane);
         WaveRelease();
-        if (s2.done) {
+        if (s.done) {
           val0 = R * term0;
         } else {
-          val0 = WaveSum(lane < R ? pgx::SearchLeaf<G>(s2, a.seed, e + id_offset, t, R, lane, limit) : 0);
+          val0 = tree::WaveSum(lane < R ? pgx::SearchLeaf<G>(s, a.seed, e + id_offset, t, R, lane, limit) : 0);
         }
         break;
       }
@@ -353,32 +311,11 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
     WaveRelease();
     __syncthreads();
     WaveAcquire();
-    if (broken) depth = 0;
-    for (int d = 0; d < depth; ++d) {
-      const int p = path[d];
-      const int act = p & 255;
-      if ((act & (kSearchBlock - 1)) == lane) {
-        Node& nd = nodes[p >> 8];
-        nd.v[act] += 1;
-        nd.w0[act] += val0;
-      }
-    }
+    tree::Backup(nodes, path, broken ? 0 : depth, val0, lane);
     __syncthreads();  // the path is read before the next simulation overwrites it
   }
   WaveAcquire();
-  const int sign = pgx::SearchSign<G>(root);
-  pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    if (act < A) {
-      const int v = broken ? 0 : nodes[0].v[act];
-      visits[act] = v;
-      returns[act] = broken ? 0 : sign * nodes[0].w0[act];
-      if (!broken && pgx::Has(root.m, act)) mine = pgx::SearchBetter(mine, pgx::SearchPick{(float)v, act, 1});
-    }
-  }
-  const int best = WaveBest(mine).action;  // (-1 without a legal action)
+  const int best = tree::RootResult<G>(nodes[0], root, broken, lane, visits, returns);
   if (lane == 0) {
     a.action[row] = best;
     if (broken) *err = kErrSearch;
@@ -387,10 +324,10 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
 
 // Guided search (pgx_guided.hip.h): the search above cut into launches at every new leaf, so that the caller's model
 // supplies the priors and the leaf value.  One wave per root, one block per wave; block i works on root i of the
-// session: its GuidedRoot record and its S + 1 nodes, which stay in the session's memory between launches.
-//   lane ownership  as in PgxSearchKernel: lane j owns actions j and j + 64 of every node and is the only lane that
-//                   writes their child / v / w0 / p -- at the node's making, when the priors arrive, at expansion and
-//                   in backup.  The priors row of the root is read coalesced by the owning lanes.
+// session: its GuidedRoot record and its nodes, which stay in the session's memory between launches.
+//   lane ownership  as in pgx_tree.hip.h: lane j owns actions j and j + 64 of every node and is the only lane that
+//                   writes their child / v / w0 / p -- at the node's making, when the priors arrive (GuidedAnswer), at
+//                   expansion and in backup.  The priors row of the leaf is read coalesced by the owning lanes.
 //   control flow    the status, the pending leaf, the picked action and the child are wave-uniform: they come out of a
 //                   load of one address, a butterfly reduction or a register broadcast.
 //   hand-offs       lane 0 stores a new node's State and term0 and the root record with its path; other lanes load
@@ -440,32 +377,46 @@ __device__ __forceinline__ void GuidedEmitIdle(const Args& a, int row, int n, in
   if (lane < n) a.status[row + lane] = (unsigned char)pgx::kGuidedIdle;
 }
 
+// the leaf rows of root `row` when its position `s` is handed out, at begin and after a reroot: the root's own row
+// (idle when the root is over), and for a wide session (slot 0 holds the root) the idle rows of its other slots
+template <int G, bool WIDE>
+__device__ __forceinline__ void GuidedEmitRoot(const GuidedArgs& a, int row, int lane, bool over, const pgx::State& s) {
+  const int W = WIDE ? a.width : 1;
+  GuidedEmitLeaf<G>(a, row * W, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
+  if (WIDE) GuidedEmitIdle<G>(a, row * W + 1, W - 1, lane);
+}
+
+// The answer to a pending leaf (status 0 or 1): for status 0 its owner lanes store the caller's priors row `lrow` and
+// the caller's value counts, for status 1 the finished game's term0.  Returns val0, seat 0's value of the leaf.
 template <int G>
+__device__ __forceinline__ float GuidedAnswer(const GuidedArgs& a, size_t lrow, pgx::GuidedNode<G>& leaf, int status,
+                                              int lane) {
+  if (status != pgx::kGuidedEvaluate) return (float)leaf.term0;
+  tree::ForOwned<G>(lane, [&](int, int act) {
+    leaf.p[act] = pgx::GuidedClean(a.priors[lrow * pgx::Dims<G>::A + act]);
+  });
+  return (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[lrow]);
+}
+
+// WIDE: a wide session (below): the record is pgx::GuidedWideRoot, the root goes to slot 0 (leaf row i * W), the other
+// slots are idle and their rows zeros.
+template <int G, bool WIDE>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedBegin(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, GuidedArgs a) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
   const int e = ids[row];
   const bool over = cm.done[e] != 0;  // (an env before its first reset is)
   const pgx::State root = st[e];
   Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
-  if (lane == 0) {
-    n0.s = root;
-    n0.term0 = 0;
-    pgx::GuidedClearRoot(static_cast<pgx::GuidedRoot*>(a.roots)[row], over);
-  }
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(n0, lane + kSearchBlock * j);
-  }
+  tree::MakeNode<G>(n0, root, 0, lane, [&](Node&) { tree::GuidedRec<WIDE>(a.roots, row, a.width).Clear(over); });
   WaveRelease();
-  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+  GuidedEmitRoot<G, WIDE>(a, row, lane, over, root);
 }
 
 template <int G>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, unsigned* err) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
   const int S = a.simulations;
@@ -475,28 +426,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
   int status = rec.status;
   pgx::State s{};  // the pending leaf's position when the launch ends
   if (status != pgx::kGuidedIdle) {
-    Node& leaf = nodes[rec.pending];
-    float val0;
-    if (status == pgx::kGuidedEvaluate) {
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        const int act = lane + kSearchBlock * j;
-        if (act < A) leaf.p[act] = pgx::GuidedClean(a.priors[(size_t)row * A + act]);
-      }
-      val0 = (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[row]);
-    } else {
-      val0 = (float)leaf.term0;
-    }
-    const int backed = rec.depth;
-    for (int d = 0; d < backed; ++d) {
-      const int p = rec.path[d];
-      const int act = p & 255;
-      if ((act & (kSearchBlock - 1)) == lane) {
-        Node& nd = nodes[p >> 8];
-        nd.v[act] += 1;
-        nd.w0[act] += val0;
-      }
-    }
+    const float val0 = GuidedAnswer<G>(a, (size_t)row, nodes[rec.pending], status, lane);
+    tree::Backup(nodes, rec.path, rec.depth, val0, lane);
     WaveRelease();
     int count = rec.count;
     // the round's last call -- or the root's memory is used up (a rerooted tree may come to that): a normal end
@@ -509,36 +440,16 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
       WaveAcquire();
       s = nodes[0].s;
       for (;;) {
-        Node& nd = nodes[node];
         int child[SL], v[SL];
         float w0[SL], pr[SL];
-        int own = 0;
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-          const int act = lane + kSearchBlock * j;
-          child[j] = -1;
-          v[j] = 0;
-          w0[j] = pr[j] = 0.0f;
-          if (act < A) {
-            child[j] = nd.child[act];
-            v[j] = nd.v[act];
-            w0[j] = nd.w0[act];
-            pr[j] = nd.p[act];
-          }
-          own += v[j];
-        }
-        const int total = WaveSum(own);
+        const int total = tree::WaveSum(tree::LoadPuctEdges<G>(nodes[node], lane, child, v, w0, pr));
         const int sign = pgx::SearchSign<G>(s);
         pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-          const int act = lane + kSearchBlock * j;
-          if (act < A && pgx::Has(s.m, act)) {
-            mine = pgx::SearchBetter(
-                mine, pgx::SearchPick{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), act, 1});
-          }
-        }
-        const int act = WaveBest(mine).action;
+        tree::ForLegal<G>(lane, s.m, [&](int j, int act) {
+          mine = pgx::SearchBetter(
+              mine, pgx::SearchPick{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), act, 1});
+        });
+        const int act = tree::WaveBest(mine).action;
         // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
         if (act < 0 || depth >= pgx::kSearchMaxPath) {
           broken = true;
@@ -546,28 +457,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
         }
         if (lane == 0) rec.path[depth] = node << 8 | act;
         ++depth;
-        const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
-        int c = __shfl(child[0], owner, kSearchBlock);
-        if (SL > 1) {
-          const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
-          c = slot == 1 ? c1 : c;
-        }
-        if (c < 0) {
-          c = count++;  // (count < capacity: checked before the descent, which makes one node at the most)
-          if (lane == owner) nd.child[act] = c;
-          Node& nn = nodes[c];
-          pgx::State s2;
-          const int term0 = pgx::SearchExpand<G>(s, act, s2);
-          if (lane == 0) {
-            nn.s = s2;
-            nn.term0 = term0;
-          }
-#pragma unroll
-          for (int j = 0; j < SL; ++j) {
-            if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(nn, lane + kSearchBlock * j);
-          }
-          node = c;
-          s = s2;
+        const int c = tree::OwnerChild<SL>(child, act);
+        if (c < 0) {  // (count < capacity: checked before the descent, which makes one node at the most)
+          tree::Expand<G>(nodes, node, s, act, count, lane);
           break;
         }
         node = c;
@@ -592,31 +484,18 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
   GuidedEmitLeaf<G>(a, row, lane, status, s);
 }
 
-// (WIDE: the root record of a wide session, pgx::GuidedWideRoot with its stride; one row per root either way)
-template <int G, bool WIDE = false>
+// (WIDE: the root record of a wide session; one row per root either way)
+template <int G, bool WIDE>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int A = pgx::Dims<G>::A;
   using Node = pgx::GuidedNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
   const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
   WaveAcquire();
-  const bool over = WIDE ? pgx::GuidedWideRootAt(a.roots, row, a.width).over != 0
-                         : static_cast<const pgx::GuidedRoot*>(a.roots)[row].over != 0;
+  const bool over = tree::GuidedRec<WIDE>(a.roots, row, a.width).over();
   const pgx::State root = n0.s;
-  const float sign = (float)pgx::SearchSign<G>(root);
-  pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    if (act < A) {
-      const int v = over ? 0 : n0.v[act];
-      a.visits[(size_t)row * A + act] = v;
-      a.vals[(size_t)row * A + act] = over ? 0.0f : sign * n0.w0[act];
-      if (!over && pgx::Has(root.m, act)) mine = pgx::SearchBetter(mine, pgx::SearchPick{(float)v, act, 1});
-    }
-  }
-  const int best = WaveBest(mine).action;  // (-1 without a legal action)
-  if (lane == 0) a.action[row] = best;
+  const int best = tree::RootResult<G>(n0, root, over, lane, a.visits + (size_t)row * A, a.vals + (size_t)row * A);
+  if (lane == 0) a.action[row] = best;  // (-1 without a legal action)
 }
 
 // reroot (pgx_guided.hip.h "Tree reuse"): the subtree under the played move becomes the tree, compacted in place.  One
@@ -629,41 +508,29 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
 //                  reward pairs in scratch instead of LDS
 //   mark           the nodes in index order; whether node i is kept is one LDS word, so the branch is wave-uniform; the
 //                  lanes of a kept node mark its children, whose indices are all above i
-//   rank           64 nodes a trip: a lane's mark, an inclusive wave scan by register shifts, the carry of the trips
-//                  before; the rank replaces the mark
+//   rank           64 nodes a trip: a lane's mark, an inclusive wave scan by register shifts (WaveScan), the carry of
+//                  the trips before; the rank replaces the mark
 //   copy           the nodes in index order again, kept ones only (wave-uniform); new index < old index, so a store
 //                  lands on a slot that no later trip loads
 // The table's hand-offs between lanes sit between wavefront-scope release and acquire fences with the block's barrier
 // between them, as the path of PgxSearchKernel; so do the loads of what earlier launches stored and the stores that
 // later launches load.
-__device__ __forceinline__ int WaveScan(int x, int lane) {  // the inclusive prefix sum over the wave's lanes
-#pragma unroll
-  for (int m = 1; m < kSearchBlock; m <<= 1) {
-    const int y = __shfl_up(x, m, kSearchBlock);
-    if (lane >= m) x += y;
-  }
-  return x;
-}
-
 constexpr int kRerootTables[3] = {512, 2048, pgx::kGuidedMaxNodes};
 
 // WIDE: a wide session (pgx_guided.hip.h "Several leaves per launch"): the record is pgx::GuidedWideRoot, the new root goes
 // to slot 0 (leaf row i * W), the other slots become idle whatever they held, and their rows are zeros.
-template <int G, int CAP, bool WIDE = false>
+template <int G, int CAP, bool WIDE>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int A = pgx::Dims<G>::A;
   using Node = pgx::GuidedNode<G>;
   __shared__ int32_t table[CAP];  // (a.capacity <= CAP)
   const int row = blockIdx.x, lane = threadIdx.x;
-  pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[WIDE ? 0 : row];  // (not touched when WIDE)
-  pgx::GuidedWideRoot& wrec = pgx::GuidedWideRootAt(a.roots, WIDE ? row : 0, WIDE ? a.width : 1);  // (only WIDE)
+  const tree::GuidedRec<WIDE> rec(a.roots, row, a.width);
   Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
   WaveAcquire();
   const int act = a.actions[row];
-  const int rec_count = WIDE ? wrec.count : rec.count;
-  const bool rec_idle = WIDE ? (wrec.over != 0 || wrec.broken != 0) : (rec.over != 0 || rec.broken != 0);
-  const int old_count = std::min(std::max(rec_count, 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
-  bool over = rec_idle || act < 0 || act >= A;
+  const int old_count = std::min(std::max(rec.count(), 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
+  bool over = rec.idle() || act < 0 || act >= A;
   int count = old_count;
   pgx::State s = nodes[0].s;
   if (!over) {
@@ -671,14 +538,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
     if (c < 0 || c >= old_count) {      // (never >= count) a move the search did not try: a fresh tree on its position
       pgx::State s2;
       const int term0 = pgx::SearchExpand<G>(s, act, s2);
-      if (lane == 0) {
-        nodes[0].s = s2;
-        nodes[0].term0 = term0;
-      }
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(nodes[0], lane + kSearchBlock * j);
-      }
+      tree::MakeNode<G>(nodes[0], s2, term0, lane);
       s = s2;
       count = 1;
     } else {
@@ -689,13 +549,10 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
       WaveAcquire();
       for (int i = c; i < old_count; ++i) {
         if (table[i] != 0) {
-#pragma unroll
-          for (int j = 0; j < SL; ++j) {
-            if (lane + kSearchBlock * j < A) {
-              const int ch = nodes[i].child[lane + kSearchBlock * j];
-              if (ch < old_count) pgx::GuidedRerootReach(table, ch);  // (never >= count)
-            }
-          }
+          tree::ForOwned<G>(lane, [&](int, int e) {
+            const int ch = nodes[i].child[e];
+            if (ch < old_count) pgx::GuidedRerootReach(table, ch);  // (never >= count)
+          });
           WaveRelease();
           __syncthreads();
           WaveAcquire();
@@ -705,7 +562,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
       for (int base = 0; base < old_count; base += kSearchBlock) {
         const int i = base + lane;
         const int m = i < old_count && table[i] != 0 ? 1 : 0;
-        const int upto = WaveScan(m, lane);
+        const int upto = tree::WaveScan(m, lane);
         if (i < old_count) table[i] = pgx::GuidedRerootRank(kept + upto - m, m != 0);
         kept += __shfl(upto, kSearchBlock - 1, kSearchBlock);
       }
@@ -721,38 +578,27 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
             to.s = from.s;
             to.term0 = from.term0;
           }
-#pragma unroll
-          for (int j = 0; j < SL; ++j) {
-            const int e = lane + kSearchBlock * j;
-            if (e < A) {
-              const int ch = from.child[e];
-              to.child[e] = pgx::GuidedRerootEdge(table, ch < old_count ? ch : -1);
-              to.v[e] = from.v[e];
-              to.w0[e] = from.w0[e];
-              to.p[e] = from.p[e];
-            }
-          }
+          tree::ForOwned<G>(lane, [&](int, int e) {
+            const int ch = from.child[e];
+            to.child[e] = pgx::GuidedRerootEdge(table, ch < old_count ? ch : -1);
+            to.v[e] = from.v[e];
+            to.w0[e] = from.w0[e];
+            to.p[e] = from.p[e];
+          });
         }
       }
       count = kept;
     }
     over = s.done != 0;
   }
-  if (WIDE) {
-    if (lane == 0) pgx::GuidedWideClearRoot(wrec, a.width, count, over);
-    WaveRelease();
-    GuidedEmitLeaf<G>(a, row * a.width, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
-    GuidedEmitIdle<G>(a, row * a.width + 1, a.width - 1, lane);
-    return;
-  }
-  if (lane == 0) pgx::GuidedRerootRoot(rec, count, over);
+  if (lane == 0) rec.Reset(count, over);
   WaveRelease();
-  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, s);
+  GuidedEmitRoot<G, WIDE>(a, row, lane, over, s);
 }
 
-// Several leaves per launch (pgx_guided.hip.h "Several leaves per launch"): PgxGuidedBegin / PgxGuidedAdvance for a
-// session whose roots have W slots.  One wave per root, one block per wave, the lane ownership and the fences of
-// PgxGuidedAdvance.
+// Several leaves per launch (pgx_guided.hip.h "Several leaves per launch"): PgxGuidedAdvance for a session whose roots
+// have W slots (PgxGuidedBegin<G, true> begins it).  One wave per root, one block per wave, the lane ownership and the
+// fences of PgxGuidedAdvance.
 //   phase A    the slots in order: the owner lanes store the slot's priors row (row i * W + j) and add along its path,
 //              read from the root record (one address a load: wave-uniform), in slot order, then path order
 //   phase B    up to W descents.  Lane i holds depth and pending leaf of slot i of THIS launch in registers, and the
@@ -770,33 +616,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
 // `lpath` is static, in three width buckets (WB = 4, 16, 32: 4, 16 and 32 KiB), for the reason given at kRerootTables.
 constexpr int kWideBuckets[3] = {4, 16, pgx::kGuidedMaxWidth};
 
-template <int G>
-__global__ __launch_bounds__(kSearchBlock) void PgxGuidedBeginWide(CommonDev cm, const pgx::State* st,
-                                                                   const int* __restrict__ ids, GuidedArgs a) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
-  using Node = pgx::GuidedNode<G>;
-  const int row = blockIdx.x, lane = threadIdx.x, W = a.width;
-  const int e = ids[row];
-  const bool over = cm.done[e] != 0;  // (an env before its first reset is)
-  const pgx::State root = st[e];
-  Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
-  if (lane == 0) {
-    n0.s = root;
-    n0.term0 = 0;
-    pgx::GuidedWideClearRoot(pgx::GuidedWideRootAt(a.roots, row, W), W, 1, over);
-  }
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    if (lane + kSearchBlock * j < A) pgx::GuidedClearEdge<G>(n0, lane + kSearchBlock * j);
-  }
-  WaveRelease();
-  GuidedEmitLeaf<G>(a, row * W, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
-  GuidedEmitIdle<G>(a, row * W + 1, W - 1, lane);
-}
-
 template <int G, int WB>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs a, unsigned* err) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
   __shared__ int32_t lpath[pgx::kSearchMaxPath * WB];  // [depth][slot]: node << 8 | action  (a.width <= WB)
   const int row = blockIdx.x, lane = threadIdx.x;
@@ -810,29 +632,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
   for (int j = 0; j < W; ++j) {
     const int status = slots[j].status;
     if (status == pgx::kGuidedIdle) continue;
-    Node& leaf = nodes[slots[j].pending];
-    const size_t lrow = (size_t)row * W + j;
-    float val0;
-    if (status == pgx::kGuidedEvaluate) {
-#pragma unroll
-      for (int q = 0; q < SL; ++q) {
-        const int act = lane + kSearchBlock * q;
-        if (act < A) leaf.p[act] = pgx::GuidedClean(a.priors[lrow * A + act]);
-      }
-      val0 = (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[lrow]);
-    } else {
-      val0 = (float)leaf.term0;
-    }
+    const float val0 = GuidedAnswer<G>(a, (size_t)row * W + j, nodes[slots[j].pending], status, lane);
     const int backed = std::min(slots[j].depth, pgx::kSearchMaxPath);
-    for (int d = 0; d < backed; ++d) {
-      const int p = slots[j].path[d];
-      const int act = p & 255;
-      if ((act & (kSearchBlock - 1)) == lane) {
-        Node& nd = nodes[p >> 8];
-        nd.v[act] += 1;
-        nd.w0[act] += val0;
-      }
-    }
+    tree::Backup(nodes, slots[j].path, backed, val0, lane);
     if (backed > 0) ++done;
   }
   WaveRelease();
@@ -850,24 +652,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
     bool collided = false;
     pgx::State s = root;
     for (;;) {
-      Node& nd = nodes[node];
-      int child[SL], v[SL], o[SL];
+      int child[SL], v[SL], o[SL] = {};
       float w0[SL], pr[SL];
-      int own = 0;
-#pragma unroll
-      for (int q = 0; q < SL; ++q) {
-        const int act = lane + kSearchBlock * q;
-        child[q] = -1;
-        v[q] = o[q] = 0;
-        w0[q] = pr[q] = 0.0f;
-        if (act < A) {
-          child[q] = nd.child[act];
-          v[q] = nd.v[act];
-          w0[q] = nd.w0[act];
-          pr[q] = nd.p[act];
-        }
-        own += v[q];
-      }
+      const int own = tree::LoadPuctEdges<G>(nodes[node], lane, child, v, w0, pr);
       // the virtual losses: the earlier slots of this launch whose path runs through `node`
       int mine_e = -1;
       if (lane < j && depth < my_depth) mine_e = lpath[depth * WB + lane];
@@ -878,23 +665,18 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
         const int i = __ffsll((long long)mb) - 1;
         mb &= mb - 1;
         const int ai = __shfl(mine_e, i, kSearchBlock) & 255;
-#pragma unroll
-        for (int q = 0; q < SL; ++q) {
-          if (ai == lane + kSearchBlock * q) o[q] += 1;
-        }
+        tree::ForSlots<G>(lane, [&](int q, int act, bool) {
+          if (ai == act) o[q] += 1;
+        });
       }
-      const int total = WaveSum(own) + osum;
+      const int total = tree::WaveSum(own) + osum;
       const int sign = pgx::SearchSign<G>(s);
       pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-      for (int q = 0; q < SL; ++q) {
-        const int act = lane + kSearchBlock * q;
-        if (act < A && pgx::Has(s.m, act)) {
-          mine = pgx::SearchBetter(
-              mine, pgx::SearchPick{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), act, 1});
-        }
-      }
-      const int act = WaveBest(mine).action;
+      tree::ForLegal<G>(lane, s.m, [&](int q, int act) {
+        mine = pgx::SearchBetter(
+            mine, pgx::SearchPick{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), act, 1});
+      });
+      const int act = tree::WaveBest(mine).action;
       if (act < 0 || depth >= pgx::kSearchMaxPath) {  // unreachable from a position of the game (PgxGuidedAdvance)
         broken = true;
         break;
@@ -904,28 +686,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
         slots[j].path[depth] = node << 8 | act;
       }
       ++depth;
-      const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
-      int c = __shfl(child[0], owner, kSearchBlock);
-      if (SL > 1) {
-        const int c1 = __shfl(child[SL - 1], owner, kSearchBlock);
-        c = slot == 1 ? c1 : c;
-      }
-      if (c < 0) {
-        c = count++;  // (count < capacity: checked before the descent, which makes one node at the most)
-        if (lane == owner) nd.child[act] = c;
-        Node& nn = nodes[c];
-        pgx::State s2;
-        const int term0 = pgx::SearchExpand<G>(s, act, s2);
-        if (lane == 0) {
-          nn.s = s2;
-          nn.term0 = term0;
-        }
-#pragma unroll
-        for (int q = 0; q < SL; ++q) {
-          if (lane + kSearchBlock * q < A) pgx::GuidedClearEdge<G>(nn, lane + kSearchBlock * q);
-        }
-        node = c;
-        s = s2;
+      const int c = tree::OwnerChild<SL>(child, act);
+      if (c < 0) {  // (count < capacity: checked before the descent, which makes one node at the most)
+        tree::Expand<G>(nodes, node, s, act, count, lane);
         break;
       }
       node = c;
@@ -974,39 +737,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
 
 // Gumbel search (pgx_gumbel.hip.h): the session, lane ownership, hand-offs and leaves of the guided kernels above with
 // another pick.  Where PUCT needs one integer sum and one arg-max per node, a node here costs these wave reductions,
-// all register butterflies (no LDS), every result wave-uniform:
+// all register butterflies (tree::WaveReduce, no LDS), every result wave-uniform:
 //   GumbelEval      N (int sum) and vmax (int max); SUM p q and SUM p over the visited edges (float, in the header's
 //                   order: the lane's two terms added first, then the butterfly); min and max of the completed Q
-//   GumbelImproved  max of logit + sigma, SUM of the exponentials
+//   GumbelImproved  max of logit + sigma, SUM of the exponentials (tree::WaveSoftmax)
 //   the pick        an arg-max (interior); at the root the legal count (int sum), the largest logit and an arg-max
-// and the leaf whose logits arrive costs a max and a float SUM for its p.  The table of considered visits is walked
-// per root by every lane on wave-uniform integers (scalar work), not read from memory.
-__device__ __forceinline__ float WaveSumF(float x) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x = x + __shfl_xor(x, m, kSearchBlock);
-  return x;
-}
-__device__ __forceinline__ float WaveMaxF(float x) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(x, m, kSearchBlock);
-    x = o > x ? o : x;
-  }
-  return x;
-}
-__device__ __forceinline__ float WaveMinF(float x) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(x, m, kSearchBlock);
-    x = o < x ? o : x;
-  }
-  return x;
-}
-__device__ __forceinline__ int WaveMaxI(int x) {
-#pragma unroll
-  for (int m = kSearchBlock / 2; m >= 1; m >>= 1) x = std::max(x, __shfl_xor(x, m, kSearchBlock));
-  return x;
-}
+// and the leaf whose logits arrive costs a max and a float SUM for its p (WaveSoftmax again).  The table of considered
+// visits is walked per root by every lane on wave-uniform integers (scalar work), not read from memory.
 
 // a lane's edges of one node (slot j: action lane + 64 j) with what the picks need of the whole node
 template <int G>
@@ -1021,18 +758,16 @@ struct GumbelEdges {
 template <int G>
 __device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const pgx::State& s, int lane, float c_visit,
                                            float c_scale, GumbelEdges<G>& e) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
   const int sign = pgx::SearchSign<G>(s);
   float p[SL], q[SL];
   int own = 0, top = 0;
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    e.legal[j] = act < A && pgx::Has(s.m, act);
+  tree::ForSlots<G>(lane, [&](int j, int act, bool owned) {
+    e.legal[j] = owned && pgx::Has(s.m, act);
     e.child[j] = -1;
     e.v[j] = 0;
     e.w0[j] = e.logit[j] = p[j] = 0.0f;
-    if (act < A) {
+    if (owned) {
       e.child[j] = nd.child[act];
       e.v[j] = nd.v[act];
       e.w0[j] = nd.w0[act];
@@ -1043,9 +778,9 @@ __device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const p
       own += e.v[j];
       top = std::max(top, e.v[j]);
     }
-  }
-  e.total = WaveSum(own);
-  e.vmax = WaveMaxI(top);
+  });
+  e.total = tree::WaveSum(own);
+  e.vmax = tree::WaveMax(top);
   float pq[2] = {0.0f, 0.0f}, pp[2] = {0.0f, 0.0f};
 #pragma unroll
   for (int j = 0; j < SL; ++j) {
@@ -1056,8 +791,8 @@ __device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const p
       pp[j] = p[j];
     }
   }
-  const float sum_pq = WaveSumF(pq[0] + pq[1]);
-  const float sum_p = WaveSumF(pp[0] + pp[1]);
+  const float sum_pq = tree::WaveSum(pq[0] + pq[1]);
+  const float sum_p = tree::WaveSum(pp[0] + pp[1]);
   const float mix = pgx::GumbelMix(nd.raw, sign, e.total, sum_pq, sum_p);
   float cq[SL], lo = FLT_MAX, hi = -FLT_MAX;
 #pragma unroll
@@ -1068,8 +803,8 @@ __device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const p
       hi = cq[j] > hi ? cq[j] : hi;
     }
   }
-  lo = WaveMinF(lo);
-  hi = WaveMaxF(hi);
+  lo = tree::WaveMin(lo);
+  hi = tree::WaveMax(hi);
   const float scale = pgx::GumbelScale(c_visit, c_scale, e.vmax);
 #pragma unroll
   for (int j = 0; j < SL; ++j) e.sigma[j] = e.legal[j] ? pgx::GumbelSigma(scale, cq[j], lo, hi) : 0.0f;
@@ -1079,19 +814,10 @@ __device__ __forceinline__ void GumbelEval(const pgx::GumbelNode<G>& nd, const p
 template <int G>
 __device__ __forceinline__ void GumbelImproved(const GumbelEdges<G>& e, float* pi) {
   constexpr int SL = pgx::SearchSlotsPerLane<G>();
-  float x[SL], top = -FLT_MAX;
+  float x[SL], ex[2];
 #pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    x[j] = e.logit[j] + e.sigma[j];
-    if (e.legal[j]) top = x[j] > top ? x[j] : top;
-  }
-  top = WaveMaxF(top);
-  float ex[2] = {0.0f, 0.0f};
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    if (e.legal[j]) ex[j] = pgx::GumbelExp(x[j] - top);
-  }
-  const float sum = WaveSumF(ex[0] + ex[1]);
+  for (int j = 0; j < SL; ++j) x[j] = e.logit[j] + e.sigma[j];
+  const float sum = tree::WaveSoftmax<SL>(x, e.legal, ex);
 #pragma unroll
   for (int j = 0; j < SL; ++j) pi[j] = e.legal[j] ? ex[j] / sum : 0.0f;
 }
@@ -1101,7 +827,7 @@ __device__ __forceinline__ void GumbelImproved(const GumbelEdges<G>& e, float* p
 template <int G>
 __device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx::GumbelRoot<G>& rec, int lane,
                                               int considered, int simulations, bool final) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
   int legal = 0;
   float top = -FLT_MAX;
 #pragma unroll
@@ -1111,26 +837,24 @@ __device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx
       top = e.logit[j] > top ? e.logit[j] : top;
     }
   }
-  legal = WaveSum(legal);
-  top = WaveMaxF(top);
+  legal = tree::WaveSum(legal);
+  top = tree::WaveMax(top);
   const int cv =
       final ? e.vmax : pgx::GumbelConsideredVisit(std::min(considered, legal), simulations, e.total);
   pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    if (act < A && e.legal[j] && e.v[j] == cv) {
+  tree::ForOwned<G>(lane, [&](int j, int act) {
+    if (e.legal[j] && e.v[j] == cv) {
       mine = pgx::SearchBetter(
           mine, pgx::SearchPick{pgx::GumbelRootScore(rec.gumbel[act], e.logit[j], top, e.sigma[j]), act, 1});
     }
-  }
-  return WaveBest(mine).action;
+  });
+  return tree::WaveBest(mine).action;
 }
 
 template <int G>
 __global__ __launch_bounds__(kSearchBlock) void PgxGumbelBegin(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, GumbelArgs a) {
-  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  constexpr int A = pgx::Dims<G>::A;
   using Node = pgx::GumbelNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
   const int e = ids[row];
@@ -1138,20 +862,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelBegin(CommonDev cm, con
   const pgx::State root = st[e];
   Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
   pgx::GumbelRoot<G>& rec = static_cast<pgx::GumbelRoot<G>*>(a.roots)[row];
-  if (lane == 0) {
-    n0.s = root;
-    n0.term0 = 0;
-    n0.raw = 0.0f;
+  tree::MakeNode<G>(n0, root, 0, lane, [&](Node& n) {
+    n.raw = 0.0f;
     pgx::GuidedClearRoot(rec.r, over);
-  }
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    if (act < A) {
-      pgx::GumbelClearEdge<G>(n0, act);
-      rec.gumbel[act] = pgx::GumbelCleanNoise(a.gumbel[(size_t)row * A + act]);
-    }
-  }
+  });
+  tree::ForOwned<G>(lane, [&](int, int act) {
+    rec.gumbel[act] = pgx::GumbelCleanNoise(a.gumbel[(size_t)row * A + act]);
+  });
   WaveRelease();
   GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
 }
@@ -1173,45 +890,23 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, u
     if (status == pgx::kGuidedEvaluate) {
       // the leaf's logits arrive: logit and p of its legal actions (illegal entries are not read), and its raw
       const pgx::State ls = leaf.s;
-      float lg[SL], top = -FLT_MAX;
+      float lg[SL], ex[2];
       bool legal[SL];
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        const int act = lane + kSearchBlock * j;
-        legal[j] = act < A && pgx::Has(ls.m, act);
+      tree::ForSlots<G>(lane, [&](int j, int act, bool owned) {
+        legal[j] = owned && pgx::Has(ls.m, act);
         lg[j] = legal[j] ? pgx::GumbelCleanLogit(a.logits[(size_t)row * A + act]) : 0.0f;
-        if (legal[j]) top = lg[j] > top ? lg[j] : top;
-      }
-      top = WaveMaxF(top);
-      float ex[2] = {0.0f, 0.0f};
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        if (legal[j]) ex[j] = pgx::GumbelExp(lg[j] - top);
-      }
-      const float sum = WaveSumF(ex[0] + ex[1]);
-#pragma unroll
-      for (int j = 0; j < SL; ++j) {
-        const int act = lane + kSearchBlock * j;
-        if (act < A) {
-          leaf.logit[act] = lg[j];
-          leaf.p[act] = legal[j] ? pgx::GumbelPrior(ex[j], sum) : 0.0f;
-        }
-      }
+      });
+      const float sum = tree::WaveSoftmax<SL>(lg, legal, ex);
+      tree::ForOwned<G>(lane, [&](int j, int act) {
+        leaf.logit[act] = lg[j];
+        leaf.p[act] = legal[j] ? pgx::GumbelPrior(ex[j], sum) : 0.0f;
+      });
       val0 = (float)pgx::SearchSign<G>(ls) * pgx::GuidedCleanV(a.values[row]);
       if (lane == 0) leaf.raw = val0;
     } else {
       val0 = (float)leaf.term0;
     }
-    const int backed = rec.r.depth;
-    for (int d = 0; d < backed; ++d) {
-      const int p = rec.r.path[d];
-      const int act = p & 255;
-      if ((act & (kSearchBlock - 1)) == lane) {
-        Node& nd = nodes[p >> 8];
-        nd.v[act] += 1;
-        nd.w0[act] += val0;
-      }
-    }
+    tree::Backup(nodes, rec.r.path, rec.r.depth, val0, lane);
     WaveRelease();
     if (a.call >= S) {
       status = pgx::kGuidedIdle;
@@ -1222,9 +917,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, u
       WaveAcquire();
       s = nodes[0].s;
       for (;;) {
-        Node& nd = nodes[node];
         GumbelEdges<G> e;
-        GumbelEval<G>(nd, s, lane, a.c_visit, a.c_scale, e);
+        GumbelEval<G>(nodes[node], s, lane, a.c_visit, a.c_scale, e);
         int act;
         if (node == 0) {
           act = GumbelRootPick<G>(e, rec, lane, a.considered, S, false);
@@ -1232,14 +926,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, u
           float pi[SL];
           GumbelImproved<G>(e, pi);
           pgx::SearchPick mine = pgx::SearchNone();
-#pragma unroll
-          for (int j = 0; j < SL; ++j) {
+          tree::ForSlots<G>(lane, [&](int j, int b, bool) {
             if (e.legal[j]) {
-              mine = pgx::SearchBetter(mine, pgx::SearchPick{pgx::GumbelInteriorScore(pi[j], e.v[j], e.total),
-                                                             lane + kSearchBlock * j, 1});
+              mine = pgx::SearchBetter(mine,
+                                       pgx::SearchPick{pgx::GumbelInteriorScore(pi[j], e.v[j], e.total), b, 1});
             }
-          }
-          act = WaveBest(mine).action;
+          });
+          act = tree::WaveBest(mine).action;
         }
         // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
         if (act < 0 || depth >= pgx::kSearchMaxPath) {
@@ -1248,33 +941,14 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, u
         }
         if (lane == 0) rec.r.path[depth] = node << 8 | act;
         ++depth;
-        const int owner = act & (kSearchBlock - 1), slot = act / kSearchBlock;
-        int c = __shfl(e.child[0], owner, kSearchBlock);
-        if (SL > 1) {
-          const int c1 = __shfl(e.child[SL - 1], owner, kSearchBlock);
-          c = slot == 1 ? c1 : c;
-        }
+        const int c = tree::OwnerChild<SL>(e.child, act);
         if (c < 0) {
           if (count > S) {  // (one node per call: never; the session's memory ends here)
             broken = true;
             break;
           }
-          c = count++;
-          if (lane == owner) nd.child[act] = c;
-          Node& nn = nodes[c];
-          pgx::State s2;
-          const int term0 = pgx::SearchExpand<G>(s, act, s2);
-          if (lane == 0) {
-            nn.s = s2;
-            nn.term0 = term0;
-            nn.raw = pgx::GumbelFreshRaw(s2, term0);
-          }
-#pragma unroll
-          for (int j = 0; j < SL; ++j) {
-            if (lane + kSearchBlock * j < A) pgx::GumbelClearEdge<G>(nn, lane + kSearchBlock * j);
-          }
-          node = c;
-          s = s2;
+          tree::Expand<G>(nodes, node, s, act, count, lane,
+                          [](Node& n, const pgx::State& s2, int term0) { n.raw = pgx::GumbelFreshRaw(s2, term0); });
           break;
         }
         node = c;
@@ -1306,21 +980,14 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelResult(GumbelArgs a) {
   WaveAcquire();
   const bool over = rec.r.over != 0;
   const pgx::State root = n0.s;
-  const float sign = (float)pgx::SearchSign<G>(root);
   GumbelEdges<G> e;
   GumbelEval<G>(n0, root, lane, a.c_visit, a.c_scale, e);
   float pi[SL];
   GumbelImproved<G>(e, pi);
   const int best = GumbelRootPick<G>(e, rec, lane, a.considered, a.simulations, true);
-#pragma unroll
-  for (int j = 0; j < SL; ++j) {
-    const int act = lane + kSearchBlock * j;
-    if (act < A) {
-      a.visits[(size_t)row * A + act] = over ? 0 : e.v[j];
-      a.vals[(size_t)row * A + act] = over ? 0.0f : sign * e.w0[j];
-      a.weights[(size_t)row * A + act] = over ? 0.0f : pi[j];
-    }
-  }
+  // the rows of the guided result with the improved policy as a third column; the action is the root pick's
+  tree::RootResult<G>(n0, root, over, lane, a.visits + (size_t)row * A, a.vals + (size_t)row * A,
+                      [&](int j, int act) { a.weights[(size_t)row * A + act] = over ? 0.0f : pi[j]; });
   if (lane == 0) a.action[row] = over ? -1 : best;
 }
 
@@ -1386,8 +1053,7 @@ class PgxPool : public Pool {
   int SearchActions() const override { return pgx::Dims<G>::A; }
   size_t SearchNodeBytes() const override { return sizeof(pgx::SearchNode<G>); }
   void Search(const int* d_ids, const SearchArgs& a) override {
-    hipLaunchKernelGGL(PgxSearchKernel<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
-                       a, cfg_.env_id_offset, err_dev_);
+    LaunchRoots(PgxSearchKernel<G>, a.k, common_, state_, d_ids, a, cfg_.env_id_offset, err_dev_);
   }
   bool HasGuided() const override { return true; }
   void GuidedShape(int32_t shape[4]) const override {
@@ -1397,70 +1063,43 @@ class PgxPool : public Pool {
   size_t GuidedRootBytes() const override { return sizeof(pgx::GuidedRoot); }
   size_t GuidedWideRootBytes(int width) const override { return pgx::GuidedWideRootBytes(width); }
   size_t GuidedWideLiveOffset() const override { return offsetof(pgx::GuidedWideRoot, live); }
-  void GuidedBeginWide(const int* d_ids, const GuidedArgs& a) override {
-    hipLaunchKernelGGL(PgxGuidedBeginWide<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_,
-                       d_ids, a);
-  }
-  void GuidedAdvanceWide(const GuidedArgs& a) override {
-    if (a.width <= kWideBuckets[0]) {
-      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[0]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                         stream_, a, err_dev_);
-    } else if (a.width <= kWideBuckets[1]) {
-      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[1]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                         stream_, a, err_dev_);
+  // a.width != 0: a wide session; the plain kernels otherwise
+  void GuidedBegin(const int* d_ids, const GuidedArgs& a) override {
+    if (a.width != 0) {
+      LaunchRoots(PgxGuidedBegin<G, true>, a.k, common_, state_, d_ids, a);
     } else {
-      hipLaunchKernelGGL((PgxGuidedAdvanceWide<G, kWideBuckets[2]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                         stream_, a, err_dev_);
+      LaunchRoots(PgxGuidedBegin<G, false>, a.k, common_, state_, d_ids, a);
     }
   }
-  void GuidedBegin(const int* d_ids, const GuidedArgs& a) override {
-    hipLaunchKernelGGL(PgxGuidedBegin<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
-                       a);
-  }
   void GuidedAdvance(const GuidedArgs& a) override {
-    hipLaunchKernelGGL(PgxGuidedAdvance<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a, err_dev_);
+    if (a.width == 0) return LaunchRoots(PgxGuidedAdvance<G>, a.k, a, err_dev_);
+    Bucket<kWideBuckets>(a.width, [&](auto wb) {
+      LaunchRoots(PgxGuidedAdvanceWide<G, decltype(wb)::value>, a.k, a, err_dev_);
+    });
   }
   void GuidedResult(const GuidedArgs& a) override {
     if (a.width != 0) {
-      hipLaunchKernelGGL((PgxGuidedResult<G, true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
-      return;
+      LaunchRoots(PgxGuidedResult<G, true>, a.k, a);
+    } else {
+      LaunchRoots(PgxGuidedResult<G, false>, a.k, a);
     }
-    hipLaunchKernelGGL(PgxGuidedResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
   }
   void GuidedReroot(const GuidedArgs& a) override {
-    if (a.width != 0) {
-      if (a.capacity <= kRerootTables[0]) {
-        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[0], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                           stream_, a);
-      } else if (a.capacity <= kRerootTables[1]) {
-        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[1], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                           stream_, a);
+    Bucket<kRerootTables>(a.capacity, [&](auto cap) {
+      if (a.width != 0) {
+        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, true>, a.k, a);
       } else {
-        hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[2], true>), dim3((unsigned)a.k), dim3(kSearchBlock), 0,
-                           stream_, a);
+        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false>, a.k, a);
       }
-      return;
-    }
-    if (a.capacity <= kRerootTables[0]) {
-      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[0]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
-    } else if (a.capacity <= kRerootTables[1]) {
-      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[1]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
-    } else {
-      hipLaunchKernelGGL((PgxGuidedReroot<G, kRerootTables[2]>), dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
-    }
+    });
   }
   size_t GumbelNodeBytes() const override { return sizeof(pgx::GumbelNode<G>); }
   size_t GumbelRootBytes() const override { return sizeof(pgx::GumbelRoot<G>); }
   void GumbelBegin(const int* d_ids, const GumbelArgs& a) override {
-    hipLaunchKernelGGL(PgxGumbelBegin<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, common_, state_, d_ids,
-                       a);
+    LaunchRoots(PgxGumbelBegin<G>, a.k, common_, state_, d_ids, a);
   }
-  void GumbelAdvance(const GumbelArgs& a) override {
-    hipLaunchKernelGGL(PgxGumbelAdvance<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a, err_dev_);
-  }
-  void GumbelResult(const GumbelArgs& a) override {
-    hipLaunchKernelGGL(PgxGumbelResult<G>, dim3((unsigned)a.k), dim3(kSearchBlock), 0, stream_, a);
-  }
+  void GumbelAdvance(const GumbelArgs& a) override { LaunchRoots(PgxGumbelAdvance<G>, a.k, a, err_dev_); }
+  void GumbelResult(const GumbelArgs& a) override { LaunchRoots(PgxGumbelResult<G>, a.k, a); }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
     if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";
@@ -1477,6 +1116,24 @@ class PgxPool : public Pool {
   }
 
  private:
+  // a tree-search kernel: one block of one wave per root
+  template <class... P, class... Q>
+  void LaunchRoots(void (*kernel)(P...), int k, const Q&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)k), dim3(kSearchBlock), 0, stream_, args...);
+  }
+  // f(std::integral_constant<int, b>) for the first entry b >= value of an ascending table (the last one otherwise):
+  // the static LDS arrays of PgxGuidedReroot and PgxGuidedAdvanceWide come in such sizes
+  template <const int (&Table)[3], int I = 0, class F>
+  static void Bucket(int value, F f) {
+    if constexpr (I == 2) {
+      f(std::integral_constant<int, Table[2]>{});
+    } else if (value <= Table[I]) {
+      f(std::integral_constant<int, Table[I]>{});
+    } else {
+      Bucket<Table, I + 1>(value, f);
+    }
+  }
+
   pgx::State* state_{nullptr};
 };
 

@@ -1,12 +1,14 @@
-"""Several leaves per launch of the PGX guided search on the MI355X: PgxGuidedBeginWide / PgxGuidedAdvanceWide and the
-wide variants of result and reroot against the host harness of the same header
+"""Several leaves per launch of the PGX guided search on the MI355X: PgxGuidedAdvanceWide and the wide variants of
+begin, result and reroot against the host harness of the same header
 (tests/cpu_harness/pgx_guided_wide_host.cpp) fed the pool's own hidden words and the same evaluator's numbers, for all
 four games -- leaves after every call, results after every call; width 1 against the plain kernels; id order, repeated
 ids, the whole pool, a sharded pool; the pool stepped between advances; the device form with a torch model; reroot
 through both forms; the refusals through the wrapper and the raw C ABI; and the session's life cycle.
 
 The shape: a pool of 70 envs a few plies into their games with one env marked over, 11 ids out of order with one of
-them twice (11 blocks of one wave), S = 24 simulations (Hex: S = 12), width 4 -- and width 32 once, on TicTacToe."""
+them twice (11 blocks of one wave), S = 24 simulations (Hex: S = 12), width 4 -- width 16 on TicTacToe and Hex and
+width 32 once, on TicTacToe (the kernel's three path buckets) -- and 3 roots at the capacities of the reroot kernel's two
+larger tables."""
 import ctypes
 import os
 import subprocess
@@ -208,6 +210,45 @@ def test_kernels_equal_the_host_harness(ctx, harness):
 def test_width_32_on_tictactoe(harness):
     rec = check_against_harness(get_ctx("TicTacToe"), harness, 32)
     assert max((lv[2] != 2).sum(1).max() for lv in rec["leaves"]) > W
+
+
+@pytest.mark.parametrize("fam", ["TicTacToe", "Hex"])
+def test_width_16(harness, fam):
+    """The middle path bucket of PgxGuidedAdvanceWide (5 .. 16 slots), with one and with two action slots per lane."""
+    check_against_harness(get_ctx(fam), harness, 16)
+
+
+@pytest.mark.parametrize("fam,nodes", [("ConnectFour", 513), ("ConnectFour", 2049), ("ConnectFour", 8192),
+                                       ("Hex", 513), ("Hex", 2049)])
+def test_the_larger_reroot_tables_equal_the_harness(harness, fam, nodes):
+    """The wide PgxGuidedReroot with its 2048- and 8192-entry tables (capacities above 512 and above 2048): 3 roots of
+    width 4, a round of 8 simulations, a reroot by the chosen moves and a second round -- leaves after every call,
+    results after both rounds and after the reroot, bit for bit."""
+    ctx = get_ctx(fam)
+    pool, S, ids = ctx.pool, 8, IDS[:3]
+    assert OVER not in ids
+    host = Host(harness, fam, ctx.st[ids], S, nodes, W, C_PUCT)
+    leaves = pool.guided_begin(ids, S, C_PUCT, nodes, W)
+    same(leaves, host.leaves(), (fam, "begin"))
+    for move in range(2):
+        calls = 0
+        while (leaves[2] != 2).any():
+            feed = evaluator(leaves[0], leaves[1])
+            leaves = pool.guided_advance(*feed)
+            same(leaves, host.advance(*feed), (fam, move, calls))
+            calls += 1
+            assert calls <= S + 1
+        res = pool.guided_result()
+        same(res, host.result()[0], (fam, move))
+        if move == 0:
+            sent = np.where(res[2] < 0, 0, res[2]).astype(np.int32)
+            assert (res[0][np.arange(3), sent] >= 1).all()  # the most visited move has a child: the table path
+            leaves = pool.guided_reroot(sent, S)
+            same(leaves, host.reroot(sent, S), (fam, "reroot"))
+            same(pool.guided_result(), host.result()[0], (fam, "kept"))
+    pool.guided_end()
+    host.close()
+    assert np.array_equal(pool.get_state(), ctx.st) and np.array_equal(pool.snapshot(), ctx.S)
 
 
 def test_a_roomy_session_and_reroot_equal_the_harness(ctx, harness):

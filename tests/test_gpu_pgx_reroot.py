@@ -7,7 +7,8 @@ the refusals and the session's life cycle.
 
 The shape: a pool of 70 envs a few plies into their games with one env marked over, 11 ids out of order with one of
 them twice (11 blocks of one wave), S = 24 simulations (Hex: S = 12), three moves, at nodes = 2 S + 1 and at
-nodes = S + 1, where the rerooted trees run out of memory."""
+nodes = S + 1, where the rerooted trees run out of memory; and 3 roots at the capacities of the kernel's two larger
+tables (513, 2049, 8192 nodes)."""
 import ctypes
 import os
 import subprocess
@@ -298,6 +299,36 @@ def test_kernels_equal_the_host_harness_and_the_stepped_pool(ctx, harness, roomy
         assert notes.get("untried") and notes.get("last") and notes.get("high"), notes
     if not roomy:
         assert starved, "the capacity did not bind"  # memory used up: a normal end, and still the harness
+
+
+@pytest.mark.parametrize("fam,nodes", [("ConnectFour", 513), ("ConnectFour", 2049), ("ConnectFour", 8192),
+                                       ("Hex", 513), ("Hex", 2049)])
+def test_the_larger_reroot_tables_equal_the_harness(harness, fam, nodes):
+    """PgxGuidedReroot with its 2048- and 8192-entry tables (capacities above 512 and above 2048), one and two action
+    slots per lane: 3 roots, a round of 8 simulations, a reroot by the chosen moves and a second round -- leaves after
+    every call, results after both rounds and after the reroot, bit for bit."""
+    ctx = get_ctx(fam)
+    pool, S, ids = ctx.pool, 8, IDS[:3]
+    assert OVER not in ids
+    host = Host(harness, fam, ctx.st[ids], S, nodes, C_PUCT)
+    leaves = pool.guided_begin(ids, S, C_PUCT, nodes)
+    same(leaves, host.leaves(), (fam, "begin"))
+    for move in range(2):
+        for t in range(S + 1):
+            feed = stand_in(leaves[0], leaves[1])
+            leaves = pool.guided_advance(*feed)
+            same(leaves, host.advance(*feed), (fam, move, t))
+        res = pool.guided_result()
+        same(res, host.result()[0], (fam, move))
+        if move == 0:
+            sent = np.where(res[2] < 0, 0, res[2]).astype(np.int32)
+            assert (res[0][np.arange(3), sent] >= 1).all()  # the most visited move has a child: the table path
+            leaves = pool.guided_reroot(sent, S)
+            same(leaves, host.reroot(sent, S), (fam, "reroot"))
+            same(pool.guided_result(), host.result()[0], (fam, "kept"))
+    pool.guided_end()
+    host.close()
+    assert np.array_equal(pool.get_state(), ctx.st) and np.array_equal(pool.snapshot(), ctx.S)
 
 
 @pytest.mark.parametrize("fam", GAMES)

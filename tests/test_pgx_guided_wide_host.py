@@ -375,6 +375,39 @@ def test_three_moves_of_a_wide_session_with_reroot(libs, tid):
     assert total >= 2
 
 
+@pytest.mark.parametrize("tid", ["TicTacToe-v1", "Hex-v1"])
+def test_width_16(libs, tid):
+    """The width of the kernel's middle path bucket (5 .. 16 slots)."""
+    S = sims(tid)
+    game_, pos = start(libs, tid)
+    pair = Pair(libs, game_, pos, S, 1.25, 16)
+    (visits, _, action, nodes, done), seen = pair.round()
+    pair.close()
+    assert visits.sum() == S == done[0] and nodes[0] <= S + 1 and pos.mask[action[0]]
+    assert seen[0] == [0] + [2] * 15 and pair.advances[0] < S + 1
+    if pos.mask.sum() >= 16:
+        assert max(sum(st != 2 for st in row) for row in seen) > 4  # more leaves in a launch than the first bucket holds
+
+
+@pytest.mark.parametrize("tid,nodes", [("ConnectFour-v1", 513), ("ConnectFour-v1", 2049), ("ConnectFour-v1", 8192),
+                                       ("Hex-v1", 513), ("Hex-v1", 2049)])
+def test_wide_reroot_at_capacities_above_512_and_2048_nodes(libs, tid, nodes):
+    """The capacities of the reroot kernel's two larger tables: a round of 8 simulations, a reroot by the chosen move,
+    a second round."""
+    S, W = 8, 4
+    game_, pos = start(libs, tid)
+    pair = Pair(libs, game_, pos, S, 1.25, W, nodes=nodes)
+    (visits, _, action, _, done), _ = pair.round()
+    a = int(action[0])
+    assert done[0] == S and visits[0][a] >= 1  # the most visited move has a child: the table path runs
+    pair.reroot(a)
+    if pair.host.status[0][0] == 0:  # (else the move ended the game)
+        assert pair.kept == visits[0][a] - 1 and 1 <= pair.host.result()[3][0] <= visits[0][a]
+        (after, _, _, used, done), _ = pair.round()
+        assert after.sum() == pair.kept + S and done[0] == S and used[0] <= nodes
+    pair.close()
+
+
 def test_reroot_with_pending_slots(libs):
     """The host forms refuse a reroot while a slot is pending; the device form cannot look: the pending slots are dropped,
     nothing of them is backed up, and their nodes stay unevaluated."""

@@ -279,6 +279,27 @@ def test_capacity_ends_a_root_without_an_error(libs, tid):
     pair.close()
 
 
+@pytest.mark.parametrize("tid,nodes", [("ConnectFour-v1", 513), ("ConnectFour-v1", 2049), ("ConnectFour-v1", 8192),
+                                       ("Hex-v1", 513), ("Hex-v1", 2049)])
+def test_capacities_above_512_and_2048_nodes(libs, tid, nodes):
+    """The capacities at which the kernel's mark / rank table is the 2048- and the 8192-entry one (513, 2049; 8192 is
+    the limit): a round of 8 simulations, a reroot by the chosen move, a second round -- harness against restatement
+    after every call, as everywhere in Pair."""
+    S = 8
+    game_, pos = start(libs, tid, True)
+    pair = Pair(libs, game_, pos, S, 1.25, nodes)
+    (visits, _, action, _), _ = pair.round()
+    a = int(action[0])
+    assert visits[0][a] >= 1  # the most visited of S >= 1 visits: it has a child, so the table path runs
+    pair.reroot(a)
+    kept = pair.host.result()
+    if pair.host.status[0] == 0:  # (else the move ended the game)
+        assert kept[0].sum() == visits[0][a] - 1 and 1 <= kept[3][0] <= visits[0][a]
+        (after, _, _, used), _ = pair.round()
+        assert after.sum() == kept[0].sum() + S and used[0] <= kept[3][0] + S
+    pair.close()
+
+
 @pytest.mark.parametrize("played", ["swap", "cell"])
 def test_hex_second_slots_and_the_swap(libs, played):
     """Case 6: Hex one stone in, flat priors, S > 121, so every root move has a child: play the swap (action 121) or a
