@@ -424,13 +424,15 @@ class _ShardedPools:
         return self.pools[0].gumbel_actions()
 
     def gumbel_begin(self, gumbel: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
-                     c_visit: float = 50.0, c_scale: float = 0.1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     c_visit: float = 50.0, c_scale: float = 0.1,
+                     batch: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A Gumbel session in every shard that owns listed envs, all shards at once; row i of `gumbel` goes with
         env_ids[i].  The search depends on the positions and the caller's numbers only, so the rows are those of the
-        unsharded pool."""
+        unsharded pool.  `batch`: a batch session in every shard (`DevicePool.gumbel_begin`)."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
         ids = native.check_gumbel(env_ids, simulations, max_considered, c_visit, c_scale)
+        batch = native.check_gumbel_batch(batch)
         self.gumbel_actions()
         h, w, c, a = self.guided_shape()
         gumbel = native.check_gumbel_noise(gumbel, len(ids), a)
@@ -440,25 +442,28 @@ class _ShardedPools:
             raise ValueError(f"env_id {int(bad[0])} out of range")
         parts = [np.flatnonzero(shard == s) for s in range(len(self.pools))]
         k = len(ids)
-        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
-                  np.empty(k, dtype=np.uint8))
+        leaves = self._guided_empty(k, batch)
 
         def begin(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.gumbel_begin(gumbel[idx], ids[idx], simulations, max_considered, c_visit,
-                                                      c_scale)):
+                                                      c_scale, batch or None)):
                 o[idx] = part
 
         self._each(begin, parts)
         self._guided = (k, a, parts)
         self._guided_nodes = None  # (no reroot of a Gumbel session)
+        self._gumbel_batch = batch
         return leaves
 
     def gumbel_advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         k, a, parts = self._guided_session("gumbel_advance")
-        logits, values = native.check_gumbel_rows(logits, values, k, a)
-        h, w, c, _ = self.guided_shape()
-        leaves = (np.empty((k, h, w, c), dtype=np.bool_), np.empty((k, a), dtype=np.bool_),
-                  np.empty(k, dtype=np.uint8))
+        batch = getattr(self, "_gumbel_batch", 0)
+        if batch:  # the rows of root i are rows i B .. i B + B - 1: split by root
+            logits, values = native.check_gumbel_batch_rows(logits, values, k, batch, a)
+            logits, values = logits.reshape(k, batch, a), values.reshape(k, batch)
+        else:
+            logits, values = native.check_gumbel_rows(logits, values, k, a)
+        leaves = self._guided_empty(k, batch)
 
         def advance(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.gumbel_advance(logits[idx], values[idx])):

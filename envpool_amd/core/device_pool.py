@@ -662,40 +662,59 @@ class DevicePool:
         return int(out[3])
 
     def gumbel_begin(self, gumbel: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
-                     c_visit: float = 50.0, c_scale: float = 0.1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     c_visit: float = 50.0, c_scale: float = 0.1,
+                     batch: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Opens the pool's guided-search session with the Gumbel policy (include/envpool_amd.h: epa_gumbel_begin has
         the contract), replacing any earlier session of either policy: Gumbel top-`max_considered` sampling with
         sequential halving at the root, the caller's logits and values at every new leaf.  `gumbel` float32 [k, A] is
         the caller's Gumbel(0, 1) noise per root action (zeros: the noise-free evaluation mode); the library draws no
-        random numbers.  Returns the first leaves as `guided_begin` does.  Nothing of the pool changes."""
+        random numbers.  Returns the first leaves as `guided_begin` does.  Nothing of the pool changes.  `batch` = B,
+        1 .. 32, opens a BATCH session (epa_gumbel_begin_batch): B slots per root, and every advance makes up to B
+        simulations of the root's current level of sequential halving, chosen together from one scoring of the root;
+        every leaf array and the rows of `gumbel_advance` then carry a slot axis ([k, B, ...]), a slot of status 2
+        has nothing pending, and the round is complete when all statuses are 2.  None: a plain session."""
         ids = native.check_gumbel(self._ids(env_ids), simulations, max_considered, c_visit, c_scale)
+        batch = native.check_gumbel_batch(batch)
         a = self.gumbel_actions()
         gumbel = native.check_gumbel_noise(gumbel, len(ids), a)
-        obs, mask, status = self._guided_leaves(len(ids))
-        native.check(self._lib.epa_gumbel_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                min(int(max_considered), a), float(c_visit), float(c_scale),
-                                                gumbel.ctypes.data, obs.ctypes.data, mask.ctypes.data,
-                                                status.ctypes.data))
-        self._guided_k, self._guided_policy = len(ids), "gumbel"
+        obs, mask, status = self._guided_leaves(len(ids), batch)
+        if batch:
+            native.check(self._lib.epa_gumbel_begin_batch(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                          min(int(max_considered), a), batch, float(c_visit),
+                                                          float(c_scale), gumbel.ctypes.data, obs.ctypes.data,
+                                                          mask.ctypes.data, status.ctypes.data))
+        else:
+            native.check(self._lib.epa_gumbel_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                    min(int(max_considered), a), float(c_visit), float(c_scale),
+                                                    gumbel.ctypes.data, obs.ctypes.data, mask.ctypes.data,
+                                                    status.ctypes.data))
+        self._guided_k, self._guided_policy, self._gumbel_batch = len(ids), "gumbel", batch
         return obs, mask, status
 
     def gumbel_advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """One simulation of every root of the Gumbel session, one launch: `logits` float32 [k, A] (any sign) and
         `values` float32 [k] (for the seat that moves at the leaf) answer the leaves handed out last; returns the next
         leaves.  Call it simulations + 1 times.  Rows that are not finite, logits above 1e30 in magnitude and values
-        outside -1 .. 1 raise ValueError before any launch."""
+        outside -1 .. 1 raise ValueError before any launch.  A batch session takes [k, B, A] and [k, B] (or the
+        flattened rows), answers every pending slot and returns leaves with the slot axis; call it until every
+        status is 2."""
         k = self._guided_open("gumbel_advance", "gumbel")
-        logits, values = native.check_gumbel_rows(logits, values, k, self.guided_shape()[3])
-        obs, mask, status = self._guided_leaves(k)
-        native.check(self._lib.epa_gumbel_advance(self._h, logits.ctypes.data, values.ctypes.data, k, obs.ctypes.data,
-                                                  mask.ctypes.data, status.ctypes.data))
+        batch = getattr(self, "_gumbel_batch", 0)
+        if batch:  # a batch session: rows [k, B, ..] or flattened, the leaves with the slot axis
+            logits, values = native.check_gumbel_batch_rows(logits, values, k, batch, self.guided_shape()[3])
+        else:
+            logits, values = native.check_gumbel_rows(logits, values, k, self.guided_shape()[3])
+        obs, mask, status = self._guided_leaves(k, batch)
+        native.check(self._lib.epa_gumbel_advance(self._h, logits.ctypes.data, values.ctypes.data, len(values),
+                                                  obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
         return obs, mask, status
 
     def gumbel_result(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """(visits int32 [k, A], values float32 [k, A], action int32 [k]: the recommended move -- the best of the most
         visited root actions by gumbel + logit + sigma(q); -1 for an env that was over --, weights float32 [k, A]: the
         improved policy softmax(logits + sigma(completed q)) of the root, the training target).  Valid any time after
-        gumbel_begin, complete after simulations + 1 advances."""
+        gumbel_begin, complete after simulations + 1 advances (a batch session: when every status is 2).  One row per
+        root, whatever the batch."""
         k = self._guided_open("gumbel_result", "gumbel")
         a = self.guided_shape()[3]
         visits = np.empty((k, a), dtype=np.int32)
@@ -708,17 +727,26 @@ class DevicePool:
 
     def gumbel_begin_device(self, d_gumbel: int, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None,
                             simulations: int = 32, max_considered: int = 16, c_visit: float = 50.0,
-                            c_scale: float = 0.1) -> int:
+                            c_scale: float = 0.1, batch: Any = None) -> int:
         """`gumbel_begin` on device memory: the noise is read at the raw address `d_gumbel` (float32 [k, A], 4-byte
         aligned; the kernel takes entries that are not finite as 0) and the leaves are written at `d_obs`, `d_mask`
-        and `d_status`: only enqueued on the pool's stream.  Returns k."""
+        and `d_status`: only enqueued on the pool's stream.  Returns k.  With `batch` = B the leaf arrays have k B
+        rows, and so have those of `gumbel_advance_device` (its `k` is k B); the noise keeps k rows."""
         ids = native.check_gumbel(self._ids(env_ids), simulations, max_considered, c_visit, c_scale)
+        batch = native.check_gumbel_batch(batch)
         a = self.gumbel_actions()
-        native.check(self._lib.epa_gumbel_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                       min(int(max_considered), a), float(c_visit), float(c_scale),
-                                                       ctypes.c_void_p(d_gumbel), ctypes.c_void_p(d_obs),
-                                                       ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
-        self._guided_k, self._guided_policy = len(ids), "gumbel"
+        if batch:
+            native.check(self._lib.epa_gumbel_begin_batch_device(
+                self._h, ids.ctypes.data, len(ids), int(simulations), min(int(max_considered), a), batch,
+                float(c_visit), float(c_scale), ctypes.c_void_p(d_gumbel), ctypes.c_void_p(d_obs),
+                ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        else:
+            native.check(self._lib.epa_gumbel_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
+                                                           min(int(max_considered), a), float(c_visit),
+                                                           float(c_scale), ctypes.c_void_p(d_gumbel),
+                                                           ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                           ctypes.c_void_p(d_status)))
+        self._guided_k, self._guided_policy, self._gumbel_batch = len(ids), "gumbel", batch
         return len(ids)
 
     def gumbel_advance_device(self, d_logits: int, d_values: int, k: int, d_obs: int, d_mask: int,

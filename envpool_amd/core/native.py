@@ -30,6 +30,7 @@ PLAYOUT_MAX_REPEATS = 4096
 SEARCH_MAX_SIMULATIONS = 4096
 GUIDED_MAX_NODES = 8192  # EPA_GUIDED_MAX_NODES: the largest node capacity of a guided-search root
 GUIDED_MAX_WIDTH = 32    # EPA_GUIDED_MAX_WIDTH: the most slots (leaves per launch) of a wide guided-search root
+GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per launch) of a batch Gumbel root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
@@ -144,6 +145,9 @@ def lib() -> ctypes.CDLL:
         "epa_guided_begin_wide_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_begin_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
+        "epa_gumbel_begin_batch": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
+        "epa_gumbel_begin_batch_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp,
+                                                vp]),
         "epa_gumbel_advance": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "epa_gumbel_advance_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "epa_gumbel_result": (i32, [vp, vp, vp, vp, vp]),
@@ -187,7 +191,7 @@ EXPORTED_SYMBOLS = [
     "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
     "epa_guided_begin_wide", "epa_guided_begin_wide_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
-    "epa_gumbel_result", "epa_gumbel_result_device",
+    "epa_gumbel_result", "epa_gumbel_result_device", "epa_gumbel_begin_batch", "epa_gumbel_begin_batch_device",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -400,6 +404,31 @@ def check_gumbel_rows(logits: Any, values: Any, k: int, actions: int) -> tuple[n
     if not ((values >= -1) & (values <= 1)).all():
         raise ValueError("gumbel_advance: values must be in -1 .. 1")
     return logits, values
+
+
+def check_gumbel_batch(batch: Any) -> int:
+    """The batch (slots per root) of a gumbel_begin call after its check: ValueError outside 1 .. 32.  None: 0, a plain
+    session."""
+    if batch is None:
+        return 0
+    if isinstance(batch, bool) or int(batch) != batch or not 1 <= int(batch) <= GUMBEL_MAX_BATCH:
+        raise ValueError(f"gumbel_begin: batch = {batch} must be 1 .. {GUMBEL_MAX_BATCH}")
+    return int(batch)
+
+
+def check_gumbel_batch_rows(logits: Any, values: Any, k: int, batch: int,
+                            actions: int) -> tuple[np.ndarray, np.ndarray]:
+    """The rows of a host-form gumbel_advance of a batch session, given with the slot axis ([k, B, A] and [k, B]) or
+    flattened ([k B, A] and [k B]), as contiguous float32 arrays [k B, A] and [k B] after the checks of
+    check_gumbel_rows."""
+    with np.errstate(over="ignore"):
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+    if logits.shape not in ((k, batch, actions), (k * batch, actions)):
+        raise ValueError(f"gumbel_advance: logits of shape {logits.shape} for a session of [{k}, {batch}, {actions}]")
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    if values.shape not in ((k, batch), (k * batch,)):
+        raise ValueError(f"gumbel_advance: values of shape {values.shape} for a session of [{k}, {batch}]")
+    return check_gumbel_rows(logits.reshape(k * batch, actions), values.reshape(-1), k * batch, actions)
 
 
 def device_count() -> int:

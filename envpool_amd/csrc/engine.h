@@ -195,6 +195,8 @@ struct GumbelArgs {
   int considered;           // m: the most root actions considered
   float c_visit;
   float c_scale;
+  int batch;                // 0: a plain session (the plain kernels ignore it); 1 .. EPA_GUMBEL_MAX_BATCH: a batch one,
+                            // whose logits, values, obs, mask and status below have k * batch rows
   void* roots;              // [k], 16-byte aligned
   void* nodes;              // [k][simulations + 1], 16-byte aligned
   const float* gumbel;      // begin: [k][A]
@@ -450,8 +452,14 @@ class Pool {
   virtual void GumbelBegin(const int* d_ids, const GumbelArgs& a);
   virtual void GumbelAdvance(const GumbelArgs& a);
   virtual void GumbelResult(const GumbelArgs& a);
+  // batch sessions (pgx_gumbel.hip.h "A level per launch"): a.batch slots per root; the three hooks above serve them
+  // too (a.batch != 0: the family chooses its kernels)
+  virtual size_t GumbelBatchRootBytes(int batch) const { (void)batch; return 0; }  // a multiple of 16
   void GumbelBeginCall(const int32_t* ids, int k, int simulations, int considered, float c_visit, float c_scale,
                        const void* gumbel, void* obs, void* mask, void* status, bool device);
+  // ... with `batch` slots per root (0: a plain session): the leaf arrays have k * batch rows from then on
+  void GumbelBeginBatchCall(const int32_t* ids, int k, int simulations, int considered, int batch, float c_visit,
+                            float c_scale, const void* gumbel, void* obs, void* mask, void* status, bool device);
   void GumbelAdvanceCall(const void* logits, const void* values, int k, void* obs, void* mask, void* status,
                          bool device);
   void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
@@ -653,6 +661,7 @@ class Pool {
     bool gumbel{false};     // the session's policy: PUCT or Gumbel
     int k{0}, simulations{0}, calls{0};
     int width{0};           // slots per root of a wide PUCT session; 0: a plain session
+    int batch{0};           // slots per root of a batch Gumbel session; 0: a plain session
     int capacity{0};        // nodes per root (PUCT: simulations + 1 .. EPA_GUIDED_MAX_NODES; Gumbel: simulations + 1)
     float c_puct{0.0f};
     int considered{0};      // Gumbel: m, c_visit, c_scale

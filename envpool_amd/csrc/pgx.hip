@@ -825,8 +825,8 @@ __device__ __forceinline__ void GumbelImproved(const GumbelEdges<G>& e, float* p
 // the root pick: `final` picks among the most visited actions (the result), otherwise among those of the considered
 // visit count of simulation N(root); -1 without such an action
 template <int G>
-__device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx::GumbelRoot<G>& rec, int lane,
-                                              int considered, int simulations, bool final) {
+__device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const float* gumbel, int lane, int considered,
+                                              int simulations, bool final) {
   constexpr int SL = pgx::SearchSlotsPerLane<G>();
   int legal = 0;
   float top = -FLT_MAX;
@@ -845,13 +845,20 @@ __device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx
   tree::ForOwned<G>(lane, [&](int j, int act) {
     if (e.legal[j] && e.v[j] == cv) {
       mine = pgx::SearchBetter(
-          mine, pgx::SearchPick{pgx::GumbelRootScore(rec.gumbel[act], e.logit[j], top, e.sigma[j]), act, 1});
+          mine, pgx::SearchPick{pgx::GumbelRootScore(gumbel[act], e.logit[j], top, e.sigma[j]), act, 1});
     }
   });
   return tree::WaveBest(mine).action;
 }
-
 template <int G>
+__device__ __forceinline__ int GumbelRootPick(const GumbelEdges<G>& e, const pgx::GumbelRoot<G>& rec, int lane,
+                                              int considered, int simulations, bool final) {
+  return GumbelRootPick<G>(e, rec.gumbel, lane, considered, simulations, final);
+}
+
+// BATCH: a batch session (below): the record is pgx::GumbelBatchRoot with its slots, the root goes to slot 0 (leaf row
+// i * B), the other slots are idle and their rows zeros.
+template <int G, bool BATCH>
 __global__ __launch_bounds__(kSearchBlock) void PgxGumbelBegin(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, GumbelArgs a) {
   constexpr int A = pgx::Dims<G>::A;
@@ -861,16 +868,18 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelBegin(CommonDev cm, con
   const bool over = cm.done[e] != 0;  // (an env before its first reset is)
   const pgx::State root = st[e];
   Node& n0 = static_cast<Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
-  pgx::GumbelRoot<G>& rec = static_cast<pgx::GumbelRoot<G>*>(a.roots)[row];
+  const tree::GumbelRec<G, BATCH> rec(a.roots, row, a.batch);
   tree::MakeNode<G>(n0, root, 0, lane, [&](Node& n) {
     n.raw = 0.0f;
-    pgx::GuidedClearRoot(rec.r, over);
+    rec.Clear(over);
   });
   tree::ForOwned<G>(lane, [&](int, int act) {
-    rec.gumbel[act] = pgx::GumbelCleanNoise(a.gumbel[(size_t)row * A + act]);
+    rec.gumbel()[act] = pgx::GumbelCleanNoise(a.gumbel[(size_t)row * A + act]);
   });
   WaveRelease();
-  GuidedEmitLeaf<G>(a, row, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+  const int B = BATCH ? a.batch : 1;
+  GuidedEmitLeaf<G>(a, row * B, lane, over ? pgx::kGuidedIdle : pgx::kGuidedEvaluate, root);
+  if (BATCH) GuidedEmitIdle<G>(a, row * B + 1, B - 1, lane);
 }
 
 template <int G>
@@ -970,21 +979,194 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvance(GumbelArgs a, u
   GuidedEmitLeaf<G>(a, row, lane, status, s);
 }
 
+// A level per launch (pgx_gumbel.hip.h "A level per launch"): PgxGumbelAdvance for a session whose roots have B slots
+// (PgxGumbelBegin<G, true> begins it).  One wave per root, one block per wave, the lane ownership and the fences of
+// PgxGumbelAdvance.
+//   phase A    the slots in order: the owner lanes store the slot's logits row (row i * B + j) with its p, lane 0 its
+//              raw, and the owner lanes add along its path, read from the record (one address a load: wave-uniform)
+//   phase B    the root is evaluated once and each lane keeps the root scores of its actions in registers.  The b picks
+//              are b arg-max butterflies; each masks the winner out at its owner lane.  Nothing is sorted in memory.
+//              The descents run one after the other.  They go through different root actions, so none loads what
+//              another stored: there is no path table in LDS, no collision test, no barrier between two descents.
+//   leaves     slot j's State is in registers when its descent ends: its rows are emitted then; the idle slots' rows
+//              are zeroed in one sweep at the end.
+// GumbelAnswer and GumbelInteriorPick are what PgxGumbelAdvance does in line; that kernel keeps its text, so that its
+// code object stays what it was.
+
+// The answer to a pending leaf (status 0 or 1): for status 0 its owner lanes store the caller's logits row `lrow` and
+// the p they give, lane 0 the leaf's raw; for status 1 the finished game's term0 counts.  Returns val0.
 template <int G>
+__device__ __forceinline__ float GumbelAnswer(const GumbelArgs& a, size_t lrow, pgx::GumbelNode<G>& leaf, int status,
+                                              int lane) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  if (status != pgx::kGuidedEvaluate) return (float)leaf.term0;
+  const pgx::State ls = leaf.s;
+  float lg[SL], ex[2];
+  bool legal[SL];
+  tree::ForSlots<G>(lane, [&](int j, int act, bool owned) {
+    legal[j] = owned && pgx::Has(ls.m, act);
+    lg[j] = legal[j] ? pgx::GumbelCleanLogit(a.logits[lrow * A + act]) : 0.0f;
+  });
+  const float sum = tree::WaveSoftmax<SL>(lg, legal, ex);
+  tree::ForOwned<G>(lane, [&](int j, int act) {
+    leaf.logit[act] = lg[j];
+    leaf.p[act] = legal[j] ? pgx::GumbelPrior(ex[j], sum) : 0.0f;
+  });
+  const float val0 = (float)pgx::SearchSign<G>(ls) * pgx::GuidedCleanV(a.values[lrow]);
+  if (lane == 0) leaf.raw = val0;
+  return val0;
+}
+
+// the interior pick of an evaluated node; -1 without a legal action
+template <int G>
+__device__ __forceinline__ int GumbelInteriorPick(const GumbelEdges<G>& e, int lane) {
+  float pi[pgx::SearchSlotsPerLane<G>()];
+  GumbelImproved<G>(e, pi);
+  pgx::SearchPick mine = pgx::SearchNone();
+  tree::ForSlots<G>(lane, [&](int j, int b, bool) {
+    if (e.legal[j]) {
+      mine = pgx::SearchBetter(mine, pgx::SearchPick{pgx::GumbelInteriorScore(pi[j], e.v[j], e.total), b, 1});
+    }
+  });
+  return tree::WaveBest(mine).action;
+}
+
+static_assert(pgx::kGumbelMaxBatch == EPA_GUMBEL_MAX_BATCH, "the C ABI states the header's limit");
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxGumbelAdvanceBatch(GumbelArgs a, unsigned* err) {
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GumbelNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int S = a.simulations, B = std::min(a.batch, pgx::kGumbelMaxBatch);
+  pgx::GumbelBatchRoot<G>& rec = pgx::GumbelBatchRootAt<G>(a.roots, row, a.batch);
+  pgx::GuidedWideSlot* slots = pgx::GumbelBatchSlots(rec);
+  Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)(S + 1);
+  WaveAcquire();
+  // A. the answers
+  for (int j = 0; j < B; ++j) {
+    const int status = slots[j].status;
+    if (status == pgx::kGuidedIdle) continue;
+    const float val0 = GumbelAnswer<G>(a, (size_t)row * B + j, nodes[slots[j].pending], status, lane);
+    tree::Backup(nodes, slots[j].path, std::min(slots[j].depth, pgx::kSearchMaxPath), val0, lane);
+  }
+  WaveRelease();
+  // B. the descents of what is left of the level
+  int count = rec.count, j = 0;
+  bool broken = false;
+  if (rec.over == 0 && rec.broken == 0) {
+    WaveAcquire();
+    const pgx::State root = nodes[0].s;
+    GumbelEdges<G> e0;
+    GumbelEval<G>(nodes[0], root, lane, a.c_visit, a.c_scale, e0);
+    if (e0.total < S) {
+      int legal = 0;
+      float top = -FLT_MAX;
+#pragma unroll
+      for (int q = 0; q < SL; ++q) {
+        if (e0.legal[q]) {
+          ++legal;
+          top = e0.logit[q] > top ? e0.logit[q] : top;
+        }
+      }
+      legal = tree::WaveSum(legal);
+      top = tree::WaveMax(top);
+      const int m_eff = std::min(a.considered, legal);
+      const int cv = pgx::GumbelConsideredVisit(m_eff, S, e0.total);
+      const int b = std::min(B, pgx::GumbelLevelLeft(m_eff, S, e0.total));
+      float score[SL];
+      bool cand[SL];
+      tree::ForSlots<G>(lane, [&](int q, int act, bool) {
+        cand[q] = e0.legal[q] && e0.v[q] == cv;
+        score[q] = cand[q] ? pgx::GumbelRootScore(rec.gumbel[act], e0.logit[q], top, e0.sigma[q]) : 0.0f;
+      });
+      for (; j < b; ++j) {
+        pgx::SearchPick mine = pgx::SearchNone();
+        tree::ForSlots<G>(lane, [&](int q, int act, bool) {
+          if (cand[q]) mine = pgx::SearchBetter(mine, pgx::SearchPick{score[q], act, 1});
+        });
+        int act = tree::WaveBest(mine).action;
+        if (act < 0) {  // fewer than b actions of this visit count; none at all is no position of the game
+          broken = j == 0;
+          break;
+        }
+        tree::ForSlots<G>(lane, [&](int q, int mine_act, bool) {
+          if (mine_act == act) cand[q] = false;
+        });
+        int node = 0, depth = 0;
+        int c = tree::OwnerChild<SL>(e0.child, act);
+        pgx::State s = root;
+        for (;;) {
+          if (lane == 0) slots[j].path[depth] = node << 8 | act;
+          ++depth;
+          if (c < 0) {
+            if (count > S) {  // (one node per simulation: never; the session's memory ends here)
+              broken = true;
+              break;
+            }
+            tree::Expand<G>(nodes, node, s, act, count, lane,
+                            [](Node& n, const pgx::State& s2, int term0) { n.raw = pgx::GumbelFreshRaw(s2, term0); });
+            break;
+          }
+          node = c;
+          WaveAcquire();
+          s = nodes[node].s;
+          if (s.done) break;
+          GumbelEdges<G> e;
+          GumbelEval<G>(nodes[node], s, lane, a.c_visit, a.c_scale, e);
+          act = GumbelInteriorPick<G>(e, lane);
+          // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
+          if (act < 0 || depth >= pgx::kSearchMaxPath) {
+            broken = true;
+            break;
+          }
+          c = tree::OwnerChild<SL>(e.child, act);
+        }
+        if (broken) break;
+        const int status = s.done ? pgx::kGuidedTerminal : pgx::kGuidedEvaluate;
+        if (lane == 0) {
+          slots[j].pending = node;
+          slots[j].status = status;
+          slots[j].depth = depth;
+        }
+        GuidedEmitLeaf<G>(a, row * B + j, lane, status, s);
+      }
+    }
+  }
+  if (broken) j = 0;  // a broken position ends all slots of the root
+  // the record: the answered slots and the slots without a descent are idle
+  if (lane >= j && lane < B) {
+    slots[lane].status = pgx::kGuidedIdle;
+    slots[lane].depth = 0;
+  }
+  if (lane == 0) {
+    rec.count = count;
+    rec.live = j;
+    if (broken) {
+      rec.broken = 1;
+      *err = kErrGumbel;
+    }
+  }
+  WaveRelease();
+  GuidedEmitIdle<G>(a, row * B + j, B - j, lane);
+}
+
+// (BATCH: the root record of a batch session; one row per root either way)
+template <int G, bool BATCH>
 __global__ __launch_bounds__(kSearchBlock) void PgxGumbelResult(GumbelArgs a) {
   constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GumbelNode<G>;
   const int row = blockIdx.x, lane = threadIdx.x;
-  const pgx::GumbelRoot<G>& rec = static_cast<const pgx::GumbelRoot<G>*>(a.roots)[row];
+  const tree::GumbelRec<G, BATCH> rec(a.roots, row, a.batch);
   const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)(a.simulations + 1)];
   WaveAcquire();
-  const bool over = rec.r.over != 0;
+  const bool over = rec.over();
   const pgx::State root = n0.s;
   GumbelEdges<G> e;
   GumbelEval<G>(n0, root, lane, a.c_visit, a.c_scale, e);
   float pi[SL];
   GumbelImproved<G>(e, pi);
-  const int best = GumbelRootPick<G>(e, rec, lane, a.considered, a.simulations, true);
+  const int best = GumbelRootPick<G>(e, rec.gumbel(), lane, a.considered, a.simulations, true);
   // the rows of the guided result with the improved policy as a third column; the action is the root pick's
   tree::RootResult<G>(n0, root, over, lane, a.visits + (size_t)row * A, a.vals + (size_t)row * A,
                       [&](int j, int act) { a.weights[(size_t)row * A + act] = over ? 0.0f : pi[j]; });
@@ -1095,11 +1277,26 @@ class PgxPool : public Pool {
   }
   size_t GumbelNodeBytes() const override { return sizeof(pgx::GumbelNode<G>); }
   size_t GumbelRootBytes() const override { return sizeof(pgx::GumbelRoot<G>); }
+  size_t GumbelBatchRootBytes(int batch) const override { return pgx::GumbelBatchRootBytes<G>(batch); }
+  // a.batch != 0: a batch session; the plain kernels otherwise
   void GumbelBegin(const int* d_ids, const GumbelArgs& a) override {
-    LaunchRoots(PgxGumbelBegin<G>, a.k, common_, state_, d_ids, a);
+    if (a.batch != 0) {
+      LaunchRoots(PgxGumbelBegin<G, true>, a.k, common_, state_, d_ids, a);
+    } else {
+      LaunchRoots(PgxGumbelBegin<G, false>, a.k, common_, state_, d_ids, a);
+    }
   }
-  void GumbelAdvance(const GumbelArgs& a) override { LaunchRoots(PgxGumbelAdvance<G>, a.k, a, err_dev_); }
-  void GumbelResult(const GumbelArgs& a) override { LaunchRoots(PgxGumbelResult<G>, a.k, a); }
+  void GumbelAdvance(const GumbelArgs& a) override {
+    if (a.batch != 0) return LaunchRoots(PgxGumbelAdvanceBatch<G>, a.k, a, err_dev_);
+    LaunchRoots(PgxGumbelAdvance<G>, a.k, a, err_dev_);
+  }
+  void GumbelResult(const GumbelArgs& a) override {
+    if (a.batch != 0) {
+      LaunchRoots(PgxGumbelResult<G, true>, a.k, a);
+    } else {
+      LaunchRoots(PgxGumbelResult<G, false>, a.k, a);
+    }
+  }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
     if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";

@@ -43,6 +43,50 @@
 //      take part is +0.0f), then a butterfly x += x[lane ^ w] for w = 32, 16, 8, 4, 2, 1 (GumbelWaveSum restates it for
 //      the host).  Maxima, minima and integer sums are order-free;
 //  (c) every float operation is written out in order and the build uses -ffp-contract=off and no fast-math.
+//
+// A level per launch (batch sessions; DESIGN.md "PGX Gumbel search: a level per launch").  A LEVEL is the run of
+// consecutive simulations with the same considered visit count cv.  All simulations of a level go through different
+// root actions, so their descents live in disjoint subtrees: they cannot collide, need no virtual loss, and their
+// interior picks do not see each other.  A batch session makes up to B = batch (1 .. kGumbelMaxBatch) of them in one
+// launch.  Every root has B SLOTS, each what the plain session keeps once per root (pending node, status, path); row
+// i * B + j of every leaf and answer array is slot j of root i.  The root rule differs from the plain session's, which
+// re-scores the root before every simulation: a launch scores the root once and takes its actions together.
+//   begin_batch(gumbel, ids, S, m, B, c_visit, c_scale):
+//     as begin.  Slot 0 = {pending 0, path [], status: env over ? 2 : 0}.  Slots 1..B-1 status 2.
+//   advance(logits, values), call number 0 .. S:
+//     A. answers.  Slots j = 0..B-1 in this order, status_j != 2, L = pending_j:
+//          status 0: L.logit / L.p / L.raw from row (i, j) exactly as the plain advance stores them; val0 = L.raw
+//          status 1: val0 = (float) L.term0
+//          backup along path_j in path order (v += 1, w0 += val0 in float32).  status_j = 2; path_j = []
+//     B. t = N(root) after A (the sum of the root's v over legal actions).
+//        If t >= S, or the root is over or broken: nothing more.
+//        m_eff = min(m, legal root actions);  cv = GumbelConsideredVisit(m_eff, S, t)
+//        r = GumbelLevelLeft(m_eff, S, t): the number of t' in t .. S-1 with GumbelConsideredVisit(m_eff, S, t') == cv
+//        b = min(B, r)
+//        Evaluate the root ONCE (the sigma of the tree as it stands after A).
+//        score(a) = GumbelRootScore(gumbel[a], logit[a], lmax, sg(a)).
+//        chosen = the b legal actions with v[a] == cv of the largest score, ties: the lowest a, in that order.
+//        Fewer than b such actions: take those there are.  None: the root is broken (the error word, -3; every slot
+//        ends with status 2 and the root begins no further descent).
+//        Descents j = 0 .. len(chosen)-1 in that order:
+//          path = [(0, chosen[j])], then the plain session's loop below the root (interior pick, expand or step down,
+//          stop at a finished game or kSearchMaxPath).  Node indices are handed out in slot order.
+//        Slot j = {pending, path, status 0 or 1}.  The other slots keep status 2.
+//     emit: every slot's row.  Rows of status 1 or 2 are zeros.
+//   result: the plain Gumbel result.  One row per root, not per slot.
+// Consequences:
+//   - B = 1 is the plain session, call for call, bit for bit: b = 1 and the one chosen action is the plain root pick
+//   - the status-0 and status-1 slots of one launch belong to pairwise different root actions and their paths share no
+//     node but the root: backup order changes no float (slot order is the stated order all the same)
+//   - a descent makes at most one node, so count <= S + 1 and the node memory per root is that of the plain session
+//   - while t < S every advance completes at least one simulation; a round is complete -- all k B statuses 2 -- after
+//     exactly 1 + SUM over the levels of ceil(level size / B) advances, at most S + 1.  Later advances, up to call
+//     number S, change nothing; a call number above S is refused
+//   - after a complete round the root's visits sum to S and their sorted counts are the plain session's for the same
+//     (m_eff, S), whatever the evaluator
+//   - with an evaluator whose values are all 0 and no simulation reaching a finished game, sigma is 0 at every node
+//     and the root order is fixed: the results equal the plain session's for every B, bit for bit, node for node
+//   - with other values the result differs from the plain session's: sigma does not move inside a launch
 #ifndef ENVPOOL_AMD_CSRC_PGX_GUMBEL_HIP_H_
 #define ENVPOOL_AMD_CSRC_PGX_GUMBEL_HIP_H_
 
@@ -113,6 +157,66 @@ PGX_HD inline int GumbelConsideredVisit(int m, int S, int t) {
     t -= e * c;
     vis += e;
     c = c / 2 < 2 ? 2 : c / 2;
+  }
+}
+
+// What is left of the level of simulation t (t < S): the number of t' in t .. S-1 whose considered visit count is that
+// of t.  The same walk of the table.
+PGX_HD inline int GumbelLevelLeft(int m, int S, int t) {
+  const int to_end = S - t;
+  if (m <= 1) return to_end < 1 ? to_end : 1;  // (cv = t: every simulation is a level of its own)
+  int l = 0;
+  while ((1 << l) < m) ++l;
+  int c = m;
+  for (;;) {
+    int e = S / (l * c);
+    e = e < 1 ? 1 : e;
+    if (t < e * c) {
+      const int left = c - t % c;
+      return left < to_end ? left : to_end;
+    }
+    t -= e * c;
+    c = c / 2 < 2 ? 2 : c / 2;
+  }
+}
+
+// ---- batch sessions: a level per launch ----
+constexpr int kGumbelMaxBatch = kGuidedMaxWidth;
+
+// What a batch session keeps per root beside its nodes: this record, then its B slots (GuidedWideSlot).
+template <int G>
+struct alignas(16) GumbelBatchRoot {
+  int32_t count;   // nodes made
+  int32_t over;    // the env was over at begin
+  int32_t broken;  // advance met a position that is no position of the game
+  int32_t live;    // slots whose status is not 2
+  float gumbel[SearchEdges<G>()];
+};
+template <int G>
+PGX_HD inline size_t GumbelBatchRootBytes(int batch) {
+  return sizeof(GumbelBatchRoot<G>) + (size_t)batch * sizeof(GuidedWideSlot);
+}
+template <int G>
+PGX_HD inline GumbelBatchRoot<G>& GumbelBatchRootAt(void* roots, int row, int batch) {
+  char* at = static_cast<char*>(roots) + (size_t)row * GumbelBatchRootBytes<G>(batch);
+  return *reinterpret_cast<GumbelBatchRoot<G>*>(at);
+}
+template <int G>
+PGX_HD inline GuidedWideSlot* GumbelBatchSlots(GumbelBatchRoot<G>& r) {
+  return reinterpret_cast<GuidedWideSlot*>(&r + 1);
+}
+// a batch root record at begin (the noise row apart): slot 0 holds the root, the others are idle
+template <int G>
+PGX_HD inline void GumbelBatchClearRoot(GumbelBatchRoot<G>& r, int batch, bool over) {
+  r.count = 1;
+  r.over = over ? 1 : 0;
+  r.broken = 0;
+  r.live = over ? 0 : 1;
+  GuidedWideSlot* sl = GumbelBatchSlots(r);
+  for (int j = 0; j < batch; ++j) {
+    sl[j].pending = 0;
+    sl[j].status = (j == 0 && !over) ? kGuidedEvaluate : kGuidedIdle;
+    sl[j].depth = 0;
   }
 }
 

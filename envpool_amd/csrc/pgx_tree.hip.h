@@ -258,6 +258,30 @@ struct GuidedRec<true> {
   __device__ __forceinline__ void Reset(int count, bool over) const { GuidedWideClearRoot(r, width, count, over); }
 };
 
+// The root record of a Gumbel session, plain (GumbelRoot, one leaf row per root) or batch (GumbelBatchRoot with its
+// slots, `batch` leaf rows per root, the root's own in slot 0), for the kernels that serve both.
+template <int G, bool BATCH>
+struct GumbelRec;
+template <int G>
+struct GumbelRec<G, false> {
+  GumbelRoot<G>& r;
+  __device__ __forceinline__ GumbelRec(void* roots, int row, int /*batch*/)
+      : r(static_cast<GumbelRoot<G>*>(roots)[row]) {}
+  __device__ __forceinline__ bool over() const { return r.r.over != 0; }
+  __device__ __forceinline__ float* gumbel() const { return r.gumbel; }
+  __device__ __forceinline__ void Clear(bool over) const { GuidedClearRoot(r.r, over); }  // at begin
+};
+template <int G>
+struct GumbelRec<G, true> {
+  GumbelBatchRoot<G>& r;
+  int batch;
+  __device__ __forceinline__ GumbelRec(void* roots, int row, int batch_)
+      : r(GumbelBatchRootAt<G>(roots, row, batch_)), batch(batch_) {}
+  __device__ __forceinline__ bool over() const { return r.over != 0; }
+  __device__ __forceinline__ float* gumbel() const { return r.gumbel; }
+  __device__ __forceinline__ void Clear(bool over) const { GumbelBatchClearRoot(r, batch, over); }
+};
+
 }  // namespace tree
 }  // namespace pgx
 }  // namespace epa

@@ -165,15 +165,39 @@ class GumbelSearch:
         gs = env.gumbel_search(ids, simulations=32, max_considered=16, seed=0)
         result = gs.run(lambda obs, mask, status: model(obs, mask))     # S + 1 evaluations, then closes
 
-    or step by step, as `GuidedSearch`: `leaves`, `advance(logits [k, A], values [k])`, `result()`, `close()`."""
+    or step by step, as `GuidedSearch`: `leaves`, `advance(logits [k, A], values [k])`, `result()`, `close()`.
+
+    A halving level per launch: `batch=B` (2 .. 32) gives every root B slots, and one advance makes up to B simulations
+    of the root's current level of sequential halving -- the simulations with the same considered visit count, which
+    go through different root actions, so nothing collides and no virtual loss is needed.  The launch scores the root
+    once and takes its actions together (the plain session re-scores it before every simulation, so the two differ
+    where the values are not constant).  S = 32, m = 16, B = 16 costs 5 model calls of k B rows, not 33 of k.
+    `leaves` then carry a slot axis (obs [k, B, H, W, C], mask [k, B, A], status [k, B]; a slot of status 2 has
+    nothing pending) and `advance` takes logits [k, B, A] and values [k, B], or the same flattened to k B rows.  The
+    round is over when `done` is true; `run` flattens the rows for `evaluate` -- which therefore is the function
+    written for the plain session -- and loops until then:
+
+        while playing:
+            result = env.gumbel_search(ids, simulations=32, max_considered=16, batch=16).run(evaluate)
+            env.step(result.action, ids)"""
 
     def __init__(self, pool: Any, ids: np.ndarray, simulations: int, max_considered: int, gumbel: np.ndarray,
-                 c_visit: float, c_scale: float):
+                 c_visit: float, c_scale: float, batch: int = 1):
         self._pool = pool
         self.simulations = int(simulations)
         self.calls = 0
-        self.leaves = pool.gumbel_begin(gumbel, ids, int(simulations), int(max_considered), float(c_visit),
-                                        float(c_scale))
+        self.batch = int(batch)
+        if self.batch > 1:
+            self.leaves = pool.gumbel_begin(gumbel, ids, int(simulations), int(max_considered), float(c_visit),
+                                            float(c_scale), self.batch)
+        else:
+            self.leaves = pool.gumbel_begin(gumbel, ids, int(simulations), int(max_considered), float(c_visit),
+                                            float(c_scale))
+
+    @property
+    def done(self) -> bool:
+        """Whether the round is complete: nothing is pending, all statuses are 2."""
+        return bool((np.asarray(self.leaves[2]) == 2).all())
 
     def advance(self, logits: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         if self._pool is None:
@@ -191,8 +215,13 @@ class GumbelSearch:
 
     def run(self, evaluate: Any) -> GumbelResult:
         """Calls `evaluate(obs, mask, status) -> (logits, values)` until simulations + 1 advances are made, returns
-        the result and closes the session."""
-        while self.calls <= self.simulations:
+        the result and closes the session.  A batch session calls it with the rows flattened to [k B, ...] until the
+        round is `done`, at most simulations + 1 times."""
+        while self.batch > 1 and not self.done and self.calls <= self.simulations:
+            obs, mask, status = self.leaves
+            self.advance(*evaluate(obs.reshape((-1,) + obs.shape[2:]), mask.reshape(-1, mask.shape[-1]),
+                                   status.reshape(-1)))
+        while self.batch == 1 and self.calls <= self.simulations:
             self.advance(*evaluate(*self.leaves))
         out = self.result()
         self.close()
@@ -377,7 +406,8 @@ class EnvPoolMixin(ABC):
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
         pool has one at a time, and a new one replaces it.  Nothing of the pool changes.  The arguments are checked
         before any native call.  `policy="gumbel"` is `gumbel_search(env_ids, simulations, **gumbel)` instead (c_puct
-        is not used) and returns a `GumbelSearch`.  `nodes` (PUCT only): the node capacity per root, simulations + 1 ..
+        is not used; `batch=` among them: a halving level per launch) and returns a `GumbelSearch`.
+        `nodes` (PUCT only): the node capacity per root, simulations + 1 ..
         8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree.  `width`
         (PUCT only), 1 .. 32: the leaves per root and launch (`GuidedSearch`: "Several leaves per launch"); 1 is the
         plain session."""
@@ -402,7 +432,7 @@ class EnvPoolMixin(ABC):
 
     def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
                       seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1,
-                      width: int = 1) -> GumbelSearch:
+                      width: int = 1, batch: int = 1) -> GumbelSearch:
         """Extension (the PGX board games): opens a Gumbel search (Danihelka et al., ICLR 2022) from the current
         position of every listed env (global ids; None: all): Gumbel top-`max_considered` sampling without replacement
         at the root, sequential halving of the `simulations` over those actions, a deterministic rule inside the tree;
@@ -410,11 +440,13 @@ class EnvPoolMixin(ABC):
         `weights` the policy training target.  `gumbel` float32 [k, A] is the root noise (zeros: no noise, for
         evaluation); None draws it on the host from numpy.random.Generator(PCG64(seed)), seed=None unseeded.  Returns
         the `GumbelSearch` session; it is the pool's one guided-search session.  Nothing of the pool changes.  The
-        arguments are checked before any native call.  `width` other than 1 raises: sequential halving has its own
-        schedule, and several leaves per launch are a feature of the PUCT sessions."""
+        arguments are checked before any native call.  `batch`, 1 .. 32: the simulations of a halving level per root
+        and launch (`GumbelSearch`: "A halving level per launch"); 1 is the plain session.  `width` other than 1
+        raises: it is the virtual-loss rule of the PUCT sessions, and a Gumbel session batches by level instead."""
         if width != 1:
             raise ValueError("gumbel_search: width is an argument of policy='puct' (several leaves per launch not "
                              "implemented for gumbel sessions)")
+        native.check_gumbel_batch(batch)
         ids = native.check_gumbel(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, max_considered, c_visit, c_scale)
         pool = self._gumbel()
@@ -422,7 +454,8 @@ class EnvPoolMixin(ABC):
         if gumbel is None:
             gumbel = np.random.Generator(np.random.PCG64(seed)).gumbel(size=(len(ids), actions)).astype(np.float32)
         gumbel = native.check_gumbel_noise(gumbel, len(ids), actions)
-        return GumbelSearch(pool, ids, int(simulations), int(max_considered), gumbel, float(c_visit), float(c_scale))
+        return GumbelSearch(pool, ids, int(simulations), int(max_considered), gumbel, float(c_visit), float(c_scale),
+                            int(batch))
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

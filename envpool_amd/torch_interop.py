@@ -346,18 +346,32 @@ def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: in
 
 def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
                          gumbel: Any = None, seed: Any = None, c_visit: float = 50.0,
-                         c_scale: float = 0.1) -> tuple[Any, Any, Any, Any]:
+                         c_scale: float = 0.1, batch: Any = None,
+                         advances: Any = None) -> tuple[Any, Any, Any, Any]:
     """A whole Gumbel search (`pool.gumbel_begin` ..) with the evaluator on the device, as `guided_search_device`:
     `evaluate(obs, mask, status)` gets torch tensors on the pool's device and returns (logits float32 [k, A], values
     float32 [k]) there; nothing crosses PCIe and the host never waits.  `gumbel` is a float32 [k, A] tensor on the
     pool's device, or None: torch draws Gumbel(0, 1) noise there (from a generator seeded with `seed`, or torch's
     default one).  Returns (visits int32 [k, A], values float32 [k, A], action int32 [k], weights float32 [k, A]) on
-    the device and closes the session."""
+    the device and closes the session.
+    `batch` = B (1 .. 32) opens a batch session, a halving level per launch: `evaluate` gets and returns k B rows,
+    flattened (row i B + j is slot j of root i; a slot of status 2 has nothing pending), so a model function written
+    for the plain session works unchanged.  `advances=None` reads one reduced status byte per launch -- the one host
+    wait -- and stops when the round is complete; an integer makes exactly that many advances with no host wait: roots
+    that are not finished then simply have fewer visits, which the result shows."""
     import torch
 
     if env_ids is None:
         env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
     ids = native.check_gumbel(env_ids, simulations, max_considered, c_visit, c_scale)
+    batch = native.check_gumbel_batch(batch)
+    if advances is not None and not batch:
+        raise ValueError("gumbel_search_device: advances is an argument of a batch session (batch=)")
+    most = int(simulations) + 1
+    if advances is not None:
+        if isinstance(advances, bool) or int(advances) != advances or not 1 <= int(advances) <= most:
+            raise ValueError(f"gumbel_search_device: advances = {advances} must be 1 .. simulations + 1 = {most}")
+        most = int(advances)
     a = pool.gumbel_actions()
     h, w, c, _ = pool.guided_shape()
     k = len(ids)
@@ -369,21 +383,24 @@ def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     gumbel = gumbel.to(device=dev, dtype=torch.float32).contiguous()
     if tuple(gumbel.shape) != (k, a):
         raise ValueError(f"gumbel_begin: gumbel of shape {tuple(gumbel.shape)} for a session of [{k}, {a}]")
-    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
-    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
-    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    rows = k * batch if batch else k
+    obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
+    status = torch.empty((rows,), dtype=torch.uint8, device=dev)
     _order_both_ways(pool, dev, lambda: pool.gumbel_begin_device(gumbel.data_ptr(), obs.data_ptr(), mask.data_ptr(),
                                                                  status.data_ptr(), ids, simulations, max_considered,
-                                                                 c_visit, c_scale))
-    for _ in range(int(simulations) + 1):
+                                                                 c_visit, c_scale, batch or None))
+    for _ in range(most):
+        if batch and advances is None and not bool((status != 2).any().item()):
+            break  # the round is complete: nothing is pending
         logits, values = evaluate(obs, mask, status)
         logits = logits.to(device=dev, dtype=torch.float32).contiguous()
         values = values.to(device=dev, dtype=torch.float32).contiguous().view(-1)
-        if tuple(logits.shape) != (k, a) or tuple(values.shape) != (k,):
+        if tuple(logits.shape) != (rows, a) or tuple(values.shape) != (rows,):
             pool.guided_end()
             raise ValueError(f"gumbel_search_device: evaluate returned logits {tuple(logits.shape)} and values "
-                             f"{tuple(values.shape)} for a session of [{k}, {a}]")
-        _order_both_ways(pool, dev, lambda: pool.gumbel_advance_device(logits.data_ptr(), values.data_ptr(), k,
+                             f"{tuple(values.shape)} for a session of [{rows}, {a}]")
+        _order_both_ways(pool, dev, lambda: pool.gumbel_advance_device(logits.data_ptr(), values.data_ptr(), rows,
                                                                        obs.data_ptr(), mask.data_ptr(),
                                                                        status.data_ptr()))
     visits = torch.empty((k, a), dtype=torch.int32, device=dev)

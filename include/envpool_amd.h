@@ -690,6 +690,38 @@ int epa_gumbel_result(epa_pool* pool, int32_t* visits, float* values, int32_t* a
 int epa_gumbel_result_device(epa_pool* pool, void* device_visits, void* device_values, void* device_action,
                              void* device_weights);
 
+/* Gumbel search, a halving level per launch (csrc/pgx_gumbel.hip.h "A level per launch" is the authority): a BATCH
+ * session of batch B, 1 .. EPA_GUMBEL_MAX_BATCH, keeps B slots per root -- each a pending leaf, a status and a path --
+ * and one advance answers every pending slot and then makes up to B simulations of the root's current LEVEL of
+ * sequential halving (the run of simulations with the same considered visit count).  They go through different root
+ * actions, so their descents live in disjoint subtrees: no virtual loss, no collision, nothing dropped.  S = 32 with
+ * m = 16 and B = 16 costs 5 model calls of k * B rows (levels of 16, 8, 4, 4) instead of 33 calls of k rows.
+ *   The root rule is the batch session's own: a launch scores the root ONCE, on the tree as it stands after the
+ *   answers -- t = N(root), cv as above, r = what is left of the level, b = min(B, r) -- and takes the b legal actions
+ *   with v[a] == cv of the largest (gumbel[a] + (logit[a] - max legal logit)) + sg(a), ties the lowest a, in that
+ *   order, for slots 0 .. b-1 (fewer if there are fewer; none ends the root as above).  Below the root each descent
+ *   is the plain session's.  The plain session re-scores the root before every simulation, so with values that are
+ *   not constant the two give different results; B = 1 is the plain session call for call, bit for bit.
+ *   Through this interface a batch session is a session of k * B rows: obs, mask and status of begin and advance, and
+ *   logits and values of advance, have k * B rows, row i * B + j for slot j of root i; `k` of epa_gumbel_advance is
+ *   k * B.  The noise has one row per root, and epa_gumbel_result gives one row per root.
+ *   A slot of status 2 has nothing pending and its rows are zeros.  A round is complete when all k * B statuses are 2:
+ *   for a root of m_eff considered actions after 1 + the sum over its levels of ceil(level size / B) advances, at most
+ *   S + 1; later advances up to call number S change nothing, and a call number above S is refused.  Each root keeps
+ *   S + 1 nodes, as in the plain session.
+ *   EPA_ERR_INVALID, before any launch, beside the refusals of epa_gumbel_begin: a batch outside 1 ..
+ *     EPA_GUMBEL_MAX_BATCH; advance with a row count other than k * B.  The tree limit EPA_SEARCH_MAX_TREE_BYTES counts
+ *     the batch root records (about 1 KiB per slot).  epa_guided_reroot refuses every Gumbel session.
+ * The _device form takes device pointers and only enqueues. */
+#define EPA_GUMBEL_MAX_BATCH 32
+int epa_gumbel_begin_batch(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                           int32_t max_considered, int32_t batch, float c_visit, float c_scale, const float* gumbel,
+                           uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_gumbel_begin_batch_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                                  int32_t max_considered, int32_t batch, float c_visit, float c_scale,
+                                  const void* device_gumbel, void* device_obs, void* device_mask,
+                                  void* device_status);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).

@@ -41,6 +41,15 @@ JSON line.  W = 1 is the plain session (S + 1 advances of k rows), the others ar
               k and evaluator (when W = 1 is in the same run): the cost of one wide launch in plain launches' worth of
               descents
   session     one pair of events around begin, all advances (and the evaluator's launches) and the result; the median
+
+    python tools/bench_guided.py --gumbel --batch 1,4,16 [--simulations 32,64] [--considered 16] [--evaluators ..] ...
+
+Gumbel sessions, a halving level per launch: per game, k freshly reset roots, S, batch B and evaluator, m = 16 in the
+device form with fixed seeded noise, one JSON line.  B = 1 is the plain session (S + 1 advances of k rows), the others
+are batch sessions (k B rows).  The evaluators are those of --width, as logits (const: zeros; hash: 8 cos(obs . P) on
+the legal actions).  `advances`, `advance` and `session` as for --width; `vs_plain` = the median batch launch over B
+times the plain Gumbel advance of the same game, k, S and evaluator; `puct_advance_us_per_launch` is the plain PUCT
+advance (constant priors) of the same game, k and S, measured in the same run.
 """
 import argparse
 import json
@@ -266,6 +275,127 @@ def measure_wide(torch, ti, DevicePool, fam, k, width, evaluator, args, plain_us
     return out
 
 
+def puct_advance_us(torch, pool, stream, dev, k, sims, args):
+    """The median plain PUCT advance launch of `pool` over `reps` sessions of `sims` simulations, constant priors."""
+    h, w, c, a = pool.guided_shape()
+    obs = torch.empty((k, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((k, a), dtype=torch.bool, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    priors = torch.full((k, a), 1.0 / a, dtype=torch.float32, device=dev)
+    values = torch.zeros((k,), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    launches = []
+    for rep in range(args.warmup + args.reps):
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(sims + 2)]
+        pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, sims, C_PUCT)
+        evs[0].record(stream)
+        for t in range(sims + 1):
+            pool.guided_advance_device(priors.data_ptr(), values.data_ptr(), k, obs.data_ptr(), mask.data_ptr(),
+                                       status.data_ptr())
+            evs[t + 1].record(stream)
+        evs[-1].synchronize()
+        torch.cuda.synchronize(dev)
+        if rep >= args.warmup:
+            launches += [evs[t].elapsed_time(evs[t + 1]) for t in range(sims + 1)]
+    pool.guided_end()
+    return float(np.median(launches)) * 1e3
+
+
+def measure_gumbel(torch, ti, DevicePool, fam, k, sims, batch, evaluator, args, plain_us, puct_us):
+    m = args.considered
+    pool = DevicePool(fam, k, seed=0)
+    dev = torch.device("cuda", pool.device)
+    stream = torch.cuda.ExternalStream(pool.stream, device=dev)
+    ids = torch.arange(k, dtype=torch.int32, device=dev)
+    ti.send_device_tensors(pool, None, ids)  # reset: every env at the start of a game
+    ti.recv_device_tensors(pool)
+    h, w, c, a = pool.guided_shape()
+    rows = k * batch
+    obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
+    mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
+    status = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    visits = torch.empty((k, a), dtype=torch.int32, device=dev)
+    vals = torch.empty((k, a), dtype=torch.float32, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    weights = torch.empty((k, a), dtype=torch.float32, device=dev)
+    const = (torch.zeros((rows, a), dtype=torch.float32, device=dev),
+             torch.zeros((rows,), dtype=torch.float32, device=dev))
+    gen = torch.Generator().manual_seed(7)
+    w_p = torch.randn((h * w * c, a), generator=gen).to(dev)
+    w_v = (torch.randn((h * w * c,), generator=gen) * 0.2).to(dev)
+    u = torch.rand((k, a), generator=gen).clamp_(1e-20, 1.0 - 1e-7)
+    noise = (-torch.log(-torch.log(u))).to(dev).contiguous()
+    if (fam, k, sims) not in puct_us:
+        puct_us[(fam, k, sims)] = puct_advance_us(torch, pool, stream, dev, k, sims, args)
+    torch.cuda.synchronize(dev)
+
+    def evaluate():
+        if evaluator == "const":
+            return const
+        x = obs.reshape(rows, -1).to(torch.float32)
+        return (8.0 * torch.cos(x @ w_p) * mask.to(torch.float32)).contiguous(), torch.tanh(x @ w_v).contiguous()
+
+    def begin():
+        pool.gumbel_begin_device(noise.data_ptr(), obs.data_ptr(), mask.data_ptr(), status.data_ptr(), None, sims, m,
+                                 batch=None if batch == 1 else batch)
+
+    def result():
+        pool.gumbel_result_device(visits.data_ptr(), vals.data_ptr(), action.data_ptr(), weights.data_ptr())
+
+    def event():
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(stream)
+        return ev
+
+    with torch.cuda.stream(stream):
+        # the session that counts: a host wait after every launch
+        begin()
+        advances, leaves = 0, 0
+        while bool((status != 2).any()):
+            leaves += int((status == 0).sum())
+            logits, values = evaluate()
+            pool.gumbel_advance_device(logits.data_ptr(), values.data_ptr(), rows, obs.data_ptr(), mask.data_ptr(),
+                                       status.data_ptr())
+            advances += 1
+            assert advances <= sims + 1
+        result()
+        torch.cuda.synchronize(dev)
+        assert bool((visits.sum(1) == sims).all())
+        launches, sessions = [], []
+        for rep in range(args.warmup + args.reps):
+            timed = []
+            first = event()
+            begin()
+            for t in range(advances):
+                logits, values = evaluate()
+                e0 = event()
+                pool.gumbel_advance_device(logits.data_ptr(), values.data_ptr(), rows, obs.data_ptr(),
+                                           mask.data_ptr(), status.data_ptr())
+                timed.append((e0, event()))
+            result()
+            last = event()
+            last.synchronize()
+            torch.cuda.synchronize(dev)
+            assert bool((visits.sum(1) == sims).all()) and bool((status == 2).all())
+            if rep >= args.warmup:
+                launches += [x.elapsed_time(y) for x, y in timed]
+                sessions.append(first.elapsed_time(last))
+    pool.guided_end()
+    pool.close()
+    us = float(np.median(launches)) * 1e3
+    out = {"game": fam, "roots": k, "policy": "gumbel", "simulations": sims, "considered": m, "batch": batch,
+           "evaluator": evaluator, "advances_per_round": advances,
+           "leaves_per_launch_per_root": round(leaves / (advances * k), 3), "advance_us_per_launch": round(us, 2),
+           "advance_us_min_max": [round(min(launches) * 1e3, 2), round(max(launches) * 1e3, 2)],
+           "session_ms": round(float(np.median(sessions)), 3), "session_ms_all": [round(x, 3) for x in sessions],
+           "puct_advance_us_per_launch": round(puct_us[(fam, k, sims)], 2)}
+    if batch == 1:
+        plain_us[(fam, k, sims, evaluator)] = us
+    elif (fam, k, sims, evaluator) in plain_us:
+        out["vs_plain"] = round(us / (batch * plain_us[(fam, k, sims, evaluator)]), 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="Othello,Hex")
@@ -275,7 +405,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reroot", action="store_true", help="time guided_reroot_device instead (tree reuse)")
     ap.add_argument("--width", default=None, help="several leaves per launch instead: the widths, e.g. 1,4,8,16")
-    ap.add_argument("--evaluators", default="const,hash", help="with --width: const, hash or both")
+    ap.add_argument("--evaluators", default="const,hash", help="with --width or --gumbel: const, hash or both")
+    ap.add_argument("--gumbel", action="store_true", help="Gumbel sessions instead, a halving level per launch")
+    ap.add_argument("--batch", default="1,4,16", help="with --gumbel: the batches; 1 is the plain session")
+    ap.add_argument("--simulations", default="32,64", help="with --gumbel: the simulations per move")
+    ap.add_argument("--considered", type=int, default=16, help="with --gumbel: m")
     args = ap.parse_args()
     import torch
 
@@ -283,9 +417,20 @@ def main():
     from envpool_amd.core.device_pool import DevicePool
 
     sink = open(args.out, "w") if args.out else None
-    plain_us = {}
+    plain_us, puct_us = {}, {}
     for fam in args.games.split(","):
         for k in [int(x) for x in args.sizes.split(",")]:
+            if args.gumbel:
+                for sims in [int(x) for x in args.simulations.split(",")]:
+                    for evaluator in args.evaluators.split(","):
+                        for batch in [int(x) for x in args.batch.split(",")]:
+                            text = json.dumps(measure_gumbel(torch, ti, DevicePool, fam, k, sims, batch, evaluator,
+                                                             args, plain_us, puct_us))
+                            print(text, flush=True)
+                            if sink:
+                                sink.write(text + "\n")
+                                sink.flush()
+                continue
             if args.width:
                 for evaluator in args.evaluators.split(","):
                     for width in [int(x) for x in args.width.split(",")]:
