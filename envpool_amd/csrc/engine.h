@@ -138,6 +138,20 @@ struct SearchArgs {
   void* nodes;              // 16-byte aligned
 };
 
+// One solve launch (Pool::Solve): k listed envs, row i of the five device result arrays being env row i's, and the
+// stacks of the roots' lanes, k * Pool::SolveRootBytes(depth) bytes.
+struct SolveArgs {
+  int k;
+  int depth;                // 0: no horizon
+  long long max_nodes;
+  int8_t* value;            // [k]
+  int8_t* q;                // [k][A]
+  int32_t* action;          // [k]
+  uint8_t* status;          // [k]
+  long long* nodes;         // [k], 8-byte aligned
+  void* stack;              // 16-byte aligned
+};
+
 // A device allocation whose life is shorter than its pool's: it has ONE owner, which holds it by value, and goes when
 // the owner says so or dies.  (Everything that lives as long as the pool comes from Pool::DevAlloc and is freed by
 // ~Pool; a buffer of one call comes from Pool::SideScratch.  This is for what a caller opens and closes: the
@@ -402,6 +416,20 @@ class Pool {
   void SearchDevice(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies,
                     uint64_t seed, void* d_visits, void* d_returns, void* d_action);
 
+  // Exact solve (include/envpool_amd.h: epa_solve; the PGX board games, pgx_solve.hip.h): for every listed env, the
+  // minimax value of its position -- to the end of the game, or to a horizon of `depth` plies -- per root action, by
+  // alpha-beta in one launch.  Nothing of the pool changes.  The family hook launches on stream_ for local ids, the
+  // lanes' stacks in `a.stack` (the side scratch block); a family without one keeps the defaults, and both entry
+  // points throw std::runtime_error("solve not implemented for this environment").  A row is SearchActions() wide.
+  // SolveHost returns the results in host memory (one stream synchronisation); SolveDevice only enqueues.
+  virtual bool HasSolve() const { return false; }
+  virtual size_t SolveRootBytes(int /*depth*/) const { return 0; }  // a root's stacks; a multiple of 16
+  virtual void Solve(const int* d_ids, const SolveArgs& a);
+  void SolveHost(const int32_t* ids, int k, int depth, long long max_nodes, int8_t* value, int8_t* q, int32_t* action,
+                 uint8_t* status, int64_t* nodes);
+  void SolveDevice(const int32_t* ids, int k, int depth, long long max_nodes, void* d_value, void* d_q, void* d_action,
+                   void* d_status, void* d_nodes);
+
   // Guided tree search (include/envpool_amd.h: epa_guided_begin; the PGX board games, pgx_guided.hip.h): a search
   // whose tree stays on the device between launches and that stops at every new leaf, so that the caller supplies
   // the priors and the leaf values.  A pool has at most one session.  Its memory -- root records, nodes and the
@@ -653,6 +681,8 @@ class Pool {
   void CheckPlayout(const int32_t* ids, int k, int repeats, int max_plies, unsigned flags) const;
   // search's checks; throws before anything is enqueued.  Returns the bytes of the tree scratch.
   size_t CheckSearch(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies) const;
+  // the checks of a solve call, before any launch; returns the bytes of the stacks
+  size_t CheckSolve(const int32_t* ids, int k, int depth, long long max_nodes) const;
   // the pool's guided-search session
   struct GuidedSession {
     bool open{false};

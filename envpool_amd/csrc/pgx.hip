@@ -29,6 +29,8 @@
 // PgxGuidedAdvanceWide) keep W slots per root and descend up to W times per launch, steered apart by virtual losses.
 // Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
 // policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
+// Exact solve: pgx_solve.hip.h, alpha-beta with the top of the tree in LDS and the lanes' stacks in the pool's side
+// scratch (PgxSolveKernel).
 #include <algorithm>
 #include <string>
 
@@ -40,6 +42,7 @@
 #include "pgx_playout.hip.h"
 #include "pgx_render.hip.h"
 #include "pgx_search.hip.h"
+#include "pgx_solve.hip.h"
 #include "pgx_tree.hip.h"
 #include "render_kernel.hip.h"
 
@@ -319,6 +322,94 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
   if (lane == 0) {
     a.action[row] = best;
     if (broken) *err = kErrSearch;
+  }
+}
+
+// Exact solve (pgx_solve.hip.h): one wave per root, one block per wave; block i solves listed env i.  The steps of the
+// header's traversal, with every hand-off through LDS between two block barriers (a block is one wave, and the control
+// flow around the barriers is wave-uniform: it depends on LDS words all lanes read, and on wave reductions):
+//   top tree   SolveTop in LDS (19 KiB: 256 positions and 11 bytes of links and values per node).  Lane 0 lays a level
+//              out (SolveTopPlan), the lanes make its positions, node hi + lane, + 64, .. (SolveTopMake)
+//   lanes      SolveLaneSlice: the lane's node in registers, its stack in the side scratch -- word w of ply p of lane j
+//              of root i at 16-byte word i * plies * 320 + (p * 5 + w) * 64 + j, plies = D or kSolveMaxDepth: a push
+//              is five stores and a pop five loads of 1 KiB per wave, each in one piece
+//   rounds     after a slice: `nodes` is a wave sum (WaveSum), the flags wave maxima; lane 0 runs SolveCombine
+//   result     lane 0 writes the row (SolveRootResult)
+// The loop of a slice is divergent per lane: a round lasts as long as its slowest lane's kSolveSlice positions, and
+// lanes whose entries are done idle.  No floating point.
+constexpr unsigned kErrSolve = 5;  // a solve met a running position without a legal action
+static_assert(pgx::kSolveMaxDepth == EPA_SOLVE_MAX_DEPTH, "the C ABI states the header's limits");
+
+template <int G>
+__global__ __launch_bounds__(kSearchBlock) void PgxSolveKernel(CommonDev cm, const pgx::State* st,
+                                                               const int* __restrict__ ids, SolveArgs a,
+                                                               unsigned* err) {
+  constexpr int A = pgx::Dims<G>::A;
+  __shared__ pgx::SolveTop top;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int e = ids[row];
+  int8_t* q = a.q + (size_t)row * A;
+  if (cm.done[e] != 0) {  // over at the call (an env before its first reset is)
+    if (lane == 0) {
+      pgx::SolveNoResult<G>(q, a.value + row, a.action + row);
+      a.status[row] = (uint8_t)pgx::kSolveOver;
+      a.nodes[row] = 0;
+    }
+    return;
+  }
+  const int limit = pgx::SolveLimit(a.depth);
+  const bool hard = a.depth == 0;
+  pgx::SolveWord* stack =
+      reinterpret_cast<pgx::SolveWord*>(static_cast<char*>(a.stack) + (size_t)row * pgx::SolveStackBytes(a.depth));
+  const pgx::State root = st[e];
+  if (lane == 0) pgx::SolveTopInit(top, root);
+  pgx::SolveFlags flags{0, root.m == 0 ? 1 : 0};
+  long long count = 1;
+  bool gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
+  __syncthreads();
+  while (!gave_up) {  // the top tree
+    if (lane == 0) pgx::SolveTopPlan(top);
+    __syncthreads();
+    const int hi = top.hi, next = top.next_n;
+    if (next == top.n) break;
+    for (int c = hi + lane; c < next; c += kSearchBlock) pgx::SolveTopMake<G>(top, c, limit, hard, flags);
+    flags.overflow = tree::WaveMax(flags.overflow);
+    flags.broken = tree::WaveMax(flags.broken);
+    __syncthreads();
+    if (lane == 0) pgx::SolveTopAdvance(top);
+    __syncthreads();
+    count = next;
+    gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
+  }
+  if (!gave_up) {
+    if (lane == 0) pgx::SolveTopFrontier(top);
+    __syncthreads();
+    pgx::SolveLane l;
+    pgx::SolveLaneInit(l, lane);
+    for (;;) {  // the rounds
+      if (tree::WaveMax(pgx::SolveLaneBusy(l, top) ? 1 : 0) == 0) break;
+      pgx::SolveLaneSlice<G>(l, top, stack, lane, pgx::kSolveSlice, limit, hard);
+      count = top.n + tree::WaveSum(l.visited);
+      flags.overflow = tree::WaveMax(flags.overflow | l.flags.overflow);
+      flags.broken = tree::WaveMax(flags.broken | l.flags.broken);
+      gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
+      __syncthreads();
+      if (gave_up) break;
+      if (lane == 0) pgx::SolveCombine(top);
+      __syncthreads();
+    }
+  }
+  if (lane == 0) {
+    a.nodes[row] = count;
+    if (gave_up) {
+      pgx::SolveNoResult<G>(q, a.value + row, a.action + row);
+      a.status[row] = (uint8_t)pgx::kSolveGivenUp;
+      if (flags.broken) *err = kErrSolve;
+    } else {
+      pgx::SolveCombine(top);
+      pgx::SolveRootResult<G>(top, q, a.value + row, a.action + row);
+      a.status[row] = (uint8_t)pgx::kSolveSolved;
+    }
   }
 }
 
@@ -1237,6 +1328,11 @@ class PgxPool : public Pool {
   void Search(const int* d_ids, const SearchArgs& a) override {
     LaunchRoots(PgxSearchKernel<G>, a.k, common_, state_, d_ids, a, cfg_.env_id_offset, err_dev_);
   }
+  bool HasSolve() const override { return true; }
+  size_t SolveRootBytes(int depth) const override { return pgx::SolveStackBytes(depth); }
+  void Solve(const int* d_ids, const SolveArgs& a) override {
+    LaunchRoots(PgxSolveKernel<G>, a.k, common_, state_, d_ids, a, err_dev_);
+  }
   bool HasGuided() const override { return true; }
   void GuidedShape(int32_t shape[4]) const override {
     shape[0] = pgx::Dims<G>::H, shape[1] = pgx::Dims<G>::W, shape[2] = pgx::Dims<G>::C, shape[3] = pgx::Dims<G>::A;
@@ -1302,6 +1398,7 @@ class PgxPool : public Pool {
     if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";
     if (code == kErrState) return "PGX: set_state was given words that are no position of the game";
     if (code == kErrSearch) return "PGX: search met a position that is no position of the game";
+    if (code == kErrSolve) return "PGX: solve met a position that is no position of the game";
     return Pool::ErrorText(code);
   }
 

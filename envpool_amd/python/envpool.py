@@ -35,6 +35,16 @@ class Search(NamedTuple):
     action: np.ndarray   # int32 [k]: the most visited action (the lowest on ties); -1: the env is over
 
 
+class Solve(NamedTuple):
+    """What `solve` returns: numpy arrays over [k listed envs, A actions]; exact values, seen from the root's mover."""
+
+    value: np.ndarray   # int8 [k]: +1 a forced win, 0, -1 a forced loss (within the horizon); 0 unless status is 0
+    q: np.ndarray       # int8 [k, A]: the value through each legal root action; -128: illegal, or status is not 0
+    action: np.ndarray  # int32 [k]: the lowest action whose q equals value; -1 unless status is 0
+    status: np.ndarray  # uint8 [k]: 0 solved, 1 given up (max_nodes), 2 the env is over
+    nodes: np.ndarray   # int64 [k]: the positions visited
+
+
 class GuidedResult(NamedTuple):
     """What a guided search returns: numpy arrays over [k listed envs, A actions]."""
 
@@ -398,6 +408,15 @@ class EnvPoolMixin(ABC):
                                   simulations, leaf_playouts, c_puct, max_plies)
         return Search(*self._search(ids, int(simulations), int(leaf_playouts), float(c_puct), int(max_plies),
                                     int(seed)))
+
+    def solve(self, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20) -> Solve:
+        """Extension (the PGX board games): the exact minimax value of the current position of every listed env
+        (global ids; None: all), by alpha-beta in one kernel launch; no model, no random numbers.  `depth`: the
+        horizon in plies -- value +1 is then a forced win within `depth` plies, -1 a forced loss, 0 neither --, 0: to
+        the end of the game.  A root that visits more than `max_nodes` positions is given up (status 1).  Nothing of
+        the pool changes.  The arguments are checked before any native call."""
+        ids = native.check_solve(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), depth, max_nodes)
+        return Solve(*self._solve(ids, int(depth), int(max_nodes)))
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
                       nodes: Any = None, width: int = 1, **gumbel: Any) -> Any:

@@ -232,6 +232,29 @@ def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_pl
     return visits, returns, action
 
 
+def solve_device(pool: Any, env_ids: Any = None, depth: int = 0,
+                 max_nodes: int = 1 << 20) -> tuple[Any, Any, Any, Any, Any]:
+    """`pool.solve` without the way down: (value int8 [k], q int8 [k, A], action int32 [k], status uint8 [k], nodes
+    int64 [k]) as torch tensors on the pool's device, written by the solve kernel straight into torch's memory (no PCIe
+    transfer, no host synchronisation: the call only enqueues) and ordered against torch's current stream like
+    `search_device`."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_solve(env_ids, depth, max_nodes)
+    k, a = len(ids), pool.solve_actions()
+    dev = torch.device("cuda", pool.device)
+    value = torch.empty((k,), dtype=torch.int8, device=dev)
+    q = torch.empty((k, a), dtype=torch.int8, device=dev)
+    action = torch.empty((k,), dtype=torch.int32, device=dev)
+    status = torch.empty((k,), dtype=torch.uint8, device=dev)
+    nodes = torch.empty((k,), dtype=torch.int64, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.solve_device(value.data_ptr(), q.data_ptr(), action.data_ptr(),
+                                                          status.data_ptr(), nodes.data_ptr(), ids, depth, max_nodes))
+    return value, q, action, status, nodes
+
+
 def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations: int, leaves: tuple,
                          what: str, width: int = 0, advances: Any = None) -> tuple[Any, Any, Any]:
     """simulations + 1 advances from the emitted `leaves` and the result, every launch ordered both ways.  A wide

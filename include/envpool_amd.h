@@ -493,6 +493,45 @@ int epa_search_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t
                       float c_puct, int32_t max_plies, uint64_t seed, void* device_visits, void* device_returns,
                       void* device_action);
 
+/* PGX solve (no reference analogue; the four PGX board games): the exact minimax value of every listed env's current
+ * position -- the state after every send / reset issued before the call, as for epa_snapshot -- per root action, by
+ * alpha-beta in one kernel launch, one wave per root.  No model, no random numbers; nothing of the pool changes and no
+ * result rows are produced.  The contract (csrc/pgx_solve.hip.h), D = depth, A = the game's number of actions:
+ *   D = 0 means no horizon, up to EPA_SOLVE_MAX_DEPTH plies (a whole Hex or Othello game fits).  T_D(root) is the game
+ *   tree from the root, cut after D plies.  A leaf that is a finished game has the value of its last step's reward for
+ *   the mover at the root (+1, 0, -1); a leaf cut by the horizon has value 0; interior values are plain minimax, an
+ *   Othello pass and Hex's swap being plies like any other.  Results, row i for env_ids[i]:
+ *     value  [k]    int8    the maximum of q over the legal actions
+ *     q      [k, A] int8    per legal root action the minimax value of T_D through it, seen from the root's mover;
+ *                           -128 for an illegal action
+ *     action [k]    int32   the lowest legal action whose q equals value
+ *     status [k]    uint8   0 solved; 1 given up: more than max_nodes positions were visited for this root, or a line
+ *                           went past EPA_SOLVE_MAX_DEPTH plies; 2 the env is over at the call (every env before its
+ *                           first reset is).  A row with status 1 or 2 has value 0, action -1 and q -128 throughout.
+ *     nodes  [k]    int64   the positions visited
+ *   With D > 0, value +1 means a forced win within D plies, -1 a forced loss within D plies, 0 neither: the tactical
+ *   check of bounded cost.  D = 0 gives the game-theoretic value.
+ *   The values are exact and so independent of the traversal.  `nodes`, and which rows are given up at a tight
+ *   max_nodes, depend on it (max_nodes is looked at between rounds of 512 positions per lane, so a row that is given
+ *   up reports somewhat more than max_nodes; a solved row never does); for them the contract is determinism: the same
+ *   call gives the same bytes, and a row depends on its position, D and max_nodes only, not on the order of the ids,
+ *   repeated ids or how the pool is sharded.
+ *   EPA_ERR_INVALID, before any launch: D outside 0 .. EPA_SOLVE_MAX_DEPTH, max_nodes < 1, k <= 0, more than num_envs
+ *     ids or an id outside the pool (the id checks of epa_search), and stacks (k roots x 64 lanes x D plies, D = 0:
+ *     EPA_SOLVE_MAX_DEPTH, x 80 bytes) above EPA_SEARCH_MAX_TREE_BYTES: the message names the largest k that fits.
+ *   Every other family fails with EPA_ERR_RUNTIME "solve not implemented for this environment".
+ *   A position that is no position of the game (a running game without a legal action) sets the pool's error word:
+ *   epa_solve and the next recv fail with EPA_ERR_RUNTIME, and that root's row is given up.
+ * A row is epa_search_actions wide.  epa_solve returns the results in host memory (one stream synchronisation).
+ * epa_solve_device writes them to device memory of the pool's device (action 4-byte, nodes 8-byte aligned) and only
+ * enqueues on epa_stream(pool), like epa_search_device. */
+#define EPA_SOLVE_MAX_DEPTH 128
+int epa_solve(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t depth, int64_t max_nodes, int8_t* value,
+              int8_t* q, int32_t* action, uint8_t* status, int64_t* nodes);
+int epa_solve_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t depth, int64_t max_nodes,
+                     void* device_value, void* device_q, void* device_action, void* device_status,
+                     void* device_nodes);
+
 /* Guided tree search (no reference analogue; the four PGX board games): a PUCT search whose tree lives on the device
  * between calls and that stops at every new leaf, so that the caller -- a policy / value model next to the pool in
  * HBM -- supplies the priors and the leaf values (AlphaZero-style).  One kernel launch per simulation, one wave per
