@@ -358,15 +358,18 @@ class _ShardedPools:
                 np.empty(lead, dtype=np.uint8))
 
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
-                     nodes: int = 0, width: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     nodes: int = 0, width: Any = None, tactics: int = 0,
+                     tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A session in every shard that owns listed envs, all shards at once.  The search has no random numbers and
         no dependence on the env id, so the rows are those of the unsharded pool.  `width`: a wide session in every
-        shard (`DevicePool.guided_begin`)."""
+        shard (`DevicePool.guided_begin`).  `tactics`, `tactics_nodes`: the exact leaf status in every shard; what it
+        decides depends on the leaf's position alone, so the rows stay those of the unsharded pool."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
         ids = native.check_guided(env_ids, simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
+        tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
         h, w, c, a = self.guided_shape()
         shard = (ids - self.offset) // self.per
         bad = ids[(shard < 0) | (shard >= len(self.pools))]
@@ -376,6 +379,8 @@ class _ShardedPools:
         k = len(ids)
         leaves = self._guided_empty(k, width)
         extra = (int(nodes or 0), width) if width else ((nodes,) if nodes else ())
+        if tactics:
+            extra = (int(nodes or 0), width or None, tactics, tactics_nodes)
 
         def begin(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct, *extra)):
@@ -435,6 +440,17 @@ class _ShardedPools:
 
         self._each(result, parts)
         return out
+
+    def guided_decided(self, with_nodes: bool = False) -> Any:
+        k, a, parts = self._guided_session("guided_decided")
+        out = (np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int64))
+
+        def decided(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(out, p.guided_decided(with_nodes=True)):
+                o[idx] = part
+
+        self._each(decided, parts)
+        return out if with_nodes else out[0]
 
     def guided_end(self) -> None:
         _, _, parts = self._guided_session("guided_end")

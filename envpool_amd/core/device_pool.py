@@ -549,7 +549,8 @@ class DevicePool:
                 np.empty(lead, dtype=np.uint8))
 
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
-                     nodes: int = 0, width: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     nodes: int = 0, width: Any = None, tactics: int = 0,
+                     tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Opens the pool's guided-search session (the PGX board games; RuntimeError("guided search not implemented
         for this environment") elsewhere) on the current positions of the listed envs (global ids; None: the whole
         pool), replacing any earlier one: a PUCT search whose tree stays on the device and that stops at every new
@@ -560,13 +561,21 @@ class DevicePool:
         the room `guided_reroot` needs to keep a subtree and grow it.  `width` = W, 1 .. 32, opens a WIDE session
         (epa_guided_begin_wide): W slots per root, up to W leaves per root and advance, steered apart by virtual
         losses; every leaf array and the rows of `guided_advance` then carry a slot axis ([k, W, ...]), a slot of
-        status 2 has nothing pending, and the round is complete when all statuses are 2.  None: a plain session."""
+        status 2 has nothing pending, and the round is complete when all statuses are 2.  None: a plain session.
+        `tactics` = D, 1 .. 16, turns on the exact leaf status (epa_guided_begin_tactics): every new leaf other than
+        the root is solved D plies deep with at most `tactics_nodes` positions, and a leaf that is a forced win or loss
+        comes back with status 1 and backs up +-1 for good; 0: off, today's calls."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
+        tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
         self.guided_shape()
         obs, mask, status = self._guided_leaves(len(ids), width)
-        if width:
+        if tactics:
+            native.check(self._lib.epa_guided_begin_tactics(
+                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+                tactics_nodes, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
+        elif width:
             native.check(self._lib.epa_guided_begin_wide(self._h, ids.ctypes.data, len(ids), int(simulations),
                                                          int(nodes or 0), width, float(c_puct), obs.ctypes.data,
                                                          mask.ctypes.data, status.ctypes.data))
@@ -639,13 +648,28 @@ class DevicePool:
         native.check(self._lib.epa_guided_result(self._h, visits.ctypes.data, values.ctypes.data, action.ctypes.data))
         return visits, values, action
 
+    def guided_decided(self, with_nodes: bool = False) -> Any:
+        """int32 [k]: the leaves the exact leaf status decided per root since guided_begin (zeros without `tactics`); a
+        reroot does not reduce it.  with_nodes: (decided, int64 [k] positions the solver visited per root)."""
+        k = self._guided_open("guided_decided", "puct")
+        decided, nodes = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int64)
+        native.check(self._lib.epa_guided_decided(self._h, decided.ctypes.data, nodes.ctypes.data))
+        return (decided, nodes) if with_nodes else decided
+
+    def guided_decided_device(self, d_decided: int, d_nodes: int = 0) -> None:
+        """`guided_decided` into device memory (int32 [k]; `d_nodes`: int64 [k] or 0): only enqueued."""
+        self._guided_open("guided_decided", "puct")
+        native.check(self._lib.epa_guided_decided_device(self._h, ctypes.c_void_p(d_decided),
+                                                         ctypes.c_void_p(d_nodes or None)))
+
     def guided_end(self) -> None:
         """Closes the session (of either policy) and releases its device memory; ValueError without one."""
         native.check(self._lib.epa_guided_end(self._h))
         self._guided_k = None
 
     def guided_begin_device(self, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None, simulations: int = 64,
-                            c_puct: float = 1.25, nodes: int = 0, width: Any = None) -> int:
+                            c_puct: float = 1.25, nodes: int = 0, width: Any = None, tactics: int = 0,
+                            tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> int:
         """`guided_begin` with the leaves written to device memory at the raw addresses `d_obs` (k H W C bytes),
         `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k.  With `width`
         = W the arrays have k W rows, and so have those of `guided_advance_device` (its `k` is k W) and of
@@ -653,7 +677,12 @@ class DevicePool:
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
-        if width:
+        tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
+        if tactics:
+            native.check(self._lib.epa_guided_begin_tactics_device(
+                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+                tactics_nodes, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        elif width:
             native.check(self._lib.epa_guided_begin_wide_device(
                 self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct),
                 ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))

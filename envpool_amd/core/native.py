@@ -30,6 +30,9 @@ PLAYOUT_MAX_REPEATS = 4096
 SEARCH_MAX_SIMULATIONS = 4096
 GUIDED_MAX_NODES = 8192  # EPA_GUIDED_MAX_NODES: the largest node capacity of a guided-search root
 GUIDED_MAX_WIDTH = 32    # EPA_GUIDED_MAX_WIDTH: the most slots (leaves per launch) of a wide guided-search root
+GUIDED_MAX_TACTICS = 16  # EPA_GUIDED_MAX_TACTICS: the largest horizon of a guided search's exact leaf status
+GUIDED_MAX_TACTICS_NODES = 1 << 20  # EPA_GUIDED_MAX_TACTICS_NODES: the largest node budget of one leaf's solve
+GUIDED_TACTICS_NODES = 4096         # EPA_GUIDED_TACTICS_NODES: its default
 GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per launch) of a batch Gumbel root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
@@ -147,6 +150,12 @@ def lib() -> ctypes.CDLL:
         "epa_guided_reroot_device": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "epa_guided_begin_wide": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "epa_guided_begin_wide_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
+        "epa_guided_begin_tactics": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, ctypes.c_int64, vp, vp,
+                                           vp]),
+        "epa_guided_begin_tactics_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, ctypes.c_int64, vp,
+                                                  vp, vp]),
+        "epa_guided_decided": (i32, [vp, vp, vp]),
+        "epa_guided_decided_device": (i32, [vp, vp, vp]),
         "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_begin_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
         "epa_gumbel_begin_batch": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
@@ -195,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
     "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
     "epa_guided_begin_wide", "epa_guided_begin_wide_device",
+    "epa_guided_begin_tactics", "epa_guided_begin_tactics_device", "epa_guided_decided", "epa_guided_decided_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device", "epa_gumbel_begin_batch", "epa_gumbel_begin_batch_device",
     "epa_atari_post_create",
@@ -324,6 +334,19 @@ def check_guided_width(width: Any) -> int:
     if isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= GUIDED_MAX_WIDTH:
         raise ValueError(f"guided_begin: width = {width} must be 1 .. {GUIDED_MAX_WIDTH}")
     return int(width)
+
+
+def check_guided_tactics(tactics: Any, tactics_nodes: Any) -> tuple[int, int]:
+    """(D, M) of a guided_begin call's exact leaf status after their checks: ValueError for a `tactics` outside 0 .. 16
+    (None or 0: off) or a `tactics_nodes` outside 1 .. 2^20."""
+    if tactics is None:
+        tactics = 0
+    if isinstance(tactics, bool) or int(tactics) != tactics or not 0 <= int(tactics) <= GUIDED_MAX_TACTICS:
+        raise ValueError(f"guided_begin: tactics = {tactics} must be 0 .. {GUIDED_MAX_TACTICS}")
+    if (isinstance(tactics_nodes, bool) or int(tactics_nodes) != tactics_nodes
+            or not 1 <= int(tactics_nodes) <= GUIDED_MAX_TACTICS_NODES):
+        raise ValueError(f"guided_begin: tactics_nodes = {tactics_nodes} must be 1 .. {GUIDED_MAX_TACTICS_NODES}")
+    return int(tactics), int(tactics_nodes)
 
 
 def check_guided_wide_rows(priors: Any, values: Any, k: int, width: int, actions: int) -> tuple[np.ndarray, np.ndarray]:

@@ -200,6 +200,16 @@ struct GuidedArgs {
   int32_t* action;          // [k]
 };
 
+// The solver stage of an advance of a guided session with tactics (Pool::GuidedTactics; pgx_guided.hip.h "Exact leaf
+// status"): the horizon and the node budget of a leaf's solve, the session's counters and the slots' stacks.
+struct TacticsArgs {
+  int depth;                // D: 1 .. EPA_GUIDED_MAX_TACTICS
+  long long max_nodes;      // M
+  int32_t* decided;         // [k]: leaves decided since begin
+  long long* nodes;         // [k]: positions the solver visited since begin, 8-byte aligned
+  void* stack;              // [k * max(width, 1)] stacks of Pool::SolveRootBytes(D) bytes, 16-byte aligned
+};
+
 // One launch of a Gumbel-search session (Pool::GumbelBegin / GumbelAdvance / GumbelResult; pgx_gumbel.hip.h): as
 // GuidedArgs, with the Gumbel noise at begin, logits instead of priors, and the improved policy among the results.
 struct GumbelArgs {
@@ -448,6 +458,8 @@ class Pool {
   virtual void GuidedAdvance(const GuidedArgs& a);
   virtual void GuidedResult(const GuidedArgs& a);
   virtual void GuidedReroot(const GuidedArgs& a);
+  // exact leaf status (pgx_guided.hip.h "Exact leaf status"): the solver stage after an advance's descents
+  virtual void GuidedTactics(const GuidedArgs& a, const TacticsArgs& t);
   // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; the four hooks above serve
   // them too (a.width != 0: the family chooses its kernels)
   virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
@@ -459,6 +471,12 @@ class Pool {
   // ... with `width` slots per root (0: a plain session): the leaf arrays have k * width rows from then on
   void GuidedBeginWideCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct, void* obs,
                            void* mask, void* status, bool device);
+  // Exact leaf status: begin with tactics = D (0: off, exactly the calls above) and tactics_nodes = M; width 0: a
+  // plain session.  GuidedDecidedCall: the session's counters, decided int32 [k] and (may be null) the solver's
+  // visited positions int64 [k]; the device form only enqueues.
+  void GuidedBeginTacticsCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct,
+                              int tactics, long long tactics_nodes, void* obs, void* mask, void* status, bool device);
+  void GuidedDecidedCall(void* decided, void* nodes, bool device);
   // Tree reuse (pgx_guided.hip.h "Tree reuse"): after the round's last advance, the subtree under actions[i] becomes
   // root i's tree, `simulations` the length of the next round, and the new roots are emitted as begin emits its own.
   // actions: a host array (checked against 0 .. A-1 here) or a device pointer (the kernel ends such a root).  PUCT
@@ -686,7 +704,8 @@ class Pool {
   // the pool's guided-search session
   struct GuidedSession {
     bool open{false};
-    DeviceBlock mem;        // the session's one device allocation: roots, nodes, then the host forms' staging
+    DeviceBlock mem;        // the session's one device allocation: roots, nodes, the host forms' staging, and with
+                            // tactics the counters and the solver's stacks
     char* pinned{nullptr};  // the host forms' pinned block, laid out like the staging
     bool gumbel{false};     // the session's policy: PUCT or Gumbel
     int k{0}, simulations{0}, calls{0};
@@ -697,6 +716,9 @@ class Pool {
     int considered{0};      // Gumbel: m, c_visit, c_scale
     float c_visit{0.0f}, c_scale{0.0f};
     size_t nodes_off{0}, stage_off{0};
+    int tactics{0};         // exact leaf status: D (0: off), M, and the offset of its block behind the staging:
+    long long tactics_nodes{0};  // decided int32 [k], nodes int64 [k], then the slots' stacks
+    size_t tactics_off{0};
     // offsets into the staging: priors (Gumbel: the noise at begin, then logits), values, obs, mask, status, visits,
     // vals, action, the end of a PUCT session's staging, and behind it a Gumbel session's weights and their end
     size_t off[10]{};
@@ -706,6 +728,7 @@ class Pool {
   void GuidedRequire(const char* what) const;          // throws without a session
   void GuidedRequirePolicy(const char* what, bool gumbel) const;  // ... or with one of the other policy
   GuidedArgs GuidedArgsOf(bool device) const;          // the session's pointers; staging arrays for a host form
+  TacticsArgs TacticsArgsOf() const;                   // (a session with tactics)
   GumbelArgs GumbelArgsOf(bool device) const;
   uint64_t family_hash_{0};
   // concurrent batches (async mode)

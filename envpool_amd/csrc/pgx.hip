@@ -30,7 +30,8 @@
 // Gumbel search: pgx_gumbel.hip.h, the same session with Gumbel root sampling, sequential halving and the improved
 // policy as its result (PgxGumbelBegin / PgxGumbelAdvance / PgxGumbelResult).
 // Exact solve: pgx_solve.hip.h, alpha-beta with the top of the tree in LDS and the lanes' stacks in the pool's side
-// scratch (PgxSolveKernel).
+// scratch (PgxSolveKernel).  Its traversal (SolveWave) also serves the exact leaf status of a guided session with
+// tactics (PgxGuidedTactics, a launch behind every advance: a wave per slot solves the slot's new leaf).
 #include <algorithm>
 #include <string>
 
@@ -340,6 +341,61 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
 constexpr unsigned kErrSolve = 5;  // a solve met a running position without a legal action
 static_assert(pgx::kSolveMaxDepth == EPA_SOLVE_MAX_DEPTH, "the C ABI states the header's limits");
 
+// what the traversal of one root came to: the positions visited, whether the root is given up, the broken flag
+struct SolveOutcome {
+  long long nodes;
+  bool gave_up;
+  int broken;
+};
+
+// The traversal for the block's root, shared by PgxSolveKernel and PgxGuidedTactics: the top tree, the rounds.  Every
+// field of the outcome is wave-uniform.  A root that is not given up has every child of the root known after one more
+// SolveCombine, which the caller's lane 0 runs (it has made every earlier LDS hand-off already).
+template <int G>
+__device__ __forceinline__ SolveOutcome SolveWave(pgx::SolveTop& top, const pgx::State& root, pgx::SolveWord* stack,
+                                                  int depth, long long max_nodes, int lane) {
+  const int limit = pgx::SolveLimit(depth);
+  const bool hard = depth == 0;
+  if (lane == 0) pgx::SolveTopInit(top, root);
+  pgx::SolveFlags flags{0, root.m == 0 ? 1 : 0};
+  long long count = 1;
+  bool gave_up = pgx::SolveGaveUp(count, max_nodes, flags);
+  __syncthreads();
+  while (!gave_up) {  // the top tree
+    if (lane == 0) pgx::SolveTopPlan(top);
+    __syncthreads();
+    const int hi = top.hi, next = top.next_n;
+    if (next == top.n) break;
+    for (int c = hi + lane; c < next; c += kSearchBlock) pgx::SolveTopMake<G>(top, c, limit, hard, flags);
+    flags.overflow = tree::WaveMax(flags.overflow);
+    flags.broken = tree::WaveMax(flags.broken);
+    __syncthreads();
+    if (lane == 0) pgx::SolveTopAdvance(top);
+    __syncthreads();
+    count = next;
+    gave_up = pgx::SolveGaveUp(count, max_nodes, flags);
+  }
+  if (!gave_up) {
+    if (lane == 0) pgx::SolveTopFrontier(top);
+    __syncthreads();
+    pgx::SolveLane l;
+    pgx::SolveLaneInit(l, lane);
+    for (;;) {  // the rounds
+      if (tree::WaveMax(pgx::SolveLaneBusy(l, top) ? 1 : 0) == 0) break;
+      pgx::SolveLaneSlice<G>(l, top, stack, lane, pgx::kSolveSlice, limit, hard);
+      count = top.n + tree::WaveSum(l.visited);
+      flags.overflow = tree::WaveMax(flags.overflow | l.flags.overflow);
+      flags.broken = tree::WaveMax(flags.broken | l.flags.broken);
+      gave_up = pgx::SolveGaveUp(count, max_nodes, flags);
+      __syncthreads();
+      if (gave_up) break;
+      if (lane == 0) pgx::SolveCombine(top);
+      __syncthreads();
+    }
+  }
+  return SolveOutcome{count, gave_up, flags.broken};
+}
+
 template <int G>
 __global__ __launch_bounds__(kSearchBlock) void PgxSolveKernel(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, SolveArgs a,
@@ -357,54 +413,16 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSolveKernel(CommonDev cm, con
     }
     return;
   }
-  const int limit = pgx::SolveLimit(a.depth);
-  const bool hard = a.depth == 0;
   pgx::SolveWord* stack =
       reinterpret_cast<pgx::SolveWord*>(static_cast<char*>(a.stack) + (size_t)row * pgx::SolveStackBytes(a.depth));
   const pgx::State root = st[e];
-  if (lane == 0) pgx::SolveTopInit(top, root);
-  pgx::SolveFlags flags{0, root.m == 0 ? 1 : 0};
-  long long count = 1;
-  bool gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
-  __syncthreads();
-  while (!gave_up) {  // the top tree
-    if (lane == 0) pgx::SolveTopPlan(top);
-    __syncthreads();
-    const int hi = top.hi, next = top.next_n;
-    if (next == top.n) break;
-    for (int c = hi + lane; c < next; c += kSearchBlock) pgx::SolveTopMake<G>(top, c, limit, hard, flags);
-    flags.overflow = tree::WaveMax(flags.overflow);
-    flags.broken = tree::WaveMax(flags.broken);
-    __syncthreads();
-    if (lane == 0) pgx::SolveTopAdvance(top);
-    __syncthreads();
-    count = next;
-    gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
-  }
-  if (!gave_up) {
-    if (lane == 0) pgx::SolveTopFrontier(top);
-    __syncthreads();
-    pgx::SolveLane l;
-    pgx::SolveLaneInit(l, lane);
-    for (;;) {  // the rounds
-      if (tree::WaveMax(pgx::SolveLaneBusy(l, top) ? 1 : 0) == 0) break;
-      pgx::SolveLaneSlice<G>(l, top, stack, lane, pgx::kSolveSlice, limit, hard);
-      count = top.n + tree::WaveSum(l.visited);
-      flags.overflow = tree::WaveMax(flags.overflow | l.flags.overflow);
-      flags.broken = tree::WaveMax(flags.broken | l.flags.broken);
-      gave_up = pgx::SolveGaveUp(count, a.max_nodes, flags);
-      __syncthreads();
-      if (gave_up) break;
-      if (lane == 0) pgx::SolveCombine(top);
-      __syncthreads();
-    }
-  }
+  const SolveOutcome out = SolveWave<G>(top, root, stack, a.depth, a.max_nodes, lane);
   if (lane == 0) {
-    a.nodes[row] = count;
-    if (gave_up) {
+    a.nodes[row] = out.nodes;
+    if (out.gave_up) {
       pgx::SolveNoResult<G>(q, a.value + row, a.action + row);
       a.status[row] = (uint8_t)pgx::kSolveGivenUp;
-      if (flags.broken) *err = kErrSolve;
+      if (out.broken) *err = kErrSolve;
     } else {
       pgx::SolveCombine(top);
       pgx::SolveRootResult<G>(top, q, a.value + row, a.action + row);
@@ -679,6 +697,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
         }
       }
       count = kept;
+      // exact leaf status, rule 5: a decided node that becomes the root runs on (lane 0 copied it to node 0 above)
+      if (pgx::GuidedTacticsReopen(s) && lane == 0) nodes[0].s.done = 0;
     }
     over = s.done != 0;
   }
@@ -824,6 +844,62 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
   }
   WaveRelease();
   GuidedEmitIdle<G>(a, row * W + j, W - j, lane);
+}
+
+// Exact leaf status (pgx_guided.hip.h "Exact leaf status"): the solver stage of an advance of a session with
+// tactics = D > 0, enqueued on the same stream right after PgxGuidedAdvance or PgxGuidedAdvanceWide, whose record
+// stores it loads (the header's release / acquire rule between launches).  One wave per slot, one block per wave:
+// block i * W + j looks at slot j of root i (W = 1 for a plain session) and returns at once unless rule 1 hands the
+// slot's leaf to the solver.  Otherwise it is PgxSolveKernel's traversal (SolveWave) on the leaf's position with the
+// slot's own stack out of the session's memory, and for a decided leaf lane 0 marks the node, sets the slot's status
+// and bumps the root's counter (an atomic add: a root's slots are different blocks), and the wave zeroes the slot's
+// obs and mask rows (GuidedEmitLeaf: 16-byte words where aligned).  Two slots of status 0 never share a node, so no
+// two blocks write the same node or slot.  Every branch around a barrier depends on loads of one address or on
+// SolveWave's wave-uniform outcome.
+static_assert(pgx::kGuidedMaxTactics == EPA_GUIDED_MAX_TACTICS &&
+                  pgx::kGuidedMaxTacticsNodes == EPA_GUIDED_MAX_TACTICS_NODES,
+              "the C ABI states the header's limits");
+template <int G, bool WIDE>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedTactics(GuidedArgs a, TacticsArgs t) {
+  using Node = pgx::GuidedNode<G>;
+  __shared__ pgx::SolveTop top;
+  const int W = WIDE ? a.width : 1;
+  const int slot = blockIdx.x, row = slot / W, lane = threadIdx.x;
+  int32_t* status_at;
+  int32_t* pending_at;
+  if (WIDE) {
+    pgx::GuidedWideSlot& sl = pgx::GuidedWideSlots(pgx::GuidedWideRootAt(a.roots, row, a.width))[slot - row * W];
+    status_at = &sl.status;
+    pending_at = &sl.pending;
+  } else {
+    pgx::GuidedRoot& rec = static_cast<pgx::GuidedRoot*>(a.roots)[row];
+    status_at = &rec.status;
+    pending_at = &rec.pending;
+  }
+  WaveAcquire();
+  const int pending = *pending_at;
+  if (!pgx::GuidedTacticsLooksAt(*status_at, pending) || pending < 0 || pending >= a.capacity) return;
+  Node& leaf = (static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity)[pending];
+  const pgx::State s = leaf.s;
+  if (s.done) return;  // (never with status 0)
+  pgx::SolveWord* stack =
+      reinterpret_cast<pgx::SolveWord*>(static_cast<char*>(t.stack) + (size_t)slot * pgx::SolveStackBytes(t.depth));
+  const SolveOutcome out = SolveWave<G>(top, s, stack, t.depth, t.max_nodes, lane);
+  if (lane == 0) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(t.nodes + row), (unsigned long long)out.nodes);
+    if (!out.gave_up) pgx::SolveCombine(top);
+  }
+  if (out.gave_up) return;  // rule 2: everything stays as it was
+  __syncthreads();
+  const int v = top.val[0];  // the root's minimax value: every child is known
+  if (!pgx::GuidedTacticsDecides(pgx::kSolveSolved, v == pgx::kSolveUnknown ? 0 : v)) return;
+  if (lane == 0) {
+    pgx::GuidedTacticsMark<G>(leaf, v);
+    *status_at = pgx::kGuidedTerminal;
+    atomicAdd(t.decided + row, 1);
+  }
+  WaveRelease();
+  GuidedEmitLeaf<G>(a, slot, lane, pgx::kGuidedTerminal, s);
 }
 
 // Gumbel search (pgx_gumbel.hip.h): the session, lane ownership, hand-offs and leaves of the guided kernels above with
@@ -1370,6 +1446,13 @@ class PgxPool : public Pool {
         LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false>, a.k, a);
       }
     });
+  }
+  void GuidedTactics(const GuidedArgs& a, const TacticsArgs& t) override {
+    if (a.width != 0) {
+      LaunchRoots(PgxGuidedTactics<G, true>, a.k * a.width, a, t);
+    } else {
+      LaunchRoots(PgxGuidedTactics<G, false>, a.k, a, t);
+    }
   }
   size_t GumbelNodeBytes() const override { return sizeof(pgx::GumbelNode<G>); }
   size_t GumbelRootBytes() const override { return sizeof(pgx::GumbelRoot<G>); }

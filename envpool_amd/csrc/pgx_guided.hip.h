@@ -124,6 +124,33 @@
 // while any status is not 2.  The device form cannot look: slots still pending there are dropped, their paths
 // discarded and nothing backed up; their nodes stay unevaluated (priors 0) -- the caller finishes the round first.
 //
+// Exact leaf status (DESIGN.md "PGX guided search: exact leaf status").  A PUCT session, plain or wide, may be begun
+// with tactics = D (1 .. kGuidedMaxTactics; 0: off, and nothing below applies) and tactics_nodes = M (1 .. 2^20).
+// advance then has one more stage, AFTER all descents of the launch and before the leaves are final:
+//   1. looked at: every slot whose status is 0 and whose pending leaf is not node 0 (GuidedTacticsLooksAt).  The root
+//      is always handed out for evaluation; slots of status 1 or 2 are not looked at.
+//   2. the leaf's position goes to the solver under the contract of pgx_solve.hip.h, unchanged: T_D of that position
+//      with max_nodes = M.  Solve status "solved" and value v != 0: the leaf is DECIDED (GuidedTacticsDecides).  A
+//      value of 0, or a leaf given up, leaves everything as it was: the caller evaluates that leaf.
+//   3. a decided leaf is, for the rest of the session, a finished game whose last reward is v for the seat that moves
+//      there (GuidedTacticsMark): State.done = kGuidedDecided (a second non-zero value, so every test of `done` treats
+//      the node as finished), term0 = SearchSign(leaf) * v.  The slot's status becomes 1 and its obs and mask rows
+//      zeros; the caller's row for it is ignored, the next advance backs up (float) term0 along the slot's path, and a
+//      later descent that arrives at the node stops there with status 1, exactly as at a finished game.
+//   4. wide sessions: the decision comes after the launch's descents.  Inside the launch a later descent that reaches
+//      the new leaf still meets a status-0 pending leaf: a COLLISION by the rule above.  From the next launch on two
+//      slots may reach the decided node together; both have status 1 and both back up term0, as for a finished game.
+//   5. reroot: a decided node that becomes the new root (c >= 0) stops being decided (GuidedTacticsReopen): its game
+//      runs on, it is handed out with status 0, its term0 is not used, and result() does not report -1 for it.
+//      Decided nodes deeper in the kept subtree stay decided, bit for bit.  c < 0 makes a fresh root, undecided.  The
+//      new root is node 0, which rule 1 never looks at: reroot has no solver stage.
+//   6. result() is unchanged.  `decided` int32 [k] counts the leaves decided since begin and is not reduced by reroot.
+//   7. the solver's values are exact and its given-up rows depend on the position, D and M only, so which leaves are
+//      decided depends on the session's arguments, the positions and the caller's rows -- not on id order or sharding.
+// In one sentence: the session is the plain guided search of the game in which a decided position counts as finished
+// with result v.  The mark lives in State.done, the counters in a block of their own per session: GuidedNode and the
+// root records are unchanged, and a session with tactics = 0 is, byte for byte, the one described above.
+//
 // There are no random numbers.  Only seat 0's value is stored, as in pgx_search.hip.h: the games are zero-sum.  Build
 // without fast-math and with -ffp-contract=off.
 #ifndef ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
@@ -265,6 +292,28 @@ PGX_HD inline void GuidedWideClearRoot(GuidedWideRoot& r, int width, int count, 
     sl[j].status = (j == 0 && !over) ? kGuidedEvaluate : kGuidedIdle;
     sl[j].depth = 0;
   }
+}
+
+// ---- exact leaf status: tactics = D ----
+constexpr int kGuidedMaxTactics = 16;              // the largest horizon D
+constexpr long long kGuidedMaxTacticsNodes = 1 << 20;  // the largest M
+constexpr int kGuidedDecided = 2;                  // State.done of a decided node (1: the game ended by a step)
+
+// rule 1: a slot's leaf goes to the solver
+PGX_HD inline bool GuidedTacticsLooksAt(int status, int pending) { return status == kGuidedEvaluate && pending != 0; }
+// rule 2: what the solver said decides the leaf (solve_status: SolveStatus of pgx_solve.hip.h, 0 = solved)
+PGX_HD inline bool GuidedTacticsDecides(int solve_status, int value) { return solve_status == 0 && value != 0; }
+// rule 3: the node of a decided leaf; v is its value for the seat that moves there
+template <int G>
+PGX_HD inline void GuidedTacticsMark(GuidedNode<G>& leaf, int v) {
+  leaf.term0 = SearchSign<G>(leaf.s) * v;
+  leaf.s.done = kGuidedDecided;
+}
+// rule 5: the position of a node that becomes the root; true: it was decided and runs on now
+PGX_HD inline bool GuidedTacticsReopen(State& s) {
+  if (s.done != kGuidedDecided) return false;
+  s.done = 0;
+  return true;
 }
 
 // bytes of one emitted obs row: the mover's [H, W, C] block of the kObs key

@@ -85,15 +85,26 @@ class GuidedSearch:
         while playing:
             result = gs.run(evaluate, close=False)      # about 9 model calls of 8 k rows, not 65 of k
             env.step(result.action, ids)
-            gs.reroot(result.action)"""
+            gs.reroot(result.action)
+
+    Exact leaf status: `tactics=D` (1 .. 16) solves every new leaf other than the root D plies deep (the solver of
+    `env.solve`, at most `tactics_nodes` positions per leaf) after the advance's descents.  A leaf that is a forced win
+    or loss within D plies needs no evaluation: it comes back with status 1 and zero rows, whatever `advance` is given
+    for it is ignored, and the exact +-1 is backed up from then on, as for a finished game.  Every other leaf is
+    evaluated as before.  `decided` counts such leaves per root.  After `reroot` onto a decided position the game runs
+    on: the new root is handed out for evaluation like any other."""
 
     def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float, nodes: Any = None,
-                 width: int = 1):
+                 width: int = 1, tactics: int = 0, tactics_nodes: int = native.GUIDED_TACTICS_NODES):
         self._pool = pool
         self.simulations = int(simulations)
         self.calls = 0
         self.width = int(width)
-        if self.width > 1:
+        self.tactics = int(tactics)
+        if self.tactics:
+            self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes or 0),
+                                            self.width if self.width > 1 else None, self.tactics, int(tactics_nodes))
+        elif self.width > 1:
             self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes or 0), self.width)
         elif nodes is None:
             self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct))
@@ -104,6 +115,14 @@ class GuidedSearch:
     def done(self) -> bool:
         """Whether the round is complete: nothing is pending, all statuses are 2."""
         return bool((np.asarray(self.leaves[2]) == 2).all())
+
+    @property
+    def decided(self) -> np.ndarray:
+        """int32 [k]: the leaves the exact leaf status (`tactics=`) decided per root since the session began; a reroot
+        does not reduce it.  Zeros without `tactics`."""
+        if self._pool is None:
+            raise ValueError("guided search: the session is closed")
+        return self._pool.guided_decided()
 
     def advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         if self._pool is None:
@@ -419,7 +438,8 @@ class EnvPoolMixin(ABC):
         return Solve(*self._solve(ids, int(depth), int(max_nodes)))
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
-                      nodes: Any = None, width: int = 1, **gumbel: Any) -> Any:
+                      nodes: Any = None, width: int = 1, tactics: int = 0,
+                      tactics_nodes: int = native.GUIDED_TACTICS_NODES, **gumbel: Any) -> Any:
         """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
         (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
@@ -429,9 +449,14 @@ class EnvPoolMixin(ABC):
         `nodes` (PUCT only): the node capacity per root, simulations + 1 ..
         8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree.  `width`
         (PUCT only), 1 .. 32: the leaves per root and launch (`GuidedSearch`: "Several leaves per launch"); 1 is the
-        plain session."""
+        plain session.  `tactics` (PUCT only), 1 .. 16: the exact leaf status (`GuidedSearch`: "Exact leaf status"),
+        every new leaf solved that many plies deep with at most `tactics_nodes` (1 .. 2^20) positions; 0: off."""
         native.check_guided_width(width)
+        tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
         if policy == "gumbel":
+            if tactics:
+                raise ValueError("guided_search: tactics is an argument of policy='puct' (exact leaf status not "
+                                 "implemented for gumbel sessions)")
             if width != 1:
                 raise ValueError("guided_search: width is an argument of policy='puct' (several leaves per launch not "
                                  "implemented for gumbel sessions)")
@@ -447,11 +472,14 @@ class EnvPoolMixin(ABC):
                                   simulations, c_puct)
         if nodes is not None:
             native.check_guided_nodes(simulations, nodes)
+        if tactics:
+            return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes, int(width), tactics,
+                                tactics_nodes)
         return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes, int(width))
 
     def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
                       seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1,
-                      width: int = 1, batch: int = 1) -> GumbelSearch:
+                      width: int = 1, batch: int = 1, tactics: int = 0) -> GumbelSearch:
         """Extension (the PGX board games): opens a Gumbel search (Danihelka et al., ICLR 2022) from the current
         position of every listed env (global ids; None: all): Gumbel top-`max_considered` sampling without replacement
         at the root, sequential halving of the `simulations` over those actions, a deterministic rule inside the tree;
@@ -465,6 +493,9 @@ class EnvPoolMixin(ABC):
         if width != 1:
             raise ValueError("gumbel_search: width is an argument of policy='puct' (several leaves per launch not "
                              "implemented for gumbel sessions)")
+        if tactics:
+            raise ValueError("gumbel_search: tactics is an argument of policy='puct' (exact leaf status not implemented "
+                             "for gumbel sessions)")
         native.check_gumbel_batch(batch)
         ids = native.check_gumbel(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, max_considered, c_visit, c_scale)

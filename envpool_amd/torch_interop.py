@@ -294,7 +294,8 @@ def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations
 
 def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
                          c_puct: float = 1.25, nodes: Any = None, keep_open: bool = False, width: Any = None,
-                         advances: Any = None) -> tuple[Any, Any, Any]:
+                         advances: Any = None, tactics: int = 0,
+                         tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[Any, Any, Any]:
     """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
     gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
     and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
@@ -306,7 +307,10 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     of root i; a slot of status 2 has nothing pending), so a model function written for the plain session works
     unchanged.  `advances=None` reads one reduced status byte per launch -- the one host wait -- and stops when the
     round is complete; an integer makes exactly that many advances with no host wait: roots that are not finished then
-    simply have fewer visits, which the result shows."""
+    simply have fewer visits, which the result shows.
+    `tactics` = D (1 .. 16), `tactics_nodes`: the exact leaf status (`DevicePool.guided_begin`): the solver's launch
+    is enqueued behind every advance, so `evaluate` sees decided leaves as rows of status 1; the session keeps it
+    through `guided_reroot_device`, and `guided_decided_device` gives the counters (before the session is closed)."""
     import torch
 
     if env_ids is None:
@@ -314,6 +318,7 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     ids = native.check_guided(env_ids, simulations, c_puct)
     native.check_guided_nodes(simulations, nodes)
     width = native.check_guided_width(width)
+    tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
     if advances is not None and not width:
         raise ValueError("guided_search_device: advances is an argument of a wide session (width=)")
     h, w, c, a = pool.guided_shape()
@@ -323,7 +328,12 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
     mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
     status = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    if width:
+    if tactics:
+        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
+                                                                     status.data_ptr(), ids, simulations, c_puct,
+                                                                     int(nodes or 0), width or None, tactics,
+                                                                     tactics_nodes))
+    elif width:
         _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
                                                                      status.data_ptr(), ids, simulations, c_puct,
                                                                      int(nodes or 0), width))
@@ -336,6 +346,19 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     if not keep_open:
         pool.guided_end()
     return out
+
+
+def guided_decided_device(pool: Any) -> Any:
+    """int32 [k] on the pool's device: the leaves the exact leaf status (`tactics=`) decided per root of the pool's
+    open PUCT session since it began; a reroot does not reduce it.  Only enqueued, ordered both ways against torch's
+    current stream."""
+    import torch
+
+    k = pool._guided_open("guided_decided", "puct")
+    dev = torch.device("cuda", pool.device)
+    decided = torch.empty((k,), dtype=torch.int32, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_decided_device(decided.data_ptr()))
+    return decided
 
 
 def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: int,

@@ -677,6 +677,35 @@ int epa_guided_begin_wide_device(epa_pool* pool, const int32_t* env_ids, int32_t
                                  int32_t nodes, int32_t width, float c_puct, void* device_obs, void* device_mask,
                                  void* device_status);
 
+/* Guided search, exact leaf status (PUCT sessions, plain or wide; csrc/pgx_guided.hip.h "Exact leaf status" is the
+ * authority): a session begun with tactics = D, 1 .. EPA_GUIDED_MAX_TACTICS, hands every new leaf other than the root
+ * to the exact solver (epa_solve's contract, unchanged: the tree of D plies from the leaf's position, max_nodes =
+ * tactics_nodes, 1 .. EPA_GUIDED_MAX_TACTICS_NODES) after the advance's descents.  A leaf the solver decides -- status
+ * solved, value v != 0 -- is from then on a finished game whose last reward is v for the seat that moves there: its
+ * row has status 1 and zeros in obs and mask, the caller's row for it is ignored, and +-1 is backed up.  A value of 0
+ * or a leaf given up is evaluated by the caller as before.  A decided node that a reroot makes the root runs on: it is
+ * handed out with status 0.  Which leaves are decided does not depend on id order or sharding.
+ *   width = 0: a plain session; 1 .. EPA_GUIDED_MAX_WIDTH: a wide one.  nodes = 0: simulations + 1.
+ *   tactics = 0: exactly epa_guided_begin / _nodes / _wide: the same launches and the same bytes.
+ *   epa_guided_decided: decided int32 [k], the leaves decided per root since begin (a reroot does not reduce it);
+ *     nodes int64 [k] (may be null), the positions the solver visited per root since begin.  Zeros for a session
+ *     without tactics.
+ *   EPA_ERR_INVALID, before any launch, beside the refusals of epa_guided_begin_wide: tactics outside 0 ..
+ *     EPA_GUIDED_MAX_TACTICS; tactics_nodes outside 1 .. EPA_GUIDED_MAX_TACTICS_NODES; the trees plus the solver's
+ *     stacks (5120 bytes x D per slot) above EPA_SEARCH_MAX_TREE_BYTES: the message names the largest k that fits.
+ * The _device forms take device pointers and only enqueue. */
+#define EPA_GUIDED_MAX_TACTICS 16
+#define EPA_GUIDED_MAX_TACTICS_NODES (1 << 20)
+#define EPA_GUIDED_TACTICS_NODES 4096 /* the default of the Python layers */
+int epa_guided_begin_tactics(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t nodes,
+                             int32_t width, float c_puct, int32_t tactics, int64_t tactics_nodes, uint8_t* obs,
+                             uint8_t* mask, uint8_t* status);
+int epa_guided_begin_tactics_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                                    int32_t nodes, int32_t width, float c_puct, int32_t tactics,
+                                    int64_t tactics_nodes, void* device_obs, void* device_mask, void* device_status);
+int epa_guided_decided(epa_pool* pool, int32_t* decided, int64_t* nodes);
+int epa_guided_decided_device(epa_pool* pool, void* device_decided, void* device_nodes);
+
 /* Gumbel search (no reference analogue; the four PGX board games): the guided-search session above with a second
  * selection policy -- Gumbel top-m sampling without replacement at the root, sequential halving of the simulations
  * over those m actions, a deterministic rule inside the tree, and the improved policy softmax(logits + sigma(completed
