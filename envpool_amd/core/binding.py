@@ -359,17 +359,20 @@ class _ShardedPools:
 
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
                      nodes: int = 0, width: Any = None, tactics: int = 0,
-                     tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     tactics_nodes: int = native.GUIDED_TACTICS_NODES,
+                     prove: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A session in every shard that owns listed envs, all shards at once.  The search has no random numbers and
         no dependence on the env id, so the rows are those of the unsharded pool.  `width`: a wide session in every
         shard (`DevicePool.guided_begin`).  `tactics`, `tactics_nodes`: the exact leaf status in every shard; what it
-        decides depends on the leaf's position alone, so the rows stay those of the unsharded pool."""
+        decides depends on the leaf's position alone, so the rows stay those of the unsharded pool.  `prove`: proven
+        values in every shard; a proof depends on the root's own tree alone."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
         ids = native.check_guided(env_ids, simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
         tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
+        prove = native.check_guided_prove(prove)
         h, w, c, a = self.guided_shape()
         shard = (ids - self.offset) // self.per
         bad = ids[(shard < 0) | (shard >= len(self.pools))]
@@ -381,6 +384,8 @@ class _ShardedPools:
         extra = (int(nodes or 0), width) if width else ((nodes,) if nodes else ())
         if tactics:
             extra = (int(nodes or 0), width or None, tactics, tactics_nodes)
+        if prove:
+            extra = (int(nodes or 0), width or None, tactics, tactics_nodes, True)
 
         def begin(s: int, p: DevicePool, idx: Any) -> None:
             for o, part in zip(leaves, p.guided_begin(ids[idx], simulations, c_puct, *extra)):
@@ -451,6 +456,17 @@ class _ShardedPools:
 
         self._each(decided, parts)
         return out if with_nodes else out[0]
+
+    def guided_proof(self) -> tuple[np.ndarray, np.ndarray]:
+        k, a, parts = self._guided_session("guided_proof")
+        out = (np.empty(k, dtype=np.int8), np.empty((k, a), dtype=np.int8))
+
+        def proof(s: int, p: DevicePool, idx: Any) -> None:
+            for o, part in zip(out, p.guided_proof()):
+                o[idx] = part
+
+        self._each(proof, parts)
+        return out
 
     def guided_end(self) -> None:
         _, _, parts = self._guided_session("guided_end")

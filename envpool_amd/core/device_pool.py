@@ -550,7 +550,8 @@ class DevicePool:
 
     def guided_begin(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25,
                      nodes: int = 0, width: Any = None, tactics: int = 0,
-                     tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                     tactics_nodes: int = native.GUIDED_TACTICS_NODES,
+                     prove: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Opens the pool's guided-search session (the PGX board games; RuntimeError("guided search not implemented
         for this environment") elsewhere) on the current positions of the listed envs (global ids; None: the whole
         pool), replacing any earlier one: a PUCT search whose tree stays on the device and that stops at every new
@@ -564,14 +565,22 @@ class DevicePool:
         status 2 has nothing pending, and the round is complete when all statuses are 2.  None: a plain session.
         `tactics` = D, 1 .. 16, turns on the exact leaf status (epa_guided_begin_tactics): every new leaf other than
         the root is solved D plies deep with at most `tactics_nodes` positions, and a leaf that is a forced win or loss
-        comes back with status 1 and backs up +-1 for good; 0: off, today's calls."""
+        comes back with status 1 and backs up +-1 for good; 0: off, today's calls.
+        `prove` = True turns on proven values (epa_guided_begin_prove): exact values of finished games and decided
+        leaves climb the tree, proven subtrees are closed, a proven root ends its round early, and the result's action
+        is never a move proven to lose while another is not; `guided_proof` reads the proofs.  False: today's calls."""
         ids = native.check_guided(self._ids(env_ids), simulations, c_puct)
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
         tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
+        prove = native.check_guided_prove(prove)
         self.guided_shape()
         obs, mask, status = self._guided_leaves(len(ids), width)
-        if tactics:
+        if prove:
+            native.check(self._lib.epa_guided_begin_prove(
+                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+                tactics_nodes, native.GUIDED_PROVE, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
+        elif tactics:
             native.check(self._lib.epa_guided_begin_tactics(
                 self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
                 tactics_nodes, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
@@ -656,6 +665,20 @@ class DevicePool:
         native.check(self._lib.epa_guided_decided(self._h, decided.ctypes.data, nodes.ctypes.data))
         return (decided, nodes) if with_nodes else decided
 
+    def guided_proof(self) -> tuple[np.ndarray, np.ndarray]:
+        """Proven values (`prove=True`), at any time: (value int8 [k], the root's proven value for its mover; q int8
+        [k, A], per legal root action the proven value of its child for the root's mover).  -128: unproven, no child,
+        an illegal action, a root that is over -- and everywhere for a session without `prove`."""
+        k = self._guided_open("guided_proof", "puct")
+        value, q = np.empty(k, dtype=np.int8), np.empty((k, self.guided_shape()[3]), dtype=np.int8)
+        native.check(self._lib.epa_guided_proof(self._h, value.ctypes.data, q.ctypes.data))
+        return value, q
+
+    def guided_proof_device(self, d_value: int, d_q: int) -> None:
+        """`guided_proof` into device memory (int8 [k] and int8 [k, A]): only enqueued."""
+        self._guided_open("guided_proof", "puct")
+        native.check(self._lib.epa_guided_proof_device(self._h, ctypes.c_void_p(d_value), ctypes.c_void_p(d_q)))
+
     def guided_decided_device(self, d_decided: int, d_nodes: int = 0) -> None:
         """`guided_decided` into device memory (int32 [k]; `d_nodes`: int64 [k] or 0): only enqueued."""
         self._guided_open("guided_decided", "puct")
@@ -669,7 +692,7 @@ class DevicePool:
 
     def guided_begin_device(self, d_obs: int, d_mask: int, d_status: int, env_ids: Any = None, simulations: int = 64,
                             c_puct: float = 1.25, nodes: int = 0, width: Any = None, tactics: int = 0,
-                            tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> int:
+                            tactics_nodes: int = native.GUIDED_TACTICS_NODES, prove: bool = False) -> int:
         """`guided_begin` with the leaves written to device memory at the raw addresses `d_obs` (k H W C bytes),
         `d_mask` (k A bytes) and `d_status` (k bytes): only enqueued on the pool's stream.  Returns k.  With `width`
         = W the arrays have k W rows, and so have those of `guided_advance_device` (its `k` is k W) and of
@@ -678,7 +701,13 @@ class DevicePool:
         cap = native.check_guided_nodes(simulations, nodes)
         width = native.check_guided_width(width)
         tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
-        if tactics:
+        prove = native.check_guided_prove(prove)
+        if prove:
+            native.check(self._lib.epa_guided_begin_prove_device(
+                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+                tactics_nodes, native.GUIDED_PROVE, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                ctypes.c_void_p(d_status)))
+        elif tactics:
             native.check(self._lib.epa_guided_begin_tactics_device(
                 self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
                 tactics_nodes, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))

@@ -33,6 +33,8 @@ GUIDED_MAX_WIDTH = 32    # EPA_GUIDED_MAX_WIDTH: the most slots (leaves per laun
 GUIDED_MAX_TACTICS = 16  # EPA_GUIDED_MAX_TACTICS: the largest horizon of a guided search's exact leaf status
 GUIDED_MAX_TACTICS_NODES = 1 << 20  # EPA_GUIDED_MAX_TACTICS_NODES: the largest node budget of one leaf's solve
 GUIDED_TACTICS_NODES = 4096         # EPA_GUIDED_TACTICS_NODES: its default
+GUIDED_PROVE = 1         # EPA_GUIDED_PROVE: the flag of a guided search with proven values
+GUIDED_UNPROVEN = -128   # EPA_GUIDED_UNPROVEN: "no proven value" in guided_proof's arrays
 GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per launch) of a batch Gumbel root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
@@ -154,6 +156,12 @@ def lib() -> ctypes.CDLL:
                                            vp]),
         "epa_guided_begin_tactics_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, ctypes.c_int64, vp,
                                                   vp, vp]),
+        "epa_guided_begin_prove": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, ctypes.c_int64, i32, vp, vp,
+                                         vp]),
+        "epa_guided_begin_prove_device": (i32, [vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, ctypes.c_int64, i32,
+                                                vp, vp, vp]),
+        "epa_guided_proof": (i32, [vp, vp, vp]),
+        "epa_guided_proof_device": (i32, [vp, vp, vp]),
         "epa_guided_decided": (i32, [vp, vp, vp]),
         "epa_guided_decided_device": (i32, [vp, vp, vp]),
         "epa_gumbel_begin": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]),
@@ -205,6 +213,7 @@ EXPORTED_SYMBOLS = [
     "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
     "epa_guided_begin_wide", "epa_guided_begin_wide_device",
     "epa_guided_begin_tactics", "epa_guided_begin_tactics_device", "epa_guided_decided", "epa_guided_decided_device",
+    "epa_guided_begin_prove", "epa_guided_begin_prove_device", "epa_guided_proof", "epa_guided_proof_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device", "epa_gumbel_begin_batch", "epa_gumbel_begin_batch_device",
     "epa_atari_post_create",
@@ -347,6 +356,15 @@ def check_guided_tactics(tactics: Any, tactics_nodes: Any) -> tuple[int, int]:
             or not 1 <= int(tactics_nodes) <= GUIDED_MAX_TACTICS_NODES):
         raise ValueError(f"guided_begin: tactics_nodes = {tactics_nodes} must be 1 .. {GUIDED_MAX_TACTICS_NODES}")
     return int(tactics), int(tactics_nodes)
+
+
+def check_guided_prove(prove: Any) -> bool:
+    """`prove` of a guided_begin call after its check: ValueError unless it is a bool (None: False)."""
+    if prove is None:
+        return False
+    if not isinstance(prove, (bool, np.bool_)):
+        raise ValueError(f"guided_begin: prove = {prove!r} must be True or False")
+    return bool(prove)
 
 
 def check_guided_wide_rows(priors: Any, values: Any, k: int, width: int, actions: int) -> tuple[np.ndarray, np.ndarray]:

@@ -460,6 +460,12 @@ class Pool {
   virtual void GuidedReroot(const GuidedArgs& a);
   // exact leaf status (pgx_guided.hip.h "Exact leaf status"): the solver stage after an advance's descents
   virtual void GuidedTactics(const GuidedArgs& a, const TacticsArgs& t);
+  // proven values (pgx_guided.hip.h "Proven values"): advance, result and reroot of a session begun with
+  // EPA_GUIDED_PROVE, and its read-out (value int8 [k], q int8 [k][A], device memory)
+  virtual void GuidedAdvanceProve(const GuidedArgs& a);
+  virtual void GuidedResultProve(const GuidedArgs& a);
+  virtual void GuidedRerootProve(const GuidedArgs& a);
+  virtual void GuidedProof(const GuidedArgs& a, signed char* value, signed char* q);
   // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; the four hooks above serve
   // them too (a.width != 0: the family chooses its kernels)
   virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
@@ -477,6 +483,12 @@ class Pool {
   void GuidedBeginTacticsCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct,
                               int tactics, long long tactics_nodes, void* obs, void* mask, void* status, bool device);
   void GuidedDecidedCall(void* decided, void* nodes, bool device);
+  // Proven values: begin with a flags word (EPA_GUIDED_PROVE; 0: exactly the call above).  GuidedProofCall: value int8
+  // [k] and q int8 [k][A]; -128 everywhere for a session without the flag; the device form only enqueues.
+  void GuidedBeginProveCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct,
+                            int tactics, long long tactics_nodes, int flags, void* obs, void* mask, void* status,
+                            bool device);
+  void GuidedProofCall(void* value, void* q, bool device);
   // Tree reuse (pgx_guided.hip.h "Tree reuse"): after the round's last advance, the subtree under actions[i] becomes
   // root i's tree, `simulations` the length of the next round, and the new roots are emitted as begin emits its own.
   // actions: a host array (checked against 0 .. A-1 here) or a device pointer (the kernel ends such a root).  PUCT
@@ -719,6 +731,8 @@ class Pool {
     int tactics{0};         // exact leaf status: D (0: off), M, and the offset of its block behind the staging:
     long long tactics_nodes{0};  // decided int32 [k], nodes int64 [k], then the slots' stacks
     size_t tactics_off{0};
+    int flags{0};           // EPA_GUIDED_PROVE: proven values; its read-out's staging (int8 [k] and [k][A]) is the
+    size_t proof_off{0};    // allocation's last block
     // offsets into the staging: priors (Gumbel: the noise at begin, then logits), values, obs, mask, status, visits,
     // vals, action, the end of a PUCT session's staging, and behind it a Gumbel session's weights and their end
     size_t off[10]{};

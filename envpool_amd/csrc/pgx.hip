@@ -507,6 +507,43 @@ __device__ __forceinline__ float GuidedAnswer(const GuidedArgs& a, size_t lrow, 
   return (float)pgx::SearchSign<G>(leaf.s) * pgx::GuidedCleanV(a.values[lrow]);
 }
 
+// Proven values (pgx_guided.hip.h "Proven values"), rule 3: the climb from a slot of status 1 whose statistics have
+// just been backed up along `path`.  From the last entry up: the node below must be proven (one address: wave-uniform), rule
+// 2 at the entry's node is the wave's (tree::WaveProof), and lane 0 marks a proven node other than node 0; the mark is
+// a hand-off to the lanes that read it one entry higher, hence the fences.  Returns the root's proven value when the
+// climb arrives there with one, pgx::kGuidedUnproven otherwise.
+template <int G>
+__device__ __forceinline__ int GuidedClimb(pgx::GuidedNode<G>* nodes, int capacity, const int32_t* path, int depth,
+                                           int pending, int lane) {
+  constexpr int SL = pgx::SearchSlotsPerLane<G>();
+  int below = pending;
+  for (int d = depth - 1; d >= 0; --d) {
+    if ((unsigned)below >= (unsigned)capacity) break;  // (never)
+    WaveAcquire();
+    if (nodes[below].s.done == 0) break;
+    const int n = path[d] >> 8;
+    if ((unsigned)n >= (unsigned)capacity) break;  // (never)
+    pgx::GuidedNode<G>& nd = nodes[n];
+    const pgx::State s = nd.s;
+    int child[SL], cv[SL];
+    tree::LoadChildren<G>(nd, lane, child);
+    const int v = tree::WaveProof<G>(nodes, capacity, child, s.m, pgx::SearchSign<G>(s), lane, cv);
+    if (v == pgx::kGuidedUnproven) break;
+    if (n == 0) return v;
+    if (lane == 0) pgx::GuidedTacticsMark<G>(nd, v);
+    WaveRelease();
+    below = n;
+  }
+  return pgx::kGuidedUnproven;
+}
+
+// Rule 4: the pick among the lane's candidates `open` (the legal actions whose child is not proven -1 for the mover)
+// and, only if the wave has none of those, among `all` legal actions.
+__device__ __forceinline__ int GuidedProvePick(pgx::SearchPick open, pgx::SearchPick all) {
+  const int act = tree::WaveBest(open).action;
+  return act >= 0 ? act : tree::WaveBest(all).action;
+}
+
 // WIDE: a wide session (below): the record is pgx::GuidedWideRoot, the root goes to slot 0 (leaf row i * W), the other
 // slots are idle and their rows zeros.
 template <int G, bool WIDE>
@@ -523,7 +560,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedBegin(CommonDev cm, con
   GuidedEmitRoot<G, WIDE>(a, row, lane, over, root);
 }
 
-template <int G>
+// PROVE: a session with proven values (pgx_guided.hip.h "Proven values"): the climb after a status-1 answer, the pick
+// that skips proven losses, no descent from a proven root.  The instantiations without it are the kernels as they were.
+template <int G, bool PROVE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, unsigned* err) {
   constexpr int SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
@@ -539,8 +578,22 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
     tree::Backup(nodes, rec.path, rec.depth, val0, lane);
     WaveRelease();
     int count = rec.count;
+    bool proven = false;
+    if constexpr (PROVE) {
+      int proof = pgx::GuidedProofDecode(rec.pad[0]);
+      if (status == pgx::kGuidedTerminal) {
+        const int got =
+            GuidedClimb<G>(nodes, a.capacity, rec.path, std::min(rec.depth, pgx::kSearchMaxPath), rec.pending, lane);
+        if (got != pgx::kGuidedUnproven) {  // (a root proven before: the same value again)
+          proof = got;
+          if (lane == 0) rec.pad[0] = pgx::GuidedProofEncode(proof);
+        }
+      }
+      proven = proof != pgx::kGuidedUnproven;
+    }
     // the round's last call -- or the root's memory is used up (a rerooted tree may come to that): a normal end
-    if (a.call >= S || count >= a.capacity) {
+    // (-- or, PROVE, the root is proven)
+    if (a.call >= S || count >= a.capacity || proven) {
       status = pgx::kGuidedIdle;
       if (lane == 0) rec.status = status;
     } else {
@@ -554,11 +607,24 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
         const int total = tree::WaveSum(tree::LoadPuctEdges<G>(nodes[node], lane, child, v, w0, pr));
         const int sign = pgx::SearchSign<G>(s);
         pgx::SearchPick mine = pgx::SearchNone();
-        tree::ForLegal<G>(lane, s.m, [&](int j, int act) {
-          mine = pgx::SearchBetter(
-              mine, pgx::SearchPick{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), act, 1});
-        });
-        const int act = tree::WaveBest(mine).action;
+        int act;
+        if constexpr (PROVE) {
+          int cv[SL];
+          tree::ChildProofs<G>(nodes, a.capacity, child, s.m, sign, lane, cv);
+          pgx::SearchPick all = pgx::SearchNone();
+          tree::ForLegal<G>(lane, s.m, [&](int j, int b) {
+            const pgx::SearchPick p{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), b, 1};
+            all = pgx::SearchBetter(all, p);
+            if (!pgx::GuidedProofClosed(cv[j])) mine = pgx::SearchBetter(mine, p);
+          });
+          act = GuidedProvePick(mine, all);
+        } else {
+          tree::ForLegal<G>(lane, s.m, [&](int j, int b) {
+            mine = pgx::SearchBetter(
+                mine, pgx::SearchPick{pgx::GuidedScore(v[j], w0[j], pr[j], total, sign, a.c_puct), b, 1});
+          });
+          act = tree::WaveBest(mine).action;
+        }
         // unreachable from a position of the game (PgxSearchKernel): reported through the pool's error word
         if (act < 0 || depth >= pgx::kSearchMaxPath) {
           broken = true;
@@ -594,7 +660,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvance(GuidedArgs a, u
 }
 
 // (WIDE: the root record of a wide session; one row per root either way)
-template <int G, bool WIDE>
+// (PROVE: proven values, rule 6: the action is picked among the actions that GuidedProofPlays admits)
+template <int G, bool WIDE, bool PROVE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   constexpr int A = pgx::Dims<G>::A;
   using Node = pgx::GuidedNode<G>;
@@ -603,8 +670,44 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedResult(GuidedArgs a) {
   WaveAcquire();
   const bool over = tree::GuidedRec<WIDE>(a.roots, row, a.width).over();
   const pgx::State root = n0.s;
-  const int best = tree::RootResult<G>(n0, root, over, lane, a.visits + (size_t)row * A, a.vals + (size_t)row * A);
+  int best = tree::RootResult<G>(n0, root, over, lane, a.visits + (size_t)row * A, a.vals + (size_t)row * A);
+  if constexpr (PROVE) {
+    if (!over) {
+      constexpr int SL = pgx::SearchSlotsPerLane<G>();
+      const int proof = pgx::GuidedProofDecode(tree::GuidedRec<WIDE>(a.roots, row, a.width).proof());
+      int child[SL], cv[SL];
+      tree::LoadChildren<G>(n0, lane, child);
+      tree::ChildProofs<G>(&n0, a.capacity, child, root.m, pgx::SearchSign<G>(root), lane, cv);
+      pgx::SearchPick mine = pgx::SearchNone();
+      tree::ForLegal<G>(lane, root.m, [&](int j, int act) {
+        if (!pgx::GuidedProofPlays(proof, cv[j])) return;
+        mine = pgx::SearchBetter(mine, pgx::SearchPick{(float)n0.v[act], act, 1});
+      });
+      const int act = tree::WaveBest(mine).action;
+      if (act >= 0) best = act;  // (none left: all legal actions, RootResult's pick)
+    }
+  }
   if (lane == 0) a.action[row] = best;  // (-1 without a legal action)
+}
+
+// Proven values, rule 7: the root's proven value and per legal root action its child's, for the root's mover.
+template <int G, bool WIDE>
+__global__ __launch_bounds__(kSearchBlock) void PgxGuidedProof(GuidedArgs a, signed char* value, signed char* q) {
+  constexpr int A = pgx::Dims<G>::A, SL = pgx::SearchSlotsPerLane<G>();
+  using Node = pgx::GuidedNode<G>;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const Node& n0 = static_cast<const Node*>(a.nodes)[(size_t)row * (size_t)a.capacity];
+  WaveAcquire();
+  const tree::GuidedRec<WIDE> rec(a.roots, row, a.width);
+  const bool over = rec.over();
+  const pgx::State root = n0.s;
+  int child[SL], cv[SL];
+  tree::LoadChildren<G>(n0, lane, child);
+  tree::ChildProofs<G>(&n0, a.capacity, child, root.m, pgx::SearchSign<G>(root), lane, cv);
+  tree::ForOwned<G>(lane, [&](int j, int act) {
+    q[(size_t)row * A + act] = (signed char)(over ? pgx::kGuidedUnproven : cv[j]);
+  });
+  if (lane == 0) value[row] = (signed char)(over ? pgx::kGuidedUnproven : pgx::GuidedProofDecode(rec.proof()));
 }
 
 // reroot (pgx_guided.hip.h "Tree reuse"): the subtree under the played move becomes the tree, compacted in place.  One
@@ -628,7 +731,8 @@ constexpr int kRerootTables[3] = {512, 2048, pgx::kGuidedMaxNodes};
 
 // WIDE: a wide session (pgx_guided.hip.h "Several leaves per launch"): the record is pgx::GuidedWideRoot, the new root goes
 // to slot 0 (leaf row i * W), the other slots become idle whatever they held, and their rows are zeros.
-template <int G, int CAP, bool WIDE>
+// PROVE: proven values, rule 8: rule 2 once at the new node 0 over its kept children; the root's proof is set anew.
+template <int G, int CAP, bool WIDE, bool PROVE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
   constexpr int A = pgx::Dims<G>::A;
   using Node = pgx::GuidedNode<G>;
@@ -641,6 +745,7 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
   const int old_count = std::min(std::max(rec.count(), 1), std::min(a.capacity, CAP));  // (always 1 .. capacity)
   bool over = rec.idle() || act < 0 || act >= A;
   int count = old_count;
+  int proof = pgx::kGuidedUnproven;
   pgx::State s = nodes[0].s;
   if (!over) {
     const int c = nodes[0].child[act];  // one address: wave-uniform
@@ -699,10 +804,24 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
       count = kept;
       // exact leaf status, rule 5: a decided node that becomes the root runs on (lane 0 copied it to node 0 above)
       if (pgx::GuidedTacticsReopen(s) && lane == 0) nodes[0].s.done = 0;
+      if constexpr (PROVE) {
+        if (s.done == 0) {  // (the copies' State and term0 are lane 0's stores)
+          constexpr int SL = pgx::SearchSlotsPerLane<G>();
+          WaveRelease();
+          __syncthreads();
+          WaveAcquire();
+          int child[SL], cv[SL];
+          tree::LoadChildren<G>(nodes[0], lane, child);
+          proof = tree::WaveProof<G>(nodes, std::min(count, a.capacity), child, s.m, pgx::SearchSign<G>(s), lane, cv);
+        }
+      }
     }
     over = s.done != 0;
   }
-  if (lane == 0) rec.Reset(count, over);
+  if (lane == 0) {
+    rec.Reset(count, over);
+    if constexpr (PROVE) rec.proof() = pgx::GuidedProofEncode(proof);
+  }
   WaveRelease();
   GuidedEmitRoot<G, WIDE>(a, row, lane, over, s);
 }
@@ -727,7 +846,9 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedReroot(GuidedArgs a) {
 // `lpath` is static, in three width buckets (WB = 4, 16, 32: 4, 16 and 32 KiB), for the reason given at kRerootTables.
 constexpr int kWideBuckets[3] = {4, 16, pgx::kGuidedMaxWidth};
 
-template <int G, int WB>
+// PROVE: proven values, as in PgxGuidedAdvance: the climb after each status-1 slot's backup in phase A, the pick that
+// skips proven losses, and no descent from a proven root.
+template <int G, int WB, bool PROVE = false>
 __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs a, unsigned* err) {
   constexpr int SL = pgx::SearchSlotsPerLane<G>();
   using Node = pgx::GuidedNode<G>;
@@ -739,6 +860,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
   Node* nodes = static_cast<Node*>(a.nodes) + (size_t)row * (size_t)a.capacity;
   WaveAcquire();
   int done = rec.done;
+  int proof = pgx::kGuidedUnproven;
+  if constexpr (PROVE) proof = pgx::GuidedProofDecode(rec.pad[0]);
   // A. the answers
   for (int j = 0; j < W; ++j) {
     const int status = slots[j].status;
@@ -747,11 +870,21 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
     const int backed = std::min(slots[j].depth, pgx::kSearchMaxPath);
     tree::Backup(nodes, slots[j].path, backed, val0, lane);
     if (backed > 0) ++done;
+    if constexpr (PROVE) {
+      if (status == pgx::kGuidedTerminal) {  // (every such slot climbs, also under a root proven before)
+        WaveRelease();
+        const int got = GuidedClimb<G>(nodes, a.capacity, slots[j].path, backed, slots[j].pending, lane);
+        if (got != pgx::kGuidedUnproven) {
+          proof = got;
+          if (lane == 0) rec.pad[0] = pgx::GuidedProofEncode(proof);
+        }
+      }
+    }
   }
   WaveRelease();
-  // B. the descents
+  // B. the descents (PROVE: none from a proven root)
   int count = rec.count;
-  const bool idle = rec.over != 0 || rec.broken != 0;
+  const bool idle = rec.over != 0 || rec.broken != 0 || (PROVE && proof != pgx::kGuidedUnproven);
   int my_depth = 0, my_pend = -1;  // lane i: slot i of this launch; the pending leaf only with status 0
   int j = 0;
   bool broken = false;
@@ -783,11 +916,24 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
       const int total = tree::WaveSum(own) + osum;
       const int sign = pgx::SearchSign<G>(s);
       pgx::SearchPick mine = pgx::SearchNone();
-      tree::ForLegal<G>(lane, s.m, [&](int q, int act) {
-        mine = pgx::SearchBetter(
-            mine, pgx::SearchPick{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), act, 1});
-      });
-      const int act = tree::WaveBest(mine).action;
+      int act;
+      if constexpr (PROVE) {
+        int cv[SL];
+        tree::ChildProofs<G>(nodes, a.capacity, child, s.m, sign, lane, cv);
+        pgx::SearchPick all = pgx::SearchNone();
+        tree::ForLegal<G>(lane, s.m, [&](int q, int b) {
+          const pgx::SearchPick p{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), b, 1};
+          all = pgx::SearchBetter(all, p);
+          if (!pgx::GuidedProofClosed(cv[q])) mine = pgx::SearchBetter(mine, p);
+        });
+        act = GuidedProvePick(mine, all);
+      } else {
+        tree::ForLegal<G>(lane, s.m, [&](int q, int b) {
+          mine = pgx::SearchBetter(
+              mine, pgx::SearchPick{pgx::GuidedWideScore(v[q], w0[q], pr[q], o[q], total, sign, a.c_puct), b, 1});
+        });
+        act = tree::WaveBest(mine).action;
+      }
       if (act < 0 || depth >= pgx::kSearchMaxPath) {  // unreachable from a position of the game (PgxGuidedAdvance)
         broken = true;
         break;
@@ -856,6 +1002,8 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGuidedAdvanceWide(GuidedArgs 
 // obs and mask rows (GuidedEmitLeaf: 16-byte words where aligned).  Two slots of status 0 never share a node, so no
 // two blocks write the same node or slot.  Every branch around a barrier depends on loads of one address or on
 // SolveWave's wave-uniform outcome.
+static_assert(pgx::kGuidedProve == EPA_GUIDED_PROVE && pgx::kGuidedUnproven == EPA_GUIDED_UNPROVEN,
+              "the C ABI states the header's values");
 static_assert(pgx::kGuidedMaxTactics == EPA_GUIDED_MAX_TACTICS &&
                   pgx::kGuidedMaxTacticsNodes == EPA_GUIDED_MAX_TACTICS_NODES,
               "the C ABI states the header's limits");
@@ -1446,6 +1594,36 @@ class PgxPool : public Pool {
         LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false>, a.k, a);
       }
     });
+  }
+  // proven values (pgx_guided.hip.h "Proven values"): the PROVE instantiations, and the read-out
+  void GuidedAdvanceProve(const GuidedArgs& a) override {
+    if (a.width == 0) return LaunchRoots(PgxGuidedAdvance<G, true>, a.k, a, err_dev_);
+    Bucket<kWideBuckets>(a.width, [&](auto wb) {
+      LaunchRoots(PgxGuidedAdvanceWide<G, decltype(wb)::value, true>, a.k, a, err_dev_);
+    });
+  }
+  void GuidedResultProve(const GuidedArgs& a) override {
+    if (a.width != 0) {
+      LaunchRoots(PgxGuidedResult<G, true, true>, a.k, a);
+    } else {
+      LaunchRoots(PgxGuidedResult<G, false, true>, a.k, a);
+    }
+  }
+  void GuidedRerootProve(const GuidedArgs& a) override {
+    Bucket<kRerootTables>(a.capacity, [&](auto cap) {
+      if (a.width != 0) {
+        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, true, true>, a.k, a);
+      } else {
+        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false, true>, a.k, a);
+      }
+    });
+  }
+  void GuidedProof(const GuidedArgs& a, signed char* value, signed char* q) override {
+    if (a.width != 0) {
+      LaunchRoots(PgxGuidedProof<G, true>, a.k, a, value, q);
+    } else {
+      LaunchRoots(PgxGuidedProof<G, false>, a.k, a, value, q);
+    }
   }
   void GuidedTactics(const GuidedArgs& a, const TacticsArgs& t) override {
     if (a.width != 0) {

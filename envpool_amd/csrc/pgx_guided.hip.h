@@ -151,6 +151,54 @@
 // with result v.  The mark lives in State.done, the counters in a block of their own per session: GuidedNode and the
 // root records are unchanged, and a session with tactics = 0 is, byte for byte, the one described above.
 //
+// Proven values (DESIGN.md "PGX guided search: proven values"; MCTS-Solver, Winands, Bjornsson, Saito 2008).  A PUCT
+// session, plain or wide, with or without nodes=, tactics= and reroot, may be begun with the flag kGuidedProve; without
+// it nothing below applies.  sign(n) = SearchSign<G>(n.state); kGuidedUnproven = -128 stands for "no proven value".
+//   1. proven node.  A node is proven when state.done != 0, as before: 1 a finished game, kGuidedDecided a position
+//      marked with an exact result.  Its value for seat 0 is term0 in {-1, 0, +1}; for the mover of a node n above it,
+//      sign(n) * term0 (GuidedProofOf).  Interior nodes marked under rule 3 carry the same mark, GuidedTacticsMark with
+//      the proven value, which may be 0.  Every test of `done` then treats the node as finished: descents stop there
+//      with status 1 and (float) term0 is backed up from then on.  Node 0 is never marked: the root's proof lives in
+//      pad[0] of GuidedRoot / GuidedWideRoot (GuidedProofEncode: 0 unproven, else value + 2).  No record grows.
+//   2. the rule at a node n over its legal actions (bits of n.state.m; GuidedProofAdd / Merge / Value): if some legal a
+//      has a child proven +1 for n's mover, n is proven +1; otherwise, if every legal a has a child and all of them
+//      are proven, n is proven with the maximum of their values for n's mover (-1, 0 or +1); otherwise n is unproven.
+//   3. climb, in the answer stage of an advance, right after the statistics of a slot whose status was 1 have been
+//      backed up along its path (wide: slot by slot in slot order, after that slot's backup).  The path entries from
+//      the last to the first, c = the node below the entry (the next entry's node; the pending leaf for the last):
+//      c unproven: stop.  Rule 2 at the entry's node n; n unproven: stop.  n is node 0: store the root's proof and
+//      stop.  Otherwise mark n and go on.  A mark never changes once set: proofs are exact, and deriving one again
+//      (another slot's path through a marked node) gives the same value.  Slots of status 0 never climb.  Rule 2 is
+//      the wave's job: every lane reads (done, term0) of the children of the actions it owns, one reduction decides.
+//   4. selection.  score / wscore are unchanged.  A pick skips every legal action whose child is proven -1 for the
+//      node's mover (GuidedProofClosed) -- finished games, decided leaves and marked interior nodes alike; ties stay
+//      "the lowest action".  A node that a descent reaches has such an action left, or it would have been marked and
+//      the descent would have stopped above it -- with one exception: a node whose last open actions were closed by
+//      EARLIER DESCENTS OF THE SAME LAUNCH of a wide session (they reached finished games below it; the climb comes
+//      with the next advance), or by slots a device-form reroot dropped.  There the pick is over all legal actions, as
+//      without the flag: it reaches a proven child, status 1, and the next answer stage marks the node.  The root that
+//      runs out of actions is proven (rule 5).  A pick learns a child's proof from the child's two words.
+//   5. proven root.  A root whose proof is set begins no further descent in this round: status 2 (plain), stage B
+//      begins nothing (wide).  A normal end like count == C, no error; later advances change nothing for that root.
+//   6. result.  visits and values are unchanged.  action (GuidedProofPlays): for a proven root the most visited legal
+//      action whose child is proven with the root's proven value for the root's mover; for an unproven root the most
+//      visited legal action whose child is not proven -1 for the root's mover (all legal actions if none is left: the
+//      case of rule 4); the lowest on ties; -1 for a root that is over.
+//   7. proof.  value int8 [k]: the root's proven value for its mover, -128 if unproven or over.  q int8 [k, A]: per
+//      legal root action the proven value of its child for the root's mover, -128 if unproven, without a child or
+//      illegal (solve()'s convention), and for a root that is over.  It can be read at any time; a session without
+//      the flag gives -128 everywhere.
+//   8. reroot.  The compaction is unchanged and marks in the kept subtree stay bit for bit.  A marked node that
+//      becomes node 0 is reopened (GuidedTacticsReopen, with or without tactics).  Then rule 2 is applied once to the
+//      new node 0 over its kept children and the root's proof is set accordingly; a fresh root (c < 0) and a root that
+//      is over are unproven.  The new root is handed out at advance 0 as always and, if proven, then begins no
+//      descent.
+//   9. tactics.  With tactics = D the decided leaves have status 1 and so feed the climb at the next advance; without
+//      it only finished games do.  The tactics stage itself is unchanged.
+//  10. without the flag the kernels launched, their arguments, the layouts and every byte stay as they are.
+// In one sentence: the session is the guided search of the game in which every position whose value follows from
+// proven positions below it counts as finished with that value, and in which no one walks into a proven loss.
+//
 // There are no random numbers.  Only seat 0's value is stored, as in pgx_search.hip.h: the games are zero-sum.  Build
 // without fast-math and with -ffp-contract=off.
 #ifndef ENVPOOL_AMD_CSRC_PGX_GUIDED_HIP_H_
@@ -314,6 +362,39 @@ PGX_HD inline bool GuidedTacticsReopen(State& s) {
   if (s.done != kGuidedDecided) return false;
   s.done = 0;
   return true;
+}
+
+// ---- proven values: the flag kGuidedProve ----
+constexpr int kGuidedProve = 1;       // the flags word of begin
+constexpr int kGuidedUnproven = -128;  // "no proven value" in proof's arrays and in the pieces below
+
+// rule 1: the value of a node (its State.done and term0) for a mover of `sign`
+PGX_HD inline int GuidedProofOf(int done, int term0, int sign) { return done != 0 ? sign * term0 : kGuidedUnproven; }
+// rule 2 over a node's legal actions: the largest proven child value and the legal actions without a proven child
+struct GuidedProofAcc {
+  int best;
+  int open;
+};
+PGX_HD inline GuidedProofAcc GuidedProofNone() { return GuidedProofAcc{kGuidedUnproven, 0}; }
+// one legal action, cv: its child's value for the node's mover, kGuidedUnproven without a proven child
+PGX_HD inline GuidedProofAcc GuidedProofAdd(GuidedProofAcc x, int cv) {
+  return GuidedProofAcc{cv > x.best ? cv : x.best, x.open + (cv == kGuidedUnproven ? 1 : 0)};
+}
+PGX_HD inline GuidedProofAcc GuidedProofMerge(GuidedProofAcc x, GuidedProofAcc y) {
+  return GuidedProofAcc{y.best > x.best ? y.best : x.best, x.open + y.open};
+}
+PGX_HD inline int GuidedProofValue(GuidedProofAcc x) {
+  if (x.best == 1) return 1;
+  return x.open == 0 ? x.best : kGuidedUnproven;  // (no legal action: best is kGuidedUnproven)
+}
+// rule 1: the root's proof in its record's pad word
+PGX_HD inline int GuidedProofEncode(int v) { return v == kGuidedUnproven ? 0 : v + 2; }
+PGX_HD inline int GuidedProofDecode(int word) { return word >= 1 && word <= 3 ? word - 2 : kGuidedUnproven; }
+// rule 4: a pick skips the action of a child of this value
+PGX_HD inline bool GuidedProofClosed(int cv) { return cv == -1; }
+// rule 6: whether a legal root action whose child has value cv takes part in the result's pick
+PGX_HD inline bool GuidedProofPlays(int root_proof, int cv) {
+  return root_proof != kGuidedUnproven ? cv == root_proof : !GuidedProofClosed(cv);
 }
 
 // bytes of one emitted obs row: the mover's [H, W, C] block of the kObs key

@@ -211,6 +211,43 @@ __device__ __forceinline__ int LoadPuctEdges(const GuidedNode<G>& nd, int lane, 
   return own;
 }
 
+// Proven values (pgx_guided.hip.h "Proven values") at the node whose legal-action set is `m`, whose mover has `sign`
+// and whose child indices the lanes hold in child[] (LoadPuctEdges; -1 past the last action): cv[j] becomes the proven
+// value of the child of the lane's slot j for that mover -- kGuidedUnproven for an illegal action, no child or an
+// unproven one -- read from the child's two words.  Returns the lane's share of rule 2.  The children's State and term0
+// were stored by lane 0: the caller's acquire fence precedes.
+template <int G, class M>
+__device__ __forceinline__ GuidedProofAcc ChildProofs(const GuidedNode<G>* nodes, int capacity, const int* child,
+                                                      const M& m, int sign, int lane, int* cv) {
+  GuidedProofAcc acc = GuidedProofNone();
+  ForSlots<G>(lane, [&](int j, int act, bool owned) {
+    cv[j] = kGuidedUnproven;
+    if (owned && Has(m, act)) {
+      if ((unsigned)child[j] < (unsigned)capacity) {
+        const GuidedNode<G>& c = nodes[child[j]];
+        cv[j] = GuidedProofOf(c.s.done, c.term0, sign);
+      }
+      acc = GuidedProofAdd(acc, cv[j]);
+    }
+  });
+  return acc;
+}
+// rule 2 at that node: the wave's reduction of the lanes' shares gives its proven value (wave-uniform;
+// kGuidedUnproven: none)
+template <int G, class M>
+__device__ __forceinline__ int WaveProof(const GuidedNode<G>* nodes, int capacity, const int* child, const M& m,
+                                         int sign, int lane, int* cv) {
+  GuidedProofAcc acc = ChildProofs<G>(nodes, capacity, child, m, sign, lane, cv);
+  acc.best = WaveMax(acc.best);
+  acc.open = WaveSum(acc.open);
+  return GuidedProofValue(acc);
+}
+// the lane's child indices of a guided node (-1 past the last action), for WaveProof where no pick follows
+template <int G>
+__device__ __forceinline__ void LoadChildren(const GuidedNode<G>& nd, int lane, int* child) {
+  ForSlots<G>(lane, [&](int j, int act, bool owned) { child[j] = owned ? nd.child[act] : -1; });
+}
+
 // The result rows of a root from its node n0 (position `root`): visits = v, vals = w0 times the root mover's sign (int
 // or float, as the node's w0); zero rows when `zero` (a root that is over, or broken).  `column(j, act)` stores what
 // else a policy gives per action.  Returns the most visited legal action (ties: the lowest), -1 without one or when
@@ -242,6 +279,7 @@ struct GuidedRec<false> {
   __device__ __forceinline__ int count() const { return r.count; }
   __device__ __forceinline__ bool over() const { return r.over != 0; }
   __device__ __forceinline__ bool idle() const { return r.over != 0 || r.broken != 0; }
+  __device__ __forceinline__ int32_t& proof() const { return r.pad[0]; }  // proven values: GuidedProofEncode
   __device__ __forceinline__ void Clear(bool over) const { GuidedClearRoot(r, over); }                   // at begin
   __device__ __forceinline__ void Reset(int count, bool over) const { GuidedRerootRoot(r, count, over); }  // reroot
 };
@@ -254,6 +292,7 @@ struct GuidedRec<true> {
   __device__ __forceinline__ int count() const { return r.count; }
   __device__ __forceinline__ bool over() const { return r.over != 0; }
   __device__ __forceinline__ bool idle() const { return r.over != 0 || r.broken != 0; }
+  __device__ __forceinline__ int32_t& proof() const { return r.pad[0]; }
   __device__ __forceinline__ void Clear(bool over) const { GuidedWideClearRoot(r, width, 1, over); }
   __device__ __forceinline__ void Reset(int count, bool over) const { GuidedWideClearRoot(r, width, count, over); }
 };

@@ -53,6 +53,15 @@ class GuidedResult(NamedTuple):
     action: np.ndarray  # int32 [k]: the most visited legal action (the lowest on ties); -1: the env was over
 
 
+class Proof(NamedTuple):
+    """What `GuidedSearch.proof` returns: the proven values of a session opened with `prove=True`, seen from the root's
+    mover; -128: none."""
+
+    value: np.ndarray  # int8 [k]: the root's proven value, +1, 0 or -1; -128: unproven, or the env was over
+    q: np.ndarray      # int8 [k, A]: the proven value of the child of each legal root action; -128: unproven, no child,
+                       # illegal (the convention of `Solve.q`)
+
+
 class GuidedSearch:
     """A pool's guided-search session (`env.guided_search`): a PUCT search of every listed env whose tree stays on
     the device and that stops at every new leaf for the caller's priors and value.
@@ -92,16 +101,34 @@ class GuidedSearch:
     or loss within D plies needs no evaluation: it comes back with status 1 and zero rows, whatever `advance` is given
     for it is ignored, and the exact +-1 is backed up from then on, as for a finished game.  Every other leaf is
     evaluated as before.  `decided` counts such leaves per root.  After `reroot` onto a decided position the game runs
-    on: the new root is handed out for evaluation like any other."""
+    on: the new root is handed out for evaluation like any other.
+
+    Proven values: `prove=True` (MCTS-Solver) lets exact values climb the tree.  Finished games and decided leaves are
+    proven; a node with a move to a position proven lost for the opponent is proven won, and a node whose every move
+    leads to a proven position is proven with the best of them.  A proven node counts as a finished game from then on,
+    no descent takes a move proven to lose while another is left, a root that is proven ends its round early (its
+    rows have status 2; `run` just goes on for the others), and `result().action` is the most visited move that keeps
+    the proven value -- never a move proven to lose while another is not.  `proof` reads the proofs at any time.  With
+    `tactics=` the decided leaves feed the proofs, without it only finished games do:
+
+        gs = env.guided_search(ids, simulations=64, tactics=2, prove=True)
+        result = gs.run(evaluate, close=False)
+        won = gs.proof.value == 1                       # roots with a forced win; result.action plays it"""
 
     def __init__(self, pool: Any, ids: np.ndarray, simulations: int, c_puct: float, nodes: Any = None,
-                 width: int = 1, tactics: int = 0, tactics_nodes: int = native.GUIDED_TACTICS_NODES):
+                 width: int = 1, tactics: int = 0, tactics_nodes: int = native.GUIDED_TACTICS_NODES,
+                 prove: bool = False):
         self._pool = pool
         self.simulations = int(simulations)
         self.calls = 0
         self.width = int(width)
         self.tactics = int(tactics)
-        if self.tactics:
+        self.prove = bool(prove)
+        if self.prove:
+            self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes or 0),
+                                            self.width if self.width > 1 else None, self.tactics, int(tactics_nodes),
+                                            True)
+        elif self.tactics:
             self.leaves = pool.guided_begin(ids, int(simulations), float(c_puct), int(nodes or 0),
                                             self.width if self.width > 1 else None, self.tactics, int(tactics_nodes))
         elif self.width > 1:
@@ -123,6 +150,14 @@ class GuidedSearch:
         if self._pool is None:
             raise ValueError("guided search: the session is closed")
         return self._pool.guided_decided()
+
+    @property
+    def proof(self) -> Proof:
+        """The proven values (`prove=True`) of the roots and of the children of their actions, at any time; -128
+        everywhere without `prove`."""
+        if self._pool is None:
+            raise ValueError("guided search: the session is closed")
+        return Proof(*self._pool.guided_proof())
 
     def advance(self, priors: Any, values: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         if self._pool is None:
@@ -439,7 +474,7 @@ class EnvPoolMixin(ABC):
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
                       nodes: Any = None, width: int = 1, tactics: int = 0,
-                      tactics_nodes: int = native.GUIDED_TACTICS_NODES, **gumbel: Any) -> Any:
+                      tactics_nodes: int = native.GUIDED_TACTICS_NODES, prove: bool = False, **gumbel: Any) -> Any:
         """Extension (the PGX board games): opens a guided tree search from the current position of every listed env
         (global ids; None: all) -- PUCT selection with the priors and leaf values the caller supplies, one kernel
         launch per simulation, the tree on the device (AlphaZero-style search).  Returns the `GuidedSearch` session; a
@@ -450,10 +485,16 @@ class EnvPoolMixin(ABC):
         8192 (None: simulations + 1), the room `GuidedSearch.reroot` needs to keep the played move's subtree.  `width`
         (PUCT only), 1 .. 32: the leaves per root and launch (`GuidedSearch`: "Several leaves per launch"); 1 is the
         plain session.  `tactics` (PUCT only), 1 .. 16: the exact leaf status (`GuidedSearch`: "Exact leaf status"),
-        every new leaf solved that many plies deep with at most `tactics_nodes` (1 .. 2^20) positions; 0: off."""
+        every new leaf solved that many plies deep with at most `tactics_nodes` (1 .. 2^20) positions; 0: off.
+        `prove` (PUCT only): proven values (`GuidedSearch`: "Proven values"), exact values climb the tree; False:
+        off."""
         native.check_guided_width(width)
         tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
+        prove = native.check_guided_prove(prove)
         if policy == "gumbel":
+            if prove:
+                raise ValueError("guided_search: prove is an argument of policy='puct' (proven values not "
+                                 "implemented for gumbel sessions)")
             if tactics:
                 raise ValueError("guided_search: tactics is an argument of policy='puct' (exact leaf status not "
                                  "implemented for gumbel sessions)")
@@ -472,6 +513,9 @@ class EnvPoolMixin(ABC):
                                   simulations, c_puct)
         if nodes is not None:
             native.check_guided_nodes(simulations, nodes)
+        if prove:
+            return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes, int(width), tactics,
+                                tactics_nodes, True)
         if tactics:
             return GuidedSearch(self._guided(), ids, int(simulations), float(c_puct), nodes, int(width), tactics,
                                 tactics_nodes)
@@ -479,7 +523,7 @@ class EnvPoolMixin(ABC):
 
     def gumbel_search(self, env_ids: Any = None, simulations: int = 32, max_considered: int = 16, gumbel: Any = None,
                       seed: Any = None, c_visit: float = 50.0, c_scale: float = 0.1,
-                      width: int = 1, batch: int = 1, tactics: int = 0) -> GumbelSearch:
+                      width: int = 1, batch: int = 1, tactics: int = 0, prove: bool = False) -> GumbelSearch:
         """Extension (the PGX board games): opens a Gumbel search (Danihelka et al., ICLR 2022) from the current
         position of every listed env (global ids; None: all): Gumbel top-`max_considered` sampling without replacement
         at the root, sequential halving of the `simulations` over those actions, a deterministic rule inside the tree;
@@ -496,6 +540,9 @@ class EnvPoolMixin(ABC):
         if tactics:
             raise ValueError("gumbel_search: tactics is an argument of policy='puct' (exact leaf status not implemented "
                              "for gumbel sessions)")
+        if native.check_guided_prove(prove):
+            raise ValueError("gumbel_search: prove is an argument of policy='puct' (proven values not implemented for "
+                             "gumbel sessions)")
         native.check_gumbel_batch(batch)
         ids = native.check_gumbel(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids),
                                   simulations, max_considered, c_visit, c_scale)

@@ -295,7 +295,7 @@ def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations
 def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulations: int = 64,
                          c_puct: float = 1.25, nodes: Any = None, keep_open: bool = False, width: Any = None,
                          advances: Any = None, tactics: int = 0,
-                         tactics_nodes: int = native.GUIDED_TACTICS_NODES) -> tuple[Any, Any, Any]:
+                         tactics_nodes: int = native.GUIDED_TACTICS_NODES, prove: bool = False) -> tuple[Any, Any, Any]:
     """A whole guided search (`pool.guided_begin` ..) with the evaluator on the device: `evaluate(obs, mask, status)`
     gets torch tensors on the pool's device (bool [k, H, W, C], bool [k, A], uint8 [k]) written by the search kernels
     and returns (priors float32 [k, A], values float32 [k]) there; nothing crosses PCIe and the host never waits.
@@ -310,7 +310,10 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     simply have fewer visits, which the result shows.
     `tactics` = D (1 .. 16), `tactics_nodes`: the exact leaf status (`DevicePool.guided_begin`): the solver's launch
     is enqueued behind every advance, so `evaluate` sees decided leaves as rows of status 1; the session keeps it
-    through `guided_reroot_device`, and `guided_decided_device` gives the counters (before the session is closed)."""
+    through `guided_reroot_device`, and `guided_decided_device` gives the counters (before the session is closed).
+    `prove` = True: proven values (`DevicePool.guided_begin`); a proven root's rows have status 2 for the rest of the
+    round, the session keeps the flag through `guided_reroot_device`, and `guided_proof_device` reads the proofs
+    (before the session is closed)."""
     import torch
 
     if env_ids is None:
@@ -319,6 +322,7 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     native.check_guided_nodes(simulations, nodes)
     width = native.check_guided_width(width)
     tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
+    prove = native.check_guided_prove(prove)
     if advances is not None and not width:
         raise ValueError("guided_search_device: advances is an argument of a wide session (width=)")
     h, w, c, a = pool.guided_shape()
@@ -328,7 +332,12 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
     mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
     status = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    if tactics:
+    if prove:
+        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
+                                                                     status.data_ptr(), ids, simulations, c_puct,
+                                                                     int(nodes or 0), width or None, tactics,
+                                                                     tactics_nodes, True))
+    elif tactics:
         _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
                                                                      status.data_ptr(), ids, simulations, c_puct,
                                                                      int(nodes or 0), width or None, tactics,
@@ -359,6 +368,20 @@ def guided_decided_device(pool: Any) -> Any:
     decided = torch.empty((k,), dtype=torch.int32, device=dev)
     _order_both_ways(pool, dev, lambda: pool.guided_decided_device(decided.data_ptr()))
     return decided
+
+
+def guided_proof_device(pool: Any) -> tuple[Any, Any]:
+    """(value int8 [k], q int8 [k, A]) on the pool's device: the proven values (`prove=True`) of the roots of the
+    pool's open PUCT session and of the children of their actions, -128 for none (`DevicePool.guided_proof`).  Only
+    enqueued, ordered both ways against torch's current stream."""
+    import torch
+
+    k = pool._guided_open("guided_proof", "puct")
+    dev = torch.device("cuda", pool.device)
+    value = torch.empty((k,), dtype=torch.int8, device=dev)
+    q = torch.empty((k, pool.guided_shape()[3]), dtype=torch.int8, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.guided_proof_device(value.data_ptr(), q.data_ptr()))
+    return value, q
 
 
 def guided_reroot_device(pool: Any, evaluate: Any, actions: Any, simulations: int,

@@ -706,6 +706,33 @@ int epa_guided_begin_tactics_device(epa_pool* pool, const int32_t* env_ids, int3
 int epa_guided_decided(epa_pool* pool, int32_t* decided, int64_t* nodes);
 int epa_guided_decided_device(epa_pool* pool, void* device_decided, void* device_nodes);
 
+/* Guided search, proven values (PUCT sessions, plain or wide, with or without nodes, tactics and reroot;
+ * csrc/pgx_guided.hip.h "Proven values" is the authority; MCTS-Solver): a session begun with flags = EPA_GUIDED_PROVE
+ * lets exact values climb the tree.  A finished game and a decided leaf are proven nodes; a node with a child proven +1
+ * for its mover is proven +1, a node whose every legal move leads to a proven child is proven with the best of their
+ * values (-1, 0 or +1), and such a node counts as finished from then on.  A pick never takes a move whose child is a
+ * proven loss for the mover while another is left, a proven root begins no further descent (its rows have status 2 for
+ * the rest of the round), and epa_guided_result's action is the most visited move that keeps the root's proven value,
+ * or for an unproven root the most visited move not proven to lose.  visits and values are unchanged.
+ *   epa_guided_begin_prove: the arguments of epa_guided_begin_tactics (tactics = 0: no solver stage) and flags.
+ *     flags = 0: exactly epa_guided_begin_tactics, the same launches and the same bytes.
+ *   epa_guided_proof, at any time: value int8 [k], the root's proven value for its mover; q int8 [k][A], per legal
+ *     root action the proven value of its child for the root's mover; EPA_GUIDED_UNPROVEN for unproven, no child,
+ *     illegal, a root that is over, and everywhere for a session without the flag.
+ *   EPA_ERR_INVALID, before any launch, beside the refusals of epa_guided_begin_tactics: a flags bit other than
+ *     EPA_GUIDED_PROVE.
+ * The _device forms take device pointers and only enqueue. */
+#define EPA_GUIDED_PROVE 1
+#define EPA_GUIDED_UNPROVEN (-128)
+int epa_guided_begin_prove(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations, int32_t nodes,
+                           int32_t width, float c_puct, int32_t tactics, int64_t tactics_nodes, int32_t flags,
+                           uint8_t* obs, uint8_t* mask, uint8_t* status);
+int epa_guided_begin_prove_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t simulations,
+                                  int32_t nodes, int32_t width, float c_puct, int32_t tactics, int64_t tactics_nodes,
+                                  int32_t flags, void* device_obs, void* device_mask, void* device_status);
+int epa_guided_proof(epa_pool* pool, int8_t* value, int8_t* q);
+int epa_guided_proof_device(epa_pool* pool, void* device_value, void* device_q);
+
 /* Gumbel search (no reference analogue; the four PGX board games): the guided-search session above with a second
  * selection policy -- Gumbel top-m sampling without replacement at the root, sequential halving of the simulations
  * over those m actions, a deterministic rule inside the tree, and the improved policy softmax(logits + sigma(completed
