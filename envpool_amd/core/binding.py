@@ -325,13 +325,14 @@ class _ShardedPools:
         self._each(run, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
         return visits, returns, action
 
-    def solve(self, env_ids: Any = None, depth: int = 0,
-              max_nodes: int = 1 << 20) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    def solve(self, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20,
+              table_bits: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """Solves envs of any shards, rows in request order: every shard solves its ids, all shards at once.  A row
-        depends on its position, depth and max_nodes only, so the rows are those of the unsharded pool."""
+        depends on its position, depth, max_nodes and table_bits only (a table is private to a lane of the row's
+        wave), so the rows are those of the unsharded pool."""
         if env_ids is None:
             env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
-        ids = native.check_solve(env_ids, depth, max_nodes)
+        ids = native.check_solve(env_ids, depth, max_nodes, table_bits)
         shard = (ids - self.offset) // self.per
         bad = ids[(shard < 0) | (shard >= len(self.pools))]
         if len(bad):
@@ -341,7 +342,7 @@ class _ShardedPools:
                np.empty(k, dtype=np.uint8), np.empty(k, dtype=np.int64))
 
         def run(s: int, p: DevicePool, idx: Any) -> None:
-            for whole, part in zip(out, p.solve(ids[idx], depth, max_nodes)):
+            for whole, part in zip(out, p.solve(ids[idx], depth, max_nodes, table_bits)):
                 whole[idx] = part
 
         self._each(run, [np.flatnonzero(shard == s) for s in range(len(self.pools))])
@@ -688,11 +689,13 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
                 raise RuntimeError("search not implemented for this environment")
             return search(env_ids, simulations, leaf_playouts, c_puct, max_plies, seed)
 
-        def _solve(self, env_ids: Any, depth: int, max_nodes: int) -> Any:
+        def _solve(self, env_ids: Any, depth: int, max_nodes: int, table_bits: int = 0) -> Any:
             solve = getattr(self._pool, "solve", None)
             if solve is None:  # a pool with its own executor
                 raise RuntimeError("solve not implemented for this environment")
-            return solve(env_ids, depth, max_nodes)
+            if table_bits == 0:  # today's call
+                return solve(env_ids, depth, max_nodes)
+            return solve(env_ids, depth, max_nodes, table_bits)
 
         def _guided(self) -> Any:
             if getattr(self._pool, "guided_begin", None) is None:  # a pool with its own executor

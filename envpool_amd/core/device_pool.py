@@ -501,8 +501,8 @@ class DevicePool:
             raise RuntimeError("solve not implemented for this environment")
         return int(n.value)
 
-    def solve(self, env_ids: Any = None, depth: int = 0,
-              max_nodes: int = 1 << 20) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    def solve(self, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20,
+              table_bits: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """The exact minimax value of the current position of every listed env (global ids; None: the whole pool),
         by alpha-beta in one kernel launch, one wave per root (the PGX board games; RuntimeError("solve not
         implemented for this environment") elsewhere).  `depth` D: the horizon in plies (a position the horizon cuts
@@ -510,28 +510,31 @@ class DevicePool:
         through each legal root action, seen from the root's mover, -128 for an illegal one, action int32 [k]: the
         lowest action of that value, status uint8 [k]: 0 solved, 1 given up after more than `max_nodes` positions, 2
         the env is over -- then value 0, action -1, q -128 --, nodes int64 [k]: the positions visited).  Nothing of the
-        pool changes."""
-        ids = native.check_solve(self._ids(env_ids), depth, max_nodes)
+        pool changes.  `table_bits` = b, 1 .. 16 (epa_solve_table): every lane of a root's wave keeps a private
+        transposition table of 2^b entries for the call, so a position it meets again is not searched again; the same
+        values wherever both solve the row, other `nodes`; 0: no tables, today's call."""
+        ids = native.check_solve(self._ids(env_ids), depth, max_nodes, table_bits)
         k, a = len(ids), self.solve_actions()
         value = np.empty(k, dtype=np.int8)
         q = np.empty((k, a), dtype=np.int8)
         action = np.empty(k, dtype=np.int32)
         status = np.empty(k, dtype=np.uint8)
         nodes = np.empty(k, dtype=np.int64)
-        native.check(self._lib.epa_solve(self._h, ids.ctypes.data, k, int(depth), int(max_nodes), value.ctypes.data,
-                                         q.ctypes.data, action.ctypes.data, status.ctypes.data, nodes.ctypes.data))
+        native.check(self._lib.epa_solve_table(self._h, ids.ctypes.data, k, int(depth), int(max_nodes),
+                                               int(table_bits), value.ctypes.data, q.ctypes.data, action.ctypes.data,
+                                               status.ctypes.data, nodes.ctypes.data))
         return value, q, action, status, nodes
 
     def solve_device(self, d_value: int, d_q: int, d_action: int, d_status: int, d_nodes: int, env_ids: Any = None,
-                     depth: int = 0, max_nodes: int = 1 << 20) -> None:
+                     depth: int = 0, max_nodes: int = 1 << 20, table_bits: int = 0) -> None:
         """`solve` into device memory at the raw addresses `d_value` (k bytes), `d_q` (k A bytes), `d_action` (4 k
         bytes, 4-byte aligned), `d_status` (k bytes) and `d_nodes` (8 k bytes, 8-byte aligned): only enqueued on the
         pool's stream, nothing is copied to the host (torch_interop.solve_device wraps it)."""
-        ids = native.check_solve(self._ids(env_ids), depth, max_nodes)
-        native.check(self._lib.epa_solve_device(self._h, ids.ctypes.data, len(ids), int(depth), int(max_nodes),
-                                                ctypes.c_void_p(d_value), ctypes.c_void_p(d_q),
-                                                ctypes.c_void_p(d_action), ctypes.c_void_p(d_status),
-                                                ctypes.c_void_p(d_nodes)))
+        ids = native.check_solve(self._ids(env_ids), depth, max_nodes, table_bits)
+        native.check(self._lib.epa_solve_table_device(self._h, ids.ctypes.data, len(ids), int(depth), int(max_nodes),
+                                                      int(table_bits), ctypes.c_void_p(d_value), ctypes.c_void_p(d_q),
+                                                      ctypes.c_void_p(d_action), ctypes.c_void_p(d_status),
+                                                      ctypes.c_void_p(d_nodes)))
 
     # -- guided tree search --------------------------------------------------------
     def guided_shape(self) -> tuple[int, int, int, int]:

@@ -38,6 +38,7 @@ GUIDED_UNPROVEN = -128   # EPA_GUIDED_UNPROVEN: "no proven value" in guided_proo
 GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per launch) of a batch Gumbel root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
+SOLVE_MAX_TABLE_BITS = 16  # EPA_SOLVE_MAX_TABLE_BITS: a lane's transposition table has at most 2^16 entries
 SOLVE_ILLEGAL = -128     # q of an illegal action, and of every action of a row that is not solved
 DTYPES = {0: np.int32, 1: np.float32, 2: np.float64, 3: np.bool_, 4: np.uint8, 5: np.int8}
 
@@ -138,6 +139,8 @@ def lib() -> ctypes.CDLL:
         "epa_search_device": (i32, [vp, vp, i32, i32, i32, ctypes.c_float, i32, ctypes.c_uint64, vp, vp, vp]),
         "epa_solve": (i32, [vp, vp, i32, i32, ctypes.c_int64, vp, vp, vp, vp, vp]),
         "epa_solve_device": (i32, [vp, vp, i32, i32, ctypes.c_int64, vp, vp, vp, vp, vp]),
+        "epa_solve_table": (i32, [vp, vp, i32, i32, ctypes.c_int64, i32, vp, vp, vp, vp, vp]),
+        "epa_solve_table_device": (i32, [vp, vp, i32, i32, ctypes.c_int64, i32, vp, vp, vp, vp, vp]),
         "epa_guided_shape": (i32, [vp, P(i32)]),
         "epa_guided_begin": (i32, [vp, vp, i32, i32, ctypes.c_float, vp, vp, vp]),
         "epa_guided_begin_device": (i32, [vp, vp, i32, i32, ctypes.c_float, vp, vp, vp]),
@@ -207,7 +210,7 @@ EXPORTED_SYMBOLS = [
     "epa_state_dim", "epa_get_state", "epa_set_state", "epa_render_size", "epa_render", "epa_render_device",
     "epa_snapshot_bytes", "epa_snapshot", "epa_restore", "epa_snapshot_device", "epa_restore_device", "epa_fork",
     "epa_playout", "epa_playout_device", "epa_search_actions", "epa_search", "epa_search_device",
-    "epa_solve", "epa_solve_device",
+    "epa_solve", "epa_solve_device", "epa_solve_table", "epa_solve_table_device",
     "epa_guided_shape", "epa_guided_begin", "epa_guided_begin_device", "epa_guided_advance",
     "epa_guided_advance_device", "epa_guided_result", "epa_guided_result_device", "epa_guided_end",
     "epa_guided_begin_nodes", "epa_guided_begin_nodes_device", "epa_guided_reroot", "epa_guided_reroot_device",
@@ -294,15 +297,18 @@ def check_search(env_ids: Any, simulations: int, leaf_playouts: int, c_puct: flo
     return ids
 
 
-def check_solve(env_ids: Any, depth: int, max_nodes: int) -> np.ndarray:
+def check_solve(env_ids: Any, depth: int, max_nodes: int, table_bits: int = 0) -> np.ndarray:
     """The ids of a solve call as a flat int32 array, after the argument checks every layer makes before the native
-    call: ValueError for a depth outside 0 .. 128, max_nodes below 1 (or past int64) and no ids.  (Ids outside the pool
-    and the size of the stacks are the engine's to refuse.)"""
+    call: ValueError for a depth outside 0 .. 128, max_nodes below 1 (or past int64), table_bits outside 0 .. 16 and
+    no ids.  (Ids outside the pool and the size of the stacks and tables are the engine's to refuse.)"""
     ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
     if isinstance(depth, bool) or int(depth) != depth or not 0 <= int(depth) <= SOLVE_MAX_DEPTH:
         raise ValueError(f"solve: depth = {depth} must be 0 .. {SOLVE_MAX_DEPTH}")
     if isinstance(max_nodes, bool) or int(max_nodes) != max_nodes or not 1 <= int(max_nodes) < 2**63:
         raise ValueError(f"solve: max_nodes = {max_nodes} must be at least 1")
+    if (isinstance(table_bits, bool) or int(table_bits) != table_bits
+            or not 0 <= int(table_bits) <= SOLVE_MAX_TABLE_BITS):
+        raise ValueError(f"solve: table_bits = {table_bits} must be in 0 .. {SOLVE_MAX_TABLE_BITS}")
     if len(ids) == 0:
         raise ValueError("solve env_ids must not be empty")
     return ids

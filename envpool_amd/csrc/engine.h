@@ -139,7 +139,8 @@ struct SearchArgs {
 };
 
 // One solve launch (Pool::Solve): k listed envs, row i of the five device result arrays being env row i's, and the
-// stacks of the roots' lanes, k * Pool::SolveRootBytes(depth) bytes.
+// stacks of the roots' lanes, k * Pool::SolveRootBytes(depth) bytes.  table_bits > 0: the lanes' transposition tables
+// behind them, k * Pool::SolveTableBytes(table_bits) bytes, all zero at the launch.
 struct SolveArgs {
   int k;
   int depth;                // 0: no horizon
@@ -150,6 +151,8 @@ struct SolveArgs {
   uint8_t* status;          // [k]
   long long* nodes;         // [k], 8-byte aligned
   void* stack;              // 16-byte aligned
+  void* table;              // 16-byte aligned; null without tables
+  int table_bits;           // 0: no tables
 };
 
 // A device allocation whose life is shorter than its pool's: it has ONE owner, which holds it by value, and goes when
@@ -434,11 +437,14 @@ class Pool {
   // SolveHost returns the results in host memory (one stream synchronisation); SolveDevice only enqueues.
   virtual bool HasSolve() const { return false; }
   virtual size_t SolveRootBytes(int /*depth*/) const { return 0; }  // a root's stacks; a multiple of 16
+  virtual size_t SolveTableBytes(int /*table_bits*/) const { return 0; }  // a root's tables; a multiple of 16
   virtual void Solve(const int* d_ids, const SolveArgs& a);
-  void SolveHost(const int32_t* ids, int k, int depth, long long max_nodes, int8_t* value, int8_t* q, int32_t* action,
-                 uint8_t* status, int64_t* nodes);
-  void SolveDevice(const int32_t* ids, int k, int depth, long long max_nodes, void* d_value, void* d_q, void* d_action,
-                   void* d_status, void* d_nodes);
+  // table_bits = b > 0 (epa_solve_table): every lane's private transposition table of 2^b entries, behind the stacks
+  // in the side scratch block, cleared on stream_ before the launch; 0: no tables, and no further launch.
+  void SolveHost(const int32_t* ids, int k, int depth, long long max_nodes, int table_bits, int8_t* value, int8_t* q,
+                 int32_t* action, uint8_t* status, int64_t* nodes);
+  void SolveDevice(const int32_t* ids, int k, int depth, long long max_nodes, int table_bits, void* d_value, void* d_q,
+                   void* d_action, void* d_status, void* d_nodes);
 
   // Guided tree search (include/envpool_amd.h: epa_guided_begin; the PGX board games, pgx_guided.hip.h): a search
   // whose tree stays on the device between launches and that stops at every new leaf, so that the caller supplies
@@ -711,8 +717,9 @@ class Pool {
   void CheckPlayout(const int32_t* ids, int k, int repeats, int max_plies, unsigned flags) const;
   // search's checks; throws before anything is enqueued.  Returns the bytes of the tree scratch.
   size_t CheckSearch(const int32_t* ids, int k, int simulations, int leaf_playouts, float c_puct, int max_plies) const;
-  // the checks of a solve call, before any launch; returns the bytes of the stacks
-  size_t CheckSolve(const int32_t* ids, int k, int depth, long long max_nodes) const;
+  // the checks of a solve call, before any launch; returns the bytes of the stacks (the tables follow them:
+  // k * SolveTableBytes(table_bits))
+  size_t CheckSolve(const int32_t* ids, int k, int depth, long long max_nodes, int table_bits) const;
   // the pool's guided-search session
   struct GuidedSession {
     bool open{false};

@@ -338,8 +338,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSearchKernel(CommonDev cm, co
 //   result     lane 0 writes the row (SolveRootResult)
 // The loop of a slice is divergent per lane: a round lasts as long as its slowest lane's kSolveSlice positions, and
 // lanes whose entries are done idle.  No floating point.
+//   tables     TABLE (table_bits > 0): lane j's transposition table, 2^table_bits entries of 32 bytes at entry
+//              (i * 64 + j) << table_bits of the table buffer, which the engine zeroed on the stream before the launch.
+//              A lane loads and stores its own entries only (two 16-byte words each, a probe's two loads issued
+//              together), in program order: no fence.  TABLE = false is the kernel without any of it.
 constexpr unsigned kErrSolve = 5;  // a solve met a running position without a legal action
 static_assert(pgx::kSolveMaxDepth == EPA_SOLVE_MAX_DEPTH, "the C ABI states the header's limits");
+static_assert(pgx::kSolveMaxTableBits == EPA_SOLVE_MAX_TABLE_BITS, "the C ABI states the header's limits");
 
 // what the traversal of one root came to: the positions visited, whether the root is given up, the broken flag
 struct SolveOutcome {
@@ -351,9 +356,10 @@ struct SolveOutcome {
 // The traversal for the block's root, shared by PgxSolveKernel and PgxGuidedTactics: the top tree, the rounds.  Every
 // field of the outcome is wave-uniform.  A root that is not given up has every child of the root known after one more
 // SolveCombine, which the caller's lane 0 runs (it has made every earlier LDS hand-off already).
-template <int G>
+template <int G, bool TABLE = false>
 __device__ __forceinline__ SolveOutcome SolveWave(pgx::SolveTop& top, const pgx::State& root, pgx::SolveWord* stack,
-                                                  int depth, long long max_nodes, int lane) {
+                                                  int depth, long long max_nodes, int lane,
+                                                  pgx::SolveWord* table = nullptr, int table_bits = 0) {
   const int limit = pgx::SolveLimit(depth);
   const bool hard = depth == 0;
   if (lane == 0) pgx::SolveTopInit(top, root);
@@ -382,7 +388,7 @@ __device__ __forceinline__ SolveOutcome SolveWave(pgx::SolveTop& top, const pgx:
     pgx::SolveLaneInit(l, lane);
     for (;;) {  // the rounds
       if (tree::WaveMax(pgx::SolveLaneBusy(l, top) ? 1 : 0) == 0) break;
-      pgx::SolveLaneSlice<G>(l, top, stack, lane, pgx::kSolveSlice, limit, hard);
+      pgx::SolveLaneSlice<G, TABLE>(l, top, stack, lane, pgx::kSolveSlice, limit, hard, table, table_bits);
       count = top.n + tree::WaveSum(l.visited);
       flags.overflow = tree::WaveMax(flags.overflow | l.flags.overflow);
       flags.broken = tree::WaveMax(flags.broken | l.flags.broken);
@@ -396,7 +402,7 @@ __device__ __forceinline__ SolveOutcome SolveWave(pgx::SolveTop& top, const pgx:
   return SolveOutcome{count, gave_up, flags.broken};
 }
 
-template <int G>
+template <int G, bool TABLE>
 __global__ __launch_bounds__(kSearchBlock) void PgxSolveKernel(CommonDev cm, const pgx::State* st,
                                                                const int* __restrict__ ids, SolveArgs a,
                                                                unsigned* err) {
@@ -416,7 +422,13 @@ __global__ __launch_bounds__(kSearchBlock) void PgxSolveKernel(CommonDev cm, con
   pgx::SolveWord* stack =
       reinterpret_cast<pgx::SolveWord*>(static_cast<char*>(a.stack) + (size_t)row * pgx::SolveStackBytes(a.depth));
   const pgx::State root = st[e];
-  const SolveOutcome out = SolveWave<G>(top, root, stack, a.depth, a.max_nodes, lane);
+  pgx::SolveWord* table = nullptr;  // the lane's own
+  if (TABLE) {
+    table = pgx::SolveLaneTable(reinterpret_cast<pgx::SolveWord*>(static_cast<char*>(a.table) +
+                                                                  (size_t)row * pgx::SolveTableBytes(a.table_bits)),
+                                lane, a.table_bits);
+  }
+  const SolveOutcome out = SolveWave<G, TABLE>(top, root, stack, a.depth, a.max_nodes, lane, table, a.table_bits);
   if (lane == 0) {
     a.nodes[row] = out.nodes;
     if (out.gave_up) {
@@ -1554,8 +1566,13 @@ class PgxPool : public Pool {
   }
   bool HasSolve() const override { return true; }
   size_t SolveRootBytes(int depth) const override { return pgx::SolveStackBytes(depth); }
+  size_t SolveTableBytes(int table_bits) const override { return pgx::SolveTableBytes(table_bits); }
   void Solve(const int* d_ids, const SolveArgs& a) override {
-    LaunchRoots(PgxSolveKernel<G>, a.k, common_, state_, d_ids, a, err_dev_);
+    if (a.table_bits != 0) {
+      LaunchRoots(PgxSolveKernel<G, true>, a.k, common_, state_, d_ids, a, err_dev_);
+      return;
+    }
+    LaunchRoots(PgxSolveKernel<G, false>, a.k, common_, state_, d_ids, a, err_dev_);
   }
   bool HasGuided() const override { return true; }
   void GuidedShape(int32_t shape[4]) const override {

@@ -50,6 +50,40 @@
 // (p * 5 + w) * 64 + j: the 64 lanes' words of one ply are contiguous, a wave's store or load of one word is 1 KiB in
 // one piece.  It is touched on the way down (a push: 5 stores) and up (a pop: 5 loads) only; a position whose game is
 // over or that the horizon cuts is valued from registers.
+//
+// Transposition tables (table_bits = b, 1 .. kSolveMaxTableBits; DESIGN.md "PGX solve: transposition tables").  b = 0
+// is the traversal above, untouched (the TABLE = false instantiations).  With b > 0 every lane of the root's wave owns
+// a private table of 2^b entries, empty (all bytes zero) at the start of the call and kept over the frontier entries
+// the lane takes.  A lane reads and writes its own table only, so the determinism rule above still holds: a row
+// depends on its position, D, max_nodes and b.
+//   stored   when a node is finished (the "done with" branch of SolveLaneSlice), with r >= kSolveTableFloor plies left
+//            (r = the limit minus the node's depth in T_D; with D = 0 the limit is the cap): a lower and an upper bound
+//            of its value for its mover, from the fail-hard result v and the window [alpha0, beta] it started with --
+//            v <= alpha0: [-1, v]; v >= beta: [v, 1]; otherwise [v, v].  alpha0 travels on the stack (bits 122 and 123
+//            of word 4).  A node left unfinished (a dead entry, a give-up) stores nothing.  A store always replaces.
+//   probed   a child that Step just made, that runs on and is above the horizon, with r >= kSolveTableFloor, before
+//            it is pushed (the Step is counted in `nodes` as before).  A hit gives a value only where that is sound:
+//            lo = hi, lo >= the child's beta, or hi <= the child's alpha; bounds cut, they never narrow a window.
+//   key      a hit needs every field equal that the value for the mover depends on; the hash only picks the slot.
+//            What Step reads, per game, and so what the key holds:
+//              a, b     all games (TicTacToe / ConnectFour: the colours' cells; Hex / Othello: the mover's and the
+//                       other's)
+//              flags    TicTacToe / ConnectFour: turn (the colour that places; a, b are absolute).  Hex: turn as one of
+//                       four classes -- 0 (the next ply opens the swap), 1 (the swap is open), even >= 2, odd >= 3 --:
+//                       Step reads turn & 1 (the mover's edges) and turn == 1, and turn + 1 of class c is of a class
+//                       that c fixes.  Othello: passed != 0.
+//              r        always, also for D = 0: the value at r plies left is not the value at r' (the horizon cuts
+//                       elsewhere; with D = 0 a line may pass the cap elsewhere), and an Othello pass lets a position
+//                       occur at two depths.
+//            Left out: cp -- the value is the mover's, whoever sits there: every reward is mapped to seats through
+//            cp, and SolveTerminal maps it back through the same cp (Hex: HexCurrent) --; Othello's turn, which Step
+//            only flips; m, a function of a, b and (Hex) turn == 1 by Step and SetHidden alike; done, 0 for every
+//            position that is stored or probed.
+//   entry    32 bytes, two 16-byte words: word 0 = a (bits 0 .. 120) and meta bits 0 .. 6 in bits 121 .. 127; word 1 =
+//            b and meta bits 7 .. 13 likewise (no game has a cell above 120).  meta: bits 0 .. 3 the bounds, 1 + 3 (lo
+//            + 1) + (hi + 1), 0: the entry is empty; bits 4 .. 5 the flags; bits 6 .. 12 r - 1; bit 13 zero.  Entry i
+//            of lane j of a root at 32-byte entry j * 2^b + i of the root's k-th part of the table buffer
+//            (SolveTableBytes per root).
 #ifndef ENVPOOL_AMD_CSRC_PGX_SOLVE_HIP_H_
 #define ENVPOOL_AMD_CSRC_PGX_SOLVE_HIP_H_
 
@@ -65,6 +99,8 @@ constexpr int kSolveSlice = 512;     // positions a lane may visit in one round
 constexpr int kSolveUnknown = 2;     // a node's value before it is known
 constexpr int kSolveIllegal = -128;  // q of an illegal action, and of every action of a row that is not solved
 constexpr int kSolveWords = 5;       // 16-byte words per ply and lane of the stack
+constexpr int kSolveMaxTableBits = 16;
+constexpr int kSolveTableFloor = 2;  // positions with fewer plies left are neither probed nor stored
 enum SolveStatus : int { kSolveSolved = 0, kSolveGivenUp = 1, kSolveOver = 2 };
 
 // plies a line may have: the horizon, or the cap; `hard`: a line that reaches it undecided is given up, not cut
@@ -79,6 +115,70 @@ struct alignas(16) SolveWord {
 };
 PGX_HD inline SolveWord* SolveSlot(SolveWord* stack, int lane, int ply, int w) {
   return stack + ((size_t)ply * kSolveWords + w) * kSolveWave + lane;
+}
+
+
+// ---- transposition table (the header comment has the contract and the layout) ----
+// bytes of one root's tables: 64 lanes x 2^bits entries of 32 bytes; 0 without a table
+PGX_HD inline size_t SolveTableBytes(int bits) { return bits == 0 ? 0 : ((size_t)kSolveWave * 32) << bits; }
+// lane j's table in a root's part of the buffer
+PGX_HD inline SolveWord* SolveLaneTable(SolveWord* root_table, int lane, int bits) {
+  return root_table + ((size_t)lane * 2 << bits);
+}
+
+// an entry's four 64-bit halves with the bounds zero
+struct SolveKey {
+  uint64_t w[4];
+};
+constexpr int kSolveMetaShift = 57;  // bit 121 of a 16-byte word, in its high half
+constexpr uint64_t kSolveBoundsMask = 15ull << kSolveMetaShift;
+
+template <int G>
+PGX_HD inline int SolveTableFlags(const State& s) {
+  if (G == kHex) return s.turn < 2 ? s.turn : 2 + (s.turn & 1);
+  if (G == kOthello) return s.passed != 0 ? 1 : 0;
+  return s.turn & 1;
+}
+template <int G>
+PGX_HD inline SolveKey SolveTableKey(const State& s, int plies_left) {
+  const uint64_t meta = (uint64_t)SolveTableFlags<G>(s) << 4 | (uint64_t)(plies_left - 1) << 6;
+  return SolveKey{{(uint64_t)s.a, (uint64_t)(s.a >> 64) | (meta & 127) << kSolveMetaShift, (uint64_t)s.b,
+                   (uint64_t)(s.b >> 64) | (meta >> 7) << kSolveMetaShift}};
+}
+// the slot of a key in a table of 2^bits entries
+PGX_HD inline uint32_t SolveTableIndex(const SolveKey& k, int bits) {
+  uint64_t h = k.w[0] * 0x9E3779B97F4A7C15ull ^ k.w[1] * 0xC2B2AE3D27D4EB4Full ^ k.w[2] * 0x165667B19E3779F9ull ^
+               k.w[3] * 0xD6E8FEB86659FD93ull;
+  h ^= h >> 32;
+  h *= 0x9E3779B97F4A7C15ull;
+  return (uint32_t)(h >> 32) & ((1u << bits) - 1u);
+}
+// the bounds stored under the key; false: none (the slot is empty or holds another position)
+PGX_HD inline bool SolveTableLookup(const SolveWord* table, int bits, const SolveKey& k, int* lo, int* hi) {
+  const SolveWord* e = table + (size_t)SolveTableIndex(k, bits) * 2;
+  const SolveWord e0 = e[0], e1 = e[1];
+  const int code = (int)((e0.hi & kSolveBoundsMask) >> kSolveMetaShift);
+  if (code == 0 || e0.lo != k.w[0] || (e0.hi & ~kSolveBoundsMask) != k.w[1] || e1.lo != k.w[2] || e1.hi != k.w[3]) {
+    return false;
+  }
+  *lo = (code - 1) / 3 - 1;
+  *hi = (code - 1) % 3 - 1;
+  return true;
+}
+// the value of the position for its mover in the window [alpha, beta], where the stored bounds give one; else
+// kSolveUnknown
+PGX_HD inline int SolveTableProbe(const SolveWord* table, int bits, const SolveKey& k, int alpha, int beta) {
+  int lo, hi;
+  if (!SolveTableLookup(table, bits, k, &lo, &hi)) return kSolveUnknown;
+  if (lo == hi || lo >= beta) return lo;
+  if (hi <= alpha) return hi;
+  return kSolveUnknown;
+}
+PGX_HD inline void SolveTableStore(SolveWord* table, int bits, const SolveKey& k, int lo, int hi) {
+  SolveWord* e = table + (size_t)SolveTableIndex(k, bits) * 2;
+  const uint64_t code = (uint64_t)(1 + 3 * (lo + 1) + (hi + 1));
+  e[0] = SolveWord{k.w[0], k.w[1] | code << kSolveMetaShift};
+  e[1] = SolveWord{k.w[2], k.w[3]};
 }
 
 // the value of the position `s` after a step with seat 0's reward `term0`, for the seat that moves at `s`
@@ -258,6 +358,7 @@ struct SolveLane {
   State cur;
   u128 rem;
   int32_t alpha, beta;
+  int32_t alpha0;  // the alpha cur started with (used with a table only)
   int32_t sp;      // nodes on the stack below cur
   int32_t base;    // the depth of the entry's node in T_D
   int32_t entry;   // index into the frontier list; >= count: nothing left
@@ -269,7 +370,7 @@ struct SolveLane {
 PGX_HD inline void SolveLaneInit(SolveLane& l, int lane) {
   l.cur = State{};
   l.rem = 0;
-  l.alpha = l.beta = 0;
+  l.alpha = l.beta = l.alpha0 = 0;
   l.sp = l.base = 0;
   l.entry = lane;
   l.active = 0;
@@ -279,14 +380,17 @@ PGX_HD inline void SolveLaneInit(SolveLane& l, int lane) {
 
 PGX_HD inline bool SolveLaneBusy(const SolveLane& l, const SolveTop& t) { return l.active || l.entry < t.count; }
 
+template <bool TABLE = false>
 PGX_HD inline void SolvePush(SolveWord* stack, int lane, const SolveLane& l) {
   const u128 w[4] = {l.cur.a, l.cur.b, l.cur.m,
                      (u128)(uint32_t)l.cur.turn | (u128)(uint32_t)l.cur.cp << 32 | (u128)(uint32_t)l.cur.passed << 64 |
                          (u128)(uint32_t)l.cur.done << 96};
   for (int i = 0; i < 4; ++i) *SolveSlot(stack, lane, l.sp, i) = SolveWord{(uint64_t)w[i], (uint64_t)(w[i] >> 64)};
   const uint64_t ab = (uint64_t)(l.alpha + 1) | (uint64_t)(l.beta + 1) << 2;
-  *SolveSlot(stack, lane, l.sp, 4) = SolveWord{(uint64_t)l.rem, (uint64_t)(l.rem >> 64) | ab << 60};
+  const uint64_t a0 = TABLE ? (uint64_t)(l.alpha0 + 1) << 58 : 0;
+  *SolveSlot(stack, lane, l.sp, 4) = SolveWord{(uint64_t)l.rem, (uint64_t)(l.rem >> 64) | a0 | ab << 60};
 }
+template <bool TABLE = false>
 PGX_HD inline void SolvePop(const SolveWord* stack, int lane, SolveLane& l) {
   u128 w[4];
   for (int i = 0; i < 4; ++i) {
@@ -301,16 +405,17 @@ PGX_HD inline void SolvePop(const SolveWord* stack, int lane, SolveLane& l) {
   l.cur.passed = (int32_t)(uint32_t)(w[3] >> 64);
   l.cur.done = (int32_t)(uint32_t)(w[3] >> 96);
   const SolveWord x = *SolveSlot(const_cast<SolveWord*>(stack), lane, l.sp, 4);
-  l.rem = (u128)(x.hi & ((1ull << 60) - 1)) << 64 | x.lo;
+  l.rem = (u128)(x.hi & ((1ull << (TABLE ? 58 : 60)) - 1)) << 64 | x.lo;
+  if (TABLE) l.alpha0 = (int)((x.hi >> 58) & 3) - 1;
   l.alpha = (int)((x.hi >> 60) & 3) - 1;
   l.beta = (int)((x.hi >> 62) & 3) - 1;
 }
 
 // One round of one lane: up to `budget` positions visited.  Reads t.dead, t.list, the entries' nodes; writes the value
-// of the entries it finishes (its own nodes only).
-template <int G>
+// of the entries it finishes (its own nodes only).  TABLE: with the lane's own table of 2^bits entries.
+template <int G, bool TABLE = false>
 PGX_HD inline void SolveLaneSlice(SolveLane& l, SolveTop& t, SolveWord* stack, int lane, int budget, int limit,
-                                  bool hard) {
+                                  bool hard, SolveWord* table = nullptr, int bits = 0) {
   if (l.active && t.dead[t.list[l.entry]]) {  // decided above: left as it is
     l.active = 0;
     l.entry += kSolveWave;
@@ -324,12 +429,20 @@ PGX_HD inline void SolveLaneSlice(SolveLane& l, SolveTop& t, SolveWord* stack, i
       l.rem = l.cur.m;
       l.alpha = -1;
       l.beta = 1;
+      if (TABLE) l.alpha0 = -1;
       l.sp = 0;
       l.base = t.depth[node];
       l.active = 1;
     }
     if (l.alpha >= l.beta || l.rem == 0) {  // cur is done with: its value is alpha
       const int v = l.alpha;
+      if (TABLE) {
+        const int left = limit - (l.base + l.sp);
+        if (left >= kSolveTableFloor) {
+          SolveTableStore(table, bits, SolveTableKey<G>(l.cur, left), v >= l.beta ? v : v <= l.alpha0 ? -1 : v,
+                          v >= l.beta ? 1 : v);
+        }
+      }
       if (l.sp == 0) {
         t.val[t.list[l.entry]] = (int8_t)v;
         l.active = 0;
@@ -337,7 +450,7 @@ PGX_HD inline void SolveLaneSlice(SolveLane& l, SolveTop& t, SolveWord* stack, i
         continue;
       }
       --l.sp;
-      SolvePop(stack, lane, l);
+      SolvePop<TABLE>(stack, lane, l);
       if (-v > l.alpha) l.alpha = -v;
       continue;
     }
@@ -355,13 +468,24 @@ PGX_HD inline void SolveLaneSlice(SolveLane& l, SolveTop& t, SolveWord* stack, i
       if (0 > l.alpha) l.alpha = 0;
     } else {
       if (child.m == 0) l.flags.broken = 1;
-      SolvePush(stack, lane, l);
+      if (TABLE) {  // the child's window is [-beta, -alpha]
+        const int left = limit - (l.base + l.sp + 1);
+        if (left >= kSolveTableFloor) {
+          const int v = SolveTableProbe(table, bits, SolveTableKey<G>(child, left), -l.beta, -l.alpha);
+          if (v != kSolveUnknown) {
+            if (-v > l.alpha) l.alpha = -v;
+            continue;
+          }
+        }
+      }
+      SolvePush<TABLE>(stack, lane, l);
       ++l.sp;
       const int na = -l.beta, nb = -l.alpha;
       l.cur = child;
       l.rem = child.m;
       l.alpha = na;
       l.beta = nb;
+      if (TABLE) l.alpha0 = na;
     }
   }
 }

@@ -463,14 +463,19 @@ class EnvPoolMixin(ABC):
         return Search(*self._search(ids, int(simulations), int(leaf_playouts), float(c_puct), int(max_plies),
                                     int(seed)))
 
-    def solve(self, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20) -> Solve:
+    def solve(self, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20, table_bits: int = 0) -> Solve:
         """Extension (the PGX board games): the exact minimax value of the current position of every listed env
         (global ids; None: all), by alpha-beta in one kernel launch; no model, no random numbers.  `depth`: the
         horizon in plies -- value +1 is then a forced win within `depth` plies, -1 a forced loss, 0 neither --, 0: to
         the end of the game.  A root that visits more than `max_nodes` positions is given up (status 1).  Nothing of
-        the pool changes.  The arguments are checked before any native call."""
-        ids = native.check_solve(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), depth, max_nodes)
-        return Solve(*self._solve(ids, int(depth), int(max_nodes)))
+        the pool changes.  The arguments are checked before any native call.
+        `table_bits` = b, 1 .. 16, gives every lane of a root's wave a private transposition table of 2^b entries
+        (32 bytes each, 64 lanes per root) for the call: a position the lane meets again, by another order of the same
+        moves, is not searched again.  The values are the same; `nodes` is mostly smaller, so a deep solve that is
+        given up at `max_nodes` without tables may be solved with them.  0: no tables."""
+        ids = native.check_solve(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), depth, max_nodes,
+                                 table_bits)
+        return Solve(*self._solve(ids, int(depth), int(max_nodes), int(table_bits)))
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
                       nodes: Any = None, width: int = 1, tactics: int = 0,

@@ -232,17 +232,17 @@ def search_device(pool: Any, env_ids: Any = None, simulations: int = 64, leaf_pl
     return visits, returns, action
 
 
-def solve_device(pool: Any, env_ids: Any = None, depth: int = 0,
-                 max_nodes: int = 1 << 20) -> tuple[Any, Any, Any, Any, Any]:
+def solve_device(pool: Any, env_ids: Any = None, depth: int = 0, max_nodes: int = 1 << 20,
+                 table_bits: int = 0) -> tuple[Any, Any, Any, Any, Any]:
     """`pool.solve` without the way down: (value int8 [k], q int8 [k, A], action int32 [k], status uint8 [k], nodes
     int64 [k]) as torch tensors on the pool's device, written by the solve kernel straight into torch's memory (no PCIe
     transfer, no host synchronisation: the call only enqueues) and ordered against torch's current stream like
-    `search_device`."""
+    `search_device`.  `table_bits`: the lanes' transposition tables (`DevicePool.solve`); 0: none."""
     import torch
 
     if env_ids is None:
         env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
-    ids = native.check_solve(env_ids, depth, max_nodes)
+    ids = native.check_solve(env_ids, depth, max_nodes, table_bits)
     k, a = len(ids), pool.solve_actions()
     dev = torch.device("cuda", pool.device)
     value = torch.empty((k,), dtype=torch.int8, device=dev)
@@ -251,7 +251,8 @@ def solve_device(pool: Any, env_ids: Any = None, depth: int = 0,
     status = torch.empty((k,), dtype=torch.uint8, device=dev)
     nodes = torch.empty((k,), dtype=torch.int64, device=dev)
     _order_both_ways(pool, dev, lambda: pool.solve_device(value.data_ptr(), q.data_ptr(), action.data_ptr(),
-                                                          status.data_ptr(), nodes.data_ptr(), ids, depth, max_nodes))
+                                                          status.data_ptr(), nodes.data_ptr(), ids, depth, max_nodes,
+                                                          table_bits))
     return value, q, action, status, nodes
 
 

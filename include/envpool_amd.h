@@ -532,6 +532,29 @@ int epa_solve_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t 
                      void* device_value, void* device_q, void* device_action, void* device_status,
                      void* device_nodes);
 
+/* PGX solve with transposition tables (csrc/pgx_solve.hip.h "Transposition tables"): epa_solve / epa_solve_device with
+ * table_bits = b, 0 .. EPA_SOLVE_MAX_TABLE_BITS.
+ *   b = 0: exactly epa_solve / epa_solve_device (which call these entries with 0): the same launches and the same
+ *     bytes in all five results.
+ *   b > 0: every lane of a root's wave owns a private table of 2^b entries of 32 bytes in device memory, empty at the
+ *     start of every call (the engine clears the buffer on the pool's stream) and kept over the frontier entries the
+ *     lane takes.  It stores a lower and an upper bound of every finished position with at least two plies left to
+ *     the horizon (D = 0: to the cap), and a position that Step just made is looked up before it is searched.  A hit
+ *     needs the whole position, the plies left included, to be equal; the hash only picks the slot.
+ *   value, q, action and status 0 / 2 are those of epa_solve wherever both solve the row: the values are exact.
+ *   `nodes` is mostly smaller (no promise per row), and which rows are given up at a tight max_nodes follows the new
+ *   traversal.  Determinism as for epa_solve: the same call gives the same bytes, and a row depends on its position,
+ *   D, max_nodes and b only -- the tables are private to a lane, so not on id order, repeated ids or sharding.
+ *   EPA_ERR_INVALID, before any launch, beside the refusals of epa_solve: b outside 0 .. EPA_SOLVE_MAX_TABLE_BITS
+ *     ("solve: table_bits = .. must be in 0 .. 16"); the stacks plus the tables (k roots x 64 lanes x 2^b x 32 bytes)
+ *     above EPA_SEARCH_MAX_TREE_BYTES: the message names the largest k that fits. */
+#define EPA_SOLVE_MAX_TABLE_BITS 16
+int epa_solve_table(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t depth, int64_t max_nodes,
+                    int32_t table_bits, int8_t* value, int8_t* q, int32_t* action, uint8_t* status, int64_t* nodes);
+int epa_solve_table_device(epa_pool* pool, const int32_t* env_ids, int32_t k, int32_t depth, int64_t max_nodes,
+                           int32_t table_bits, void* device_value, void* device_q, void* device_action,
+                           void* device_status, void* device_nodes);
+
 /* Guided tree search (no reference analogue; the four PGX board games): a PUCT search whose tree lives on the device
  * between calls and that stops at every new leaf, so that the caller -- a policy / value model next to the pool in
  * HBM -- supplies the priors and the leaf values (AlphaZero-style).  One kernel launch per simulation, one wave per

@@ -3,6 +3,12 @@ same header (tests/cpu_harness/pgx_solve_host.cpp) on one host core:
 
   Othello      k late positions (`--othello-plies` random plies in, by committed playouts), D = 0: to the end of the game
   ConnectFour  k positions `--connect-plies` random plies in, D = 8
+  ConnectFour  `--deep-k` positions `--deep-plies` random plies in, D = 0: to the end of the game, every root with at
+               most `--deep-max-nodes` positions (the trees of some of these roots have 10^8 positions and more)
+
+`--table-bits b` (1 .. 16) solves with the lanes' transposition tables (solve table_bits=) and compares with the harness
+that has them (tests/cpu_harness/pgx_solve_table_host.cpp); without it, or with 0, the calls and the harness are the
+table-less ones.
 
 A rate is `nodes` summed over the rows -- the positions the solver visited, which the kernel and the harness count
 alike -- over the time of the call: for the GPU a host clock around `pool.solve` (launch, kernel, the copy of the five
@@ -11,9 +17,12 @@ host clock around the first `--host-rows` rows (the harness is single-threaded a
 rate is per position).  `lane_turns_used` is counted by the harness on those rows: the positions visited over the turns
 the waves' lanes had (64 lanes x 512 turns x the lockstep rounds run) -- how evenly alpha-beta's uneven subtrees fill a
 wave, whatever the machine.  At D = 0 a root's stacks are 640 KiB and 3276 roots fit the 2 GiB of scratch, so k = 4096 is
-solved in two calls, both inside the timed window.  Rows that were given up or are over are counted and reported.
+solved in two calls, both inside the timed window; a root's tables are 64 x 2^b x 32 bytes more.  Rows that were given
+up or are over are counted and reported.
 
     python tools/bench_pgx_solve.py [--k 4096] [--repeats 3] [--host-rows 64] [--othello-plies 48] [--connect-plies 6]
+                                    [--deep-k 64] [--deep-plies 24] [--deep-max-nodes 4194304] [--table-bits 0]
+                                    [--rows othello,connect,deep]
 """
 import argparse
 import ctypes
@@ -34,14 +43,15 @@ SCRATCH = 2**31  # EPA_SEARCH_MAX_TREE_BYTES
 STACK_BYTES_PER_PLY = 64 * 80
 
 
-def harness():
+def harness(table_bits):
     out = os.path.join(tempfile.mkdtemp(prefix="pgx_solve_"), "libpgxsolvehost.so")
+    source = "pgx_solve_table_host.cpp" if table_bits else "pgx_solve_host.cpp"
     subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off",
-                    os.path.join(ROOT, "tests", "cpu_harness", "pgx_solve_host.cpp"), "-o", out], check=True)
+                    os.path.join(ROOT, "tests", "cpu_harness", source), "-o", out], check=True)
     return ctypes.CDLL(out)
 
 
-def host_solve(lib, fam, st, n_act, depth, max_nodes):
+def host_solve(lib, fam, st, n_act, depth, max_nodes, table_bits):
     hid = np.ascontiguousarray(st[:, 2:], np.int32)
     done = np.ascontiguousarray(st[:, 1] != 0, np.uint8)
     k = len(hid)
@@ -50,7 +60,11 @@ def host_solve(lib, fam, st, n_act, depth, max_nodes):
     nodes, broken, rounds = np.zeros(k, np.int64), np.zeros(k, np.uint8), np.zeros(k, np.int64)
     ptr = [a.ctypes.data_as(ctypes.c_void_p) for a in (hid, done, value, q, action, status, nodes, broken, rounds)]
     t0 = time.perf_counter()
-    rc = lib.pgx_solve(CODE[fam], k, ptr[0], ptr[1], depth, ctypes.c_longlong(max_nodes), *ptr[2:])
+    if table_bits:
+        rc = lib.pgx_solve_table(CODE[fam], k, ptr[0], ptr[1], depth, ctypes.c_longlong(max_nodes), table_bits,
+                                 *ptr[2:])
+    else:
+        rc = lib.pgx_solve(CODE[fam], k, ptr[0], ptr[1], depth, ctypes.c_longlong(max_nodes), *ptr[2:])
     dt = time.perf_counter() - t0
     assert rc == 0, rc
     # the share of the lanes' turns that visited a position: a round gives each of a wave's 64 lanes up to
@@ -59,10 +73,11 @@ def host_solve(lib, fam, st, n_act, depth, max_nodes):
     return (value, q, action, status, nodes), dt, float(busy)
 
 
-def gpu_solve(pool, ids, depth, max_nodes):
+def gpu_solve(pool, ids, depth, max_nodes, table_bits):
     """pool.solve in as few calls as the scratch limit allows."""
-    per_call = SCRATCH // ((depth or 128) * STACK_BYTES_PER_PLY)
-    parts = [pool.solve(ids[i:i + per_call], depth, max_nodes) for i in range(0, len(ids), per_call)]
+    per_call = SCRATCH // ((depth or 128) * STACK_BYTES_PER_PLY + (64 * 32 << table_bits if table_bits else 0))
+    kw = dict(table_bits=table_bits) if table_bits else {}
+    parts = [pool.solve(ids[i:i + per_call], depth, max_nodes, **kw) for i in range(0, len(ids), per_call)]
     return tuple(np.concatenate(x) for x in zip(*parts)), len(parts)
 
 
@@ -74,31 +89,42 @@ def main():
     ap.add_argument("--othello-plies", type=int, default=48)
     ap.add_argument("--connect-plies", type=int, default=6)
     ap.add_argument("--max-nodes", type=int, default=1 << 40)
+    ap.add_argument("--deep-k", type=int, default=64)
+    ap.add_argument("--deep-plies", type=int, default=24)
+    ap.add_argument("--deep-max-nodes", type=int, default=1 << 22)
+    ap.add_argument("--table-bits", type=int, default=0)
+    ap.add_argument("--rows", default="othello,connect,deep")
     args = ap.parse_args()
+    bits, rows_wanted = args.table_bits, args.rows.split(",")
     from envpool_amd.core.device_pool import DevicePool
 
-    lib = harness()
-    for fam, plies, depth in (("Othello", args.othello_plies, 0), ("ConnectFour", args.connect_plies, 8)):
-        pool = DevicePool(fam, args.k, seed=0)
-        ids = np.arange(args.k, dtype=np.int32)
+    lib = harness(bits)
+    for row, fam, plies, depth, k, max_nodes in (
+            ("othello", "Othello", args.othello_plies, 0, args.k, args.max_nodes),
+            ("connect", "ConnectFour", args.connect_plies, 8, args.k, args.max_nodes),
+            ("deep", "ConnectFour", args.deep_plies, 0, args.deep_k, args.deep_max_nodes)):
+        if row not in rows_wanted:
+            continue
+        pool = DevicePool(fam, k, seed=0)
+        ids = np.arange(k, dtype=np.int32)
         pool.reset(ids)
         pool.recv_dict()
         pool.playout(ids, 1, plies, 15, commit=True)
         st = pool.get_state()
         n_act = pool.solve_actions()
-        got, calls = gpu_solve(pool, ids, depth, args.max_nodes)  # the warm-up call
+        got, calls = gpu_solve(pool, ids, depth, max_nodes, bits)  # the warm-up call
         times = []
         for _ in range(args.repeats):
             t0 = time.perf_counter()
-            again, _ = gpu_solve(pool, ids, depth, args.max_nodes)
+            again, _ = gpu_solve(pool, ids, depth, max_nodes, bits)
             times.append(time.perf_counter() - t0)
             assert all(np.array_equal(a, b) for a, b in zip(again, got))
-        rows = min(args.host_rows, args.k)
-        want, host_s, busy = host_solve(lib, fam, st[:rows], n_act, depth, args.max_nodes)
+        rows = min(args.host_rows, k)
+        want, host_s, busy = host_solve(lib, fam, st[:rows], n_act, depth, max_nodes, bits)
         equal = all(np.array_equal(g[:rows], w) for g, w in zip(got, want))
         gpu_s = float(np.median(times))
         gpu_rate, host_rate = got[4].sum() / gpu_s, want[4].sum() / max(host_s, 1e-9)
-        print(json.dumps({"game": fam, "k": args.k, "plies_in": plies, "depth": depth, "calls": calls,
+        print(json.dumps({"game": fam, "k": k, "plies_in": plies, "depth": depth, "table_bits": bits, "calls": calls,
                           "solved": int((got[3] == 0).sum()), "given_up": int((got[3] == 1).sum()),
                           "over": int((got[3] == 2).sum()), "nodes": int(got[4].sum()),
                           "nodes_max_row": int(got[4].max()), "gpu_s": round(gpu_s, 4),
