@@ -579,26 +579,9 @@ class DevicePool:
         prove = native.check_guided_prove(prove)
         self.guided_shape()
         obs, mask, status = self._guided_leaves(len(ids), width)
-        if prove:
-            native.check(self._lib.epa_guided_begin_prove(
-                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
-                tactics_nodes, native.GUIDED_PROVE, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
-        elif tactics:
-            native.check(self._lib.epa_guided_begin_tactics(
-                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
-                tactics_nodes, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
-        elif width:
-            native.check(self._lib.epa_guided_begin_wide(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                         int(nodes or 0), width, float(c_puct), obs.ctypes.data,
-                                                         mask.ctypes.data, status.ctypes.data))
-        elif nodes:
-            native.check(self._lib.epa_guided_begin_nodes(self._h, ids.ctypes.data, len(ids), int(simulations), cap,
-                                                          float(c_puct), obs.ctypes.data, mask.ctypes.data,
-                                                          status.ctypes.data))
-        else:
-            native.check(self._lib.epa_guided_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                    float(c_puct), obs.ctypes.data, mask.ctypes.data,
-                                                    status.ctypes.data))
+        native.check(self._lib.epa_guided_begin_prove(
+            self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+            tactics_nodes, native.GUIDED_PROVE if prove else 0, obs.ctypes.data, mask.ctypes.data, status.ctypes.data))
         self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
         self._guided_width = width
         return obs, mask, status
@@ -705,27 +688,10 @@ class DevicePool:
         width = native.check_guided_width(width)
         tactics, tactics_nodes = native.check_guided_tactics(tactics, tactics_nodes)
         prove = native.check_guided_prove(prove)
-        if prove:
-            native.check(self._lib.epa_guided_begin_prove_device(
-                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
-                tactics_nodes, native.GUIDED_PROVE, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
-                ctypes.c_void_p(d_status)))
-        elif tactics:
-            native.check(self._lib.epa_guided_begin_tactics_device(
-                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
-                tactics_nodes, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
-        elif width:
-            native.check(self._lib.epa_guided_begin_wide_device(
-                self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct),
-                ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
-        elif nodes:
-            native.check(self._lib.epa_guided_begin_nodes_device(
-                self._h, ids.ctypes.data, len(ids), int(simulations), cap, float(c_puct), ctypes.c_void_p(d_obs),
-                ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
-        else:
-            native.check(self._lib.epa_guided_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                           float(c_puct), ctypes.c_void_p(d_obs),
-                                                           ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
+        native.check(self._lib.epa_guided_begin_prove_device(
+            self._h, ids.ctypes.data, len(ids), int(simulations), int(nodes or 0), width, float(c_puct), tactics,
+            tactics_nodes, native.GUIDED_PROVE if prove else 0, ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+            ctypes.c_void_p(d_status)))
         self._guided_k, self._guided_policy, self._guided_nodes = len(ids), "puct", cap
         self._guided_width = width
         return len(ids)
@@ -764,6 +730,18 @@ class DevicePool:
             raise RuntimeError("gumbel search not implemented for this environment")
         return int(out[3])
 
+    def _gumbel_begin(self, form: str, ids: np.ndarray, simulations: int, considered: int, batch: int,
+                      c_visit: float, c_scale: float, *arrays: Any) -> None:
+        """The native begin of a Gumbel session, host ("") or "_device" form, `arrays` being its noise, obs, mask and
+        status.  A plain session keeps an entry point of its own: epa_gumbel_begin_batch takes a batch of 1 .. 32 and
+        refuses 0."""
+        head = (self._h, ids.ctypes.data, len(ids), int(simulations), considered)
+        tail = (float(c_visit), float(c_scale)) + arrays
+        if batch:
+            native.check(getattr(self._lib, "epa_gumbel_begin_batch" + form)(*head, batch, *tail))
+        else:
+            native.check(getattr(self._lib, "epa_gumbel_begin" + form)(*head, *tail))
+
     def gumbel_begin(self, gumbel: Any, env_ids: Any = None, simulations: int = 32, max_considered: int = 16,
                      c_visit: float = 50.0, c_scale: float = 0.1,
                      batch: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -781,16 +759,8 @@ class DevicePool:
         a = self.gumbel_actions()
         gumbel = native.check_gumbel_noise(gumbel, len(ids), a)
         obs, mask, status = self._guided_leaves(len(ids), batch)
-        if batch:
-            native.check(self._lib.epa_gumbel_begin_batch(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                          min(int(max_considered), a), batch, float(c_visit),
-                                                          float(c_scale), gumbel.ctypes.data, obs.ctypes.data,
-                                                          mask.ctypes.data, status.ctypes.data))
-        else:
-            native.check(self._lib.epa_gumbel_begin(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                    min(int(max_considered), a), float(c_visit), float(c_scale),
-                                                    gumbel.ctypes.data, obs.ctypes.data, mask.ctypes.data,
-                                                    status.ctypes.data))
+        self._gumbel_begin("", ids, simulations, min(int(max_considered), a), batch, c_visit, c_scale,
+                           gumbel.ctypes.data, obs.ctypes.data, mask.ctypes.data, status.ctypes.data)
         self._guided_k, self._guided_policy, self._gumbel_batch = len(ids), "gumbel", batch
         return obs, mask, status
 
@@ -838,17 +808,9 @@ class DevicePool:
         ids = native.check_gumbel(self._ids(env_ids), simulations, max_considered, c_visit, c_scale)
         batch = native.check_gumbel_batch(batch)
         a = self.gumbel_actions()
-        if batch:
-            native.check(self._lib.epa_gumbel_begin_batch_device(
-                self._h, ids.ctypes.data, len(ids), int(simulations), min(int(max_considered), a), batch,
-                float(c_visit), float(c_scale), ctypes.c_void_p(d_gumbel), ctypes.c_void_p(d_obs),
-                ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status)))
-        else:
-            native.check(self._lib.epa_gumbel_begin_device(self._h, ids.ctypes.data, len(ids), int(simulations),
-                                                           min(int(max_considered), a), float(c_visit),
-                                                           float(c_scale), ctypes.c_void_p(d_gumbel),
-                                                           ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
-                                                           ctypes.c_void_p(d_status)))
+        self._gumbel_begin("_device", ids, simulations, min(int(max_considered), a), batch, c_visit, c_scale,
+                           ctypes.c_void_p(d_gumbel), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                           ctypes.c_void_p(d_status))
         self._guided_k, self._guided_policy, self._gumbel_batch = len(ids), "gumbel", batch
         return len(ids)
 

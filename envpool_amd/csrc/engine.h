@@ -201,6 +201,21 @@ struct GuidedArgs {
   int32_t* visits;          // [k][A]
   float* vals;              // [k][A]
   int32_t* action;          // [k]
+  int flags;                // the session's EPA_GUIDED_* flags: the family chooses its kernels (last: the words above
+                            // leave no padding)
+};
+
+// What opens a PUCT session (Pool::GuidedBeginCall).  The defaults are a plain session: every epa_guided_begin* entry
+// point sets the fields it has and leaves the others.
+struct GuidedBeginOptions {
+  int simulations{0};
+  int nodes{0};             // the capacity per root, simulations + 1 .. EPA_GUIDED_MAX_NODES; 0: simulations + 1
+  int width{0};             // slots per root, 1 .. EPA_GUIDED_MAX_WIDTH: a wide session, whose leaf arrays have
+                            // k * width rows from then on; 0: a plain session
+  float c_puct{0.0f};
+  int tactics{0};           // exact leaf status: the solver's horizon D, 1 .. EPA_GUIDED_MAX_TACTICS; 0: off
+  long long tactics_nodes{EPA_GUIDED_TACTICS_NODES};  // ... and its node budget M per leaf
+  int flags{0};             // EPA_GUIDED_PROVE: proven values
 };
 
 // The solver stage of an advance of a guided session with tactics (Pool::GuidedTactics; pgx_guided.hip.h "Exact leaf
@@ -454,7 +469,7 @@ class Pool {
   // enters through SideEnter like the other side operations: begin sees the state every send issued before it has
   // left, and the session's launches are ordered behind each other on whichever stream they land.  The host forms
   // copy through the session's pinned block and synchronise once; the device forms only enqueue and leave through
-  // SideLeave.  A family without the hooks keeps the defaults, and every entry point throws
+  // SideLeave: SessionRun below is that path, for every call of either policy.  A family without the hooks keeps the defaults, and every entry point throws
   // std::runtime_error("guided search not implemented for this environment").
   virtual bool HasGuided() const { return false; }
   virtual void GuidedShape(int32_t shape[4]) const { shape[0] = shape[1] = shape[2] = shape[3] = 0; }  // H, W, C, A
@@ -466,34 +481,22 @@ class Pool {
   virtual void GuidedReroot(const GuidedArgs& a);
   // exact leaf status (pgx_guided.hip.h "Exact leaf status"): the solver stage after an advance's descents
   virtual void GuidedTactics(const GuidedArgs& a, const TacticsArgs& t);
-  // proven values (pgx_guided.hip.h "Proven values"): advance, result and reroot of a session begun with
-  // EPA_GUIDED_PROVE, and its read-out (value int8 [k], q int8 [k][A], device memory)
-  virtual void GuidedAdvanceProve(const GuidedArgs& a);
-  virtual void GuidedResultProve(const GuidedArgs& a);
-  virtual void GuidedRerootProve(const GuidedArgs& a);
+  // proven values (pgx_guided.hip.h "Proven values"): the read-out of a session begun with EPA_GUIDED_PROVE (value
+  // int8 [k], q int8 [k][A], device memory)
   virtual void GuidedProof(const GuidedArgs& a, signed char* value, signed char* q);
-  // wide sessions (pgx_guided.hip.h "Several leaves per launch"): a.width slots per root; the four hooks above serve
-  // them too (a.width != 0: the family chooses its kernels)
+  // wide sessions (pgx_guided.hip.h "Several leaves per launch", a.width slots per root) and sessions with proven
+  // values (a.flags) go through the hooks above too: the family chooses its kernels by a.width and a.flags
   virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
   virtual size_t GuidedWideLiveOffset() const { return 0; }  // of a record's int32 count of pending slots
-  // obs / mask / status: host arrays (device == false) or device pointers.  nodes: the capacity per root, 0 for
-  // simulations + 1.
-  void GuidedBeginCall(const int32_t* ids, int k, int simulations, int nodes, float c_puct, void* obs, void* mask,
-                       void* status, bool device);
-  // ... with `width` slots per root (0: a plain session): the leaf arrays have k * width rows from then on
-  void GuidedBeginWideCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct, void* obs,
-                           void* mask, void* status, bool device);
-  // Exact leaf status: begin with tactics = D (0: off, exactly the calls above) and tactics_nodes = M; width 0: a
-  // plain session.  GuidedDecidedCall: the session's counters, decided int32 [k] and (may be null) the solver's
-  // visited positions int64 [k]; the device form only enqueues.
-  void GuidedBeginTacticsCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct,
-                              int tactics, long long tactics_nodes, void* obs, void* mask, void* status, bool device);
+  // The one begin of a PUCT session, whatever its options.  obs / mask / status: host arrays (device == false) or
+  // device pointers.
+  void GuidedBeginCall(const int32_t* ids, int k, const GuidedBeginOptions& o, void* obs, void* mask, void* status,
+                       bool device);
+  // Exact leaf status: the session's counters, decided int32 [k] and (may be null) the solver's visited positions
+  // int64 [k]; zeros for a session without tactics; the device form only enqueues.
   void GuidedDecidedCall(void* decided, void* nodes, bool device);
-  // Proven values: begin with a flags word (EPA_GUIDED_PROVE; 0: exactly the call above).  GuidedProofCall: value int8
-  // [k] and q int8 [k][A]; -128 everywhere for a session without the flag; the device form only enqueues.
-  void GuidedBeginProveCall(const int32_t* ids, int k, int simulations, int nodes, int width, float c_puct,
-                            int tactics, long long tactics_nodes, int flags, void* obs, void* mask, void* status,
-                            bool device);
+  // Proven values: value int8 [k] and q int8 [k][A]; -128 everywhere for a session without EPA_GUIDED_PROVE; the
+  // device form only enqueues.
   void GuidedProofCall(void* value, void* q, bool device);
   // Tree reuse (pgx_guided.hip.h "Tree reuse"): after the round's last advance, the subtree under actions[i] becomes
   // root i's tree, `simulations` the length of the next round, and the new roots are emitted as begin emits its own.
@@ -519,11 +522,10 @@ class Pool {
   // batch sessions (pgx_gumbel.hip.h "A level per launch"): a.batch slots per root; the three hooks above serve them
   // too (a.batch != 0: the family chooses its kernels)
   virtual size_t GumbelBatchRootBytes(int batch) const { (void)batch; return 0; }  // a multiple of 16
-  void GumbelBeginCall(const int32_t* ids, int k, int simulations, int considered, float c_visit, float c_scale,
-                       const void* gumbel, void* obs, void* mask, void* status, bool device);
-  // ... with `batch` slots per root (0: a plain session): the leaf arrays have k * batch rows from then on
-  void GumbelBeginBatchCall(const int32_t* ids, int k, int simulations, int considered, int batch, float c_visit,
-                            float c_scale, const void* gumbel, void* obs, void* mask, void* status, bool device);
+  // The one begin of a Gumbel session.  batch: slots per root, 1 .. EPA_GUMBEL_MAX_BATCH: the leaf arrays have
+  // k * batch rows from then on (the noise keeps k); 0: a plain session.
+  void GumbelBeginCall(const int32_t* ids, int k, int simulations, int considered, int batch, float c_visit,
+                       float c_scale, const void* gumbel, void* obs, void* mask, void* status, bool device);
   void GumbelAdvanceCall(const void* logits, const void* values, int k, void* obs, void* mask, void* status,
                          bool device);
   void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
@@ -748,9 +750,24 @@ class Pool {
   void GuidedFree();                                   // (no session: nothing)
   void GuidedRequire(const char* what) const;          // throws without a session
   void GuidedRequirePolicy(const char* what, bool gumbel) const;  // ... or with one of the other policy
+  // what GuidedArgs and GumbelArgs share: the session's sizes, call number, roots and nodes, and for a host form the
+  // staging arrays, `rows` among them (the caller's rows of an advance: priors or logits)
+  template <class Args>
+  Args SessionArgsOf(bool device, const float* Args::*rows) const;
   GuidedArgs GuidedArgsOf(bool device) const;          // the session's pointers; staging arrays for a host form
   TacticsArgs TacticsArgsOf() const;                   // (a session with tactics)
   GumbelArgs GumbelArgsOf(bool device) const;
+  // One session call in either form, between SideEnter and SideLeave; `launch` enqueues the call's work on stream_.
+  //   device form  launch, SideLeave: nothing waits
+  //   host form    bytes [up.lo, up.hi) of the pinned block go to the staging, launch, bytes [down.lo, down.hi) of the
+  //                staging come back to the pinned block, ONE hipStreamSynchronize(stream_); an empty range: no copy
+  // The caller fills SessionPinned() before and reads it after; its checks come before both.
+  struct StageRange {
+    size_t lo{0}, hi{0};
+  };
+  template <class Launch>
+  void SessionRun(bool device, StageRange up, StageRange down, Launch launch);
+  char* SessionPinned();  // the host forms' pinned block, allocated at its first use in a session
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

@@ -1590,51 +1590,32 @@ class PgxPool : public Pool {
       LaunchRoots(PgxGuidedBegin<G, false>, a.k, common_, state_, d_ids, a);
     }
   }
+  // ... and a.flags has EPA_GUIDED_PROVE: the PROVE instantiations (pgx_guided.hip.h "Proven values")
   void GuidedAdvance(const GuidedArgs& a) override {
-    if (a.width == 0) return LaunchRoots(PgxGuidedAdvance<G>, a.k, a, err_dev_);
-    Bucket<kWideBuckets>(a.width, [&](auto wb) {
-      LaunchRoots(PgxGuidedAdvanceWide<G, decltype(wb)::value>, a.k, a, err_dev_);
+    Flags(a.width != 0, Proves(a), [&](auto wide, auto prove) {
+      constexpr bool kProve = decltype(prove)::value;
+      if constexpr (!decltype(wide)::value) {
+        LaunchRoots(PgxGuidedAdvance<G, kProve>, a.k, a, err_dev_);
+      } else {
+        Bucket<kWideBuckets>(a.width, [&](auto wb) {
+          LaunchRoots(PgxGuidedAdvanceWide<G, decltype(wb)::value, kProve>, a.k, a, err_dev_);
+        });
+      }
     });
   }
   void GuidedResult(const GuidedArgs& a) override {
-    if (a.width != 0) {
-      LaunchRoots(PgxGuidedResult<G, true>, a.k, a);
-    } else {
-      LaunchRoots(PgxGuidedResult<G, false>, a.k, a);
-    }
+    Flags(a.width != 0, Proves(a), [&](auto wide, auto prove) {
+      LaunchRoots(PgxGuidedResult<G, decltype(wide)::value, decltype(prove)::value>, a.k, a);
+    });
   }
   void GuidedReroot(const GuidedArgs& a) override {
-    Bucket<kRerootTables>(a.capacity, [&](auto cap) {
-      if (a.width != 0) {
-        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, true>, a.k, a);
-      } else {
-        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false>, a.k, a);
-      }
+    Flags(a.width != 0, Proves(a), [&](auto wide, auto prove) {
+      Bucket<kRerootTables>(a.capacity, [&](auto cap) {
+        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, decltype(wide)::value, decltype(prove)::value>, a.k, a);
+      });
     });
   }
-  // proven values (pgx_guided.hip.h "Proven values"): the PROVE instantiations, and the read-out
-  void GuidedAdvanceProve(const GuidedArgs& a) override {
-    if (a.width == 0) return LaunchRoots(PgxGuidedAdvance<G, true>, a.k, a, err_dev_);
-    Bucket<kWideBuckets>(a.width, [&](auto wb) {
-      LaunchRoots(PgxGuidedAdvanceWide<G, decltype(wb)::value, true>, a.k, a, err_dev_);
-    });
-  }
-  void GuidedResultProve(const GuidedArgs& a) override {
-    if (a.width != 0) {
-      LaunchRoots(PgxGuidedResult<G, true, true>, a.k, a);
-    } else {
-      LaunchRoots(PgxGuidedResult<G, false, true>, a.k, a);
-    }
-  }
-  void GuidedRerootProve(const GuidedArgs& a) override {
-    Bucket<kRerootTables>(a.capacity, [&](auto cap) {
-      if (a.width != 0) {
-        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, true, true>, a.k, a);
-      } else {
-        LaunchRoots(PgxGuidedReroot<G, decltype(cap)::value, false, true>, a.k, a);
-      }
-    });
-  }
+  // the read-out of the proven values
   void GuidedProof(const GuidedArgs& a, signed char* value, signed char* q) override {
     if (a.width != 0) {
       LaunchRoots(PgxGuidedProof<G, true>, a.k, a, value, q);
@@ -1705,6 +1686,17 @@ class PgxPool : public Pool {
       Bucket<Table, I + 1>(value, f);
     }
   }
+
+  // f(std::bool_constant<a>, std::bool_constant<b>): two flags of the call as template arguments of its kernel
+  template <class F>
+  static void Flags(bool a, bool b, F f) {
+    if (a) {
+      b ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    } else {
+      b ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+    }
+  }
+  static bool Proves(const GuidedArgs& a) { return (a.flags & EPA_GUIDED_PROVE) != 0; }
 
   pgx::State* state_{nullptr};
 };

@@ -333,24 +333,9 @@ def guided_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     obs = torch.empty((rows, h, w, c), dtype=torch.bool, device=dev)
     mask = torch.empty((rows, a), dtype=torch.bool, device=dev)
     status = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    if prove:
-        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
-                                                                     status.data_ptr(), ids, simulations, c_puct,
-                                                                     int(nodes or 0), width or None, tactics,
-                                                                     tactics_nodes, True))
-    elif tactics:
-        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
-                                                                     status.data_ptr(), ids, simulations, c_puct,
-                                                                     int(nodes or 0), width or None, tactics,
-                                                                     tactics_nodes))
-    elif width:
-        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
-                                                                     status.data_ptr(), ids, simulations, c_puct,
-                                                                     int(nodes or 0), width))
-    else:
-        _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(),
-                                                                     status.data_ptr(), ids, simulations, c_puct,
-                                                                     int(nodes or 0)))
+    _order_both_ways(pool, dev, lambda: pool.guided_begin_device(obs.data_ptr(), mask.data_ptr(), status.data_ptr(),
+                                                                 ids, simulations, c_puct, int(nodes or 0),
+                                                                 width or None, tactics, tactics_nodes, prove))
     out = _guided_round_device(pool, evaluate, dev, k, simulations, (obs, mask, status), "guided_search_device",
                                width, advances)
     if not keep_open:
