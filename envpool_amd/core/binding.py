@@ -539,6 +539,64 @@ class _ShardedPools:
         self._each(result, parts)
         return out
 
+    # -- self-play recorder: one recorder per shard, each of the full capacity (host forms only) --
+    def _record_all(self, fn: Callable[[DevicePool], Any]) -> list:
+        out: list[Any] = [None] * len(self.pools)
+
+        def run(s: int, p: DevicePool, _: Any) -> None:
+            out[s] = fn(p)
+
+        self._each(run, [slice(0, self.per)] * len(self.pools))
+        return out
+
+    def _record_parts(self, what: str, env_ids: Any) -> tuple[np.ndarray, list]:
+        if env_ids is None:
+            env_ids = np.arange(self.offset, self.offset + self.per * len(self.pools), dtype=np.int32)
+        ids = native.check_record_ids(what, env_ids)
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        return ids, [np.flatnonzero(shard == s) for s in range(len(self.pools))]
+
+    def record_begin(self, capacity: int, max_plies: int = 0, symmetries: bool = False) -> tuple:
+        native.check_record(capacity, max_plies, symmetries)
+        return self._record_all(lambda p: p.record_begin(capacity, max_plies, symmetries))[0]
+
+    def record_shape(self) -> tuple:
+        return self.pools[0].record_shape()
+
+    def record_add(self, policy: Any, env_ids: Any = None) -> None:
+        """Every shard stages its ids, all shards at once; row i of `policy` goes with env_ids[i]."""
+        ids, parts = self._record_parts("recorder add", env_ids)
+        policy = native.check_record_add(policy, len(ids), self.record_shape()[3])
+        self._each(lambda s, p, idx: p.record_add(policy[idx], ids[idx]), parts)
+
+    def record_finish(self, reward: Any, done: Any, env_ids: Any = None) -> None:
+        """Every shard finishes its ids in the call's row order, all shards at once."""
+        ids, parts = self._record_parts("recorder finish", env_ids)
+        reward, done = native.check_record_finish(reward, done, len(ids))
+        self._each(lambda s, p, idx: p.record_finish(reward[idx], done[idx], ids[idx]), parts)
+
+    def record_counters(self) -> np.ndarray:
+        return np.sum(self._record_all(lambda p: p.record_counters()), axis=0)
+
+    def record_drain(self) -> tuple:
+        """The shards' samples behind each other in shard order: while nothing is dropped and the rows of a finish
+        are in id order, the unsharded pool's order."""
+        parts = self._record_all(lambda p: p.record_drain())
+        return tuple(np.concatenate(cols) for cols in zip(*parts))
+
+    def record_discard(self, env_ids: Any = None) -> None:
+        if env_ids is None:
+            self._record_all(lambda p: p.record_discard(None))
+            return
+        ids, parts = self._record_parts("recorder discard", env_ids)
+        self._each(lambda s, p, idx: p.record_discard(ids[idx]), parts)
+
+    def record_end(self) -> None:
+        self._record_all(lambda p: p.record_end())
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -705,6 +763,11 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
         def _gumbel(self) -> Any:
             if getattr(self._pool, "gumbel_begin", None) is None:  # a pool with its own executor
                 raise RuntimeError("gumbel search not implemented for this environment")
+            return self._pool
+
+        def _recorder(self) -> Any:
+            if getattr(self._pool, "record_begin", None) is None:  # a pool with its own executor
+                raise RuntimeError("recorder not implemented for this environment")
             return self._pool
 
         def _xla(self) -> Any:

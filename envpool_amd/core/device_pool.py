@@ -829,6 +829,93 @@ class DevicePool:
         native.check(self._lib.epa_gumbel_result_device(self._h, ctypes.c_void_p(d_visits), ctypes.c_void_p(d_values),
                                                         ctypes.c_void_p(d_action), ctypes.c_void_p(d_weights)))
 
+    # -- self-play recorder -------------------------------------------------------
+    def record_begin(self, capacity: int, max_plies: int = 0, symmetries: bool = False) -> tuple[int, int, int, int, int]:
+        """Opens the pool's recorder (the PGX board games; RuntimeError("recorder not implemented for this
+        environment") elsewhere): finished games become training samples in `capacity` rows of device memory
+        (csrc/pgx_record.hip.h).  `max_plies`: staged plies per env, 0: 128.  `symmetries`: every board symmetry of
+        each sample.  A pool has one recorder; a new one replaces it.  Returns (H, W, C, A, nsym)."""
+        capacity, max_plies, symmetries = native.check_record(capacity, max_plies, symmetries)
+        native.check(self._lib.epa_record_begin(self._h, capacity, max_plies,
+                                                native.RECORD_SYMMETRIES if symmetries else 0))
+        self.record_capacity = capacity  # (the rows of `record_view_device`'s arrays)
+        return self.record_shape()
+
+    def record_shape(self) -> tuple[int, int, int, int, int]:
+        """(H, W, C, A, nsym) of the open recorder."""
+        out = (ctypes.c_int32 * 5)()
+        native.check(self._lib.epa_record_shape(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3]), int(out[4])
+
+    def record_add(self, policy: Any, env_ids: Any = None) -> None:
+        """Stages the current position of every listed env (global ids that do not repeat; None: the whole pool) with
+        row i of `policy` float32 [k, A] as its policy target -- before the step.  Envs that are over are skipped."""
+        ids = native.check_record_ids("recorder add", self._ids(env_ids))
+        policy = native.check_record_add(policy, len(ids), self.record_shape()[3])
+        native.check(self._lib.epa_record_add(self._h, ids.ctypes.data, len(ids), policy.ctypes.data))
+
+    def record_finish(self, reward: Any, done: Any, env_ids: Any = None) -> None:
+        """After the step, with what it returned: reward float32 [k, 2] (or [2 k]) and done [k] of the listed envs.
+        Every env whose game ended turns its staged plies into samples, in the call's row order."""
+        ids = native.check_record_ids("recorder finish", self._ids(env_ids))
+        reward, done = native.check_record_finish(reward, done, len(ids))
+        native.check(self._lib.epa_record_finish(self._h, ids.ctypes.data, len(ids), reward.ctypes.data,
+                                                 done.ctypes.data))
+
+    def record_counters(self) -> np.ndarray:
+        """int64 [5]: the sample count, then samples and games written, dropped_games and dropped_plies since begin."""
+        out = np.zeros(5, dtype=np.int64)
+        native.check(self._lib.epa_record_counters(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def record_drain(self) -> tuple[np.ndarray, ...]:
+        """The samples so far -- (obs bool [n, H, W, C], mask bool [n, A], policy float32 [n, A], value float32 [n],
+        ply int32 [n], env_id int32 [n], sym uint8 [n]) -- and the count back to 0."""
+        h, w, c, a, _ = self.record_shape()
+        n = int(self.record_counters()[0])
+        out = (np.empty((n, h, w, c), dtype=np.bool_), np.empty((n, a), dtype=np.bool_),
+               np.empty((n, a), dtype=np.float32), np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32),
+               np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint8))
+        got = ctypes.c_int32(0)
+        native.check(self._lib.epa_record_drain(self._h, n, *[o.ctypes.data for o in out], ctypes.byref(got)))
+        return out
+
+    def record_discard(self, env_ids: Any = None) -> None:
+        """Forgets the staged plies of the listed envs (None: of every env); only enqueued."""
+        if env_ids is None:
+            native.check(self._lib.epa_record_discard(self._h, None, 0))
+            return
+        ids = native.check_record_ids("recorder discard", self._ids(env_ids))
+        native.check(self._lib.epa_record_discard(self._h, ids.ctypes.data, len(ids)))
+
+    def record_add_device(self, d_policy: int, env_ids: Any = None) -> None:
+        """`record_add` with the policy rows in device memory at the raw address `d_policy` (4 k A bytes, 4-byte
+        aligned): only enqueued on the pool's stream.  The ids must not repeat."""
+        ids = native.check_record_ids("recorder add", self._ids(env_ids))
+        native.check(self._lib.epa_record_add_device(self._h, ids.ctypes.data, len(ids), ctypes.c_void_p(d_policy)))
+
+    def record_finish_device(self, d_reward: int, d_done: int, env_ids: Any = None) -> None:
+        """`record_finish` with reward (8 k bytes, 4-byte aligned) and done (k bytes) in device memory: only enqueued.
+        The ids must not repeat."""
+        ids = native.check_record_ids("recorder finish", self._ids(env_ids))
+        native.check(self._lib.epa_record_finish_device(self._h, ids.ctypes.data, len(ids),
+                                                        ctypes.c_void_p(d_reward), ctypes.c_void_p(d_done)))
+
+    def record_view_device(self) -> tuple[list[int], int]:
+        """The raw addresses of the seven sample arrays (over the full capacity) and of the device int32 count."""
+        arrays = (ctypes.c_void_p * 7)()
+        count = ctypes.c_void_p()
+        native.check(self._lib.epa_record_view_device(self._h, arrays, ctypes.byref(count)))
+        return [int(p) for p in arrays], int(count.value)
+
+    def record_clear(self) -> None:
+        """Sets the sample count to 0 (what `record_drain` does after its copy); only enqueued."""
+        native.check(self._lib.epa_record_clear(self._h))
+
+    def record_end(self) -> None:
+        """Closes the recorder and releases its device memory; ValueError without one."""
+        native.check(self._lib.epa_record_end(self._h))
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

@@ -37,6 +37,8 @@ GUIDED_PROVE = 1         # EPA_GUIDED_PROVE: the flag of a guided search with pr
 GUIDED_UNPROVEN = -128   # EPA_GUIDED_UNPROVEN: "no proven value" in guided_proof's arrays
 GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per launch) of a batch Gumbel root
 SEARCH_MAX_LEAF_PLAYOUTS = 64
+RECORD_SYMMETRIES = 1    # EPA_RECORD_SYMMETRIES: the flag of a recorder that writes every board symmetry
+RECORD_MAX_PLIES = 256   # EPA_RECORD_MAX_PLIES: the largest max_plies of a recorder (0: 128)
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
 SOLVE_MAX_TABLE_BITS = 16  # EPA_SOLVE_MAX_TABLE_BITS: a lane's transposition table has at most 2^16 entries
 SOLVE_ILLEGAL = -128     # q of an illegal action, and of every action of a row that is not solved
@@ -176,6 +178,18 @@ def lib() -> ctypes.CDLL:
         "epa_gumbel_advance_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "epa_gumbel_result": (i32, [vp, vp, vp, vp, vp]),
         "epa_gumbel_result_device": (i32, [vp, vp, vp, vp, vp]),
+        "epa_record_begin": (i32, [vp, i32, i32, ctypes.c_uint32]),
+        "epa_record_shape": (i32, [vp, P(i32)]),
+        "epa_record_add": (i32, [vp, vp, i32, vp]),
+        "epa_record_add_device": (i32, [vp, vp, i32, vp]),
+        "epa_record_finish": (i32, [vp, vp, i32, vp, vp]),
+        "epa_record_finish_device": (i32, [vp, vp, i32, vp, vp]),
+        "epa_record_drain": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, P(i32)]),
+        "epa_record_view_device": (i32, [vp, P(vp), P(vp)]),
+        "epa_record_clear": (i32, [vp]),
+        "epa_record_discard": (i32, [vp, vp, i32]),
+        "epa_record_counters": (i32, [vp, P(ctypes.c_int64)]),
+        "epa_record_end": (i32, [vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -219,6 +233,9 @@ EXPORTED_SYMBOLS = [
     "epa_guided_begin_prove", "epa_guided_begin_prove_device", "epa_guided_proof", "epa_guided_proof_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device", "epa_gumbel_begin_batch", "epa_gumbel_begin_batch_device",
+    "epa_record_begin", "epa_record_shape", "epa_record_add", "epa_record_add_device", "epa_record_finish",
+    "epa_record_finish_device", "epa_record_drain", "epa_record_view_device", "epa_record_clear",
+    "epa_record_discard", "epa_record_counters", "epa_record_end",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -271,6 +288,49 @@ def check_playout(env_ids: Any, repeats: int, max_plies: int, commit: bool) -> n
         if len(np.unique(ids)) != len(ids):
             raise ValueError("playout: commit takes env_ids that do not repeat")
     return ids
+
+
+def check_record(capacity: int, max_plies: int, symmetries: Any) -> tuple[int, int, bool]:
+    """A recorder's (capacity, max_plies, symmetries) after the argument checks every layer makes before the native
+    call: ValueError for a capacity that is no integer of at least 1 (or past int32), max_plies outside 0 .. 256 and a
+    `symmetries` that is no bool.  (The 2 GiB limit of the staging and the samples is the engine's to refuse.)"""
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= int(capacity) < 2**31:
+        raise ValueError(f"recorder: capacity = {capacity} must be at least 1")
+    if isinstance(max_plies, bool) or int(max_plies) != max_plies or not 0 <= int(max_plies) <= RECORD_MAX_PLIES:
+        raise ValueError(f"recorder: max_plies = {max_plies} must be 0 .. {RECORD_MAX_PLIES}")
+    if not isinstance(symmetries, (bool, np.bool_)):
+        raise ValueError(f"recorder: symmetries = {symmetries!r} must be a bool")
+    return int(capacity), int(max_plies), bool(symmetries)
+
+
+def check_record_ids(what: str, env_ids: Any) -> np.ndarray:
+    """The ids of a recorder call as a flat int32 array: ValueError for no ids and for an id listed twice.  (Ids
+    outside the pool are the engine's to refuse.)"""
+    ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+    if len(ids) == 0:
+        raise ValueError(f"{what} env_ids must not be empty")
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError(f"{what}: env_ids must not repeat")
+    return ids
+
+
+def check_record_add(policy: Any, k: int, actions: int) -> np.ndarray:
+    """add's policy rows as a contiguous float32 [k, A] array (any values: the recorder cleans them)."""
+    policy = np.ascontiguousarray(policy, dtype=np.float32)
+    if policy.shape != (k, actions):
+        raise ValueError(f"recorder add: policy of shape {policy.shape} for {k} envs of {actions} actions")
+    return policy
+
+
+def check_record_finish(reward: Any, done: Any, k: int) -> tuple[np.ndarray, np.ndarray]:
+    """finish's rows as the step returned them: reward float32 [k, 2] (or [2 k], the per-player rows) and done [k]."""
+    reward = np.ascontiguousarray(reward, dtype=np.float32)
+    done = np.ascontiguousarray(done)
+    if reward.size != 2 * k or reward.ndim > 2 or (reward.ndim == 2 and reward.shape != (k, 2)):
+        raise ValueError(f"recorder finish: reward of shape {reward.shape} for {k} envs of 2 players")
+    if done.shape != (k,):
+        raise ValueError(f"recorder finish: done of shape {done.shape} for {k} envs")
+    return reward.reshape(k, 2), np.ascontiguousarray(done != 0, dtype=np.uint8)
 
 
 def check_search(env_ids: Any, simulations: int, leaf_playouts: int, c_puct: float, max_plies: int) -> np.ndarray:

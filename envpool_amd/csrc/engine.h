@@ -218,6 +218,38 @@ struct GuidedBeginOptions {
   int flags{0};             // EPA_GUIDED_PROVE: proven values
 };
 
+// One launch of a pool's recorder (Pool::RecordAdd / RecordPlan / RecordEmit; pgx_record.hip.h): the recorder's
+// staging and sample arrays, all device memory of the recorder's own block, and the rows of the call.
+struct RecordArgs {
+  int k;                    // rows of the call
+  int plies;                // staged rows per env (max_plies resolved)
+  int nsym;                 // samples per staged ply: 1, or the game's symmetries
+  int capacity;             // rows of the sample arrays
+  int id_offset;            // env_id_offset: a sample's env_id is global
+  // staging
+  void* states;             // [N][plies] family positions, 16-byte aligned
+  int32_t* elapsed;         // [N][plies]
+  float* staged_policy;     // [N][plies][policy stride], 16-byte aligned rows
+  int32_t* staged;          // [N]: n_e
+  // samples
+  unsigned char* obs;       // [capacity][H][W][C]
+  unsigned char* mask;      // [capacity][A]
+  float* policy;            // [capacity][A]
+  float* value;             // [capacity]
+  int32_t* ply;             // [capacity]
+  int32_t* env_id;          // [capacity]
+  unsigned char* sym;       // [capacity]
+  int32_t* count;           // the sample count
+  long long* counters;      // samples, games, dropped_games, dropped_plies
+  int32_t* plan;            // [N] scratch: per row of a finish the game's first sample, or a negative code
+  int32_t* items;           // [min(N plies, capacity)][2] scratch: the (row, ply) pairs a finish emits, 8-byte aligned
+  int32_t* n_items;         // their number
+  // the call's rows
+  const float* in_policy;   // add: [k][A]
+  const float* reward;      // finish: [k][2]
+  const unsigned char* done;  // finish: [k]
+};
+
 // The solver stage of an advance of a guided session with tactics (Pool::GuidedTactics; pgx_guided.hip.h "Exact leaf
 // status"): the horizon and the node budget of a leaf's solve, the session's counters and the slots' stacks.
 struct TacticsArgs {
@@ -530,6 +562,37 @@ class Pool {
                          bool device);
   void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
 
+  // Self-play recorder (include/envpool_amd.h: epa_record_begin; the PGX board games, pgx_record.hip.h): stages every
+  // env's positions and policy targets while its game runs and turns a finished game into training samples in a
+  // sample buffer on the device.  A pool has at most one recorder.  Its memory -- staging, samples, counters, the
+  // rows of the host forms -- is ONE device allocation of its own with a single owner, released by RecordEnd, by the
+  // next RecordBegin and by ~Pool; it is independent of the guided session's, and the two coexist.  Every call enters
+  // through SideEnter, so add sees the state every send issued before it has left.  The host forms copy the call's rows
+  // through the recorder's pinned block and synchronise once (drain: once for the count, once for the rows); the device
+  // forms only enqueue and leave through SideLeave.  A family without the hooks keeps the defaults, and every entry
+  // point throws std::runtime_error("recorder not implemented for this environment").
+  virtual bool HasRecord() const { return false; }
+  virtual int RecordSyms() const { return 1; }            // the game's symmetries (EPA_RECORD_SYMMETRIES)
+  virtual size_t RecordStateBytes() const { return 0; }   // a staged position; a multiple of 16
+  virtual int RecordPolicyStride() const { return 0; }    // floats of a staged policy row; a multiple of 4
+  virtual void RecordAdd(const int* d_ids, const RecordArgs& a);
+  virtual void RecordPlan(const int* d_ids, const RecordArgs& a);
+  virtual void RecordEmit(const int* d_ids, const RecordArgs& a);
+  void RecordBegin(int capacity, int max_plies, unsigned flags);
+  // policy [k][A] float32; host ids must not repeat (refused); device == true: `policy` is device memory
+  void RecordAddCall(const int32_t* ids, int k, const void* policy, bool device);
+  // reward [k][2] float32 and done [k] bytes: what the step returned
+  void RecordFinishCall(const int32_t* ids, int k, const void* reward, const void* done, bool device);
+  // the first `rows` samples into seven host arrays (rows must equal the sample count, which *count receives in any
+  // case; a mismatch throws and leaves the recorder as it is), then the count is 0
+  void RecordDrain(int rows, void* const out[7], int32_t* count);
+  void RecordView(void* out[7], void** count) const;  // the seven device arrays over the capacity, the device count
+  void RecordClear();                                  // count = 0; only enqueues
+  void RecordDiscard(const int32_t* ids, int k);       // n_e = 0 for the listed envs
+  void RecordCounters(int64_t out[5]);                 // count, samples, games, dropped_games, dropped_plies
+  void RecordShape(int32_t out[5]) const;              // H, W, C, A, nsym of the open recorder
+  void RecordEnd();
+
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
   // kernel that packs (unpack: restores) it for the listed local envs, row i at d_buf + i * ExtraBytes(), on stream_.
@@ -768,6 +831,22 @@ class Pool {
   template <class Launch>
   void SessionRun(bool device, StageRange up, StageRange down, Launch launch);
   char* SessionPinned();  // the host forms' pinned block, allocated at its first use in a session
+  // the pool's recorder
+  struct Recorder {
+    bool open{false};
+    DeviceBlock mem;        // the recorder's one device allocation, in the order of `off`
+    char* pinned{nullptr};  // the host forms' rows: policy [N][A], reward [N][2], done [N]; then int64 [5] for reads
+    int capacity{0}, plies{0}, nsym{1};
+    int32_t shape[4]{};     // H, W, C, A
+    // offsets into mem: states, elapsed, staged policy, n_e, plan, count + counters + item count (64 bytes), the seven
+    // sample arrays, the device copies of the host forms' rows (policy, reward, done), finish's item list, the end
+    size_t off[18]{};
+  };
+  Recorder record_;
+  void RecordFree();                                    // (no recorder: nothing)
+  void RecordRequire(const char* what) const;           // throws without the hooks or without a recorder
+  RecordArgs RecordArgsOf(int k) const;
+  void RecordCheckIds(const char* what, const int32_t* ids, int k) const;  // range, count, repeats
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

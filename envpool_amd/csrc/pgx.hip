@@ -32,6 +32,8 @@
 // Exact solve: pgx_solve.hip.h, alpha-beta with the top of the tree in LDS and the lanes' stacks in the pool's side
 // scratch (PgxSolveKernel).  Its traversal (SolveWave) also serves the exact leaf status of a guided session with
 // tactics (PgxGuidedTactics, a launch behind every advance: a wave per slot solves the slot's new leaf).
+// Self-play recorder: pgx_record.hip.h, finished games as training samples in the recorder's own memory (PgxRecordAdd /
+// PgxRecordPlan / PgxRecordEmit).
 #include <algorithm>
 #include <string>
 
@@ -41,6 +43,7 @@
 #include "pgx_guided.hip.h"
 #include "pgx_gumbel.hip.h"
 #include "pgx_playout.hip.h"
+#include "pgx_record.hip.h"
 #include "pgx_render.hip.h"
 #include "pgx_search.hip.h"
 #include "pgx_solve.hip.h"
@@ -1500,6 +1503,192 @@ __global__ __launch_bounds__(kSearchBlock) void PgxGumbelResult(GumbelArgs a) {
   if (lane == 0) a.action[row] = over ? -1 : best;
 }
 
+// Self-play recorder (pgx_record.hip.h): three kernels over the recorder's own memory.
+//   PgxRecordAdd   a block takes kRecordAddRows rows.  Its first threads decide, one per row, what becomes of the
+//                  env's staging (RecordAddDecide), store n_e and the elapsed step and leave (env, slot) in LDS.  Then
+//                  the whole block copies the staged rows in 16-byte words, one word per thread and trip: the four
+//                  words of the State, then the policy row's (a staged policy row is padded to whole words and starts
+//                  on a 16-byte boundary; the caller's row is read float by float, cleaned against the position's mask).
+//                  No lane walks a row of its own.  The drop counters are integer atomics: their values do not depend
+//                  on the order.
+//   PgxRecordPlan  one block: the exclusive scan of the rows' sample counts in row order, in trips of the block size
+//                  (a wave scan by shuffles, the waves' totals through LDS, a running carry), the fit decision per row,
+//                  the new count and the counters.  All integer: the order is fixed by definition.  The row's thread
+//                  also clears n_e and, for a written game, lists its plies as (row, ply) items: the emission's work,
+//                  dense from 0 because the written games are a prefix of the finished ones.
+//   PgxRecordEmit  one wave per staged ply of a written game: a fixed grid of kRecordEmitWaves waves strides over the
+//                  item list (a wave per finished ROW walked a game's plies one after the other, and with few rows
+//                  ending the launch lasted as long as the longest game on one SIMD).  No items: every wave returns
+//                  at once.  The ply's State is wave-uniform in registers, and the wave writes the ply's nsym samples
+//                  -- contiguous in each sample array -- as ONE run per array in 16-byte words (GuidedEmitRow for the
+//                  bytes, RecordEmitWords for the policy), every element read through the inverse symmetry.  Lanes
+//                  j < nsym write the scalars of sample j.  No floating-point arithmetic: policy and reward are moved.
+static_assert(pgx::kRecordMaxPlies == EPA_RECORD_MAX_PLIES && pgx::kRecordDefaultPlies == EPA_RECORD_DEFAULT_PLIES &&
+                  (unsigned long long)pgx::kRecordMaxBytes == EPA_RECORD_MAX_BYTES &&
+                  (unsigned)pgx::kRecordSymmetries == EPA_RECORD_SYMMETRIES,
+              "the C ABI states the header's limits");
+constexpr int kRecordAddRows = 32;
+constexpr int kRecordPlanBlock = 1024;
+constexpr int kRecordEmitWaves = 4096;
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void PgxRecordAdd(CommonDev cm, const pgx::State* __restrict__ st,
+                                                       const int* __restrict__ ids, RecordArgs a) {
+  constexpr int A = pgx::Dims<G>::A, PS = pgx::RecordPolicyStride<G>(), RW = 4 + PS / 4;
+  __shared__ int env[kRecordAddRows], slot[kRecordAddRows];
+  const int row0 = blockIdx.x * kRecordAddRows;
+  const int nrows = std::min(kRecordAddRows, a.k - row0);
+  if ((int)threadIdx.x < nrows) {
+    const int e = ids[row0 + threadIdx.x];
+    const int el = cm.cur_step[e], n = a.staged[e];
+    const pgx::RecordAddPlan p = pgx::RecordAddDecide(cm.done[e] != 0, n, el, a.plies);
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(a.counters);
+    if (p.drop_games != 0) atomicAdd(&ctr[2], (unsigned long long)p.drop_games);
+    if (p.drop_plies != 0) atomicAdd(&ctr[3], (unsigned long long)p.drop_plies);
+    if (p.slot >= 0) a.elapsed[(size_t)e * a.plies + p.slot] = el;
+    if (p.staged != n) a.staged[e] = p.staged;
+    env[threadIdx.x] = e;
+    slot[threadIdx.x] = p.slot;
+  }
+  __syncthreads();
+  for (int w = threadIdx.x; w < nrows * RW; w += kBlock) {
+    const int r = w / RW, q = w - r * RW;
+    if (slot[r] < 0) continue;
+    const int e = env[r];
+    const size_t dst = (size_t)e * a.plies + slot[r];
+    if (q < 4) {
+      reinterpret_cast<uint4*>(a.states)[dst * 4 + q] = reinterpret_cast<const uint4*>(st + e)[q];
+      continue;
+    }
+    const int a0 = (q - 4) * 4;
+    const pgx::u128 m = st[e].m;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.in_policy) + (size_t)(row0 + r) * A;
+    uint32_t x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = a0 + j < A ? pgx::RecordClean(src[a0 + j], pgx::Has(m, a0 + j)) : 0u;
+    reinterpret_cast<uint4*>(a.staged_policy + dst * PS)[q - 4] = make_uint4(x[0], x[1], x[2], x[3]);
+  }
+}
+
+__global__ __launch_bounds__(kRecordPlanBlock) void PgxRecordPlan(const int* __restrict__ ids, RecordArgs a) {
+  constexpr int kWaves = kRecordPlanBlock / 64;
+  __shared__ int wave_sum[kWaves];
+  __shared__ unsigned long long acc[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (t < 4) acc[t] = 0;
+  const long long base = *a.count;
+  long long carry = 0;  // the samples of the rows of earlier trips (the same in every thread)
+  unsigned long long mine[4] = {0, 0, 0, 0};  // samples, games, dropped_games, dropped_plies of this thread's rows
+  __syncthreads();
+  for (int row0 = 0; row0 < a.k; row0 += kRecordPlanBlock) {
+    const int i = row0 + t;
+    int n = 0, c = 0;
+    if (i < a.k) {
+      const int e = ids[i];
+      const bool done = a.done[i] != 0;
+      n = a.staged[e];
+      c = pgx::RecordGameSamples(done, n, a.nsym);
+      if (done && n != 0) a.staged[e] = 0;  // written or dropped: the env's staging is empty afterwards
+    }
+    int x = c;  // the wave's inclusive scan
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(x, d, 64);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) wave_sum[wv] = x;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < kWaves; ++w) {
+      const int s = wave_sum[w];
+      before += w < wv ? s : 0;
+      total += s;
+    }
+    const long long off = carry + before + (x - c);
+    if (i < a.k) {
+      int code = pgx::kRecordNoGame;
+      if (c > 0) {
+        if (pgx::RecordFits(base, off, c, a.capacity)) {
+          code = (int)(base + off);
+          mine[0] += (unsigned long long)c;
+          mine[1] += 1;
+          // the emission's work list: one item per staged ply.  Every game in front of a written one is written, so
+          // the call's items are dense from 0: this game's begin at off / nsym
+          int2* item = reinterpret_cast<int2*>(a.items) + off / a.nsym;
+          for (int p = 0; p < n; ++p) item[p] = make_int2(i, p);
+        } else {
+          code = pgx::kRecordDropped;
+          mine[2] += 1;
+          mine[3] += (unsigned long long)n;
+        }
+      }
+      a.plan[i] = code;
+    }
+    carry += total;
+    __syncthreads();  // (wave_sum is written again in the next trip)
+  }
+  for (int j = 0; j < 4; ++j) {
+    if (mine[j] != 0) atomicAdd(&acc[j], mine[j]);
+  }
+  __syncthreads();
+  if (t == 0) {
+    *a.count = (int)(base + (long long)acc[0]);
+    *a.n_items = (int)(acc[0] / (unsigned long long)a.nsym);
+    for (int j = 0; j < 4; ++j) a.counters[j] += (long long)acc[j];
+  }
+}
+
+// `total` 4-byte elements at `base` (4-byte aligned) by the wave, in 16-byte words where the alignment allows
+template <class F>
+__device__ __forceinline__ void RecordEmitWords(uint32_t* base, int total, int lane, F elem) {
+  const int mis = (int)(((uintptr_t)base & 15) / 4);
+  const int head = std::min(total, mis == 0 ? 0 : 4 - mis);
+  const int words = (total - head) / 4;
+  const int tail = head + words * 4;
+  for (int i = lane; i < head; i += kSearchBlock) base[i] = elem(i);
+  for (int c = lane; c < words; c += kSearchBlock) {
+    const int i0 = head + c * 4;
+    *reinterpret_cast<uint4*>(base + i0) = make_uint4(elem(i0), elem(i0 + 1), elem(i0 + 2), elem(i0 + 3));
+  }
+  for (int i = tail + lane; i < total; i += kSearchBlock) base[i] = elem(i);
+}
+
+template <int G, bool SYM>
+__global__ __launch_bounds__(kSearchBlock) void PgxRecordEmit(const int* __restrict__ ids, RecordArgs a) {
+  constexpr int A = pgx::Dims<G>::A, OB = pgx::GuidedObsElems<G>(), PS = pgx::RecordPolicyStride<G>();
+  constexpr int NS = SYM ? pgx::RecordSyms<G>() : 1;
+  const int lane = threadIdx.x;
+  const int n_items = *a.n_items;
+  const int2* items = reinterpret_cast<const int2*>(a.items);
+  for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const int row = items[it].x, p = items[it].y;
+    const int e = ids[row];
+    const size_t at = (size_t)e * a.plies + p;  // the staged row
+    pgx::View view{};
+    view.s = static_cast<const pgx::State*>(a.states)[at];
+    const int mover = pgx::SearchMover<G>(view.s);
+    const uint32_t* pol = reinterpret_cast<const uint32_t*>(a.staged_policy) + at * PS;
+    const size_t s0 = (size_t)a.plan[row] + (size_t)p * NS;  // the ply's first sample; its NS samples are contiguous
+    GuidedEmitRow(a.obs + s0 * OB, NS * OB, lane, [&](int i) {
+      const int j = i / OB;
+      return pgx::RecordObsElem<G>(view, mover, j, i - j * OB);
+    });
+    GuidedEmitRow(a.mask + s0 * A, NS * A, lane, [&](int i) {
+      const int j = i / A;
+      return pgx::RecordMaskElem<G>(view, j, i - j * A);
+    });
+    RecordEmitWords(reinterpret_cast<uint32_t*>(a.policy) + s0 * A, NS * A, lane, [&](int i) {
+      const int j = i / A;
+      return pol[pgx::RecordPolicySource<G>(j, i - j * A)];
+    });
+    if (lane < NS) {
+      reinterpret_cast<uint32_t*>(a.value)[s0 + lane] = reinterpret_cast<const uint32_t*>(a.reward)[(size_t)row * 2 + mover];
+      a.ply[s0 + lane] = a.elapsed[at];
+      a.env_id[s0 + lane] = e + a.id_offset;
+      a.sym[s0 + lane] = (unsigned char)lane;
+    }
+  }
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -1650,6 +1839,25 @@ class PgxPool : public Pool {
       LaunchRoots(PgxGumbelResult<G, true>, a.k, a);
     } else {
       LaunchRoots(PgxGumbelResult<G, false>, a.k, a);
+    }
+  }
+  bool HasRecord() const override { return true; }
+  int RecordSyms() const override { return pgx::RecordSyms<G>(); }
+  size_t RecordStateBytes() const override { return sizeof(pgx::State); }
+  int RecordPolicyStride() const override { return pgx::RecordPolicyStride<G>(); }
+  void RecordAdd(const int* d_ids, const RecordArgs& a) override {
+    hipLaunchKernelGGL(PgxRecordAdd<G>, dim3((unsigned)((a.k + kRecordAddRows - 1) / kRecordAddRows)), dim3(kBlock), 0,
+                       stream_, common_, state_, d_ids, a);
+  }
+  void RecordPlan(const int* d_ids, const RecordArgs& a) override {
+    hipLaunchKernelGGL(PgxRecordPlan, dim3(1), dim3(kRecordPlanBlock), 0, stream_, d_ids, a);
+  }
+  // a.nsym != 1: the recorder writes the game's symmetries
+  void RecordEmit(const int* d_ids, const RecordArgs& a) override {
+    if (a.nsym != 1) {
+      LaunchRoots(PgxRecordEmit<G, true>, kRecordEmitWaves, d_ids, a);
+    } else {
+      LaunchRoots(PgxRecordEmit<G, false>, kRecordEmitWaves, d_ids, a);
     }
   }
   std::string ErrorText(unsigned code) const override {

@@ -62,6 +62,83 @@ class Proof(NamedTuple):
                        # illegal (the convention of `Solve.q`)
 
 
+class Samples(NamedTuple):
+    """What `Recorder.drain` returns: numpy arrays over the n training samples written since the last drain."""
+
+    obs: np.ndarray     # bool [n, H, W, C]: the observation of the seat to move
+    mask: np.ndarray    # bool [n, A]: the position's legal actions
+    policy: np.ndarray  # float32 [n, A]: the policy target given to `add`, 0 on illegal actions and non-finite entries
+    value: np.ndarray   # float32 [n]: the game's last reward for the seat that moved at the sample
+    ply: np.ndarray     # int32 [n]: the position's elapsed step
+    env_id: np.ndarray  # int32 [n]: the env that played the game (global id)
+    sym: np.ndarray     # uint8 [n]: the board symmetry of the sample, 0: the identity
+
+
+class Recorder:
+    """A pool's self-play recorder (`env.recorder`): it stages every env's positions and policy targets while its game
+    runs, and when a game ends it writes one training sample per staged ply -- with `symmetries=True` one per ply and
+    board symmetry -- into a sample buffer on the device, in a deterministic order.
+
+        rec = env.recorder(capacity=1 << 18, symmetries=True)
+        ...
+        rec.add(result.weights)                    # before the step: the positions as they stand
+        _, rew, term, trunc, info = env.step(action)
+        rec.finish(rew, term | trunc)              # after it: the games that ended become samples
+        s = rec.drain()                            # Samples(obs, mask, policy, value, ply, env_id, sym); count back to 0
+
+    A game that does not fit into the remaining capacity is dropped whole and counted; so is a game whose env was reset
+    or restored mid-way (`counters`).  A pool has one recorder; a new one replaces it."""
+
+    def __init__(self, pool: Any, all_ids: np.ndarray, capacity: int, max_plies: int, symmetries: bool) -> None:
+        self._pool, self._all = pool, all_ids
+        self.shape = pool.record_begin(capacity, max_plies, symmetries)
+        self.capacity = int(capacity)
+
+    def _open(self) -> Any:
+        if self._pool is None:
+            raise ValueError("recorder: the recorder is closed")
+        return self._pool
+
+    def _ids(self, env_ids: Any) -> np.ndarray:
+        return self._all if env_ids is None else _normalize_env_id(env_ids)
+
+    @property
+    def symmetries(self) -> int:
+        """Samples per staged ply: 1, or the number of the game's board symmetries."""
+        return int(self.shape[4])
+
+    def add(self, policy: Any, env_ids: Any = None) -> None:
+        """Before the step: stages the position of every listed env (global ids that do not repeat; None: all) with row
+        i of `policy` float32 [k, A] as its target.  Envs whose game is over are skipped."""
+        self._open().record_add(policy, self._ids(env_ids))
+
+    def finish(self, reward: Any, done: Any, env_ids: Any = None) -> None:
+        """After the step, with what it returned for the listed envs: reward [k, 2] and done [k] (terminated |
+        truncated).  The games that ended become samples, in the call's row order."""
+        self._open().record_finish(reward, done, self._ids(env_ids))
+
+    def drain(self) -> Samples:
+        return Samples(*self._open().record_drain())
+
+    def discard(self, env_ids: Any = None) -> None:
+        """Forgets the staged plies of the listed envs (None: of all)."""
+        self._open().record_discard(None if env_ids is None else _normalize_env_id(env_ids))
+
+    @property
+    def counters(self) -> dict[str, int]:
+        """samples and games written, dropped_games and dropped_plies since the recorder was opened."""
+        c = self._open().record_counters()
+        return dict(samples=int(c[1]), games=int(c[2]), dropped_games=int(c[3]), dropped_plies=int(c[4]))
+
+    def __len__(self) -> int:
+        return int(self._open().record_counters()[0])
+
+    def close(self) -> None:
+        if self._pool is not None:
+            self._pool.record_end()
+            self._pool = None
+
+
 class GuidedSearch:
     """A pool's guided-search session (`env.guided_search`): a PUCT search of every listed env whose tree stays on
     the device and that stops at every new leaf for the caller's priors and value.
@@ -558,6 +635,17 @@ class EnvPoolMixin(ABC):
         gumbel = native.check_gumbel_noise(gumbel, len(ids), actions)
         return GumbelSearch(pool, ids, int(simulations), int(max_considered), gumbel, float(c_visit), float(c_scale),
                             int(batch))
+
+    def recorder(self, capacity: int, max_plies: int = 0, symmetries: bool = False) -> Recorder:
+        """Extension (the PGX board games): opens the pool's self-play recorder -- `Recorder`: `add` before every step,
+        `finish` after it, and the finished games arrive as training samples (obs of the seat to move, legal mask,
+        policy target, the game's result as the value, ply, env id, symmetry) in a device buffer of `capacity` rows,
+        which `drain` hands over.  `max_plies`: the plies staged per env, 0 .. 256 (0: 128; no game of the four lasts
+        longer than 122).  `symmetries`: every board symmetry of each sample (TicTacToe, Othello: 8; ConnectFour, Hex:
+        2).  A pool has one recorder at a time; it coexists with a search session.  The arguments are checked before any
+        native call."""
+        capacity, max_plies, symmetries = native.check_record(capacity, max_plies, symmetries)
+        return Recorder(self._recorder(), np.asarray(self.all_env_ids, dtype=np.int32), capacity, max_plies, symmetries)
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -466,3 +466,66 @@ def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
                                                                   action.data_ptr(), weights.data_ptr()))
     pool.guided_end()
     return visits, vals, action, weights
+
+
+def _record_rows(what: str, t: Any, dtypes: tuple, shape: tuple, dev: Any) -> None:
+    if t.dtype not in dtypes or not t.is_contiguous() or tuple(t.shape) != shape or t.device != dev:
+        raise RuntimeError(f"{what} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
+
+
+def recorder_add_device(pool: Any, policy: Any, env_ids: Any = None) -> None:
+    """`pool.record_add` with the policy targets where the model left them: `policy` is a float32 [k, A] tensor on the
+    pool's device, read by the recorder's kernel (no PCIe transfer, no host synchronisation) and ordered against
+    torch's current stream like `playout_device`.  The ids (host, global; None: the whole pool) must not repeat."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_record_ids("recorder add", env_ids)
+    dev = torch.device("cuda", pool.device)
+    _record_rows("recorder_add_device: policy", policy, (torch.float32,), (len(ids), pool.record_shape()[3]), dev)
+    _order_both_ways(pool, dev, lambda: pool.record_add_device(policy.data_ptr(), ids))
+
+
+def recorder_finish_device(pool: Any, reward: Any, done: Any, env_ids: Any = None) -> None:
+    """`pool.record_finish` with what the step returned on the device: `reward` float32 [k, 2] (or [2 k], the
+    per-player rows of `recv_device_tensors`) and `done` bool or uint8 [k].  Only enqueued, and ordered both ways with
+    torch's current stream.  The ids (host, global; None: the whole pool) must not repeat."""
+    import torch
+
+    if env_ids is None:
+        env_ids = np.arange(pool.env_id_offset, pool.env_id_offset + pool.num_envs, dtype=np.int32)
+    ids = native.check_record_ids("recorder finish", env_ids)
+    dev = torch.device("cuda", pool.device)
+    k = len(ids)
+    _record_rows("recorder_finish_device: reward", reward, (torch.float32,), (2 * k,) if reward.dim() == 1 else (k, 2),
+                 dev)
+    _record_rows("recorder_finish_device: done", done, (torch.bool, torch.uint8), (k,), dev)
+    _order_both_ways(pool, dev, lambda: pool.record_finish_device(reward.data_ptr(), done.data_ptr(), ids))
+
+
+def recorder_view_device(pool: Any) -> tuple[tuple, Any]:
+    """The recorder's sample buffer as torch tensors that alias it -- (obs bool [capacity, H, W, C], mask bool
+    [capacity, A], policy float32 [capacity, A], value float32, ply int32, env_id int32, sym uint8 [capacity]) -- and
+    the int32 [1] count tensor: rows at and above the count are undefined.  Torch's current stream is made to wait for
+    the recorder's launches so far; the tensors stay valid until the recorder is closed or replaced, and what a later
+    `recorder_finish_device` writes is ordered by that call."""
+    import torch
+
+    h, w, c, a, _ = pool.record_shape()
+    ptrs, count = pool.record_view_device()
+    n = pool.record_capacity
+    dev = torch.device("cuda", pool.device)
+    shapes = [((n, h, w, c), np.bool_), ((n, a), np.bool_), ((n, a), np.float32), ((n,), np.float32),
+              ((n,), np.int32), ((n,), np.int32), ((n,), np.uint8)]
+    _order_both_ways(pool, dev, lambda: None)
+    arrays = tuple(torch.as_tensor(_DevArray(p, s, d), device=dev) for p, (s, d) in zip(ptrs, shapes))
+    return arrays, torch.as_tensor(_DevArray(count, (1,), np.int32), device=dev)
+
+
+def recorder_clear(pool: Any) -> None:
+    """Sets the recorder's sample count to 0 -- the device form of `drain`, once the caller has consumed the view's
+    rows on torch's current stream; ordered both ways with it."""
+    import torch
+
+    _order_both_ways(pool, torch.device("cuda", pool.device), pool.record_clear)

@@ -840,6 +840,68 @@ int epa_gumbel_begin_batch_device(epa_pool* pool, const int32_t* env_ids, int32_
                                   const void* device_gumbel, void* device_obs, void* device_mask,
                                   void* device_status);
 
+/* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
+ * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
+ * targets of the game in progress; when the game ends it writes one sample per staged ply -- or one per ply and board
+ * symmetry with EPA_RECORD_SYMMETRIES -- into seven arrays of `capacity` rows:
+ *   obs uint8 [H, W, C] of the seat to move, mask uint8 [A], policy float32 [A], value float32 (the game's last
+ *   reward for the seat that moved at the sample), ply int32 (the position's elapsed step), env_id int32 (global),
+ *   sym uint8 (the symmetry's index, 0: the identity)
+ * A pool has one recorder; its memory is one device allocation of its own, released by epa_record_end, by the next
+ * epa_record_begin and by epa_destroy, and independent of a guided-search session, which may be open at the same time.
+ *   epa_record_begin(capacity, max_plies, flags): max_plies = 0 means EPA_RECORD_DEFAULT_PLIES (no game of the four
+ *     lasts longer than 122 plies).  The staging is num_envs x max_plies rows of {the 64-byte position, the elapsed
+ *     step, the policy row}.
+ *   epa_record_add(env_ids[k], policy[k][A]): BEFORE the step.  Row i is skipped if env env_ids[i] is over (also
+ *     before its first reset).  If the env has more staged plies than elapsed steps they belong to an abandoned game
+ *     (a forced reset, a restore) and are discarded: dropped_games += 1, dropped_plies += their number.  Then, if
+ *     max_plies plies are staged, the ply is not staged (dropped_plies += 1); otherwise the position, its elapsed step
+ *     and policy'[a] = (a is legal and policy[a] is finite) ? policy[a] : 0 are staged.  No normalisation.
+ *   epa_record_finish(env_ids[k], reward[k][2], done[k]): AFTER the step, with what it returned.  Rows with done and
+ *     staged plies are finished games of c_i = plies x nsym samples; off_i is the exclusive prefix sum of c_i in row
+ *     order and base the sample count.  Game i is written at base + off_i iff base + off_i + c_i <= capacity, otherwise
+ *     dropped whole (dropped_games += 1, dropped_plies += its plies).  The count becomes base + the sum of c_i of the
+ *     written games.  Either way the env's staging is empty afterwards; rows with done = 0 are untouched.  Within a game
+ *     the samples are ordered by ply, then by symmetry.  The result depends on the arguments and the positions only.
+ *   epa_record_counters(out[5]): the sample count, then samples and games written, dropped_games and dropped_plies
+ *     since begin.
+ *   epa_record_drain(rows, ...): copies the `rows` samples to the host and sets the count to 0; `rows` must equal the
+ *     sample count (epa_record_counters), which *count receives in any case.
+ *   epa_record_view_device(arrays[7], count): the seven device arrays over the full capacity, in the order above, and
+ *     the device int32 count; rows at and above the count are undefined.  epa_record_clear sets the count to 0.
+ *   epa_record_discard(env_ids[k]): forgets the staged plies of the listed envs (env_ids = NULL: of every env).
+ *   epa_record_shape(out[5]): H, W, C, A and nsym of the open recorder.
+ * Symmetries (sample j: obs'[s_j(cell)] = obs[cell], mask'[s_j(a)] = mask[a], policy'[s_j(a)] = policy[a]):
+ *   TicTacToe, Othello: the dihedral group, nsym 8 -- j >= 4: first (r, c) -> (c, r); then j & 3 times
+ *   (r, c) -> (c, n - 1 - r); Othello's pass is fixed.  ConnectFour: nsym 2, (r, c) -> (r, 6 - c).  Hex: nsym 2,
+ *   (x, y) -> (10 - x, 10 - y); the swap action is fixed.
+ * The host forms move the call's rows through a pinned block and synchronise once (drain: twice); the _device forms
+ * take device pointers for the rows (4-byte aligned; env_ids stay host memory) and only enqueue on the pool's stream.
+ * Both see the state every send issued before them has left.
+ * Errors:
+ *   EPA_ERR_INVALID: capacity < 1, max_plies outside 0 .. EPA_RECORD_MAX_PLIES, unknown flags, staging and samples
+ *     above EPA_RECORD_MAX_BYTES; a call without a recorder; k <= 0, more than num_envs ids, an id outside the pool or
+ *     listed twice; drain with rows other than the count.
+ *   Every other family fails with EPA_ERR_RUNTIME "recorder not implemented for this environment". */
+#define EPA_RECORD_SYMMETRIES 1u
+#define EPA_RECORD_MAX_PLIES 256
+#define EPA_RECORD_DEFAULT_PLIES 128
+#define EPA_RECORD_MAX_BYTES 2147483648ull
+int epa_record_begin(epa_pool* pool, int32_t capacity, int32_t max_plies, uint32_t flags);
+int epa_record_shape(epa_pool* pool, int32_t* out);
+int epa_record_add(epa_pool* pool, const int32_t* env_ids, int32_t k, const float* policy);
+int epa_record_add_device(epa_pool* pool, const int32_t* env_ids, int32_t k, const void* device_policy);
+int epa_record_finish(epa_pool* pool, const int32_t* env_ids, int32_t k, const float* reward, const uint8_t* done);
+int epa_record_finish_device(epa_pool* pool, const int32_t* env_ids, int32_t k, const void* device_reward,
+                             const void* device_done);
+int epa_record_drain(epa_pool* pool, int32_t rows, uint8_t* obs, uint8_t* mask, float* policy, float* value,
+                     int32_t* ply, int32_t* env_id, uint8_t* sym, int32_t* count);
+int epa_record_view_device(epa_pool* pool, void** arrays, void** count);
+int epa_record_clear(epa_pool* pool);
+int epa_record_discard(epa_pool* pool, const int32_t* env_ids, int32_t k);
+int epa_record_counters(epa_pool* pool, int64_t* out);
+int epa_record_end(epa_pool* pool);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
