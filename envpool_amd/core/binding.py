@@ -474,6 +474,31 @@ class _ShardedPools:
         self._each(lambda s, p, idx: p.guided_end(), parts)
         self._guided = None
 
+    def net_run(self, net: Any, leaves: tuple, advances: Any = None) -> tuple[tuple, int]:
+        """`DevicePool.net_run` in every shard that has rows of the session, all shards at once, each with the net's
+        copy on its own device; a shard's round ends when its own rows are complete, which changes no row.  Returns
+        (the new leaves, the most advances a shard made)."""
+        _, _, parts = self._guided_session("net_run")
+        advances = native.check_net_advances(advances) or None
+        out = tuple(np.array(x) for x in leaves)
+        made = [0] * len(self.pools)
+        # a net has one copy per device, and calls that use one copy must not overlap: shards that share a device
+        # take turns, shards on different devices run at once
+        turn = {p.device: threading.Lock() for p in self.pools}
+
+        def run(s: int, p: DevicePool, idx: Any) -> None:
+            with turn[p.device]:
+                new, made[s] = p.net_run(net, tuple(np.asarray(x)[idx] for x in leaves), advances)
+            for o, part in zip(out, new):
+                o[idx] = part
+
+        self._each(run, parts)
+        return out, max(made)
+
+    def net_eval(self, net: Any, obs: Any, mask: Any, status: Any, priors: bool = False) -> tuple:
+        """`DevicePool.net_eval` on the first shard: the rows are positions, whichever shard holds their envs."""
+        return self.pools[0].net_eval(net, obs, mask, status, priors)
+
     # -- Gumbel search: the same sessions with the Gumbel policy; the noise rows follow their ids --
     def gumbel_actions(self) -> int:
         return self.pools[0].gumbel_actions()

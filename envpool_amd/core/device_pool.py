@@ -829,6 +829,71 @@ class DevicePool:
         native.check(self._lib.epa_gumbel_result_device(self._h, ctypes.c_void_p(d_visits), ctypes.c_void_p(d_values),
                                                         ctypes.c_void_p(d_action), ctypes.c_void_p(d_weights)))
 
+    # -- the built-in network (envpool_amd/pgx/net.py; csrc/pgx_net.hip.h) -------------
+    def _net_rows(self, what: str, obs: Any, mask: Any, status: Any) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Leaf arrays as contiguous bytes [rows, F], [rows, A], [rows]; ValueError for shapes that are no rows of
+        this pool's game."""
+        h, w, c, a = self.guided_shape()
+        status = np.ascontiguousarray(status).reshape(-1)
+        rows = len(status)
+        obs, mask = np.ascontiguousarray(obs), np.ascontiguousarray(mask)
+        if obs.itemsize != 1 or mask.itemsize != 1 or status.itemsize != 1:
+            raise ValueError(f"{what}: obs, mask and status must be bool or uint8 arrays")
+        if rows < 1 or obs.size != rows * h * w * c or mask.size != rows * a:
+            raise ValueError(f"{what}: obs {obs.shape} and mask {mask.shape} for {rows} rows of [{h}, {w}, {c}] "
+                             f"and [{a}]")
+        return obs, mask, status
+
+    def net_eval(self, net: Any, obs: Any, mask: Any, status: Any,
+                 priors: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """One evaluation of the built-in network `net` (envpool_amd.pgx.net.Net) on leaf rows of this pool's game
+        (epa_net_eval): (policy float32 [rows, A] -- logits, or with `priors` the softmax over the legal actions --,
+        value float32 [rows]).  A row whose status is not 0 gets zeros."""
+        obs, mask, status = self._net_rows("net_eval", obs, mask, status)
+        a = self.guided_shape()[3]
+        policy, value = np.empty((len(status), a), dtype=np.float32), np.empty(len(status), dtype=np.float32)
+        native.check(self._lib.epa_net_eval(self._h, net._handle(self.device), len(status), 1 if priors else 0,
+                                            obs.ctypes.data, mask.ctypes.data, status.ctypes.data,
+                                            policy.ctypes.data, value.ctypes.data))
+        return policy, value
+
+    def net_eval_device(self, net: Any, rows: int, priors: bool, d_obs: int, d_mask: int, d_status: int,
+                        d_policy: int, d_value: int) -> None:
+        """`net_eval` on device memory at raw addresses (policy and value 4-byte aligned): only enqueued on the
+        pool's stream."""
+        self.guided_shape()
+        native.check(self._lib.epa_net_eval_device(
+            self._h, net._handle(self.device), int(rows), 1 if priors else 0, ctypes.c_void_p(d_obs),
+            ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status), ctypes.c_void_p(d_policy), ctypes.c_void_p(d_value)))
+
+    def net_run(self, net: Any, leaves: tuple, advances: Any = None) -> tuple[tuple, int]:
+        """The open session's round with `net` as its evaluator, enqueued from C++ (epa_net_run): `leaves` are the
+        session's last (obs, mask, status); `advances`: that many pairs of evaluation and advance, None: until the
+        round is complete.  A PUCT session is fed priors, a Gumbel session logits.  Returns (the new leaves, in the
+        shapes of the old, the advances made)."""
+        self.guided_shape()
+        if getattr(self, "_guided_k", None) is None:
+            raise ValueError("net_run: the pool has no guided-search session")
+        advances = native.check_net_advances(advances)
+        shapes = [np.asarray(x).shape for x in leaves]
+        obs, mask, status = (x.copy() for x in self._net_rows("net_run", *leaves))
+        made = ctypes.c_int32(0)
+        native.check(self._lib.epa_net_run(self._h, net._handle(self.device), advances, obs.ctypes.data,
+                                           mask.ctypes.data, status.ctypes.data, ctypes.byref(made)))
+        return (obs.reshape(shapes[0]), mask.reshape(shapes[1]), status.reshape(shapes[2])), int(made.value)
+
+    def net_run_device(self, net: Any, d_obs: int, d_mask: int, d_status: int, advances: Any = None) -> int:
+        """`net_run` on the device arrays of the `_device` begin or reroot, in place: only enqueued, except that a
+        wide or batch session with `advances=None` reads one device word per advance.  Returns the advances made."""
+        self.guided_shape()
+        if getattr(self, "_guided_k", None) is None:
+            raise ValueError("net_run: the pool has no guided-search session")
+        made = ctypes.c_int32(0)
+        native.check(self._lib.epa_net_run_device(self._h, net._handle(self.device), native.check_net_advances(advances),
+                                                  ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask),
+                                                  ctypes.c_void_p(d_status), ctypes.byref(made)))
+        return int(made.value)
+
     # -- self-play recorder -------------------------------------------------------
     def record_begin(self, capacity: int, max_plies: int = 0, symmetries: bool = False) -> tuple[int, int, int, int, int]:
         """Opens the pool's recorder (the PGX board games; RuntimeError("recorder not implemented for this

@@ -178,6 +178,12 @@ def lib() -> ctypes.CDLL:
         "epa_gumbel_advance_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "epa_gumbel_result": (i32, [vp, vp, vp, vp, vp]),
         "epa_gumbel_result_device": (i32, [vp, vp, vp, vp, vp]),
+        "epa_net_create": (i32, [i32, vp, ctypes.c_size_t, P(vp)]),
+        "epa_net_destroy": (i32, [vp]),
+        "epa_net_eval": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "epa_net_eval_device": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "epa_net_run": (i32, [vp, vp, i32, vp, vp, vp, P(i32)]),
+        "epa_net_run_device": (i32, [vp, vp, i32, vp, vp, vp, P(i32)]),
         "epa_record_begin": (i32, [vp, i32, i32, ctypes.c_uint32]),
         "epa_record_shape": (i32, [vp, P(i32)]),
         "epa_record_add": (i32, [vp, vp, i32, vp]),
@@ -233,6 +239,7 @@ EXPORTED_SYMBOLS = [
     "epa_guided_begin_prove", "epa_guided_begin_prove_device", "epa_guided_proof", "epa_guided_proof_device",
     "epa_gumbel_begin", "epa_gumbel_begin_device", "epa_gumbel_advance", "epa_gumbel_advance_device",
     "epa_gumbel_result", "epa_gumbel_result_device", "epa_gumbel_begin_batch", "epa_gumbel_begin_batch_device",
+    "epa_net_create", "epa_net_destroy", "epa_net_eval", "epa_net_eval_device", "epa_net_run", "epa_net_run_device",
     "epa_record_begin", "epa_record_shape", "epa_record_add", "epa_record_add_device", "epa_record_finish",
     "epa_record_finish_device", "epa_record_drain", "epa_record_view_device", "epa_record_clear",
     "epa_record_discard", "epa_record_counters", "epa_record_end",
@@ -540,6 +547,16 @@ def check_gumbel_batch(batch: Any) -> int:
     if isinstance(batch, bool) or int(batch) != batch or not 1 <= int(batch) <= GUMBEL_MAX_BATCH:
         raise ValueError(f"gumbel_begin: batch = {batch} must be 1 .. {GUMBEL_MAX_BATCH}")
     return int(batch)
+
+
+def check_net_advances(advances: Any) -> int:
+    """The `advances` of a net_run call after its check: None is 0 (until the round is complete); ValueError for
+    anything but an integer >= 1 (the engine checks it against the session's simulations)."""
+    if advances is None:
+        return 0
+    if isinstance(advances, bool) or int(advances) != advances or int(advances) < 1:
+        raise ValueError(f"net_run: advances = {advances} must be at least 1, or None")
+    return int(advances)
 
 
 def check_gumbel_batch_rows(logits: Any, values: Any, k: int, batch: int,

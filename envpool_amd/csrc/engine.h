@@ -369,6 +369,45 @@ class HostCopier {
   size_t frontier_{0};         // pieces [0, frontier_) are complete (the caller's view)
 };
 
+// The PGX built-in network (pgx_net.hip.h is the contract, pgx_net.hip the kernel).  NetImage is a checked blob in the
+// kernel's layout: per layer the weights in 1 KiB (output tile, k-step) blocks and the bias padded to whole tiles.
+constexpr int kNetImageLayers = 18;  // 2 * 8 blocks + trunk + head
+struct NetImage {
+  int F{0}, A{0}, D{0}, L{0}, layers{0};
+  float scale_p{0}, scale_v{0};
+  std::vector<char> bytes;
+  uint32_t w_off[kNetImageLayers]{}, b_off[kNetImageLayers]{};
+  int32_t shift[kNetImageLayers]{};
+};
+// std::invalid_argument with NetParse's reason for a blob that is no network
+void NetBuildImage(const void* blob, size_t bytes, NetImage* out);
+// One PgxNetEval on `stream`: obs u8 [rows][F], mask u8 [rows][A], status u8 [rows] -> policy f32 [rows][A], value f32
+// [rows]; mode: kNetLogits 0 / kNetPriors 1; pending (or null): ORed with 1 when some row's status is not 2.
+void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, const unsigned char* obs,
+               const unsigned char* mask, const unsigned char* status, float* policy, float* value,
+               unsigned int* pending, hipStream_t stream);
+
+// A network on a device (epa_net_create): it belongs to the device, not to a pool, and owns ONE device allocation --
+// the image, the pending word, and the policy / value rows its evaluations inside epa_net_run and the host forms
+// write, grown to the largest `rows` seen.  Calls on one net are the caller's to serialise, as a pool's session is.
+class Net {
+ public:
+  Net(int device, const void* blob, size_t bytes);
+  int device() const { return device_; }
+  const NetImage& image() const { return image_; }
+  void Reserve(size_t rows);  // (growing waits for the launches that use the old block)
+  const char* d_image() const { return mem_.p; }
+  unsigned int* pending() const { return reinterpret_cast<unsigned int*>(mem_.p + image_.bytes.size()); }
+  float* value() const { return reinterpret_cast<float*>(mem_.p + image_.bytes.size() + 256); }
+  float* policy() const { return value() + ((rows_ + 63) & ~(size_t)63); }
+
+ private:
+  int device_;
+  NetImage image_;
+  DeviceBlock mem_;
+  size_t rows_{0};
+};
+
 class Pool {
  public:
   // `spec`: the family's describe result for cfg; the state keys become CommonStateKeys(spec.players) + spec.state
@@ -561,6 +600,17 @@ class Pool {
   void GumbelAdvanceCall(const void* logits, const void* values, int k, void* obs, void* mask, void* status,
                          bool device);
   void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
+
+  // The built-in network (include/envpool_amd.h: epa_net_eval, epa_net_run).  Both refuse a family without guided
+  // search as the guided calls do, and a net of another device or of another F / A than GuidedShape's with
+  // std::invalid_argument.  NetEvalCall: one evaluation of `rows` caller rows, enqueued on stream_ (host form: staged
+  // through the side scratch, complete on return).  NetRunCall: `advances` pairs of (PgxNetEval, the open session's
+  // advance through Guided / GumbelAdvanceCall's device path) on the leaf arrays, which are in / out; 0: until the
+  // round is complete -- a plain session: simulations + 1 - calls pairs without a host wait; a wide or batch session:
+  // one read of the pending word per pair.  Returns the pairs made.
+  void NetEvalCall(Net& net, int rows, int mode, const void* obs, const void* mask, const void* status, void* policy,
+                   void* value, bool device);
+  int NetRunCall(Net& net, int advances, void* obs, void* mask, void* status, bool device);
 
   // Self-play recorder (include/envpool_amd.h: epa_record_begin; the PGX board games, pgx_record.hip.h): stages every
   // env's positions and policy targets while its game runs and turns a finished game into training samples in a

@@ -272,7 +272,13 @@ class GuidedSearch:
     def run(self, evaluate: Any, close: bool = True) -> GuidedResult:
         """Calls `evaluate(obs, mask, status) -> (priors, values)` until simulations + 1 advances are made, returns
         the result and closes the session (`close=False`: leaves it open, for `reroot`).  A wide session calls it
-        with the rows flattened to [k W, ...] until the round is `done`, at most simulations + 1 times."""
+        with the rows flattened to [k W, ...] until the round is `done`, at most simulations + 1 times.  `evaluate`
+        may be the built-in network (`envpool_amd.pgx.net.Net`): the same round, enqueued from C++ in one call."""
+        if getattr(evaluate, "_is_epa_net", False):  # the built-in network: the round is enqueued from C++
+            if self._pool is None:
+                raise ValueError("guided search: the session is closed")
+            self.leaves, made = self._pool.net_run(evaluate, self.leaves)
+            self.calls += made
         while self.width > 1 and not self.done and self.calls <= self.simulations:
             obs, mask, status = self.leaves
             self.advance(*evaluate(obs.reshape((-1,) + obs.shape[2:]), mask.reshape(-1, mask.shape[-1]),
@@ -357,7 +363,13 @@ class GumbelSearch:
     def run(self, evaluate: Any) -> GumbelResult:
         """Calls `evaluate(obs, mask, status) -> (logits, values)` until simulations + 1 advances are made, returns
         the result and closes the session.  A batch session calls it with the rows flattened to [k B, ...] until the
-        round is `done`, at most simulations + 1 times."""
+        round is `done`, at most simulations + 1 times.  `evaluate` may be the built-in network
+        (`envpool_amd.pgx.net.Net`): the same round, enqueued from C++ in one call."""
+        if getattr(evaluate, "_is_epa_net", False):  # the built-in network: the round is enqueued from C++
+            if self._pool is None:
+                raise ValueError("gumbel search: the session is closed")
+            self.leaves, made = self._pool.net_run(evaluate, self.leaves)
+            self.calls += made
         while self.batch > 1 and not self.done and self.calls <= self.simulations:
             obs, mask, status = self.leaves
             self.advance(*evaluate(obs.reshape((-1,) + obs.shape[2:]), mask.reshape(-1, mask.shape[-1]),
@@ -553,6 +565,20 @@ class EnvPoolMixin(ABC):
         ids = native.check_solve(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), depth, max_nodes,
                                  table_bits)
         return Solve(*self._solve(ids, int(depth), int(max_nodes), int(table_bits)))
+
+    def evaluate(self, net: Any, env_ids: Any = None, priors: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """Extension (the PGX board games; the other families raise RuntimeError): the built-in network `net`
+        (`envpool_amd.pgx.net.Net`) on the current position of every listed env, seen by the seat to move: (policy
+        float32 [k, A] -- logits, or with `priors` the softmax over the legal actions --, value float32 [k]); an env
+        that is over gets zeros.  Playing `policy.argmax` over the legal actions is a raw-policy move without a
+        search.  It opens and closes the pool's guided-search session, so it replaces an open one."""
+        pool = self._guided()
+        ids = native.check_guided(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), 1, 0.0)
+        leaves = pool.guided_begin(ids, 1, 0.0)
+        try:
+            return pool.net_eval(net, *leaves, priors)
+        finally:
+            pool.guided_end()
 
     def guided_search(self, env_ids: Any = None, simulations: int = 64, c_puct: float = 1.25, policy: str = "puct",
                       nodes: Any = None, width: int = 1, tactics: int = 0,

@@ -272,6 +272,10 @@ def _guided_round_device(pool: Any, evaluate: Any, dev: Any, k: int, simulations
             pool.guided_end()
             raise ValueError(f"{what}: advances = {advances} must be 1 .. simulations + 1 = {most}")
         most = int(advances)
+    if getattr(evaluate, "_is_epa_net", False):  # the built-in network: the whole round is enqueued from C++
+        _order_both_ways(pool, dev, lambda: pool.net_run_device(evaluate, obs.data_ptr(), mask.data_ptr(),
+                                                                status.data_ptr(), advances))
+        most = 0
     for _ in range(most):
         if width and advances is None and not bool((status != 2).any().item()):
             break  # the round is complete: nothing is pending
@@ -445,6 +449,10 @@ def gumbel_search_device(pool: Any, evaluate: Any, env_ids: Any = None, simulati
     _order_both_ways(pool, dev, lambda: pool.gumbel_begin_device(gumbel.data_ptr(), obs.data_ptr(), mask.data_ptr(),
                                                                  status.data_ptr(), ids, simulations, max_considered,
                                                                  c_visit, c_scale, batch or None))
+    if getattr(evaluate, "_is_epa_net", False):  # the built-in network: the whole round is enqueued from C++
+        _order_both_ways(pool, dev, lambda: pool.net_run_device(evaluate, obs.data_ptr(), mask.data_ptr(),
+                                                                status.data_ptr(), advances))
+        most = 0
     for _ in range(most):
         if batch and advances is None and not bool((status != 2).any().item()):
             break  # the round is complete: nothing is pending

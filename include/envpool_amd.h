@@ -840,6 +840,52 @@ int epa_gumbel_begin_batch_device(epa_pool* pool, const int32_t* env_ids, int32_
                                   const void* device_gumbel, void* device_obs, void* device_mask,
                                   void* device_status);
 
+/* Built-in network (no reference analogue; the four PGX board games; csrc/pgx_net.hip.h is the authority): an
+ * NNUE-style policy-value network in exact integer arithmetic, evaluated by one kernel on the int8 matrix cores, as
+ * the evaluator of the guided and Gumbel sessions above.  Input: a leaf's obs, F = H W C bytes 0 / 1.  Layers: a trunk
+ * of width D, L residual blocks, a head of A + 1 rows (policy, value); int8 weights -127 .. 127, int32 biases of at
+ * most 2^30 in magnitude, rounding right shifts 0 .. 24, activations clamped to 0 .. 127.  Outputs, float32:
+ * logit[a] = p[a] * scale_p, value = clamp(p[A] * scale_v, -1, 1).  A kernel, a host build and a numpy restatement of
+ * the contract agree bit for bit.
+ *   The blob: 32 bytes { uint32 magic "PGXN", int32 version = 1, F, A, D, L, float scale_p, scale_v }, then the 2 L + 2
+ *   layers (trunk, the blocks' two each, head), each int8 [N][K] row-major padded with zeros to a multiple of 4 bytes,
+ *   int32 bias [N], int32 shift (the head's is 0).  D a multiple of 32 in 32 .. 512, L 0 .. 8, F 1 .. 512, A 1 .. 127,
+ *   scales finite in (0, 1e20].
+ *   A net is created on a device and belongs to it, not to a pool: any pool of that device whose epa_guided_shape
+ *   gives the same F and A can use it.  It owns one device allocation (the weights in the kernel's layout and the
+ *   policy / value rows of its own evaluations, grown to the largest row count seen).  Calls that use one net must not
+ *   overlap.
+ *   The eval call (pool, net, rows, mode, obs [rows, F], mask [rows, A], status [rows]) -> policy float [rows, A],
+ *   value float [rows]: one launch on the pool's stream.  mode EPA_NET_LOGITS: policy = the logits, written for every
+ *   action.  mode EPA_NET_PRIORS: the softmax over the legal actions of mask (zero elsewhere), computed as the Gumbel
+ *   kernels compute theirs.  A row whose status is not 0 gets a zero policy row and value 0.
+ *   The run call (pool, net, advances, obs, mask, status, &made) works on the pool's open session of either policy (a
+ *   PUCT session is fed priors, a Gumbel session logits): `advances` = n >= 1 enqueues n pairs of evaluation and
+ *   advance without a host wait; 0 runs until the round is complete, at most simulations + 1 advances in all -- a plain
+ *   session without a host wait, a wide or batch session with one read of a device word per advance.  obs, mask and
+ *   status are in / out: the leaves of begin, of the last advance or of reroot go in, the last leaves come out.  The
+ *   session's call counter moves as if the caller had made the advances; `made` (may be null) receives their number.
+ *   EPA_ERR_INVALID: a blob that is no network (the message names the field), a device index out of range; a net of
+ *   another device or of another F or A than the pool's; the run call without an open session or with `advances`
+ *   outside 0 .. simulations + 1 less the advances made; rows < 1, an unknown mode, null arguments.
+ *   Every family without guided search fails with EPA_ERR_RUNTIME "guided search not implemented for this
+ *   environment".
+ * The _device forms take device pointers (float arrays 4-byte aligned) and only enqueue on the pool's stream; the
+ * run call's _device form with advances = 0 on a wide or batch session still waits once per advance. */
+#define EPA_NET_LOGITS 0
+#define EPA_NET_PRIORS 1
+typedef struct epa_net epa_net;
+int epa_net_create(int32_t device, const void* blob, size_t bytes, epa_net** out);
+int epa_net_destroy(epa_net* net);
+int epa_net_eval(epa_pool* pool, epa_net* net, int32_t rows, int32_t mode, const uint8_t* obs, const uint8_t* mask,
+                 const uint8_t* status, float* policy, float* value);
+int epa_net_eval_device(epa_pool* pool, epa_net* net, int32_t rows, int32_t mode, const void* device_obs,
+                        const void* device_mask, const void* device_status, void* device_policy, void* device_value);
+int epa_net_run(epa_pool* pool, epa_net* net, int32_t advances, uint8_t* obs, uint8_t* mask, uint8_t* status,
+                int32_t* made);
+int epa_net_run_device(epa_pool* pool, epa_net* net, int32_t advances, void* device_obs, void* device_mask,
+                       void* device_status, int32_t* made);
+
 /* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
  * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
  * targets of the game in progress; when the game ends it writes one sample per staged ply -- or one per ply and board
