@@ -622,6 +622,40 @@ class _ShardedPools:
     def record_end(self) -> None:
         self._record_all(lambda p: p.record_end())
 
+    # -- self-play driver: one driver per shard; the keys take global env ids, so the shards play the unsharded pool's
+    # games --
+    def selfplay_begin(self, net: Any, **options: Any) -> None:
+        native.check_selfplay(**options)
+        for device in sorted({p.device for p in self.pools}):
+            net._handle(device)  # one copy per device, made before the shards ask for it at once
+        self._record_all(lambda p: p.selfplay_begin(net, **options))
+
+    def selfplay_run(self, plies: int, wait: bool = True) -> None:
+        """`DevicePool.selfplay_run` in every shard, each with the net's copy on its own device; shards on different
+        devices run at once.  Shards that share a device share the net's copy and its policy and value rows, and calls
+        that use one copy must not overlap ON THE DEVICE: such a shard takes its turn and is waited for before the turn
+        passes, also with `wait=False` -- only a shard alone on its device is enqueue-only."""
+        plies = native.check_selfplay_plies(plies)
+        turn = {p.device: threading.Lock() for p in self.pools}
+        shared = {d: sum(p.device == d for p in self.pools) > 1 for d in turn}
+
+        def run(p: DevicePool) -> None:
+            with turn[p.device]:
+                p.selfplay_run(plies, wait or shared[p.device])
+
+        self._guided = None
+        self._record_all(run)
+
+    def selfplay_stats(self) -> np.ndarray:
+        """The shards' statistics added up; t is every shard's."""
+        parts = self._record_all(lambda p: p.selfplay_stats())
+        out = np.sum(parts, axis=0)
+        out[5] = parts[0][5]
+        return out
+
+    def selfplay_end(self) -> None:
+        self._record_all(lambda p: p.selfplay_end())
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:
@@ -793,6 +827,11 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
         def _recorder(self) -> Any:
             if getattr(self._pool, "record_begin", None) is None:  # a pool with its own executor
                 raise RuntimeError("recorder not implemented for this environment")
+            return self._pool
+
+        def _selfplay(self) -> Any:
+            if getattr(self._pool, "selfplay_begin", None) is None:  # a pool with its own executor
+                raise RuntimeError("guided search not implemented for this environment")
             return self._pool
 
         def _xla(self) -> Any:

@@ -981,6 +981,36 @@ class DevicePool:
         """Closes the recorder and releases its device memory; ValueError without one."""
         native.check(self._lib.epa_record_end(self._h))
 
+    # -- self-play driver (csrc/pgx_selfplay.hip.h) -----------------------------------
+    def selfplay_begin(self, net: Any, **options: Any) -> None:
+        """Opens the pool's self-play driver (epa_selfplay_begin) with the built-in network `net` as the evaluator;
+        `options` are `native.check_selfplay`'s.  A pool has one driver; a new one replaces it.  It needs a pool in
+        sync mode with nothing pending in its result queue, and with `record` an open recorder."""
+        o = native.check_selfplay(**options)
+        self.guided_shape()
+        native.check(self._lib.epa_selfplay_begin(self._h, net._handle(self.device), ctypes.byref(o)))
+        self._selfplay_net = net  # (the driver uses the net's device copy: it must live as long)
+
+    def selfplay_run(self, plies: int, wait: bool = True) -> None:
+        """Plays `plies` plies of every env (epa_selfplay_run); `wait=False` only enqueues them on the pool's stream
+        (epa_selfplay_run_device).  The driver opens the pool's guided-search session ply by ply: a session the caller
+        had open is gone afterwards."""
+        plies = native.check_selfplay_plies(plies)
+        run = self._lib.epa_selfplay_run if wait else self._lib.epa_selfplay_run_device
+        self._guided_k = None
+        native.check(run(self._h, plies))
+
+    def selfplay_stats(self) -> np.ndarray:
+        """int64 [6]: games, wins0, wins1, draws, plies, t since the driver was opened; waits for the device."""
+        out = np.zeros(6, dtype=np.int64)
+        native.check(self._lib.epa_selfplay_stats(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def selfplay_end(self) -> None:
+        """Closes the driver and releases its device memory; ValueError without one.  The recorder stays open."""
+        native.check(self._lib.epa_selfplay_end(self._h))
+        self._selfplay_net = None
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

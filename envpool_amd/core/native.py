@@ -184,6 +184,11 @@ def lib() -> ctypes.CDLL:
         "epa_net_eval_device": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         "epa_net_run": (i32, [vp, vp, i32, vp, vp, vp, P(i32)]),
         "epa_net_run_device": (i32, [vp, vp, i32, vp, vp, vp, P(i32)]),
+        "epa_selfplay_begin": (i32, [vp, vp, P(SelfplayOptions)]),
+        "epa_selfplay_run": (i32, [vp, i32]),
+        "epa_selfplay_run_device": (i32, [vp, i32]),
+        "epa_selfplay_stats": (i32, [vp, P(ctypes.c_int64)]),
+        "epa_selfplay_end": (i32, [vp]),
         "epa_record_begin": (i32, [vp, i32, i32, ctypes.c_uint32]),
         "epa_record_shape": (i32, [vp, P(i32)]),
         "epa_record_add": (i32, [vp, vp, i32, vp]),
@@ -243,6 +248,7 @@ EXPORTED_SYMBOLS = [
     "epa_record_begin", "epa_record_shape", "epa_record_add", "epa_record_add_device", "epa_record_finish",
     "epa_record_finish_device", "epa_record_drain", "epa_record_view_device", "epa_record_clear",
     "epa_record_discard", "epa_record_counters", "epa_record_end",
+    "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -557,6 +563,81 @@ def check_net_advances(advances: Any) -> int:
     if isinstance(advances, bool) or int(advances) != advances or int(advances) < 1:
         raise ValueError(f"net_run: advances = {advances} must be at least 1, or None")
     return int(advances)
+
+
+class SelfplayOptions(ctypes.Structure):
+    """epa_selfplay_options (include/envpool_amd.h)."""
+
+    _fields_ = [("policy", ctypes.c_int32), ("simulations", ctypes.c_int32), ("max_considered", ctypes.c_int32),
+                ("batch", ctypes.c_int32), ("c_visit", ctypes.c_float), ("c_scale", ctypes.c_float),
+                ("c_puct", ctypes.c_float), ("width", ctypes.c_int32), ("tactics", ctypes.c_int32),
+                ("prove", ctypes.c_int32), ("tactics_nodes", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("noise", ctypes.c_int32), ("sample_plies", ctypes.c_int32), ("record", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+SELFPLAY_GUMBEL = 0  # EPA_SELFPLAY_GUMBEL / EPA_SELFPLAY_PUCT: the policies of a self-play driver
+SELFPLAY_PUCT = 1
+# the options of `selfplay` that belong to one policy, with the value that means "not given"
+_SELFPLAY_GUMBEL_ONLY = {"max_considered": None, "c_visit": None, "c_scale": None, "batch": 1, "noise": None}
+_SELFPLAY_PUCT_ONLY = {"c_puct": None, "width": 1, "tactics": 0, "tactics_nodes": None, "prove": False,
+                       "sample_plies": 0}
+
+
+def check_selfplay(policy: Any = "gumbel", simulations: Any = 32, max_considered: Any = None, c_visit: Any = None,
+                   c_scale: Any = None, batch: Any = 1, c_puct: Any = None, width: Any = 1, tactics: Any = 0,
+                   tactics_nodes: Any = None, prove: Any = False, seed: Any = 0, noise: Any = None,
+                   sample_plies: Any = 0, record: Any = True) -> SelfplayOptions:
+    """The options of a selfplay_begin call as the C struct, after the checks every layer makes before the native call.
+    ValueError for an unknown policy; for an option of the other policy, worded as `guided_search` words it; for a seed
+    outside 0 .. 2^64 - 1, a `noise` or `record` that is no bool, a `sample_plies` that is no integer >= 0; and for the
+    option values the policy's own begin refuses (`check_gumbel`, `check_gumbel_batch`, `check_guided`,
+    `check_guided_width`, `check_guided_tactics`, `check_guided_prove`).  Defaults are the searches': max_considered 16,
+    c_visit 50, c_scale 0.1, c_puct 1.25, noise on."""
+    given = dict(max_considered=max_considered, c_visit=c_visit, c_scale=c_scale, batch=batch, noise=noise,
+                 c_puct=c_puct, width=width, tactics=tactics, tactics_nodes=tactics_nodes, prove=prove,
+                 sample_plies=sample_plies)
+    if policy not in ("gumbel", "puct"):
+        raise ValueError(f"selfplay: policy = {policy!r} must be 'puct' or 'gumbel'")
+    theirs = _SELFPLAY_PUCT_ONLY if policy == "gumbel" else _SELFPLAY_GUMBEL_ONLY
+    stray = sorted(name for name, unset in theirs.items() if given[name] is not None and given[name] != unset)
+    if stray:
+        other = "puct" if policy == "gumbel" else "gumbel"
+        raise ValueError(f"selfplay: {stray} are arguments of policy='{other}'")
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64:
+        raise ValueError(f"selfplay: seed = {seed} must be an integer in 0 .. 2^64 - 1")
+    if not isinstance(record, (bool, np.bool_)):
+        raise ValueError(f"selfplay: record = {record!r} must be True or False")
+    o = SelfplayOptions()
+    o.seed, o.record, o.simulations = int(seed), int(bool(record)), int(simulations)
+    if policy == "gumbel":
+        if noise is None:
+            noise = True
+        if not isinstance(noise, (bool, np.bool_)):
+            raise ValueError(f"selfplay: noise = {noise!r} must be True or False")
+        m = 16 if max_considered is None else max_considered
+        cv, cs = 50.0 if c_visit is None else c_visit, 0.1 if c_scale is None else c_scale
+        check_gumbel(np.zeros(1, dtype=np.int32), simulations, m, cv, cs)
+        b = check_gumbel_batch(batch)
+        o.policy, o.max_considered, o.c_visit, o.c_scale = SELFPLAY_GUMBEL, int(m), float(cv), float(cs)
+        o.batch, o.noise = (b if b > 1 else 0), int(bool(noise))
+        return o  # (every PUCT field stays 0: the engine refuses anything else)
+    if isinstance(sample_plies, bool) or int(sample_plies) != sample_plies or not 0 <= int(sample_plies) < 2**31:
+        raise ValueError(f"selfplay: sample_plies = {sample_plies} must be an integer >= 0")
+    c = 1.25 if c_puct is None else c_puct
+    check_guided(np.zeros(1, dtype=np.int32), simulations, c)
+    w = check_guided_width(width)
+    t, tn = check_guided_tactics(tactics, GUIDED_TACTICS_NODES if tactics_nodes is None else tactics_nodes)
+    o.policy, o.c_puct, o.width, o.tactics, o.tactics_nodes = SELFPLAY_PUCT, float(c), (w if w > 1 else 0), t, tn
+    o.prove, o.sample_plies = int(check_guided_prove(prove)), int(sample_plies)
+    return o
+
+
+def check_selfplay_plies(plies: Any) -> int:
+    """The `plies` of a selfplay_run call after its check: ValueError for anything but an integer >= 1."""
+    if isinstance(plies, bool) or int(plies) != plies or not 1 <= int(plies) < 2**31:
+        raise ValueError(f"selfplay_run: plies = {plies} must be at least 1")
+    return int(plies)
 
 
 def check_gumbel_batch_rows(logits: Any, values: Any, k: int, batch: int,

@@ -408,6 +408,36 @@ class Net {
   size_t rows_{0};
 };
 
+// One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
+// row i is local env i of the pool, every pointer device memory.
+struct SelfplayArgs {
+  int k;                        // rows: the pool's envs
+  int id_offset;                // env_id_offset: a key takes the global id
+  int policy;                   // EPA_SELFPLAY_GUMBEL / EPA_SELFPLAY_PUCT
+  int noise;                    // 0: zero rows
+  int sample_plies;
+  uint32_t t;                   // the ply counter
+  uint64_t seed;
+  float* gumbel;                // noise: [k][A] out
+  const int32_t* visits;        // move, PUCT: the result's [k][A]
+  const int32_t* result_action; // move: the result's [k]
+  const int32_t* cur_step;      // move, PUCT: the envs' elapsed steps [N] (the family hook fills it in)
+  const float* weights;         // move, Gumbel: the result's [k][A]
+  int32_t* action;              // move: [k] out, the step's action row
+  float* target;                // move: [k][A] out, the recorder's policy rows
+  const unsigned char* done;    // tally: the step's result block
+  const float* reward;          // [k][2]
+  const int32_t* elapsed;       // [k]
+  long long* counters;          // tally: [5], 8-byte aligned
+};
+
+// What a driver is opened with (include/envpool_amd.h: epa_selfplay_options)
+using SelfplayOptions = epa_selfplay_options;
+// The driver's kernels (pgx_selfplay.hip) for PGX game `game` (pgx::kTicTacToe ...), one launch each on `stream`
+void PgxSelfplayLaunchNoise(int game, const SelfplayArgs& a, hipStream_t stream);
+void PgxSelfplayLaunchMove(int game, const SelfplayArgs& a, hipStream_t stream);
+void PgxSelfplayLaunchTally(const SelfplayArgs& a, hipStream_t stream);
+
 class Pool {
  public:
   // `spec`: the family's describe result for cfg; the state keys become CommonStateKeys(spec.players) + spec.state
@@ -560,9 +590,10 @@ class Pool {
   virtual size_t GuidedWideRootBytes(int width) const { (void)width; return 0; }  // a multiple of 16
   virtual size_t GuidedWideLiveOffset() const { return 0; }  // of a record's int32 count of pending slots
   // The one begin of a PUCT session, whatever its options.  obs / mask / status: host arrays (device == false) or
-  // device pointers.
+  // device pointers.  check_only: the call's refusals and nothing else (the self-play driver's begin asks them before
+  // its first ply).
   void GuidedBeginCall(const int32_t* ids, int k, const GuidedBeginOptions& o, void* obs, void* mask, void* status,
-                       bool device);
+                       bool device, bool check_only = false);
   // Exact leaf status: the session's counters, decided int32 [k] and (may be null) the solver's visited positions
   // int64 [k]; zeros for a session without tactics; the device form only enqueues.
   void GuidedDecidedCall(void* decided, void* nodes, bool device);
@@ -595,8 +626,10 @@ class Pool {
   virtual size_t GumbelBatchRootBytes(int batch) const { (void)batch; return 0; }  // a multiple of 16
   // The one begin of a Gumbel session.  batch: slots per root, 1 .. EPA_GUMBEL_MAX_BATCH: the leaf arrays have
   // k * batch rows from then on (the noise keeps k); 0: a plain session.
+  // check_only: as GuidedBeginCall's.
   void GumbelBeginCall(const int32_t* ids, int k, int simulations, int considered, int batch, float c_visit,
-                       float c_scale, const void* gumbel, void* obs, void* mask, void* status, bool device);
+                       float c_scale, const void* gumbel, void* obs, void* mask, void* status, bool device,
+                       bool check_only = false);
   void GumbelAdvanceCall(const void* logits, const void* values, int k, void* obs, void* mask, void* status,
                          bool device);
   void GumbelResultCall(void* visits, void* values, void* action, void* weights, bool device);
@@ -642,6 +675,26 @@ class Pool {
   void RecordCounters(int64_t out[5]);                 // count, samples, games, dropped_games, dropped_plies
   void RecordShape(int32_t out[5]) const;              // H, W, C, A, nsym of the open recorder
   void RecordEnd();
+
+  // Self-play driver (include/envpool_amd.h: epa_selfplay_begin; the PGX board games, pgx_selfplay.hip.h): plays
+  // plies of every env of the pool with a Net as the evaluator, through the device forms of the calls above --
+  // GumbelBeginCall / GuidedBeginCall, NetRunCall, *ResultCall, RecordAddCall, SendDevice, RecvDevice, RecordFinishCall --
+  // and three launches of its own in between.  A pool has at most one driver.  Its memory -- noise, leaf arrays, result
+  // arrays, action row, target rows, counters -- is ONE device allocation of its own with a single owner, released by
+  // SelfplayEnd, by the next SelfplayBegin and by ~Pool; it coexists with the session (which the driver opens ply by
+  // ply, and whose last one stays open) and the recorder.  SelfplayRun only enqueues (device == false: then waits for
+  // the stream); SelfplayStats is the one host wait.  The net must outlive the driver.  A SelfplayRun that throws
+  // partway has enqueued its earlier plies and part of one more (a recorder add without its finish) and does not
+  // count the partial ply in t: the driver must be closed after an error.  A family without the hooks
+  // keeps the defaults, and begin throws as the guided and recorder calls do.
+  virtual bool HasSelfplay() const { return false; }
+  virtual void SelfplayNoise(const SelfplayArgs& a);
+  virtual void SelfplayMove(const SelfplayArgs& a);
+  virtual void SelfplayTally(const SelfplayArgs& a);
+  void SelfplayBegin(Net& net, const SelfplayOptions& o);
+  void SelfplayRun(int plies, bool device);
+  void SelfplayStats(int64_t out[6]);  // games, wins0, wins1, draws, plies, t
+  void SelfplayEnd();
 
  protected:
   // Family hook of the snapshot's last section: bytes per env of whatever the flat state does not carry, and the
@@ -861,6 +914,10 @@ class Pool {
   };
   GuidedSession guided_;
   void GuidedFree();                                   // (no session: nothing)
+  // A begin's block of `bytes`: an open session's block of exactly that size is kept -- no free and no allocation, so
+  // the begin does not wait for the device (a self-play driver begins once per ply); any other is released first.
+  // Result-neutral: a begin initialises what it reads.
+  void GuidedReserve(size_t bytes);
   void GuidedRequire(const char* what) const;          // throws without a session
   void GuidedRequirePolicy(const char* what, bool gumbel) const;  // ... or with one of the other policy
   // what GuidedArgs and GumbelArgs share: the session's sizes, call number, roots and nodes, and for a host form the
@@ -897,6 +954,21 @@ class Pool {
   void RecordRequire(const char* what) const;           // throws without the hooks or without a recorder
   RecordArgs RecordArgsOf(int k) const;
   void RecordCheckIds(const char* what, const int32_t* ids, int k) const;  // range, count, repeats
+  // the pool's self-play driver
+  struct Selfplay {
+    bool open{false};
+    DeviceBlock mem;        // the driver's one device allocation, in the order of `off`
+    Net* net{nullptr};
+    SelfplayOptions o{};
+    uint32_t t{0};          // the ply counter
+    std::vector<int32_t> ids;  // the pool's global ids in order
+    // offsets into mem: noise, obs, mask, status (the leaf arrays, one row per root or slot), visits, vals, result
+    // action, weights, the action row, the target rows, the counters (64 bytes), the end
+    size_t off[12]{};
+  };
+  Selfplay selfplay_;
+  void SelfplayFree();                                  // (no driver: nothing)
+  void SelfplayPly();                                   // one ply, enqueued
   uint64_t family_hash_{0};
   // concurrent batches (async mode)
   std::vector<hipStream_t> compute_;     // compute_[0] is the sync-mode stream

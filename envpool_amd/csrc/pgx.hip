@@ -34,6 +34,7 @@
 // tactics (PgxGuidedTactics, a launch behind every advance: a wave per slot solves the slot's new leaf).
 // Self-play recorder: pgx_record.hip.h, finished games as training samples in the recorder's own memory (PgxRecordAdd /
 // PgxRecordPlan / PgxRecordEmit).
+// Self-play driver: pgx_selfplay.hip.h; its three kernels live in pgx_selfplay.hip, PgxPool only forwards the launches.
 #include <algorithm>
 #include <string>
 
@@ -1860,6 +1861,15 @@ class PgxPool : public Pool {
       LaunchRoots(PgxRecordEmit<G, false>, kRecordEmitWaves, d_ids, a);
     }
   }
+  // the self-play driver's launches (pgx_selfplay.hip)
+  bool HasSelfplay() const override { return true; }
+  void SelfplayNoise(const SelfplayArgs& a) override { PgxSelfplayLaunchNoise(G, a, stream_); }
+  void SelfplayMove(const SelfplayArgs& a) override {
+    SelfplayArgs b = a;
+    b.cur_step = common_.cur_step;
+    PgxSelfplayLaunchMove(G, b, stream_);
+  }
+  void SelfplayTally(const SelfplayArgs& a) override { PgxSelfplayLaunchTally(a, stream_); }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
     if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";

@@ -139,6 +139,55 @@ class Recorder:
             self._pool = None
 
 
+class Stats(NamedTuple):
+    """What a self-play driver has played since it was opened (`Selfplay.run`, `Selfplay.stats`)."""
+
+    games: int   # finished games
+    wins0: int   # ... whose last reward was positive for seat 0
+    wins1: int   # ... for seat 1
+    draws: int   # ... with both rewards 0
+    plies: int   # the sum of the finished games' lengths (elapsed steps)
+    t: int       # the driver's ply counter: plies played per env, resets included
+
+
+class Selfplay:
+    """A pool's self-play driver (`env.selfplay`): one call plays n plies of every env against itself -- root noise,
+    search round with the built-in network, move, recorder add, step with auto-reset, recorder finish, statistics --
+    enqueued from C++, with nothing leaving the device between two plies.
+
+        rec = env.recorder(capacity=1 << 18, symmetries=True)
+        env.reset()
+        sp = env.selfplay(net, policy="gumbel", simulations=32, max_considered=16, batch=16, seed=0)
+        stats = sp.run(plies=200)          # Stats(games, wins0, wins1, draws, plies, t)
+        samples = rec.drain()
+        sp.close()
+
+    `run(n, wait=False)` only enqueues and returns None; `stats()` waits.  The games depend on (seed, env id, the
+    driver's ply counter, the net, the positions) only: `run(3)` then `run(2)` is `run(5)`."""
+
+    def __init__(self, pool: Any, net: Any, options: dict) -> None:
+        self._pool = pool
+        pool.selfplay_begin(net, **options)
+
+    def _open(self) -> Any:
+        if self._pool is None:
+            raise ValueError("selfplay: the driver is closed")
+        return self._pool
+
+    def run(self, plies: int, wait: bool = True) -> Any:
+        self._open().selfplay_run(native.check_selfplay_plies(plies), bool(wait))
+        return self.stats() if wait else None
+
+    def stats(self) -> Stats:
+        return Stats(*(int(x) for x in self._open().selfplay_stats()))
+
+    def close(self) -> None:
+        """Releases the driver's device memory; an open recorder stays open."""
+        if self._pool is not None:
+            pool, self._pool = self._pool, None
+            pool.selfplay_end()
+
+
 class GuidedSearch:
     """A pool's guided-search session (`env.guided_search`): a PUCT search of every listed env whose tree stays on
     the device and that stops at every new leaf for the caller's priors and value.
@@ -672,6 +721,25 @@ class EnvPoolMixin(ABC):
         native call."""
         capacity, max_plies, symmetries = native.check_record(capacity, max_plies, symmetries)
         return Recorder(self._recorder(), np.asarray(self.all_env_ids, dtype=np.int32), capacity, max_plies, symmetries)
+
+    def selfplay(self, net: Any, policy: str = "gumbel", simulations: int = 32, seed: int = 0, record: bool = True,
+                 **options: Any) -> Selfplay:
+        """Extension (the PGX board games): opens the pool's self-play driver -- `Selfplay` -- with the built-in
+        network `net` (`envpool_amd.pgx.net.Net`) as the evaluator.  `policy="gumbel"` takes `max_considered`,
+        `c_visit`, `c_scale`, `batch` and `noise` (False: zero root noise) as `gumbel_search` does;
+        `policy="puct"` takes `c_puct`, `width`, `tactics`, `tactics_nodes`, `prove` as `guided_search` does and
+        `sample_plies`: a game's first plies are sampled from the visit counts, the later ones take the most visited
+        move.  `record` (default True) feeds the pool's open recorder.  The pool must be in sync mode with nothing
+        pending in its result queue (after `reset()` or `step()`).  A `batch` or `width` session reads one device word
+        per advance, as `search.run(net)` does; a plain session has no host wait between plies.  The arguments are
+        checked before any native call."""
+        if not getattr(net, "_is_epa_net", False):
+            raise ValueError("selfplay: net must be an envpool_amd.pgx.net.Net")
+        options = dict(options, policy=policy, simulations=simulations, seed=seed, record=record)
+        native.check_selfplay(**options)
+        if self.is_async:
+            raise ValueError("selfplay: async mode (batch_size != num_envs) is not supported")
+        return Selfplay(self._selfplay(), net, options)
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

@@ -481,6 +481,22 @@ def _record_rows(what: str, t: Any, dtypes: tuple, shape: tuple, dev: Any) -> No
         raise RuntimeError(f"{what} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
 
 
+def selfplay_device(pool: Any, net: Any, plies: int, **options: Any) -> None:
+    """`plies` plies of the pool's self-play driver (`DevicePool.selfplay_run(plies, wait=False)`), only enqueued and
+    ordered both ways with torch's current stream like the other device forms: what torch enqueued before (a `Net`'s
+    weights do not change, but the recorder's view or the envs may have been touched) is seen by the plies, and torch
+    work enqueued afterwards -- reading `recorder_view_device`'s tensors, say -- sees their samples.  With `options`
+    (`native.check_selfplay`'s), or when the pool's driver was not opened with `net`, the driver is opened first;
+    otherwise the open one continues.  `pool.selfplay_stats()` waits and reads the statistics."""
+    import torch
+
+    plies = native.check_selfplay_plies(plies)
+    if options or getattr(pool, "_selfplay_net", None) is not net:
+        pool.selfplay_begin(net, **options)
+    dev = torch.device("cuda", pool.device)
+    _order_both_ways(pool, dev, lambda: pool.selfplay_run(plies, wait=False))
+
+
 def recorder_add_device(pool: Any, policy: Any, env_ids: Any = None) -> None:
     """`pool.record_add` with the policy targets where the model left them: `policy` is a float32 [k, A] tensor on the
     pool's device, read by the recorder's kernel (no PCIe transfer, no host synchronisation) and ordered against

@@ -948,6 +948,71 @@ int epa_record_discard(epa_pool* pool, const int32_t* env_ids, int32_t k);
 int epa_record_counters(epa_pool* pool, int64_t* out);
 int epa_record_end(epa_pool* pool);
 
+/* Self-play driver (no reference analogue; the four PGX board games; csrc/pgx_selfplay.hip.h is the authority): one
+ * call plays `plies` plies of EVERY env of a pool against itself with the built-in network as the evaluator, with
+ * auto-resets, and -- with `record` -- the finished games land in the pool's open recorder.  Everything is enqueued
+ * through the device forms above; between two plies nothing leaves the device.
+ *   One ply, over all envs of the pool in id order: the root noise (Gumbel sessions; PgxSelfplayNoise), the begin of a
+ *   session of `policy` (its leaf arrays live in the driver's block), the whole round with the net (epa_net_run_device,
+ *   advances = 0), the result, the move (PgxSelfplayMove: the action row and the policy target rows), epa_record_add,
+ *   the step (epa_send_device + epa_recv_device, whose batch is pending at once), epa_record_finish on the result
+ *   block's reward and done, the tally (PgxSelfplayTally).  An env that is over gets action 0, which resets it, so the
+ *   games follow each other without the host.
+ *   Contract (csrc/pgx_selfplay.hip.h).  The driver counts its plies: t = 0 at begin, + 1 per ply, across run calls.
+ *   key(e, t) = SM(seed ^ SM((uint64(global env id e) << 32) | uint32(t))), SM = splitmix64 as in epa_playout.  Noise:
+ *   u = ((float)(SM(key + a) >> 41) + 0.5) * 2^-23, g[a] = -GumbelLog(-GumbelLog(u)), GumbelLog a float32 logarithm of
+ *   the library's own (bit-identical on host and device); noise = 0: zero rows.  Gumbel move: the result's action, 0 for
+ *   -1; target = the result's weights.  PUCT move: V = the sum of the root's visits; V = 0 or a root that was over:
+ *   action 0 and a zero target; otherwise target[a] = visits[a] / V, and the action is, while the env's elapsed step is
+ *   below sample_plies, the lowest a whose inclusive prefix sum of visits exceeds ((SM(key + 0x100) >> 32) * V) >> 32,
+ *   afterwards the most visited action (the lowest on ties).  Statistics: games, wins of seat 0 (its last reward > 0),
+ *   wins of seat 1, draws (both 0), plies (the sum of the finished games' elapsed steps).
+ *   epa_selfplay_begin(pool, net, options): opens the driver (a pool has one; a new one replaces it).  Its memory is
+ *     one device allocation of its own, released by epa_selfplay_end, the next begin and epa_destroy; it coexists with
+ *     the session and the recorder.  The options are those of epa_gumbel_begin_batch (policy EPA_SELFPLAY_GUMBEL:
+ *     simulations, max_considered, c_visit, c_scale, batch) or of epa_guided_begin_prove (EPA_SELFPLAY_PUCT:
+ *     simulations, c_puct, width, tactics, tactics_nodes, prove, and sample_plies), checked as those check them; every
+ *     field of the other policy must be 0 -- a Gumbel driver: c_puct, width, tactics, prove, tactics_nodes,
+ *     sample_plies; a PUCT driver: max_considered, batch, c_visit, c_scale, noise -- and is refused otherwise.
+ *   epa_selfplay_run(pool, plies): plays and waits for the device; epa_selfplay_run_device only enqueues on the pool's
+ *     stream (a batch or width session still reads one device word per advance, as epa_net_run does).  The driver uses
+ *     the pool's guided-search session: an open one is replaced, and the last ply's session stays open.
+ *   epa_selfplay_stats(out[6]): games, wins0, wins1, draws, plies, t since begin -- the one host wait.
+ *   A run call that fails partway (a device error, a recorder closed by another thread) has enqueued its earlier
+ *   plies and part of one more, whose recorder add may lack its finish, and t does not count the partial ply: close
+ *   the driver (epa_selfplay_end) and discard the recorder's staging (epa_record_discard) after such an error.
+ * Errors (before any launch):
+ *   EPA_ERR_RUNTIME "guided search not implemented for this environment" / "recorder not implemented ..." for the other
+ *     families.
+ *   EPA_ERR_INVALID: a net of another device or of other F / A; rows pending in the pool's result queue; async mode
+ *     (batch_size != num_envs); record without an open recorder; plies < 1; an unknown policy; option values the
+ *     session's begin refuses; options of the other policy; a call without a driver. */
+#define EPA_SELFPLAY_GUMBEL 0
+#define EPA_SELFPLAY_PUCT 1
+typedef struct epa_selfplay_options {
+  int32_t policy;
+  int32_t simulations;
+  int32_t max_considered; /* Gumbel */
+  int32_t batch;          /* Gumbel; 0: a plain session */
+  float c_visit;          /* Gumbel */
+  float c_scale;          /* Gumbel */
+  float c_puct;           /* PUCT */
+  int32_t width;          /* PUCT; 0: a plain session */
+  int32_t tactics;        /* PUCT */
+  int32_t prove;          /* PUCT */
+  int64_t tactics_nodes;  /* PUCT */
+  uint64_t seed;
+  int32_t noise;          /* Gumbel: 0 zero rows */
+  int32_t sample_plies;   /* PUCT */
+  int32_t record;         /* 1: add / finish on the pool's open recorder */
+  int32_t reserved;       /* 0 */
+} epa_selfplay_options;
+int epa_selfplay_begin(epa_pool* pool, epa_net* net, const epa_selfplay_options* options);
+int epa_selfplay_run(epa_pool* pool, int32_t plies);
+int epa_selfplay_run_device(epa_pool* pool, int32_t plies);
+int epa_selfplay_stats(epa_pool* pool, int64_t* out);
+int epa_selfplay_end(epa_pool* pool);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
