@@ -1,7 +1,7 @@
 """Generates the PGX board-game fixtures from the reference itself.  Run on a machine that has the reference tree
 (it is not on the GPU boxes):
 
-    python tests/golden/make_pgx_golden.py [/path/to/reference]
+    python tests/golden/make_pgx_golden.py [--scripted] [/path/to/reference]
 
 It compiles pgx_golden_driver.cc, which includes the reference's envpool/pgx/board_games.h in place inside its own
 AsyncEnvPool (max_num_players = 2), with the absl stand-ins of oracle/ref_shims (read only), into a temporary
@@ -15,6 +15,13 @@ directory outside the repository.  Then it writes data only:
                                    key's row is its [2, ...] block), the hidden state of every env after each of
                                    them (`hidden`, int32 words, HIDDEN below), the actions (`actions` [steps, n]),
                                    the seed and max_episode_steps
+
+  tests/golden/pgx_<id>__scripted.npz
+                                   the same arrays for scripted actions (the driver's `replay` mode): legal games
+                                   from reset found by pgx_scripted.py with the scalar restatement of the rules,
+                                   whose required content (every ConnectFour line, Othello wipe-outs, long Hex
+                                   chains, ...: see there) is asserted on the reference's output before writing.
+                                   --scripted writes these four files only and leaves every other file as it is.
 
 <name> is the id, or <id>__trunc for a run with a small max_episode_steps.  The seeds are searched until a run
 covers, per game: a win by each seat; a draw (TicTacToe, ConnectFour, Othello); an illegal-move ending of each
@@ -31,9 +38,14 @@ import types
 
 import numpy as np
 
+import pgx_scripted
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+ARGS = [a for a in sys.argv[1:] if a != "--scripted"]
+ONLY_SCRIPTED = "--scripted" in sys.argv[1:]
+REF = ARGS[0] if ARGS else "/root/reference"
+SCRIPTED_SEED, SCRIPTED_ENVS = 7, 4
 GAME = {"TicTacToe-v1": "TicTacToe", "ConnectFour-v1": "ConnectFour", "Hex-v1": "Hex", "Othello-v1": "Othello"}
 ACTIONS = {"TicTacToe": 9, "ConnectFour": 7, "Hex": 122, "Othello": 65}
 # int32 words of the driver's hidden state per env
@@ -86,10 +98,14 @@ def build(tmp: str) -> str:
     return exe
 
 
-def rollout(exe: str, tmp: str, spec: dict, game: str, n: int, steps: int, permille: int, limit, seed: int) -> dict:
+def rollout(exe: str, tmp: str, spec: dict, game: str, n: int, steps: int, permille: int, limit, seed: int,
+            script=None) -> dict:
     d = tempfile.mkdtemp(dir=tmp)
     per_env = [0 if e < n // 2 else permille for e in range(n)]
     args = [exe, "run", game, d, str(n), str(steps), str(seed), str(10007 * seed + 1)] + [str(p) for p in per_env]
+    if script is not None:
+        np.ascontiguousarray(script, np.int32).tofile(os.path.join(d, "script.bin"))
+        args = [exe, "replay", game, d, str(n), str(steps), str(seed), os.path.join(d, "script.bin")]
     if limit is not None:
         args.append(f"max_episode_steps={limit}")
     subprocess.run(args, check=True)
@@ -174,7 +190,7 @@ def main() -> None:
             specs[tid] = json.loads(subprocess.run([exe, "spec", game], check=True, capture_output=True,
                                                    text=True).stdout)
         runs = {}
-        for name, tid, n, steps, permille, limit in FIXTURES:
+        for name, tid, n, steps, permille, limit in ([] if ONLY_SCRIPTED else FIXTURES):
             game = GAME[tid]
             want = wanted(game, limit is not None)
             for seed in range(1, 400):
@@ -188,11 +204,23 @@ def main() -> None:
                 raise SystemExit(f"{name}: no seed covers {sorted(want)}")
             print(f"{name}: seed {seed}, covers {sorted(got)}")
             runs[name] = g
-    json.dump(reg, open(os.path.join(HERE, "pgx_registry.json"), "w"), indent=1, sort_keys=True)
-    json.dump(specs, open(os.path.join(HERE, "pgx_spec.json"), "w"), indent=1)
+        for tid, game in GAME.items():
+            acts = pgx_scripted.script(game, SCRIPTED_SEED, SCRIPTED_ENVS)
+            g = rollout(exe, tmp, specs[tid], game, SCRIPTED_ENVS, len(acts), 0, None, SCRIPTED_SEED, script=acts)
+            assert np.array_equal(g["actions"], acts)
+            got = pgx_scripted.check(game, g)
+            print(f"{tid}__scripted: {len(acts)} steps x {SCRIPTED_ENVS} envs, covers",
+                  {k: (len(v) if isinstance(v, set) else v) for k, v in got.items() if v})
+            runs[f"{tid}__scripted"] = g
+    if not ONLY_SCRIPTED:
+        json.dump(reg, open(os.path.join(HERE, "pgx_registry.json"), "w"), indent=1, sort_keys=True)
+        json.dump(specs, open(os.path.join(HERE, "pgx_spec.json"), "w"), indent=1)
     for name, g in runs.items():
         np.savez_compressed(os.path.join(HERE, f"pgx_{name}.npz"), **g)
-
+    # a scripted fixture is no larger than the largest of the others
+    largest = max(os.path.getsize(os.path.join(HERE, f"pgx_{name}.npz")) for name, *_ in FIXTURES)
+    for tid in GAME:
+        assert os.path.getsize(os.path.join(HERE, f"pgx_{tid}__scripted.npz")) <= largest, tid
 
 if __name__ == "__main__":
     main()

@@ -13,6 +13,8 @@
 //
 //   driver spec <game>                                                  -> JSON config defaults + specs
 //   driver run <game> <out_dir> <n> <steps> <seed> <policy_seed> <illegal_permille_of_env>... max_episode_steps=<m>
+//   driver replay <game> <out_dir> <n> <steps> <seed> <actions_file> max_episode_steps=<m>
+//                 the same outputs for the int32 actions[steps][n] of the file instead of the online policy
 //   driver bench <game> <n> <threads> <steps>                           -> JSON env-steps/s of the reference's pool
 //
 // <game>: TicTacToe ConnectFour Hex Othello
@@ -21,6 +23,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -192,13 +195,24 @@ void Run(int argc, char** argv) {
   conf["num_threads"_] = 1;
   conf["max_num_players"_] = 2;
   conf["seed"_] = std::stoi(argv[6]);
-  std::mt19937 policy((uint32_t)std::stoul(argv[7]));
+  const bool replay = std::string(argv[1]) == "replay";
+  std::mt19937 policy(replay ? 0u : (uint32_t)std::stoul(argv[7]));
+  std::vector<int32_t> script;  // replay: actions[steps][n]
+  if (replay) {
+    script.resize((size_t)steps * n);
+    std::ifstream in(argv[7], std::ios::binary);
+    in.read(reinterpret_cast<char*>(script.data()), (std::streamsize)script.size() * 4);
+    if (in.gcount() != (std::streamsize)script.size() * 4) {
+      std::cerr << "short actions file " << argv[7] << "\n";
+      std::exit(2);
+    }
+  }
   std::vector<int> permille(n, 0);
   for (int i = 8; i < argc; ++i) {
     std::string a(argv[i]);
     if (a.rfind("max_episode_steps=", 0) == 0) {
       conf["max_episode_steps"_] = std::stoi(a.substr(18));
-    } else {
+    } else if (!replay) {
       permille[i - 8] = std::stoi(a);
     }
   }
@@ -248,7 +262,7 @@ void Run(int argc, char** argv) {
     for (int e = 0; e < n; ++e) {
       bool m[Env::kActions];
       for (int j = 0; j < Env::kActions; ++j) m[j] = mask[e][j] != 0;
-      a[e] = Pick<Env>(policy, m, permille[e]);
+      a[e] = replay ? script[(size_t)t * n + e] : Pick<Env>(policy, m, permille[e]);
     }
     std::vector<Array> raw({Array(::Spec<int>({n})), Array(::Spec<int>({n})), Array(::Spec<int>({n}))});
     std::memcpy(raw[0].Data(), all.data(), 4 * n);
@@ -315,7 +329,7 @@ int Main(int argc, char** argv) {
     DumpSpec<Env>();
   } else if (cmd == "bench" && argc >= 6) {
     Bench<Env>(std::stoi(argv[3]), std::stoi(argv[4]), std::stoi(argv[5]));
-  } else if (cmd == "run" && argc >= 8) {
+  } else if ((cmd == "run" || cmd == "replay") && argc >= 8) {
     Run<Env>(argc, argv);
   } else {
     return 2;

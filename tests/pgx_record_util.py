@@ -14,6 +14,9 @@ NSYM = {"TicTacToe": 8, "ConnectFour": 2, "Hex": 2, "Othello": 8}
 # asserts them): TicTacToe, ConnectFour, Hex, Othello
 GAMES = {"TicTacToe-v1": (191, 1084), "ConnectFour-v1": (303, 5196), "Hex-v1": (48, 3565), "Othello-v1": (137, 6859)}
 TRUNC_GAMES = {"TicTacToe-v1__trunc": 16, "ConnectFour-v1__trunc": 13, "Hex-v1__trunc": 3, "Othello-v1__trunc": 8}
+# the scripted fixtures: (finished games, their plies), the fixtures' done rows and the elapsed steps at them
+SCRIPTED_GAMES = {"TicTacToe-v1__scripted": (20, 121), "ConnectFour-v1__scripted": (79, 1814),
+                  "Hex-v1__scripted": (39, 314), "Othello-v1__scripted": (14, 586)}
 
 
 def bits(a):

@@ -114,6 +114,8 @@ def test_whole_fixture_against_the_restatement_and_the_fixture(lib, name):
     want, (games, plies) = R.fixture_samples(name, id_offset=5)
     if name in R.GAMES:
         assert (games, plies) == R.GAMES[name]
+    elif name in R.SCRIPTED_GAMES:
+        assert (games, plies) == R.SCRIPTED_GAMES[name]
     else:
         assert games == R.TRUNC_GAMES[name]
     assert host.counters() == model.counters == dict(samples=plies, games=games, dropped_games=0, dropped_plies=0)
