@@ -656,6 +656,33 @@ class _ShardedPools:
     def selfplay_end(self) -> None:
         self._record_all(lambda p: p.selfplay_end())
 
+    # -- arena: one per shard; the sides take GLOBAL env ids (every shard knows its offset), so the shards play the
+    # unsharded pool's match.  selfplay_run and selfplay_end above drive and close it --
+    def arena_begin(self, net_a: Any, net_b: Any, **options: Any) -> None:
+        native.check_arena(net_a, net_b, **options)
+        for device in sorted({p.device for p in self.pools}):
+            net_a._handle(device)  # one copy of each net per device, made before the shards ask for them at once
+            net_b._handle(device)
+        self._record_all(lambda p: p.arena_begin(net_a, net_b, **options))
+
+    def arena_run(self, plies: int, wait: bool = True) -> None:
+        self.selfplay_run(plies, wait)
+
+    def arena_stats(self) -> np.ndarray:
+        """The shards' statistics added up; t is every shard's."""
+        parts = self._record_all(lambda p: p.arena_stats())
+        out = np.sum(parts, axis=0)
+        out[7] = parts[0][7]
+        return out
+
+    def arena_end(self) -> None:
+        self.selfplay_end()
+
+    def net_eval_pair(self, net_a: Any, net_b: Any, obs: Any, mask: Any, status: Any, side: Any,
+                      priors: bool = False) -> tuple:
+        """`DevicePool.net_eval_pair` on the first shard: the rows are positions, whichever shard holds their envs."""
+        return self.pools[0].net_eval_pair(net_a, net_b, obs, mask, status, side, priors)
+
     def close(self) -> None:
         self._exec.shutdown(wait=True)
         for p in self.pools:

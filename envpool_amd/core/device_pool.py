@@ -1011,6 +1011,59 @@ class DevicePool:
         native.check(self._lib.epa_selfplay_end(self._h))
         self._selfplay_net = None
 
+    # -- arena (csrc/pgx_arena.hip.h) ---------------------------------------------------
+    def net_eval_pair(self, net_a: Any, net_b: Any, obs: Any, mask: Any, status: Any, side: Any,
+                      priors: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """`net_eval` with two networks (epa_net_eval_pair): row r is evaluated by `net_a` where `side[r]` is 0 and
+        by `net_b` where it is 1, grouped by net on the device and evaluated in one launch.  Every row gets exactly
+        what `net_eval` of its net gives it."""
+        native.check_arena(net_a, net_b)
+        obs, mask, status = self._net_rows("net_eval_pair", obs, mask, status)
+        side = native.check_arena_side(side, len(status))
+        a = self.guided_shape()[3]
+        policy, value = np.empty((len(status), a), dtype=np.float32), np.empty(len(status), dtype=np.float32)
+        native.check(self._lib.epa_net_eval_pair(
+            self._h, net_a._handle(self.device), net_b._handle(self.device), len(status), 1 if priors else 0,
+            obs.ctypes.data, mask.ctypes.data, status.ctypes.data, side.ctypes.data, policy.ctypes.data,
+            value.ctypes.data))
+        return policy, value
+
+    def net_eval_pair_device(self, net_a: Any, net_b: Any, rows: int, priors: bool, d_obs: int, d_mask: int,
+                             d_status: int, d_side: int, d_policy: int, d_value: int) -> None:
+        """`net_eval_pair` on device memory at raw addresses (policy and value 4-byte aligned; a side byte that is not
+        0 counts as 1): only enqueued on the pool's stream."""
+        native.check_arena(net_a, net_b)
+        self.guided_shape()
+        native.check(self._lib.epa_net_eval_pair_device(
+            self._h, net_a._handle(self.device), net_b._handle(self.device), int(rows), 1 if priors else 0,
+            ctypes.c_void_p(d_obs), ctypes.c_void_p(d_mask), ctypes.c_void_p(d_status), ctypes.c_void_p(d_side),
+            ctypes.c_void_p(d_policy), ctypes.c_void_p(d_value)))
+
+    def arena_begin(self, net_a: Any, net_b: Any, **options: Any) -> None:
+        """Opens the pool's driver as an arena (epa_arena_begin): `net_a` moves for seat (e & 1) of the env with global
+        id e and `net_b` for the other seat.  `options` are `native.check_arena`'s: `selfplay_begin`'s, with `record`
+        False by default.  `selfplay_run` and `selfplay_end` drive and close it."""
+        o = native.check_arena(net_a, net_b, **options)
+        self.guided_shape()
+        native.check(self._lib.epa_arena_begin(self._h, net_a._handle(self.device), net_b._handle(self.device),
+                                               ctypes.byref(o)))
+        self._selfplay_net = (net_a, net_b)  # (the driver uses the nets' device copies: they must live as long)
+
+    def arena_run(self, plies: int, wait: bool = True) -> None:
+        """`selfplay_run` of an arena."""
+        self.selfplay_run(plies, wait)
+
+    def arena_stats(self) -> np.ndarray:
+        """int64 [8]: games, wins0, wins1, draws, plies, wins_a, wins_b, t since the arena was opened; waits for the
+        device.  ValueError on a driver that is no arena."""
+        out = np.zeros(8, dtype=np.int64)
+        native.check(self._lib.epa_arena_stats(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def arena_end(self) -> None:
+        """`selfplay_end` of an arena."""
+        self.selfplay_end()
+
     def _ids(self, env_ids: Any) -> np.ndarray:
         if env_ids is None:
             return np.arange(

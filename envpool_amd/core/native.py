@@ -189,6 +189,10 @@ def lib() -> ctypes.CDLL:
         "epa_selfplay_run_device": (i32, [vp, i32]),
         "epa_selfplay_stats": (i32, [vp, P(ctypes.c_int64)]),
         "epa_selfplay_end": (i32, [vp]),
+        "epa_net_eval_pair": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "epa_net_eval_pair_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "epa_arena_begin": (i32, [vp, vp, vp, P(SelfplayOptions)]),
+        "epa_arena_stats": (i32, [vp, P(ctypes.c_int64)]),
         "epa_record_begin": (i32, [vp, i32, i32, ctypes.c_uint32]),
         "epa_record_shape": (i32, [vp, P(i32)]),
         "epa_record_add": (i32, [vp, vp, i32, vp]),
@@ -249,6 +253,7 @@ EXPORTED_SYMBOLS = [
     "epa_record_finish_device", "epa_record_drain", "epa_record_view_device", "epa_record_clear",
     "epa_record_discard", "epa_record_counters", "epa_record_end",
     "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
+    "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -631,6 +636,37 @@ def check_selfplay(policy: Any = "gumbel", simulations: Any = 32, max_considered
     o.policy, o.c_puct, o.width, o.tactics, o.tactics_nodes = SELFPLAY_PUCT, float(c), (w if w > 1 else 0), t, tn
     o.prove, o.sample_plies = int(check_guided_prove(prove)), int(sample_plies)
     return o
+
+
+ARENA_MAX_ROWS = 1 << 20  # rows of one pair evaluation (csrc/pgx_arena.hip.h: kArenaMaxRows)
+
+
+def check_arena(net_a: Any, net_b: Any, record: Any = False, **options: Any) -> SelfplayOptions:
+    """The options of an arena_begin call as the C struct, after the checks every layer makes before the native call:
+    ValueError for a net that is no `envpool_amd.pgx.net.Net`, for two nets that differ in inputs (F) or actions (A) --
+    hidden width and blocks may differ --, and for everything `check_selfplay` refuses.  `record` defaults to False."""
+    for name, net in (("net_a", net_a), ("net_b", net_b)):
+        if not getattr(net, "_is_epa_net", False):
+            raise ValueError(f"arena: {name} must be an envpool_amd.pgx.net.Net")
+    if int(net_a.inputs) != int(net_b.inputs) or int(net_a.actions) != int(net_b.actions):
+        raise ValueError(f"arena: net_a has F = {int(net_a.inputs)}, A = {int(net_a.actions)} and net_b F = "
+                         f"{int(net_b.inputs)}, A = {int(net_b.actions)}: the two nets must agree in both")
+    return check_selfplay(record=record, **options)
+
+
+def check_arena_side(side: Any, rows: int) -> np.ndarray:
+    """The side bytes of a host-form net_eval_pair call as a contiguous uint8 array [rows]: ValueError for another
+    length, for more than 2^20 rows and for a value other than 0 (net_a) or 1 (net_b)."""
+    side = np.asarray(side)
+    if side.dtype == np.bool_:
+        side = side.astype(np.uint8)
+    if side.ndim != 1 or len(side) != rows:
+        raise ValueError(f"net_eval_pair: side has shape {side.shape} for {rows} rows")
+    if rows > ARENA_MAX_ROWS:
+        raise ValueError(f"net_eval_pair: rows = {rows} must be 1 .. {ARENA_MAX_ROWS}")
+    if not np.issubdtype(side.dtype, np.integer) or not ((side == 0) | (side == 1)).all():
+        raise ValueError("net_eval_pair: side must be 0 (net_a) or 1 (net_b) in every row")
+    return np.ascontiguousarray(side, dtype=np.uint8)
 
 
 def check_selfplay_plies(plies: Any) -> int:

@@ -386,10 +386,21 @@ void NetBuildImage(const void* blob, size_t bytes, NetImage* out);
 void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, const unsigned char* obs,
                const unsigned char* mask, const unsigned char* status, float* policy, float* value,
                unsigned int* pending, hipStream_t stream);
+// The pair form (pgx_arena.hip.h).  NetPlanLaunch: PgxNetPlan, the stable partition of `rows` <= 2^20 rows by `side` u8
+// [rows] into order i32 [rows] and n0 i32 [1], with `counts` (NetPlanCountBytes(rows) bytes) as its scratch.
+// NetLaunchPair: one pair PgxNetEval, row r by net side[r] through that plan; both nets of one F and A.
+constexpr int kNetPlanMaxRows = 1 << 20;  // pgx::kArenaMaxRows
+size_t NetPlanCountBytes(size_t rows);
+void NetPlanLaunch(int rows, const unsigned char* side, int32_t* counts, int32_t* order, int32_t* n0,
+                   hipStream_t stream);
+void NetLaunchPair(const NetImage& im_a, const char* d_image_a, const NetImage& im_b, const char* d_image_b, int rows,
+                   int mode, const int32_t* order, const int32_t* n0, const unsigned char* obs,
+                   const unsigned char* mask, const unsigned char* status, float* policy, float* value,
+                   unsigned int* pending, hipStream_t stream);
 
 // A network on a device (epa_net_create): it belongs to the device, not to a pool, and owns ONE device allocation --
-// the image, the pending word, and the policy / value rows its evaluations inside epa_net_run and the host forms
-// write, grown to the largest `rows` seen.  Calls on one net are the caller's to serialise, as a pool's session is.
+// the image, the pending word, the policy / value rows its evaluations inside epa_net_run and the host forms write,
+// and the plan (order, counts, n0) of the pair evaluations it leads as net A, grown to the largest `rows` seen.  Calls on one net are the caller's to serialise, as a pool's session is.
 class Net {
  public:
   Net(int device, const void* blob, size_t bytes);
@@ -399,7 +410,10 @@ class Net {
   const char* d_image() const { return mem_.p; }
   unsigned int* pending() const { return reinterpret_cast<unsigned int*>(mem_.p + image_.bytes.size()); }
   float* value() const { return reinterpret_cast<float*>(mem_.p + image_.bytes.size() + 256); }
-  float* policy() const { return value() + ((rows_ + 63) & ~(size_t)63); }
+  float* policy() const { return value() + rows_; }  // (rows_ is a multiple of 64)
+  int32_t* plan_n0() const { return reinterpret_cast<int32_t*>(mem_.p + image_.bytes.size() + 64); }
+  int32_t* plan_order() const { return reinterpret_cast<int32_t*>(policy() + rows_ * (size_t)image_.A); }
+  int32_t* plan_counts() const { return plan_order() + rows_; }
 
  private:
   int device_;
@@ -428,7 +442,10 @@ struct SelfplayArgs {
   const unsigned char* done;    // tally: the step's result block
   const float* reward;          // [k][2]
   const int32_t* elapsed;       // [k]
-  long long* counters;          // tally: [5], 8-byte aligned
+  long long* counters;          // tally: [5] (an arena: [7]), 8-byte aligned
+  int arena;                    // tally: 0 / 1, the seven counters of pgx_arena.hip.h
+  int slots;                    // arena sides: leaf rows per env
+  unsigned char* side;          // arena sides: [k * slots] out
 };
 
 // What a driver is opened with (include/envpool_amd.h: epa_selfplay_options)
@@ -436,7 +453,7 @@ using SelfplayOptions = epa_selfplay_options;
 // The driver's kernels (pgx_selfplay.hip) for PGX game `game` (pgx::kTicTacToe ...), one launch each on `stream`
 void PgxSelfplayLaunchNoise(int game, const SelfplayArgs& a, hipStream_t stream);
 void PgxSelfplayLaunchMove(int game, const SelfplayArgs& a, hipStream_t stream);
-void PgxSelfplayLaunchTally(const SelfplayArgs& a, hipStream_t stream);
+void PgxSelfplayLaunchTally(const SelfplayArgs& a, hipStream_t stream);  // (a.arena: PgxArenaTally)
 
 class Pool {
  public:
@@ -644,6 +661,14 @@ class Pool {
   void NetEvalCall(Net& net, int rows, int mode, const void* obs, const void* mask, const void* status, void* policy,
                    void* value, bool device);
   int NetRunCall(Net& net, int advances, void* obs, void* mask, void* status, bool device);
+  // The pair forms (pgx_arena.hip.h): row r is evaluated by net_a where side[r] == 0 and by net_b where it is 1; both
+  // nets pass NetRequire and so agree in F and A.  NetEvalPairCall: PgxNetPlan + one pair PgxNetEval of `rows` <= 2^20
+  // caller rows with the caller's side bytes (host form: a byte other than 0 / 1 is refused; staged like
+  // NetEvalCall's).  NetRunPairCall: NetRunCall's device form with `side` u8 device memory, one byte per leaf row,
+  // fixed for the call: the plan is made once, and policy / value rows and the plan live in net_a's allocation.
+  void NetEvalPairCall(Net& net_a, Net& net_b, int rows, int mode, const void* obs, const void* mask,
+                       const void* status, const void* side, void* policy, void* value, bool device);
+  int NetRunPairCall(Net& net_a, Net& net_b, int advances, void* obs, void* mask, void* status, const void* side);
 
   // Self-play recorder (include/envpool_amd.h: epa_record_begin; the PGX board games, pgx_record.hip.h): stages every
   // env's positions and policy targets while its game runs and turns a finished game into training samples in a
@@ -687,13 +712,18 @@ class Pool {
   // partway has enqueued its earlier plies and part of one more (a recorder add without its finish) and does not
   // count the partial ply in t: the driver must be closed after an error.  A family without the hooks
   // keeps the defaults, and begin throws as the guided and recorder calls do.
+  // The ARENA is a mode of this one driver (pgx_arena.hip.h): SelfplayBegin with a second net.  A ply then writes the
+  // side bytes of its leaf rows after the session's begin (ArenaSides), NetRunPairCall stands in place of NetRunCall,
+  // and the tally keeps seven counters; everything else is the same calls.
   virtual bool HasSelfplay() const { return false; }
   virtual void SelfplayNoise(const SelfplayArgs& a);
   virtual void SelfplayMove(const SelfplayArgs& a);
   virtual void SelfplayTally(const SelfplayArgs& a);
-  void SelfplayBegin(Net& net, const SelfplayOptions& o);
+  virtual void ArenaSides(const SelfplayArgs& a);
+  void SelfplayBegin(Net& net, const SelfplayOptions& o, Net* net_b = nullptr, const char* what = "selfplay_begin");
   void SelfplayRun(int plies, bool device);
   void SelfplayStats(int64_t out[6]);  // games, wins0, wins1, draws, plies, t
+  void ArenaStats(int64_t out[8]);     // games, wins0, wins1, draws, plies, wins_a, wins_b, t: an arena only
   void SelfplayEnd();
 
  protected:
@@ -959,14 +989,18 @@ class Pool {
     bool open{false};
     DeviceBlock mem;        // the driver's one device allocation, in the order of `off`
     Net* net{nullptr};
+    Net* net_b{nullptr};    // an arena: the net of side 1
     SelfplayOptions o{};
     uint32_t t{0};          // the ply counter
     std::vector<int32_t> ids;  // the pool's global ids in order
     // offsets into mem: noise, obs, mask, status (the leaf arrays, one row per root or slot), visits, vals, result
-    // action, weights, the action row, the target rows, the counters (64 bytes), the end
-    size_t off[12]{};
+    // action, weights, the action row, the target rows, the counters (64 bytes), the side bytes (an arena: one per
+    // leaf row), the end
+    size_t off[13]{};
   };
   Selfplay selfplay_;
+  int NetRunImpl(Net& net, Net* net_b, int advances, void* obs, void* mask, void* status, const void* side,
+                 bool device, const char* what);        // NetRunCall and NetRunPairCall
   void SelfplayFree();                                  // (no driver: nothing)
   void SelfplayPly();                                   // one ply, enqueued
   uint64_t family_hash_{0};

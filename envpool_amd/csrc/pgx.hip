@@ -40,6 +40,7 @@
 
 #include "device_common.hip.h"
 #include "engine.h"
+#include "pgx_arena.hip.h"
 #include "pgx_env.hip.h"
 #include "pgx_guided.hip.h"
 #include "pgx_gumbel.hip.h"
@@ -1690,6 +1691,16 @@ __global__ __launch_bounds__(kSearchBlock) void PgxRecordEmit(const int* __restr
   }
 }
 
+// An arena's side bytes (pgx_arena.hip.h): one thread per env, row i is local env i; the env's `slots` leaf rows get the
+// net of its root's mover.  (The state of an env that is over is whatever it was: its rows are idle and never read.)
+template <int G>
+__global__ __launch_bounds__(kBlock) void PgxArenaSides(const pgx::State* __restrict__ st, SelfplayArgs a) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.k) return;
+  const unsigned char side = (unsigned char)pgx::ArenaNetOf(i + a.id_offset, pgx::SearchMover<G>(st[i]));
+  for (int j = 0; j < a.slots; ++j) a.side[(size_t)i * a.slots + j] = side;
+}
+
 // the render kernel's painter of game G (render_kernel.hip.h)
 template <int G>
 struct PgxPainter {
@@ -1870,6 +1881,9 @@ class PgxPool : public Pool {
     PgxSelfplayLaunchMove(G, b, stream_);
   }
   void SelfplayTally(const SelfplayArgs& a) override { PgxSelfplayLaunchTally(a, stream_); }
+  void ArenaSides(const SelfplayArgs& a) override {
+    hipLaunchKernelGGL(PgxArenaSides<G>, dim3((a.k + kBlock - 1) / kBlock), dim3(kBlock), 0, stream_, state_, a);
+  }
   std::string ErrorText(unsigned code) const override {
     if (code == kErrGuided) return "PGX: guided search met a position that is no position of the game";
     if (code == kErrGumbel) return "PGX: gumbel search met a position that is no position of the game";

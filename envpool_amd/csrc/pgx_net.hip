@@ -16,6 +16,18 @@
 // (LDS as an indexed register file: no barrier), 2 KiB per 32 neurons and wave.  The head's int32 results go through
 // LDS once to turn them from (neuron in register, row on lane) to one row per lane for NetOutputs -- the one
 // barrier pair --, and the float rows leave in coalesced stores.  Weights are read from global memory (L2).
+//
+// The pair form (pgx_arena.hip.h is the contract; DESIGN.md "PGX arena"): PgxNetEval<true> takes two networks, the plan
+// `order` / `n0` of PgxNetPlan and one wave more than the single form.  A wave finds its net and its entries of the plan
+// with ArenaWaveOf, gathers its two row tiles through `order`, runs that net's layers and stores each row's value and
+// policy back to the row's own place, A floats in a run.  The weights being the A operand, a wave serves one net: the
+// plan is what puts rows of one net side by side.  Lanes past the wave's entries load nothing and store nothing but
+// stay in every MFMA and barrier.
+//
+// PgxNetPlan: the stable partition of the rows by side in two launches of single-wave blocks, 256 rows per wave as four
+// ballots.  PgxNetPlanCount leaves each block's number of side-0 rows; PgxNetPlanPlace adds up the counts of the blocks
+// in front of its own (lane l the counts l, l + 64, .., then a butterfly: the scan across blocks), takes a row's place
+// inside the wave from the popcount of the ballot below its lane, and scatters the row index.  No atomics, no LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +36,7 @@
 #include <string>
 
 #include "engine.h"
+#include "pgx_arena.hip.h"
 #include "pgx_net.hip.h"
 
 namespace epa {
@@ -87,7 +100,22 @@ __device__ inline void NetLayerTiles(const v4i* __restrict__ w, const int32_t* _
   }
 }
 
-__global__ __launch_bounds__(kWave) void PgxNetEval(NetDev net, int rows, int mode,
+// The kernel's networks: indexed by the wave's net, which is uniform, so the fields stay scalar loads from the kernel
+// arguments (two separate arguments chosen by a select would be copied to scratch)
+struct NetPair {
+  NetDev n[2];
+};
+
+// The plan of a pair evaluation (null and unused in the single form)
+struct NetPlan {
+  const int32_t* order;  // [rows]
+  const int32_t* n0;
+};
+
+// PAIR: nets.n[1] and plan are read, and the wave's rows are its entries of the plan; otherwise rows row0 .. row0 + 63.
+// A row past the wave's share is `rows`, which every `< rows` test below turns away.
+template <bool PAIR>
+__global__ __launch_bounds__(kWave) void PgxNetEval(NetPair nets, NetPlan plan, int rows, int mode,
                                                      const unsigned char* __restrict__ obs,
                                                      const unsigned char* __restrict__ mask,
                                                      const unsigned char* __restrict__ status,
@@ -95,9 +123,16 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetDev net, int rows, int mo
                                                      unsigned int* pending) {
   extern __shared__ v4i lds[];
   const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
-  const int row0 = blockIdx.x * kRowsPerWave;
+  pgx::ArenaWave wave{0, (int)blockIdx.x * kRowsPerWave, 0};
+  if constexpr (PAIR) {
+    wave = pgx::ArenaWaveOf((int)blockIdx.x, rows, *plan.n0);
+    if (wave.count == 0) return;  // (the whole wave, before any barrier)
+  }
+  const NetDev& net = nets.n[PAIR ? wave.net : 0];
+  const int row0 = wave.first;
   const int F = net.F, A = net.A, d_tiles = net.D / 32, f_tiles = (F + 31) / 32, a_tiles = (A + 1 + 31) / 32;
-  const int my_row = row0 + lane;
+  int my_row = row0 + lane;
+  if constexpr (PAIR) my_row = lane < wave.count ? plan.order[row0 + lane] : rows;
   const int my_status = my_row < rows ? (int)status[my_row] : kGuidedIdle;
   // the run loop's word: some row of the call is not idle (an ordinary atomic of one lane per wave)
   const bool wave_pending = __any(my_status != kGuidedIdle) != 0;
@@ -113,7 +148,8 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetDev net, int rows, int mo
     const bool words = (F & 3) == 0 && (reinterpret_cast<uintptr_t>(obs) & 3) == 0;
     for (int kt = 0; kt < f_tiles; ++kt) {
       for (int rt = 0; rt < 2; ++rt) {
-        const int row = row0 + 32 * rt + r;
+        int row = row0 + 32 * rt + r;
+        if constexpr (PAIR) row = __shfl(my_row, 32 * rt + r, kWave);
         v4i frag = {0, 0, 0, 0};
         if (row < rows) {
           const unsigned char* x = obs + (size_t)row * F;
@@ -173,9 +209,72 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetDev net, int rows, int mo
   }
   __syncthreads();
   if (my_row < rows) value[my_row] = pgx::NetBitsFloat(rows_io[lane * stride + A]);
-  const int n_rows = rows - row0 < kRowsPerWave ? rows - row0 : kRowsPerWave;
-  for (int i = lane; i < n_rows * A; i += kWave) {
-    policy[(size_t)row0 * A + i] = pgx::NetBitsFloat(rows_io[(i / A) * stride + i % A]);
+  if constexpr (PAIR) {
+    // entry e's A floats go to its row's own place: consecutive lanes, consecutive floats of a run
+    for (int i = lane; i < wave.count * A; i += kWave) {
+      const int e = i / A, a = i - e * A;
+      policy[(size_t)plan.order[row0 + e] * A + a] = pgx::NetBitsFloat(rows_io[e * stride + a]);
+    }
+  } else {
+    const int n_rows = rows - row0 < kRowsPerWave ? rows - row0 : kRowsPerWave;
+    for (int i = lane; i < n_rows * A; i += kWave) {
+      policy[(size_t)row0 * A + i] = pgx::NetBitsFloat(rows_io[(i / A) * stride + i % A]);
+    }
+  }
+}
+
+constexpr int kPlanChunk = 4;                     // ballots of a wave
+constexpr int kPlanRows = kPlanChunk * kWave;     // rows of a wave of the plan
+static_assert(pgx::kArenaMaxRows == kNetPlanMaxRows && pgx::kArenaMaxRows % kPlanRows == 0, "engine.h: a plan's rows");
+
+// side-0 rows of block b's rows (every lane gets the sum), and the ballot of each of its chunks
+__device__ inline int PlanBallots(const unsigned char* __restrict__ side, int rows, int lane,
+                                  unsigned long long zero[kPlanChunk]) {
+  int count = 0;
+#pragma unroll
+  for (int c = 0; c < kPlanChunk; ++c) {
+    const int row = (int)blockIdx.x * kPlanRows + c * kWave + lane;
+    zero[c] = __ballot(row < rows && side[row] == 0);
+    count += __popcll(zero[c]);
+  }
+  return count;
+}
+
+__global__ __launch_bounds__(kWave) void PgxNetPlanCount(const unsigned char* __restrict__ side, int rows,
+                                                          int32_t* __restrict__ counts) {
+  unsigned long long zero[kPlanChunk];
+  const int count = PlanBallots(side, rows, threadIdx.x, zero);
+  if (threadIdx.x == 0) counts[blockIdx.x] = count;
+}
+
+__global__ __launch_bounds__(kWave) void PgxNetPlanPlace(const unsigned char* __restrict__ side, int rows,
+                                                          const int32_t* __restrict__ counts,
+                                                          int32_t* __restrict__ order, int32_t* __restrict__ n0_out) {
+  const int lane = threadIdx.x, b = blockIdx.x, blocks = gridDim.x;
+  int before = 0, all = 0;  // the side-0 rows of the blocks in front of this one, and of all blocks
+  for (int j = lane; j < blocks; j += kWave) {
+    const int c = counts[j];
+    before += j < b ? c : 0;
+    all += c;
+  }
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) {
+    before += __shfl_xor(before, w, kWave);
+    all += __shfl_xor(all, w, kWave);
+  }
+  if (b == 0 && lane == 0) *n0_out = all;
+  unsigned long long zero[kPlanChunk];
+  PlanBallots(side, rows, lane, zero);
+  int below0 = before;  // the side-0 rows below the chunk
+#pragma unroll
+  for (int c = 0; c < kPlanChunk; ++c) {
+    const int row = b * kPlanRows + c * kWave + lane;
+    const unsigned long long mine = 1ull << lane;
+    if (row < rows) {
+      const int s = (zero[c] & mine) != 0 ? 0 : 1;
+      order[pgx::ArenaPlace(s, row, below0 + __popcll(zero[c] & (mine - 1)), all)] = row;
+    }
+    below0 += __popcll(zero[c]);
   }
 }
 
@@ -223,9 +322,8 @@ void NetBuildImage(const void* blob, size_t bytes, NetImage* out) {
   out->bytes.resize((out->bytes.size() + 255) & ~(size_t)255, 0);
 }
 
-void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, const unsigned char* obs,
-               const unsigned char* mask, const unsigned char* status, float* policy, float* value,
-               unsigned int* pending, hipStream_t stream) {
+namespace {
+NetDev DevOf(const NetImage& im, const char* d_image) {
   NetDev net{};
   net.F = im.F, net.A = im.A, net.D = im.D, net.L = im.L;
   net.scale_p = im.scale_p, net.scale_v = im.scale_v;
@@ -233,14 +331,48 @@ void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, cons
   for (int i = 0; i < im.layers; ++i) {
     net.w_off[i] = im.w_off[i], net.b_off[i] = im.b_off[i], net.shift[i] = im.shift[i];
   }
+  return net;
+}
+}  // namespace
+
+void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, const unsigned char* obs,
+               const unsigned char* mask, const unsigned char* status, float* policy, float* value,
+               unsigned int* pending, hipStream_t stream) {
+  NetPair nets{};
+  nets.n[0] = DevOf(im, d_image);
   const size_t lds = LdsBytes(im.F, im.A, im.D);
   if (lds > 48 * 1024) {
-    EPA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&PgxNetEval), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
+    EPA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&PgxNetEval<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   const int blocks = (rows + kRowsPerWave - 1) / kRowsPerWave;
-  hipLaunchKernelGGL(PgxNetEval, dim3(blocks), dim3(kWave), lds, stream, net, rows, mode, obs, mask, status, policy,
-                     value, pending);
+  hipLaunchKernelGGL(PgxNetEval<false>, dim3(blocks), dim3(kWave), lds, stream, nets, NetPlan{nullptr, nullptr},
+                     rows, mode, obs, mask, status, policy, value, pending);
+}
+
+size_t NetPlanCountBytes(size_t rows) { return 4 * ((rows + kPlanRows - 1) / kPlanRows); }
+
+void NetPlanLaunch(int rows, const unsigned char* side, int32_t* counts, int32_t* order, int32_t* n0,
+                   hipStream_t stream) {
+  const int blocks = (rows + kPlanRows - 1) / kPlanRows;
+  hipLaunchKernelGGL(PgxNetPlanCount, dim3(blocks), dim3(kWave), 0, stream, side, rows, counts);
+  hipLaunchKernelGGL(PgxNetPlanPlace, dim3(blocks), dim3(kWave), 0, stream, side, rows, counts, order, n0);
+}
+
+void NetLaunchPair(const NetImage& im_a, const char* d_image_a, const NetImage& im_b, const char* d_image_b, int rows,
+                   int mode, const int32_t* order, const int32_t* n0, const unsigned char* obs,
+                   const unsigned char* mask, const unsigned char* status, float* policy, float* value,
+                   unsigned int* pending, hipStream_t stream) {
+  // (the larger of the two nets: a wave of either fits)
+  const size_t lds = std::max(LdsBytes(im_a.F, im_a.A, im_a.D), LdsBytes(im_b.F, im_b.A, im_b.D));
+  if (lds > 48 * 1024) {
+    EPA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&PgxNetEval<true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  NetPair nets{};
+  nets.n[0] = DevOf(im_a, d_image_a), nets.n[1] = DevOf(im_b, d_image_b);
+  hipLaunchKernelGGL(PgxNetEval<true>, dim3(pgx::ArenaWaves(rows)), dim3(kWave), lds, stream, nets, NetPlan{order, n0},
+                     rows, mode, obs, mask, status, policy, value, pending);
 }
 
 }  // namespace epa

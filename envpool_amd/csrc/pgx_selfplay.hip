@@ -12,11 +12,13 @@
 //                     (visits, lowest action) maximum, both by a __shfl_xor butterfly inside the group.  Every lane
 //                     stays active through the shuffles; loads and stores are predicated.  Integers only.
 //   PgxSelfplayTally  one thread per row, a wave butterfly over the five integers, then lane 0's atomics on the
-//                     int64 counters (a wave that saw no finished game adds nothing).
+//                     int64 counters (a wave that saw no finished game adds nothing).  <true>, an arena's: the seven
+//                     counters of pgx_arena.hip.h, wins_a and wins_b by the parity of the row's global env id.
 #include <algorithm>
 #include <climits>
 
 #include "engine.h"
+#include "pgx_arena.hip.h"
 #include "pgx_env.hip.h"
 #include "pgx_selfplay.hip.h"
 
@@ -115,19 +117,30 @@ __global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayMove(SelfplayArgs a
   }
 }
 
+// ARENA: the seven counters of pgx_arena.hip.h (PgxArenaTally in the documents)
+template <bool ARENA>
 __global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayTally(SelfplayArgs a) {
+  constexpr int N = ARENA ? pgx::kArenaCounters : pgx::kSelfplayCounters;
   const int i = blockIdx.x * kSelfplayBlock + threadIdx.x;
-  int c[pgx::kSelfplayCounters] = {0, 0, 0, 0, 0};
-  if (i < a.k) pgx::SelfplayTallyRow(a.done[i] != 0, a.reward[2 * (size_t)i], a.reward[2 * (size_t)i + 1], a.elapsed[i], c);
+  int c[N] = {};
+  if (i < a.k) {
+    const bool done = a.done[i] != 0;
+    const float r0 = a.reward[2 * (size_t)i], r1 = a.reward[2 * (size_t)i + 1];
+    if constexpr (ARENA) {
+      pgx::ArenaTallyRow(done, r0, r1, a.elapsed[i], i + a.id_offset, c);
+    } else {
+      pgx::SelfplayTallyRow(done, r0, r1, a.elapsed[i], c);
+    }
+  }
 #pragma unroll
   for (int w = 32; w >= 1; w >>= 1) {
 #pragma unroll
-    for (int q = 0; q < pgx::kSelfplayCounters; ++q) c[q] += __shfl_xor(c[q], w, 64);
+    for (int q = 0; q < N; ++q) c[q] += __shfl_xor(c[q], w, 64);
   }
   if ((threadIdx.x & 63) == 0 && c[0] != 0) {
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(a.counters);
 #pragma unroll
-    for (int q = 0; q < pgx::kSelfplayCounters; ++q) {
+    for (int q = 0; q < N; ++q) {
       if (c[q] != 0) atomicAdd(&ctr[q], (unsigned long long)c[q]);
     }
   }
@@ -172,7 +185,11 @@ void PgxSelfplayLaunchMove(int game, const SelfplayArgs& a, hipStream_t stream) 
 }
 
 void PgxSelfplayLaunchTally(const SelfplayArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(PgxSelfplayTally, dim3(Blocks(a.k)), dim3(kSelfplayBlock), 0, stream, a);
+  if (a.arena != 0) {
+    hipLaunchKernelGGL(PgxSelfplayTally<true>, dim3(Blocks(a.k)), dim3(kSelfplayBlock), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(PgxSelfplayTally<false>, dim3(Blocks(a.k)), dim3(kSelfplayBlock), 0, stream, a);
+  }
 }
 
 }  // namespace epa

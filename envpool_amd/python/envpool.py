@@ -188,6 +188,59 @@ class Selfplay:
             pool.selfplay_end()
 
 
+class ArenaStats(NamedTuple):
+    """What an arena has played since it was opened (`Arena.run`, `Arena.stats`): `Stats`, and the wins by net.
+    `wins_a + wins_b + draws == games`; Elo or confidence arithmetic on them is the caller's."""
+
+    games: int   # finished games
+    wins0: int   # ... whose last reward was positive for seat 0
+    wins1: int   # ... for seat 1
+    draws: int   # ... with both rewards 0
+    plies: int   # the sum of the finished games' lengths (elapsed steps)
+    wins_a: int  # ... whose last reward was positive for net_a's seat (seat e & 1 of the env with global id e)
+    wins_b: int  # ... for net_b's seat
+    t: int       # the driver's ply counter: plies played per env, resets included
+
+
+class Arena:
+    """A pool's arena (`env.arena`): the self-play driver with two networks, which play each other in every env --
+    `net_a` holds seat 0 of the envs with an even global id and seat 1 of those with an odd one, and the env's reset
+    coin decides which seat moves first, so over a pool both nets get both seats and both colours.  A ply's search tree
+    is evaluated by the net of the seat to move at its root.
+
+        env.reset()
+        arena = env.arena(incumbent, candidate, policy="gumbel", simulations=32, batch=16, seed=0)
+        stats = arena.run(plies=200)       # ArenaStats(games, wins0, wins1, draws, plies, wins_a, wins_b, t)
+        arena.close()
+
+    Without root noise (Gumbel: `noise=True`, the default) or `sample_plies` (PUCT), all envs of a pool play one of
+    two games -- the nets are deterministic, and only the seat that moves first differs --, so a match needs one of
+    them on.  `run(n, wait=False)` only enqueues and returns None; `stats()` waits.  `run(3)` then `run(2)` is
+    `run(5)`."""
+
+    def __init__(self, pool: Any, net_a: Any, net_b: Any, options: dict) -> None:
+        self._pool = pool
+        pool.arena_begin(net_a, net_b, **options)
+
+    def _open(self) -> Any:
+        if self._pool is None:
+            raise ValueError("arena: the arena is closed")
+        return self._pool
+
+    def run(self, plies: int, wait: bool = True) -> Any:
+        self._open().arena_run(native.check_selfplay_plies(plies), bool(wait))
+        return self.stats() if wait else None
+
+    def stats(self) -> ArenaStats:
+        return ArenaStats(*(int(x) for x in self._open().arena_stats()))
+
+    def close(self) -> None:
+        """Releases the arena's device memory; an open recorder stays open."""
+        if self._pool is not None:
+            pool, self._pool = self._pool, None
+            pool.arena_end()
+
+
 class GuidedSearch:
     """A pool's guided-search session (`env.guided_search`): a PUCT search of every listed env whose tree stays on
     the device and that stops at every new leaf for the caller's priors and value.
@@ -740,6 +793,35 @@ class EnvPoolMixin(ABC):
         if self.is_async:
             raise ValueError("selfplay: async mode (batch_size != num_envs) is not supported")
         return Selfplay(self._selfplay(), net, options)
+
+    def evaluate_pair(self, net_a: Any, net_b: Any, side: Any, env_ids: Any = None,
+                      priors: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """Extension (the PGX board games): `evaluate` with two networks in one launch -- row i (the current position
+        of env_ids[i]) is evaluated by `net_a` where `side[i]` is 0 and by `net_b` where it is 1, and gets exactly what
+        `evaluate` of that net gives it.  The nets must agree in inputs and actions; width and depth may differ."""
+        native.check_arena(net_a, net_b)
+        pool = self._guided()
+        ids = native.check_guided(self.all_env_ids if env_ids is None else _normalize_env_id(env_ids), 1, 0.0)
+        side = native.check_arena_side(side, len(ids))
+        leaves = pool.guided_begin(ids, 1, 0.0)
+        try:
+            return pool.net_eval_pair(net_a, net_b, *leaves, side, priors)
+        finally:
+            pool.guided_end()
+
+    def arena(self, net_a: Any, net_b: Any, policy: str = "gumbel", simulations: int = 32, seed: int = 0,
+              record: bool = False, **options: Any) -> Arena:
+        """Extension (the PGX board games): opens the pool's self-play driver as an arena -- `Arena` -- in which the
+        built-in networks `net_a` and `net_b` (`envpool_amd.pgx.net.Net`; the same inputs and actions, any width and
+        depth) play each other: `net_a` moves for seat e & 1 of the env with global id e.  The options are those of
+        `selfplay`; `record` (default False) feeds the pool's open recorder.  Without root noise (Gumbel) or
+        `sample_plies` (PUCT), all envs of a pool play one of two games, so a match needs one of them on.  The
+        arguments are checked before any native call."""
+        options = dict(options, policy=policy, simulations=simulations, seed=seed, record=record)
+        native.check_arena(net_a, net_b, **options)
+        if self.is_async:
+            raise ValueError("arena: async mode (batch_size != num_envs) is not supported")
+        return Arena(self._selfplay(), net_a, net_b, options)
 
     def send(self, action: dict[str, Any] | np.ndarray,
              env_id: np.ndarray | None = None) -> None:

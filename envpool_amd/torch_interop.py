@@ -497,6 +497,21 @@ def selfplay_device(pool: Any, net: Any, plies: int, **options: Any) -> None:
     _order_both_ways(pool, dev, lambda: pool.selfplay_run(plies, wait=False))
 
 
+def arena_device(pool: Any, net_a: Any, net_b: Any, plies: int, **options: Any) -> None:
+    """`selfplay_device` for an arena (`DevicePool.arena_run(plies, wait=False)`): only enqueued and ordered both ways
+    with torch's current stream.  With `options` (`native.check_arena`'s), or when the pool's driver was not opened as
+    an arena of these two nets, the arena is opened first; otherwise the open one continues.  `pool.arena_stats()`
+    waits and reads the statistics."""
+    import torch
+
+    plies = native.check_selfplay_plies(plies)
+    held = getattr(pool, "_selfplay_net", None)
+    if options or not (isinstance(held, tuple) and held[0] is net_a and held[1] is net_b):
+        pool.arena_begin(net_a, net_b, **options)
+    dev = torch.device("cuda", pool.device)
+    _order_both_ways(pool, dev, lambda: pool.arena_run(plies, wait=False))
+
+
 def recorder_add_device(pool: Any, policy: Any, env_ids: Any = None) -> None:
     """`pool.record_add` with the policy targets where the model left them: `policy` is a float32 [k, A] tensor on the
     pool's device, read by the recorder's kernel (no PCIe transfer, no host synchronisation) and ordered against

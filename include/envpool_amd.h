@@ -1013,6 +1013,32 @@ int epa_selfplay_run_device(epa_pool* pool, int32_t plies);
 int epa_selfplay_stats(epa_pool* pool, int64_t* out);
 int epa_selfplay_end(epa_pool* pool);
 
+/* Arena (no reference analogue; the four PGX board games; csrc/pgx_arena.hip.h is the authority): two networks play
+ * each other in one pool, as a mode of the pool's one self-play driver.
+ *   Which net moves: net (m ^ e) & 1 for seat m of the env with GLOBAL id e, 0 = net_a, 1 = net_b: net_a holds seat 0
+ *   of the even envs and seat 1 of the odd ones, and the reset coin decides which seat moves first.  A ply's search
+ *   tree is evaluated by its root mover's net throughout.
+ *   epa_net_eval_pair(pool, net_a, net_b, rows, mode, obs, mask, status, side, policy, value): epa_net_eval with one
+ *     side byte per row, 0 or 1: row r gets exactly the policy and value epa_net_eval of that net gives it.  The rows
+ *     are grouped by net on the device (a stable partition, no atomics) and evaluated in one launch.  rows <= 2^20.
+ *   epa_arena_begin(pool, net_a, net_b, options): epa_selfplay_begin with a second net; every rule, option and refusal
+ *     of it applies to both nets, which agree in F and A with the pool (D and L may differ) and lie on its device.
+ *     epa_selfplay_run, epa_selfplay_run_device and epa_selfplay_end drive and close an arena as they do a driver, and
+ *     epa_selfplay_stats returns its six values.  A ply is the driver's with two changes: after the session's begin the
+ *     side bytes of the leaf rows are written (PgxArenaSides) and grouped (PgxNetPlan), and the round runs with the
+ *     pair evaluation.  Noise, move, recorder, step and the key are unchanged.
+ *   epa_arena_stats(out[8]): games, wins0, wins1, draws, plies, wins_a (finished games whose last reward of net_a's
+ *     seat, e & 1, is > 0), wins_b (of seat 1 - (e & 1)), t.  EPA_ERR_INVALID on a driver that is no arena.
+ * Errors (before any launch): epa_selfplay_begin's and epa_net_eval's; the host form of epa_net_eval_pair refuses a side
+ *   byte other than 0 or 1 (the device form reads any non-zero byte as 1); rows outside 1 .. 2^20. */
+int epa_net_eval_pair(epa_pool* pool, epa_net* net_a, epa_net* net_b, int32_t rows, int32_t mode, const uint8_t* obs,
+                      const uint8_t* mask, const uint8_t* status, const uint8_t* side, float* policy, float* value);
+int epa_net_eval_pair_device(epa_pool* pool, epa_net* net_a, epa_net* net_b, int32_t rows, int32_t mode,
+                             const void* device_obs, const void* device_mask, const void* device_status,
+                             const void* device_side, void* device_policy, void* device_value);
+int epa_arena_begin(epa_pool* pool, epa_net* net_a, epa_net* net_b, const epa_selfplay_options* options);
+int epa_arena_stats(epa_pool* pool, int64_t* out);
+
 /* ---- Atari post-process (K4): max-pool of the last two ALE frames, resize
  *      to 84x84, push into the frame stack (replaces AtariEnv::PushStack,
  *      envpool/atari/atari_env.h:308-346 + envpool/utils/image_process.h:27-36).
