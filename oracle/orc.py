@@ -212,6 +212,30 @@ class Oracle:
         self.lib.orc_set_state.restype = None
         self.lib.orc_set_state(self.h, ids.ctypes.data, len(ids), state.ctypes.data)
 
+    # the discrete state of a toy_text env (port oracle only): rows [i0..i11, done, current_step], int32; which
+    # i[] a family uses is stated above its functions in oracle/restate/envs.c
+    DISCRETE_DIM = 14
+
+    def get_discrete(self, ids: np.ndarray | None = None) -> np.ndarray:
+        if ids is None:
+            ids = np.arange(self.num_envs, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        out = np.zeros((len(ids), self.DISCRETE_DIM), dtype=np.int32)
+        self.lib.orc_get_discrete.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p]
+        if self.lib.orc_get_discrete(self.h, ids.ctypes.data, len(ids), out.ctypes.data) != 0:
+            raise RuntimeError("no discrete state in this oracle")
+        return out
+
+    def set_discrete(self, state: np.ndarray, ids: np.ndarray | None = None) -> None:
+        if ids is None:
+            ids = np.arange(self.num_envs, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        state = np.ascontiguousarray(state, dtype=np.int32)
+        assert state.shape == (len(ids), self.DISCRETE_DIM), state.shape
+        self.lib.orc_set_discrete.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p]
+        if self.lib.orc_set_discrete(self.h, ids.ctypes.data, len(ids), state.ctypes.data) != 0:
+            raise RuntimeError("no discrete state in this oracle")
+
     def close(self) -> None:
         if self.h:
             self.lib.orc_destroy(self.h)

@@ -17,6 +17,8 @@ void restate_step(void*, const int*, int, const void*, void**);
 void restate_destroy(void*);
 void restate_get_state(void*, const int*, int, double*);
 void restate_set_state(void*, const int*, int, const double*);
+void restate_get_discrete(void*, const int*, int, int*);
+void restate_set_discrete(void*, const int*, int, const int*);
 
 void* mjcpu_create(const char*, int, int, int, const double*, int);
 int mjcpu_num_state_keys(void*);
@@ -123,6 +125,20 @@ void orc_set_state(void* h, const int* ids, int k, const double* in) {
   handle* hd = (handle*)h;
   if (hd->kind == 0) restate_set_state(hd->h, ids, k, in);
   else mjcpu_set_state(hd->h, ids, k, in);
+}
+
+/* discrete state of the toy_text envs (restate only): rows of 14 ints, 0 on success */
+int orc_get_discrete(void* h, const int* ids, int k, int* out) {
+  handle* hd = (handle*)h;
+  if (hd->kind != 0) return -1;
+  restate_get_discrete(hd->h, ids, k, out);
+  return 0;
+}
+int orc_set_discrete(void* h, const int* ids, int k, const int* in) {
+  handle* hd = (handle*)h;
+  if (hd->kind != 0) return -1;
+  restate_set_discrete(hd->h, ids, k, in);
+  return 0;
 }
 
 const char* orc_kind(void) { return "port"; }

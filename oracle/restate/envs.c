@@ -8,7 +8,9 @@
  * PINNED: tests/test_oracle_pinned.py checks this file bit-for-bit against
  * (a) oracle/_ref (the reference compiled in place) whenever it is present and
  * (b) the golden rollouts under tests/golden/ that were generated from
- * oracle/_ref by tests/golden/make_golden.py.
+ * oracle/_ref by tests/golden/make_golden.py.  tests/test_oracle_scripted.py
+ * does the same at the branches random play never takes, under the scripted
+ * policies of tests/scripted_cases.py (tests/golden/scripted_*.npz).
  *
  * Runtime semantics restated (per env, sync mode):
  *   envpool/core/async_envpool.h:118-132  reset = force_reset || IsDone()
@@ -815,6 +817,27 @@ void restate_set_state(void* h, const int* ids, int k, const double* in) {
     for (int j = 0; j < 5; ++j) e->s[j] = in[i * 7 + j];
     e->done = in[i * 7 + 5] != 0.0;
     e->current_step = (int)in[i * 7 + 6];
+    e->elapsed_step = e->current_step;
+  }
+}
+/* The same for the discrete state of a toy_text env: [i0..i11, done, current_step] as ints (which i[] a family
+ * uses is stated above its functions), so a test can put an env at any state of its table. */
+void restate_get_discrete(void* h, const int* ids, int k, int* out) {
+  orc_pool* p = &((pool_impl*)h)->p;
+  for (int i = 0; i < k; ++i) {
+    orc_env* e = &p->envs[ids[i]];
+    for (int j = 0; j < 12; ++j) out[i * 14 + j] = e->i[j];
+    out[i * 14 + 12] = e->done;
+    out[i * 14 + 13] = e->current_step;
+  }
+}
+void restate_set_discrete(void* h, const int* ids, int k, const int* in) {
+  orc_pool* p = &((pool_impl*)h)->p;
+  for (int i = 0; i < k; ++i) {
+    orc_env* e = &p->envs[ids[i]];
+    for (int j = 0; j < 12; ++j) e->i[j] = in[i * 14 + j];
+    e->done = in[i * 14 + 12] != 0;
+    e->current_step = in[i * 14 + 13];
     e->elapsed_step = e->current_step;
   }
 }
