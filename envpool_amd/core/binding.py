@@ -622,6 +622,88 @@ class _ShardedPools:
     def record_end(self) -> None:
         self._record_all(lambda p: p.record_end())
 
+    # -- rollout collector: one collector per shard, each with the full episode capacity (host forms only).  The
+    # shards' arrays are concatenated along N, episodes merged in (step, env id) order and cut to the capacity -- the
+    # rows the unsharded pool keeps --, moments added in shard order.
+    def rollout_obs_keys(self) -> list[int]:
+        return self.pools[0].rollout_obs_keys()
+
+    def rollout_row_bytes(self) -> tuple[int, int]:
+        return self.pools[0].rollout_row_bytes()
+
+    @property
+    def num_envs(self) -> int:
+        return self.per * len(self.pools)
+
+    def rollout_begin(self, horizon: int, episodes: int = 0, moments: bool = False) -> None:
+        if self.pools[0].players != 1:
+            raise RuntimeError("rollout not implemented for this environment")
+        obs, act = self.rollout_row_bytes()
+        native.check_rollout(horizon, episodes, moments, self.num_envs, obs, act)
+        self._record_all(lambda p: p.rollout_begin(horizon, episodes, moments))
+        self.rollout_horizon, self.rollout_capacity, self._rollout_cut = int(horizon), int(episodes), 0
+
+    def rollout_shape(self) -> tuple[int, ...]:
+        sh = list(self.pools[0].rollout_shape())
+        sh[1] = self.num_envs
+        return tuple(sh)
+
+    def rollout_reset(self) -> list[np.ndarray]:
+        return [np.concatenate(cols) for cols in zip(*self._record_all(lambda p: p.rollout_reset()))]
+
+    def rollout_step(self, action: Any) -> list[np.ndarray]:
+        action = np.asarray(action)
+        if action.shape[:1] != (self.num_envs,):
+            raise RuntimeError(f"Expected action of {self.num_envs} rows, got {action.shape}")
+        rows: list[Any] = [None] * len(self.pools)
+
+        def run(s: int, p: DevicePool, _: Any) -> None:
+            rows[s] = p.rollout_step(action[s * self.per:(s + 1) * self.per])
+
+        self._each(run, [slice(0, self.per)] * len(self.pools))
+        return [np.concatenate(cols) for cols in zip(*rows)]
+
+    def rollout_batch(self) -> dict[str, np.ndarray]:
+        parts = self._record_all(lambda p: p.rollout_batch())
+        return {name: np.concatenate([b[name] for b in parts], axis=1) for name in parts[0]}
+
+    def rollout_gae(self, values: Any, gamma: float, lam: float) -> tuple[np.ndarray, np.ndarray]:
+        native.check_rollout(self.rollout_horizon, 0, False, self.num_envs, values=values, gamma=gamma, lam=lam)
+        out: list[Any] = [None] * len(self.pools)
+
+        def run(s: int, p: DevicePool, _: Any) -> None:
+            out[s] = p.rollout_gae(np.ascontiguousarray(values[:, s * self.per:(s + 1) * self.per]), gamma, lam)
+
+        self._each(run, [slice(0, self.per)] * len(self.pools))
+        return np.concatenate([o[0] for o in out], axis=1), np.concatenate([o[1] for o in out], axis=1)
+
+    def rollout_counters(self) -> np.ndarray:
+        c = np.array(self._record_all(lambda p: p.rollout_counters()))
+        out = c[0].copy()
+        out[0] = min(int(c[:, 0].sum()), self.rollout_capacity)
+        out[1] = c[:, 1].sum()
+        out[2] = c[:, 2].sum() + self._rollout_cut + int(c[:, 0].sum()) - out[0]
+        return out
+
+    def rollout_episodes(self) -> tuple[np.ndarray, ...]:
+        cols = [np.concatenate(c) for c in zip(*self._record_all(lambda p: p.rollout_episodes()))]
+        order = np.lexsort((cols[0], cols[1]))[:self.rollout_capacity]
+        self._rollout_cut += len(cols[0]) - len(order)
+        return tuple(c[order] for c in cols)
+
+    def rollout_moments(self) -> np.ndarray:
+        parts = self._record_all(lambda p: p.rollout_moments())
+        out = parts[0].copy()
+        for m in parts[1:]:
+            out = out + m
+        return out
+
+    def rollout_next(self) -> None:
+        self._record_all(lambda p: p.rollout_next())
+
+    def rollout_end(self) -> None:
+        self._record_all(lambda p: p.rollout_end())
+
     # -- self-play driver: one driver per shard; the keys take global env ids, so the shards play the unsharded pool's
     # games --
     def selfplay_begin(self, net: Any, **options: Any) -> None:
@@ -854,6 +936,12 @@ def make_native_classes(fd: FamilyDef, static_action_spec: list | None = None) -
         def _recorder(self) -> Any:
             if getattr(self._pool, "record_begin", None) is None:  # a pool with its own executor
                 raise RuntimeError("recorder not implemented for this environment")
+            return self._pool
+
+        def _rollout(self) -> Any:
+            # a pool with its own executor (Atari), or one with a row per player (the PGX games)
+            if getattr(self._pool, "rollout_begin", None) is None or fd.players != 1:
+                raise RuntimeError("rollout not implemented for this environment")
             return self._pool
 
         def _selfplay(self) -> Any:

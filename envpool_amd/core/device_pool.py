@@ -981,6 +981,167 @@ class DevicePool:
         """Closes the recorder and releases its device memory; ValueError without one."""
         native.check(self._lib.epa_record_end(self._h))
 
+    # -- rollout collector (csrc/rollout.hip.h) ----------------------------------------
+    def rollout_obs_keys(self) -> list[int]:
+        """Indices of the state keys a collector stores: the family's keys whose name starts with "obs"."""
+        return [i for i, (name, _, _) in enumerate(self.state_keys) if i >= 8 and name.startswith("obs")]
+
+    def rollout_row_bytes(self) -> tuple[int, int]:
+        """(observation bytes, action bytes) per env and slot: what `native.check_rollout` sizes the buffers with."""
+        obs = sum(int(np.prod(self.state_keys[i][2], dtype=np.int64)) * np.dtype(self.state_keys[i][1]).itemsize
+                  for i in self.rollout_obs_keys())
+        act = int(np.prod(self.action_shape, dtype=np.int64)) * np.dtype(self.action_dtype).itemsize
+        return obs, act
+
+    def rollout_begin(self, horizon: int, episodes: int = 0, moments: bool = False) -> None:
+        """Opens the pool's rollout collector (RuntimeError("rollout not implemented for this environment") for the
+        PGX games; ValueError for an async pool): time-major buffers of `horizon` steps in device memory that
+        `rollout_step` fills, `episodes` rows for finished episodes, and with `moments` the float64 power sums of the
+        float observation keys.  A pool has one collector; a new one replaces it."""
+        if self.players != 1:
+            raise RuntimeError("rollout not implemented for this environment")
+        if not self._is_sync:
+            raise ValueError("rollout: async mode (batch_size != num_envs) is not supported")
+        obs, act = self.rollout_row_bytes()
+        horizon, episodes, moments = native.check_rollout(horizon, episodes, moments, self.num_envs, obs, act)
+        native.check(self._lib.epa_rollout_begin(self._h, horizon, episodes, native.ROLLOUT_MOMENTS if moments else 0))
+        self.rollout_horizon, self.rollout_capacity = horizon, episodes
+
+    def rollout_shape(self) -> tuple[int, ...]:
+        """(T, N, episodes, t, obs keys, moment components, step counter, flags) of the open collector."""
+        out = (ctypes.c_int64 * 8)()
+        native.check(self._lib.epa_rollout_shape(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def _rollout_host_rows(self) -> tuple[list[np.ndarray], Any]:
+        outs = [np.empty((self.num_envs, *shape), dtype=dtype) for _, dtype, shape in self.state_keys]
+        return outs, (ctypes.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+
+    def rollout_reset(self) -> list[np.ndarray]:
+        """Resets every env through the collector and returns what `recv` would: the observations also land in slot 0,
+        the carried done flags and the episode accumulators are cleared and t = 0."""
+        outs, ptrs = self._rollout_host_rows()
+        k = ctypes.c_int32(0)
+        native.check(self._lib.epa_rollout_reset(self._h, 0, ptrs, len(outs), self.num_envs, ctypes.byref(k)))
+        return outs
+
+    def rollout_step(self, action: Any) -> list[np.ndarray]:
+        """One step of every env in id order with `action` [N, ...] and the collector's kernels behind it; returns what
+        `send` + `recv` return."""
+        action = np.ascontiguousarray(action, dtype=self.action_dtype)
+        want = (self.num_envs, *self.action_shape)
+        if action.size != int(np.prod(want)):
+            raise RuntimeError(f"Expected action of shape {want}, got {action.shape}")
+        outs, ptrs = self._rollout_host_rows()
+        k = ctypes.c_int32(0)
+        native.check(self._lib.epa_rollout_step(self._h, action.ctypes.data, ptrs, len(outs), self.num_envs,
+                                                ctypes.byref(k)))
+        return outs
+
+    def rollout_reset_device(self) -> tuple[list[int], int]:
+        """`rollout_reset` on the device path: only enqueued; the device pointers `recv_device` would return."""
+        n = len(self.state_keys)
+        ptrs = (ctypes.c_void_p * n)()
+        k = ctypes.c_int32(0)
+        native.check(self._lib.epa_rollout_reset(self._h, 1, ptrs, n, 0, ctypes.byref(k)))
+        return [int(p) if p else 0 for p in ptrs], k.value
+
+    def rollout_step_device(self, d_action: int, wait_event: int | None = None) -> tuple[list[int], int]:
+        """`rollout_step` with the action rows at the raw device address `d_action`: only enqueued on the pool's
+        stream; the device pointers `step_device` would return."""
+        n = len(self.state_keys)
+        ptrs = (ctypes.c_void_p * n)()
+        k = ctypes.c_int32(0)
+        native.check(self._lib.epa_rollout_step_device(self._h, ctypes.c_void_p(d_action), ctypes.c_void_p(wait_event),
+                                                       ptrs, n, ctypes.byref(k)))
+        return [int(p) if p else 0 for p in ptrs], k.value
+
+    def rollout_arrays(self) -> list[tuple[str, Any, tuple[int, ...]]]:
+        """(name, dtype, shape) of the collector's buffers in the order of `rollout_view_device`: the obs keys
+        [T+1, N, ...], then action [T, N, ...], reward float32, term, trunc, mask uint8 [T, N]."""
+        t, n = self.rollout_horizon, self.num_envs
+        out = [(self.state_keys[i][0], self.state_keys[i][1], (t + 1, n, *self.state_keys[i][2]))
+               for i in self.rollout_obs_keys()]
+        out.append(("action", self.action_dtype, (t, n, *self.action_shape)))
+        out.append(("reward", np.float32, (t, n)))
+        out += [(name, np.uint8, (t, n)) for name in ("term", "trunc", "mask")]
+        return out
+
+    def rollout_view_device(self) -> list[int]:
+        """The raw device addresses of the buffers, in the order of `rollout_arrays`."""
+        n = len(self.rollout_obs_keys()) + 5
+        arrays = (ctypes.c_void_p * n)()
+        native.check(self._lib.epa_rollout_view_device(self._h, arrays, n))
+        return [int(p) for p in arrays]
+
+    def rollout_batch(self) -> dict[str, np.ndarray]:
+        """The buffers copied to the host, by the names of `rollout_arrays`, whole: slots beyond t read 0."""
+        spec = self.rollout_arrays()
+        outs = [np.empty(shape, dtype=dtype) for _, dtype, shape in spec]
+        ptrs = (ctypes.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        native.check(self._lib.epa_rollout_batch(self._h, ptrs, len(outs)))
+        return {name: o for (name, _, _), o in zip(spec, outs)}
+
+    def rollout_gae(self, values: Any, gamma: float, lam: float) -> tuple[np.ndarray, np.ndarray]:
+        """(advantages, returns) float32 [T, N] of the full horizon from `values` float32 [T+1, N] (rollout.hip.h:
+        GaeStep)."""
+        t, n = self.rollout_horizon, self.num_envs
+        _, _, _, values, gamma, lam = native.check_rollout(t, 0, False, n, values=values, gamma=gamma, lam=lam)
+        adv, ret = np.empty((t, n), dtype=np.float32), np.empty((t, n), dtype=np.float32)
+        native.check(self._lib.epa_rollout_gae(self._h, values.ctypes.data, gamma, lam, adv.ctypes.data,
+                                               ret.ctypes.data))
+        return adv, ret
+
+    def rollout_gae_device(self, d_values: int, gamma: float, lam: float, d_adv: int, d_ret: int) -> None:
+        """`rollout_gae` on raw device addresses (float32, 4-byte aligned): only enqueued."""
+        native.check(self._lib.epa_rollout_gae_device(self._h, ctypes.c_void_p(d_values), float(np.float32(gamma)),
+                                                      float(np.float32(lam)), ctypes.c_void_p(d_adv),
+                                                      ctypes.c_void_p(d_ret)))
+
+    def rollout_counters(self) -> np.ndarray:
+        """int64 [6]: episode rows, episodes finished and dropped since begin, the step counter, t, reset done."""
+        out = np.zeros(6, dtype=np.int64)
+        native.check(self._lib.epa_rollout_counters(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def rollout_episodes(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The finished episodes so far -- (env_id int32, step int64, return float64, length int32) in (step, env id)
+        order -- and the count back to 0."""
+        n = int(self.rollout_counters()[0])
+        out = (np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64),
+               np.empty(n, dtype=np.int32))
+        got = ctypes.c_int32(0)
+        native.check(self._lib.epa_rollout_episodes(self._h, n, *[o.ctypes.data for o in out], ctypes.byref(got)))
+        return out
+
+    def rollout_episodes_view_device(self) -> tuple[list[int], int]:
+        """The raw addresses of the four episode arrays (over the capacity) and of the device int32 count."""
+        arrays = (ctypes.c_void_p * 4)()
+        count = ctypes.c_void_p()
+        native.check(self._lib.epa_rollout_episodes_view_device(self._h, arrays, ctypes.byref(count)))
+        return [int(p) for p in arrays], int(count.value)
+
+    def rollout_moments(self) -> np.ndarray:
+        """float64 [3, components]: count, sum and sum of squares per component of the float obs keys."""
+        comps = self.rollout_shape()[5]
+        out = np.zeros((3, comps), dtype=np.float64)
+        native.check(self._lib.epa_rollout_moments(self._h, out.ctypes.data, None))
+        return out
+
+    def rollout_moments_device(self) -> tuple[int, int]:
+        """(the raw device address of the [3, components] float64 accumulators, components)."""
+        d = ctypes.c_void_p()
+        native.check(self._lib.epa_rollout_moments(self._h, None, ctypes.byref(d)))
+        return int(d.value), self.rollout_shape()[5]
+
+    def rollout_next(self) -> None:
+        """Slot t becomes slot 0 and t = 0; only enqueued."""
+        native.check(self._lib.epa_rollout_next(self._h))
+
+    def rollout_end(self) -> None:
+        """Closes the collector and releases its device memory; ValueError without one."""
+        native.check(self._lib.epa_rollout_end(self._h))
+
     # -- self-play driver (csrc/pgx_selfplay.hip.h) -----------------------------------
     def selfplay_begin(self, net: Any, **options: Any) -> None:
         """Opens the pool's self-play driver (epa_selfplay_begin) with the built-in network `net` as the evaluator;

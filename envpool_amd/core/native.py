@@ -39,6 +39,8 @@ GUMBEL_MAX_BATCH = 32    # EPA_GUMBEL_MAX_BATCH: the most slots (simulations per
 SEARCH_MAX_LEAF_PLAYOUTS = 64
 RECORD_SYMMETRIES = 1    # EPA_RECORD_SYMMETRIES: the flag of a recorder that writes every board symmetry
 RECORD_MAX_PLIES = 256   # EPA_RECORD_MAX_PLIES: the largest max_plies of a recorder (0: 128)
+ROLLOUT_MOMENTS = 1      # EPA_ROLLOUT_MOMENTS: the flag of a rollout collector that keeps observation moments
+ROLLOUT_MAX_BYTES = 1 << 31  # EPA_ROLLOUT_MAX_BYTES: the buffers of one rollout collector
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
 SOLVE_MAX_TABLE_BITS = 16  # EPA_SOLVE_MAX_TABLE_BITS: a lane's transposition table has at most 2^16 entries
 SOLVE_ILLEGAL = -128     # q of an illegal action, and of every action of a row that is not solved
@@ -205,6 +207,21 @@ def lib() -> ctypes.CDLL:
         "epa_record_discard": (i32, [vp, vp, i32]),
         "epa_record_counters": (i32, [vp, P(ctypes.c_int64)]),
         "epa_record_end": (i32, [vp]),
+        "epa_rollout_begin": (i32, [vp, i32, i32, ctypes.c_uint32]),
+        "epa_rollout_shape": (i32, [vp, P(ctypes.c_int64)]),
+        "epa_rollout_reset": (i32, [vp, i32, P(vp), i32, i32, P(i32)]),
+        "epa_rollout_step": (i32, [vp, vp, P(vp), i32, i32, P(i32)]),
+        "epa_rollout_step_device": (i32, [vp, vp, vp, P(vp), i32, P(i32)]),
+        "epa_rollout_view_device": (i32, [vp, P(vp), i32]),
+        "epa_rollout_batch": (i32, [vp, P(vp), i32]),
+        "epa_rollout_gae": (i32, [vp, vp, ctypes.c_float, ctypes.c_float, vp, vp]),
+        "epa_rollout_gae_device": (i32, [vp, vp, ctypes.c_float, ctypes.c_float, vp, vp]),
+        "epa_rollout_episodes": (i32, [vp, i32, vp, vp, vp, vp, P(i32)]),
+        "epa_rollout_episodes_view_device": (i32, [vp, P(vp), P(vp)]),
+        "epa_rollout_moments": (i32, [vp, vp, P(vp)]),
+        "epa_rollout_next": (i32, [vp]),
+        "epa_rollout_counters": (i32, [vp, P(ctypes.c_int64)]),
+        "epa_rollout_end": (i32, [vp]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -252,6 +269,10 @@ EXPORTED_SYMBOLS = [
     "epa_record_begin", "epa_record_shape", "epa_record_add", "epa_record_add_device", "epa_record_finish",
     "epa_record_finish_device", "epa_record_drain", "epa_record_view_device", "epa_record_clear",
     "epa_record_discard", "epa_record_counters", "epa_record_end",
+    "epa_rollout_begin", "epa_rollout_shape", "epa_rollout_reset", "epa_rollout_step", "epa_rollout_step_device",
+    "epa_rollout_view_device", "epa_rollout_batch", "epa_rollout_gae", "epa_rollout_gae_device",
+    "epa_rollout_episodes", "epa_rollout_episodes_view_device", "epa_rollout_moments", "epa_rollout_next",
+    "epa_rollout_counters", "epa_rollout_end",
     "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_atari_post_create",
@@ -349,6 +370,47 @@ def check_record_finish(reward: Any, done: Any, k: int) -> tuple[np.ndarray, np.
     if done.shape != (k,):
         raise ValueError(f"recorder finish: done of shape {done.shape} for {k} envs")
     return reward.reshape(k, 2), np.ascontiguousarray(done != 0, dtype=np.uint8)
+
+
+def rollout_bytes(num_envs: int, horizon: int, episodes: int, obs_bytes: int, action_bytes: int) -> int:
+    """Bytes of a rollout collector's buffers (csrc/rollout.hip.h: RolloutBytes): obs [T+1, N], action, reward and the
+    three flag arrays [T, N], and 24 bytes per episode row."""
+    return (horizon + 1) * num_envs * obs_bytes + horizon * num_envs * (action_bytes + 4 + 3) + episodes * 24
+
+
+def check_rollout(horizon: Any, episodes: Any = 0, moments: Any = False, num_envs: int = 1, obs_bytes: int = 0,
+                  action_bytes: int = 0, values: Any = None, gamma: Any = None, lam: Any = None) -> tuple:
+    """A rollout collector's arguments after the checks every layer makes before the native call, with no device:
+    ValueError for a horizon that is no integer of at least 1, episodes that is no integer of at least 0, a `moments`
+    that is no bool, and buffers above the 2 GiB limit (`num_envs` envs of `obs_bytes` observation and `action_bytes`
+    action bytes each).  With `values` (and `gamma`, `lam`) also gae's arguments: values must be a float32 array of
+    shape [horizon + 1, num_envs], gamma and lam numbers in [0, 1].  Returns (horizon, episodes, moments), with values
+    (horizon, episodes, moments, values, gamma, lam) -- gamma and lam rounded to float32."""
+    if isinstance(horizon, (bool, np.bool_)) or not isinstance(horizon, (int, np.integer)) or not 1 <= int(horizon) < 2**31:
+        raise ValueError(f"rollout: horizon = {horizon!r} must be an integer of at least 1")
+    if isinstance(episodes, (bool, np.bool_)) or not isinstance(episodes, (int, np.integer)) \
+            or not 0 <= int(episodes) < 2**31:
+        raise ValueError(f"rollout: episodes = {episodes!r} must be an integer of at least 0")
+    if not isinstance(moments, (bool, np.bool_)):
+        raise ValueError(f"rollout: moments = {moments!r} must be a bool")
+    horizon, episodes, moments = int(horizon), int(episodes), bool(moments)
+    total = rollout_bytes(int(num_envs), horizon, episodes, int(obs_bytes), int(action_bytes))
+    if total > ROLLOUT_MAX_BYTES:
+        raise ValueError(f"rollout: {num_envs} envs over a horizon of {horizon} with {episodes} episode rows need "
+                         f"{total} bytes, above the limit of 2 GiB")
+    if values is None:
+        return horizon, episodes, moments
+    if not isinstance(values, np.ndarray) or values.dtype != np.float32:
+        raise ValueError(f"rollout gae: values must be a float32 array, got {getattr(values, 'dtype', type(values))}")
+    if values.shape != (horizon + 1, int(num_envs)):
+        raise ValueError(f"rollout gae: values of shape {values.shape} for [{horizon + 1}, {int(num_envs)}]")
+    out = []
+    for name, x in (("gamma", gamma), ("lam", lam)):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(x) <= 1.0:
+            raise ValueError(f"rollout gae: {name} = {x!r} must be a number in [0, 1]")
+        out.append(float(np.float32(x)))
+    return horizon, episodes, moments, np.ascontiguousarray(values), out[0], out[1]
 
 
 def check_search(env_ids: Any, simulations: int, leaf_playouts: int, c_puct: float, max_plies: int) -> np.ndarray:

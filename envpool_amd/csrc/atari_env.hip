@@ -324,6 +324,7 @@ class AtariPool : public Pool {
   }
 
   int StateDim() const override { return 0; }
+  bool HasRollout() const override { return false; }  // the envs step on the host: no device step to hook
   void GetState(const int*, int, double*) override {
     throw std::runtime_error("Atari: emulator state is opaque (no get_state)");
   }

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/envpool_amd.h"
+#include "rollout.hip.h"
 
 namespace epa {
 
@@ -284,6 +285,48 @@ struct GumbelArgs {
   int32_t* action;          // [k]
   float* weights;           // [k][A]
 };
+
+// One step of a pool's rollout collector (Pool::RolloutStep / RolloutReset; rollout.hip.h): the rows the store kernel
+// moves, the step's section of the result block, slot t of the scalar buffers, the per-env words and the episode rows.
+// Every pointer is device memory.
+struct RolloutStepArgs {
+  rollout::StoreKeys keys;      // the obs keys (reset: into slot 0; step: into slot t + 1), then the action (slot t)
+  int k;                        // rows of the batch
+  int n;                        // the pool's envs
+  int id_offset;                // env_id_offset: the batch's ids are global
+  int capacity;                 // episode rows
+  long long step;               // the collector's step counter
+  const int32_t* env_id;        // the batch: [k] (null: row i is env i)
+  const unsigned char* done;    // [k]
+  const unsigned char* trunc;   // [k]
+  const float* reward;          // [k]
+  float* rew;                   // slot t: [N]
+  unsigned char* term;
+  unsigned char* trc;
+  unsigned char* mask;
+  unsigned char* carry;         // per env: [N]
+  double* acc_ret;
+  int32_t* acc_len;
+  unsigned char* emit;          // this step's emission flags, 16-byte aligned, and what is emitted
+  double* emit_ret;
+  int32_t* emit_len;
+  int32_t* ep_env;              // episodes: [capacity]
+  long long* ep_step;
+  double* ep_ret;
+  int32_t* ep_len;
+  rollout::Control* ctl;
+};
+// The collector's kernels (rollout.hip), one launch each on `s`
+void RolloutLaunchStore(const RolloutStepArgs& a, bool scalars, hipStream_t s);
+void RolloutLaunchScan(const RolloutStepArgs& a, hipStream_t s);
+void RolloutLaunchGae(int horizon, int n, const float* reward, const unsigned char* term, const unsigned char* trunc,
+                      const unsigned char* mask, const float* values, float gamma, float lam, float* adv, float* ret,
+                      hipStream_t s);
+// x: [n][comps] of EPA_F32 / EPA_F64 -> partial [groups][comps_total][2] at component comp0; then the fold into acc
+// (count, sum, sumsq: [3][comps_total])
+void RolloutLaunchMoments(const void* x, int dtype, int n, int comps, int comp0, int comps_total, double* partial,
+                          hipStream_t s);
+void RolloutLaunchMomentsFold(const double* partial, int n, int comps_total, double* acc, hipStream_t s);
 
 struct Batch {
   // where the batch's kernels write and recv reads: the block's own device allocation (`dev_buf`), or -- a DIRECT
@@ -701,6 +744,32 @@ class Pool {
   void RecordShape(int32_t out[5]) const;              // H, W, C, A, nsym of the open recorder
   void RecordEnd();
 
+  // Rollout collector (include/envpool_amd.h: epa_rollout_begin; rollout.hip.h is the contract): an on-policy
+  // trajectory buffer in device memory that the pool's own step fills -- RolloutStep is SendDevice + the collector's
+  // kernels on the batch's stream + Recv / RecvDevice, so the rows are read from the result block in HBM.  It belongs to
+  // the base pool: every family with one row per env and a device step has it (HasRollout; PGX, two rows per env, and
+  // the host-stepped Atari pool throw std::runtime_error("rollout not implemented for this environment")).  A pool
+  // in sync mode only.  A pool has at most one collector; its memory is ONE device allocation of its own with a single
+  // owner, released by RolloutEnd, by the next RolloutBegin and by ~Pool.  While one is open, Reset is refused
+  // (std::invalid_argument): an env reset behind the collector's back would break its mask and episode accounting.
+  // The device forms only enqueue; the host forms end in one stream synchronisation.  Calls on one collector are the
+  // caller's to serialise.
+  virtual bool HasRollout() const;
+  void RolloutBegin(int horizon, int episodes, unsigned flags);
+  void RolloutShape(int64_t out[8]) const;  // T, N, episodes, t, obs keys, moment components, step counter, flags
+  int RolloutReset(bool device, void** ptrs, int n_ptrs, int cap_rows);
+  int RolloutStep(bool device, const void* action, hipEvent_t wait_event, void** ptrs, int n_ptrs, int cap_rows);
+  // the device arrays: one per obs key, then action, reward, term, trunc, mask
+  void RolloutView(void** arrays, int n) const;
+  void RolloutBatch(void* const* out, int n);  // the same arrays, whole, copied to the host
+  void RolloutGae(bool device, const void* values, float gamma, float lam, void* adv, void* ret);
+  void RolloutEpisodes(int rows, int32_t* env_id, int64_t* step, double* ret, int32_t* length, int32_t* count);
+  void RolloutEpisodesView(void* out[4], void** count) const;
+  void RolloutMoments(double* host_out, void** d_out);  // [3][components]: count, sum, sumsq
+  void RolloutNext();
+  void RolloutCounters(int64_t out[6]);  // count, finished, dropped, step counter, t, started
+  void RolloutEnd();
+
   // Self-play driver (include/envpool_amd.h: epa_selfplay_begin; the PGX board games, pgx_selfplay.hip.h): plays
   // plies of every env of the pool with a Net as the evaluator, through the device forms of the calls above --
   // GumbelBeginCall / GuidedBeginCall, NetRunCall, *ResultCall, RecordAddCall, SendDevice, RecvDevice, RecordFinishCall --
@@ -984,6 +1053,30 @@ class Pool {
   void RecordRequire(const char* what) const;           // throws without the hooks or without a recorder
   RecordArgs RecordArgsOf(int k) const;
   void RecordCheckIds(const char* what, const int32_t* ids, int k) const;  // range, count, repeats
+  // the pool's rollout collector
+  struct Rollout {
+    bool open{false};
+    bool started{false};    // RolloutReset has run
+    DeviceBlock mem;        // the collector's one device allocation, in the order of `off`
+    int horizon{0}, capacity{0}, t{0};
+    unsigned flags{0};
+    long long step{0};
+    std::vector<int> obs_keys;      // indices into keys_
+    std::vector<int> moment_keys;   // positions in obs_keys of the float keys
+    std::vector<int> moment_comp0;  // their first component
+    int comps{0};
+    std::vector<size_t> obs_off;    // per obs key
+    // offsets into mem: action, reward, term, trunc, mask, carry + acc_ret + acc_len (one zeroed run), emit, emit_ret,
+    // emit_len, the four episode arrays, the control words, the moment accumulators and partials, the staged action
+    // and values / adv / ret rows of the host forms, the end
+    size_t off[22]{};
+  };
+  Rollout rollout_;
+  void RolloutFree();
+  void RolloutRequire(const char* what) const;
+  void RolloutQuiet(const char* what) const;     // throws unless the result queue is empty
+  RolloutStepArgs RolloutArgsOf(const Batch& b) const;
+  void RolloutMomentsOf(int slot);               // enqueues the moment kernels for one obs slot
   // the pool's self-play driver
   struct Selfplay {
     bool open{false};

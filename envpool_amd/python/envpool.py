@@ -139,6 +139,110 @@ class Recorder:
             self._pool = None
 
 
+class Rollout(NamedTuple):
+    """`ro.batch()`: the collected steps, time-major, rows in env id order.  `obs` has t + 1 slots -- slot s + 1 is the
+    observation step s returned --, an array for a single obs key and a dict by state key name for several; the others
+    have t rows.  `mask[s, n]` is False where step s was the auto-reset step after a done: slot s then holds the final
+    observation of the episode before, the action was ignored and the reward is 0."""
+
+    obs: Any
+    action: np.ndarray
+    reward: np.ndarray
+    term: np.ndarray
+    trunc: np.ndarray
+    mask: np.ndarray
+
+
+class Episodes(NamedTuple):
+    """`ro.episodes()`: the episodes finished since the last call, in (step, env id) order: the global env id, the
+    collector's step counter at the step that ended it, the float64 sum of its float32 rewards, its length."""
+
+    env_id: np.ndarray
+    step: np.ndarray
+    ret: np.ndarray
+    length: np.ndarray
+
+
+class RolloutCollector:
+    """A pool's rollout collector (`env.rollout`): the pool's own step writes observations, actions, rewards and flags
+    time-major into device memory, keeps episode returns and lengths across auto-resets and, with `moments`, float64
+    power sums of the observations; `gae` computes advantages on the device (csrc/rollout.hip.h is the contract).
+
+        ro = env.rollout(horizon=128, episodes=1 << 16, moments=True)
+        obs, info = ro.reset()
+        for t in range(128):
+            obs, rew, term, trunc, info = ro.step(policy(obs))     # what env.step returns
+        b = ro.batch(); adv, ret = ro.gae(values, 0.99, 0.95); eps = ro.episodes(); ro.next()
+
+    While a collector is open the pool is driven through it: `env.reset` raises ValueError.  `moments()` returns raw
+    power sums (count, sum, sum of squares per observation component): mean = sum / count and var = sumsq / count -
+    mean^2 are the caller's to derive, and that difference cancels badly where mean^2 is much larger than the variance
+    -- centre such observations first.  A pool has one collector; a new one replaces it."""
+
+    def __init__(self, env: Any, pool: Any, horizon: int, episodes: int, moments: bool) -> None:
+        self._env, self._pool, self.horizon = env, pool, horizon
+        pool.rollout_begin(horizon, episodes, moments)
+        self._names = [pool.state_keys[i][0] for i in pool.rollout_obs_keys()]
+
+    def _open(self) -> Any:
+        if self._pool is None:
+            raise ValueError("rollout: the collector is closed")
+        return self._pool
+
+    def reset(self) -> Any:
+        """What `env.reset()` returns; the observations also land in slot 0, t = 0, and an episode under way is
+        abandoned."""
+        return self._env._to(self._open().rollout_reset(), True, self._env.config["gym_reset_return_info"])
+
+    def step(self, action: Any) -> Any:
+        """What `env.step(action)` returns, bit for bit, for the whole pool in env id order."""
+        pool = self._open()
+        converted = self._env._from(action)
+        self._env._check_action(converted)
+        return self._env._to(pool.rollout_step(converted[-1]), False, True)
+
+    @property
+    def t(self) -> int:
+        return self._open().rollout_shape()[3]
+
+    def batch(self) -> Rollout:
+        b, t = self._open().rollout_batch(), self.t
+        obs = {n: b[n][:t + 1] for n in self._names}
+        return Rollout(obs[self._names[0]] if len(obs) == 1 else obs, b["action"][:t], b["reward"][:t],
+                       b["term"][:t].view(np.bool_), b["trunc"][:t].view(np.bool_), b["mask"][:t].view(np.bool_))
+
+    def gae(self, values: Any, gamma: float = 0.99, lam: float = 0.95) -> tuple[np.ndarray, np.ndarray]:
+        """(advantages, returns) float32 [T, N] of a full horizon from `values` float32 [T + 1, N]: a terminated step
+        does not bootstrap, a truncated one bootstraps from values[t + 1] (the final observation's) and ends the
+        recurrence, a masked step has advantage 0."""
+        return self._open().rollout_gae(values, gamma, lam)
+
+    def episodes(self) -> Episodes:
+        return Episodes(*self._open().rollout_episodes())
+
+    @property
+    def counters(self) -> dict[str, int]:
+        """episode rows waiting, episodes finished and dropped (the buffer was full) since the collector was opened,
+        and the step counter."""
+        c = self._open().rollout_counters()
+        return {"count": int(c[0]), "finished": int(c[1]), "dropped": int(c[2]), "steps": int(c[3])}
+
+    def moments(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(count, sum, sumsq), float64 per component of the float obs keys (in key order, flattened), over every row
+        written into an obs slot by `reset()` and `step()`: raw power sums (see the class docstring)."""
+        m = self._open().rollout_moments()
+        return m[0], m[1], m[2]
+
+    def next(self) -> None:
+        """Slot t becomes slot 0 and t = 0; flags carried over, episode accumulators, episodes and moments are kept."""
+        self._open().rollout_next()
+
+    def close(self) -> None:
+        pool, self._pool = self._pool, None
+        if pool is not None:
+            pool.rollout_end()
+
+
 class Stats(NamedTuple):
     """What a self-play driver has played since it was opened (`Selfplay.run`, `Selfplay.stats`)."""
 
@@ -774,6 +878,18 @@ class EnvPoolMixin(ABC):
         native call."""
         capacity, max_plies, symmetries = native.check_record(capacity, max_plies, symmetries)
         return Recorder(self._recorder(), np.asarray(self.all_env_ids, dtype=np.int32), capacity, max_plies, symmetries)
+
+    def rollout(self, horizon: int, episodes: int = 0, moments: bool = False) -> RolloutCollector:
+        """Extension (every family with one row per env and a device step; the PGX games and Atari raise
+        RuntimeError("rollout not implemented for this environment")): opens the pool's rollout collector --
+        `RolloutCollector` -- with time-major buffers of `horizon` steps, `episodes` rows for finished episodes and,
+        with `moments`, observation power sums.  Sync pools only.  The arguments are checked before any native call."""
+        pool = self._rollout()
+        if self.is_async:
+            raise ValueError("rollout: async mode (batch_size != num_envs) is not supported")
+        obs, act = pool.rollout_row_bytes()
+        horizon, episodes, moments = native.check_rollout(horizon, episodes, moments, self.config["num_envs"], obs, act)
+        return RolloutCollector(self, pool, horizon, episodes, moments)
 
     def selfplay(self, net: Any, policy: str = "gumbel", simulations: int = 32, seed: int = 0, record: bool = True,
                  **options: Any) -> Selfplay:

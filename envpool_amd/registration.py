@@ -145,6 +145,17 @@ class EnvRegistry:
     def list_all_envs(self) -> list[str]:
         return list(self.specs.keys())
 
+    def rollout_supported(self, task_id: str) -> bool:
+        """Whether `env.rollout()` works for the id: every family with one row per env and a device step -- not the PGX
+        board games (two rows per env) and not Atari (stepped by a host plugin)."""
+        assert task_id in self.specs, f"{task_id} is not supported, `envpool.list_all_envs()` may help."
+        return self.specs[task_id][0].rsplit(".", 1)[-1] not in ("pgx", "atari")
+
+    def check_rollout(self, task_id: str) -> None:
+        """RuntimeError("rollout not implemented for this environment") for an id without a collector; no device."""
+        if not self.rollout_supported(task_id):
+            raise RuntimeError("rollout not implemented for this environment")
+
 
 registry = EnvRegistry()
 register = registry.register

@@ -19,7 +19,7 @@ from envpool_amd.core import native
 
 _TYPESTR = {np.dtype(np.int32): "<i4", np.dtype(np.float32): "<f4",
             np.dtype(np.float64): "<f8", np.dtype(np.bool_): "|b1",
-            np.dtype(np.uint8): "|u1", np.dtype(np.int8): "|i1"}
+            np.dtype(np.uint8): "|u1", np.dtype(np.int8): "|i1", np.dtype(np.int64): "<i8"}
 
 
 class _DevArray:
@@ -568,3 +568,103 @@ def recorder_clear(pool: Any) -> None:
     import torch
 
     _order_both_ways(pool, torch.device("cuda", pool.device), pool.record_clear)
+
+
+# -- rollout collector (csrc/rollout.hip.h): the device forms.  They only enqueue on the pool's stream and are ordered
+# both ways with torch's current stream. --
+def _rollout_tensors(pool: Any, ptrs: list, k: int, dev: Any) -> dict[str, Any]:
+    import torch
+
+    return {name: torch.as_tensor(_DevArray(ptr, pool.view_shape(i, k), dtype), device=dev)
+            for i, ((name, dtype, _), ptr) in enumerate(zip(pool.state_keys, ptrs))}
+
+
+def rollout_reset_device(pool: Any) -> dict[str, Any]:
+    """`pool.rollout_reset` on the device path: resets every env through the open collector and returns the tensors
+    `recv_device_tensors` would (valid until the second next step)."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    got: list = []
+    _order_both_ways(pool, dev, lambda: got.append(pool.rollout_reset_device()))
+    return _rollout_tensors(pool, got[0][0], got[0][1], dev)
+
+
+def rollout_step_device(pool: Any, action: Any) -> dict[str, Any]:
+    """One collector step with an action tensor [N, ...] on the pool's device: the env step and the collector's kernels
+    are enqueued behind torch's current stream -- nothing crosses PCIe -- and the tensors `recv_device_tensors` would
+    return come back, ready for the current stream."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    want = (pool.num_envs, *pool.action_shape)
+    if not action.is_contiguous() or action.dtype != _torch_dtype(pool.action_dtype) or action.device != dev \
+            or action.numel() != int(np.prod(want)):
+        raise RuntimeError(f"rollout_step_device: action must be a contiguous {np.dtype(pool.action_dtype)} tensor of "
+                           f"{want} on {dev}")
+    got: list = []
+    # (the current stream waits for the pool's stream before this returns, so `action` may be dropped right away)
+    _order_both_ways(pool, dev, lambda: got.append(pool.rollout_step_device(action.data_ptr())))
+    return _rollout_tensors(pool, got[0][0], got[0][1], dev)
+
+
+def rollout_view_device(pool: Any) -> dict[str, Any]:
+    """The collector's buffers as torch tensors that alias them, by name: each obs key [T+1, N, ...], action [T, N, ...],
+    reward float32, term, trunc, mask uint8 [T, N].  No copy; valid until the collector is closed or replaced.  Torch's
+    current stream is made to wait for the collector's launches so far."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    ptrs = pool.rollout_view_device()
+    _order_both_ways(pool, dev, lambda: None)
+    return {name: torch.as_tensor(_DevArray(p, shape, dtype), device=dev)
+            for p, (name, dtype, shape) in zip(ptrs, pool.rollout_arrays())}
+
+
+def rollout_gae_device(pool: Any, values: Any, gamma: float, lam: float, out: Any = None) -> tuple[Any, Any]:
+    """`pool.rollout_gae` with `values` float32 [T+1, N] on the pool's device: (advantages, returns) float32 [T, N]
+    tensors, written by the GAE kernel.  `out`: a pair of contiguous float32 [T, N] tensors to write into."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    t, n = pool.rollout_horizon, pool.num_envs
+    if values.dtype != torch.float32 or not values.is_contiguous() or tuple(values.shape) != (t + 1, n) \
+            or values.device != dev:
+        raise ValueError(f"rollout_gae_device: values must be a contiguous float32 tensor of {(t + 1, n)} on {dev}")
+    for name, x in (("gamma", gamma), ("lam", lam)):
+        if not 0.0 <= float(x) <= 1.0:
+            raise ValueError(f"rollout_gae_device: {name} = {x!r} must be a number in [0, 1]")
+    if out is None:
+        out = (torch.empty((t, n), dtype=torch.float32, device=dev), torch.empty((t, n), dtype=torch.float32, device=dev))
+    for o in out:
+        if o.dtype != torch.float32 or not o.is_contiguous() or tuple(o.shape) != (t, n) or o.device != dev:
+            raise ValueError(f"rollout_gae_device: out must be two contiguous float32 tensors of {(t, n)} on {dev}")
+    _order_both_ways(pool, dev, lambda: pool.rollout_gae_device(values.data_ptr(), gamma, lam, out[0].data_ptr(),
+                                                                 out[1].data_ptr()))
+    return out[0], out[1]
+
+
+def rollout_episodes_view_device(pool: Any) -> tuple[tuple, Any]:
+    """The finished episodes as torch tensors that alias the buffer -- (env_id int32, step int64, ret float64, length
+    int32, each [episodes]) -- and the int32 [1] count tensor; rows at and above the count are undefined.  Read-only:
+    `pool.rollout_episodes()` drains."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    ptrs, count = pool.rollout_episodes_view_device()
+    n = pool.rollout_capacity
+    _order_both_ways(pool, dev, lambda: None)
+    dtypes = (np.int32, np.int64, np.float64, np.int32)
+    arrays = tuple(torch.as_tensor(_DevArray(p, (n,), d), device=dev) if n else torch.empty(0, device=dev)
+                   for p, d in zip(ptrs, dtypes))
+    return arrays, torch.as_tensor(_DevArray(count, (1,), np.int32), device=dev)
+
+
+def rollout_moments_device(pool: Any) -> Any:
+    """The moment accumulators as a float64 [3, components] tensor that aliases them: count, sum, sumsq."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    ptr, comps = pool.rollout_moments_device()
+    _order_both_ways(pool, dev, lambda: None)
+    return torch.as_tensor(_DevArray(ptr, (3, comps), np.float64), device=dev)

@@ -948,6 +948,57 @@ int epa_record_discard(epa_pool* pool, const int32_t* env_ids, int32_t k);
 int epa_record_counters(epa_pool* pool, int64_t* out);
 int epa_record_end(epa_pool* pool);
 
+/* Rollout collector (csrc/rollout.hip.h is the contract; DESIGN.md section 2 "Rollout collector"): an on-policy
+ * trajectory buffer in device memory that the pool's own step fills, with episode statistics, GAE and observation
+ * moments.  For pools with one row per env and a device step in sync mode: the PGX games and Atari return
+ * EPA_ERR_RUNTIME "rollout not implemented for this environment", an async pool EPA_ERR_INVALID.  N = num_envs,
+ * T = horizon.  The buffers, rows in env id order: one [T+1][N][row] array per state key whose name starts with "obs",
+ * action [T][N][row], reward float32 [T][N], term, trunc, mask uint8 [T][N].
+ *   epa_rollout_begin(horizon >= 1, episodes >= 0, flags): one collector per pool, a new one replaces it; the buffers
+ *     must stay within EPA_ROLLOUT_MAX_BYTES.  EPA_ROLLOUT_MOMENTS: keep count, sum and sum of squares (float64) per
+ *     component of the float obs keys.  While a collector is open epa_reset is refused (EPA_ERR_INVALID).
+ *   epa_rollout_shape(out[8]): T, N, episodes, t (steps collected), obs keys, moment components, the step counter, flags.
+ *   epa_rollout_reset(device, ptrs, n_ptrs, cap_rows, k_out): resets every env, stores the observations into slot 0,
+ *     clears the carried done flags and the episode accumulators, t = 0; then device == 0: what epa_recv does with
+ *     ptrs (host arrays of cap_rows rows), else what epa_recv_device does (ptrs receive device pointers).
+ *   epa_rollout_step(action, out_ptrs, ...) / epa_rollout_step_device(d_action, wait_event, d_out_ptrs, ...): one step of
+ *     every env in id order -- epa_step_device, then the collector's kernels on the pool's stream -- and what epa_recv /
+ *     epa_recv_device returns.  EPA_ERR_INVALID before the first reset, with rows pending, and when t == T.
+ *   epa_rollout_view_device(arrays[n]): the device arrays, obs keys first, then action, reward, term, trunc, mask.
+ *   epa_rollout_batch(out_ptrs[n]): the same arrays copied whole to the host (a null pointer skips its array).
+ *   epa_rollout_gae(values [T+1][N], gamma, lam, adv, ret [T][N]) / _device: needs t == T; gamma, lam in [0, 1].
+ *   epa_rollout_episodes(rows, env_id, step, ret, length, count): the finished episodes (global env id, the step counter
+ *     of the step that ended it, the float64 return, the length) to the host, and the count back to 0; `rows` must equal
+ *     the count (epa_rollout_counters), which *count receives in any case.
+ *   epa_rollout_episodes_view_device(arrays[4], count): the four device arrays over the capacity and the device int32
+ *     count, read-only.
+ *   epa_rollout_moments(out, d_out): [3][components] float64 -- count, sum, sumsq -- to the host (out, may be NULL) and
+ *     the device address of the same (d_out, may be NULL).
+ *   epa_rollout_next(): obs slot t becomes slot 0, t = 0; everything else is kept.
+ *   epa_rollout_counters(out[6]): episode rows, episodes finished and dropped since begin, the step counter, t, and
+ *     whether a reset has run.
+ *   epa_rollout_end(): releases the collector. */
+#define EPA_ROLLOUT_MOMENTS 1u
+#define EPA_ROLLOUT_MAX_BYTES 2147483648ull
+int epa_rollout_begin(epa_pool* pool, int32_t horizon, int32_t episodes, uint32_t flags);
+int epa_rollout_shape(epa_pool* pool, int64_t* out);
+int epa_rollout_reset(epa_pool* pool, int32_t device, void** ptrs, int32_t n_ptrs, int32_t cap_rows, int32_t* k_out);
+int epa_rollout_step(epa_pool* pool, const void* action, void* const* out_ptrs, int32_t n_ptrs, int32_t cap_rows,
+                     int32_t* k_out);
+int epa_rollout_step_device(epa_pool* pool, const void* d_action, void* wait_event, void** d_out_ptrs, int32_t n_ptrs,
+                            int32_t* k_out);
+int epa_rollout_view_device(epa_pool* pool, void** arrays, int32_t n);
+int epa_rollout_batch(epa_pool* pool, void* const* out_ptrs, int32_t n);
+int epa_rollout_gae(epa_pool* pool, const float* values, float gamma, float lam, float* adv, float* ret);
+int epa_rollout_gae_device(epa_pool* pool, const void* d_values, float gamma, float lam, void* d_adv, void* d_ret);
+int epa_rollout_episodes(epa_pool* pool, int32_t rows, int32_t* env_id, int64_t* step, double* ret, int32_t* length,
+                         int32_t* count);
+int epa_rollout_episodes_view_device(epa_pool* pool, void** arrays, void** count);
+int epa_rollout_moments(epa_pool* pool, double* out, void** d_out);
+int epa_rollout_next(epa_pool* pool);
+int epa_rollout_counters(epa_pool* pool, int64_t* out);
+int epa_rollout_end(epa_pool* pool);
+
 /* Self-play driver (no reference analogue; the four PGX board games; csrc/pgx_selfplay.hip.h is the authority): one
  * call plays `plies` plies of EVERY env of a pool against itself with the built-in network as the evaluator, with
  * auto-resets, and -- with `record` -- the finished games land in the pool's open recorder.  Everything is enqueued
