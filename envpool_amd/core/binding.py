@@ -704,6 +704,45 @@ class _ShardedPools:
     def rollout_end(self) -> None:
         self._record_all(lambda p: p.rollout_end())
 
+    # -- rollout actor: one actor per shard.  The noise is keyed by the GLOBAL env id and the collector's step counter,
+    # which every shard counts alike, so the shards' rows are the unsharded pool's --
+    def actor_begin(self, actor: Any, seed: int = 0, deterministic: bool = False, actions: Any = None) -> None:
+        self._record_all(lambda p: p.actor_begin(actor, seed, deterministic, actions))
+
+    def actor_shape(self) -> tuple[int, ...]:
+        return self.pools[0].actor_shape()
+
+    def actor_end(self) -> None:
+        self._record_all(lambda p: p.actor_end())
+
+    def rollout_collect(self, steps: int = 0, wait: bool = True) -> None:
+        self._record_all(lambda p: p.rollout_collect(steps, wait))
+
+    def actor_batch(self) -> tuple[np.ndarray, np.ndarray]:
+        parts = self._record_all(lambda p: p.actor_batch())
+        return np.concatenate([a for a, _ in parts], axis=1), np.concatenate([b for _, b in parts], axis=1)
+
+    def rollout_gae_stored(self, gamma: float, lam: float) -> tuple[np.ndarray, np.ndarray]:
+        parts = self._record_all(lambda p: p.rollout_gae_stored(gamma, lam))
+        return np.concatenate([a for a, _ in parts], axis=1), np.concatenate([b for _, b in parts], axis=1)
+
+    def actor_eval(self, obs: Any, env_ids: Any, step: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Every row by the shard that holds its env."""
+        obs = [obs] if isinstance(obs, np.ndarray) else [np.asarray(o) for o in obs]
+        ids = np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        shard = (ids - self.offset) // self.per
+        bad = ids[(shard < 0) | (shard >= len(self.pools))]
+        if len(bad):
+            raise ValueError(f"env_id {int(bad[0])} out of range")
+        p0 = self.pools[0]
+        action = np.empty((len(ids), *p0.action_shape), dtype=p0.action_dtype)
+        logp, value = np.empty(len(ids), np.float32), np.empty(len(ids), np.float32)
+        for s, p in enumerate(self.pools):
+            idx = np.flatnonzero(shard == s)
+            if len(idx):
+                action[idx], logp[idx], value[idx] = p.actor_eval([o[idx] for o in obs], ids[idx], step)
+        return action, logp, value
+
     # -- self-play driver: one driver per shard; the keys take global env ids, so the shards play the unsharded pool's
     # games --
     def selfplay_begin(self, net: Any, **options: Any) -> None:

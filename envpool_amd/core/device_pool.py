@@ -1142,6 +1142,99 @@ class DevicePool:
         """Closes the collector and releases its device memory; ValueError without one."""
         native.check(self._lib.epa_rollout_end(self._h))
 
+    # -- rollout actor (csrc/actor.hip.h) ----------------------------------------------
+    def actor_begin(self, actor: Any, seed: int = 0, deterministic: bool = False, actions: Any = None) -> None:
+        """Attaches `actor` (envpool_amd.actor.Actor) to the open collector: ValueError without a collector, for a blob
+        of another F, H or kind than the pool's, and when logp and value push the collector past the 2 GiB limit.
+        `actions`: the number of actions of the env's Discrete space (the engine knows the action row, not the count;
+        default: the actor's own)."""
+        if self.players != 1:
+            raise RuntimeError("rollout not implemented for this environment")
+        if not isinstance(deterministic, (bool, np.bool_)):
+            raise ValueError(f"actor: deterministic = {deterministic!r} must be a bool")
+        if getattr(self, "rollout_horizon", None) is not None:
+            obs, act = self.rollout_row_bytes()
+            native.check_rollout(self.rollout_horizon, self.rollout_capacity, False, self.num_envs, obs, act,
+                                 actor=True)
+        blob = actor.blob()
+        low = np.ascontiguousarray(actor.low, np.float64)
+        high = np.ascontiguousarray(actor.high, np.float64)
+        native.check(self._lib.epa_actor_begin(
+            self._h, blob.ctypes.data, blob.nbytes, int(seed) & (2**64 - 1),
+            native.ACTOR_DETERMINISTIC if deterministic else 0, int(actor.actions if actions is None else actions),
+            low.ctypes.data if actor.kind == 1 else None, high.ctypes.data if actor.kind == 1 else None))
+
+    def actor_shape(self) -> tuple[int, ...]:
+        """(F, H, kind, flags) of the attached actor."""
+        out = (ctypes.c_int64 * 4)()
+        native.check(self._lib.epa_actor_shape(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def actor_end(self) -> None:
+        native.check(self._lib.epa_actor_end(self._h))
+
+    def actor_eval(self, obs: Any, env_ids: Any, step: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(action, logp, value) of the attached actor on caller rows: `obs` one array per obs key (or the array, for a
+        single key) with a row per listed global env id, at the collector step counter `step`.  Nothing of the pool
+        changes."""
+        keys = self.rollout_obs_keys()
+        obs = [obs] if isinstance(obs, np.ndarray) else list(obs)
+        ids = np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        if len(obs) != len(keys):
+            raise ValueError(f"actor eval: {len(obs)} observation arrays for {len(keys)} obs keys")
+        rows = []
+        for i, o in zip(keys, obs):
+            _, dtype, shape = self.state_keys[i]
+            o = np.ascontiguousarray(o, dtype=dtype)
+            if o.shape != (len(ids), *shape):
+                raise ValueError(f"actor eval: observation of shape {o.shape} for {(len(ids), *shape)}")
+            rows.append(o)
+        ptrs = (ctypes.c_void_p * len(rows))(*[o.ctypes.data for o in rows])
+        action = np.empty((len(ids), *self.action_shape), dtype=self.action_dtype)
+        logp, value = np.empty(len(ids), np.float32), np.empty(len(ids), np.float32)
+        native.check(self._lib.epa_actor_eval(self._h, ids.ctypes.data, len(ids), int(step), ptrs, len(rows),
+                                              action.ctypes.data, logp.ctypes.data, value.ctypes.data))
+        return action, logp, value
+
+    def actor_eval_device(self, d_obs: list[int], d_env_ids: int, k: int, step: int, d_action: int, d_logp: int,
+                          d_value: int) -> None:
+        """`actor_eval` on raw device addresses: only enqueued on the pool's stream."""
+        ptrs = (ctypes.c_void_p * len(d_obs))(*d_obs)
+        native.check(self._lib.epa_actor_eval_device(self._h, ctypes.c_void_p(d_env_ids), int(k), int(step), ptrs,
+                                                     len(d_obs), ctypes.c_void_p(d_action), ctypes.c_void_p(d_logp),
+                                                     ctypes.c_void_p(d_value)))
+
+    def actor_view_device(self) -> tuple[int, int]:
+        """The raw device addresses of logp float32 [T, N] and value float32 [T + 1, N]."""
+        logp, value = ctypes.c_void_p(), ctypes.c_void_p()
+        native.check(self._lib.epa_actor_view_device(self._h, ctypes.byref(logp), ctypes.byref(value)))
+        return int(logp.value), int(value.value)
+
+    def actor_batch(self) -> tuple[np.ndarray, np.ndarray]:
+        """(logp [T, N], value [T + 1, N]) copied to the host, whole."""
+        t, n = self.rollout_horizon, self.num_envs
+        logp, value = np.empty((t, n), np.float32), np.empty((t + 1, n), np.float32)
+        native.check(self._lib.epa_actor_batch(self._h, logp.ctypes.data, value.ctypes.data))
+        return logp, value
+
+    def rollout_collect(self, steps: int = 0, wait: bool = True) -> None:
+        """`steps` steps of the collector (0: the rest of the horizon) played by the attached actor from C++: features,
+        net, sample, step, store, scan, moments per step, then the value of slot t.  `wait=False` only enqueues."""
+        if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or int(steps) < 0:
+            raise ValueError(f"rollout collect: steps = {steps!r} must be an integer of at least 0")
+        fn = self._lib.epa_rollout_collect if wait else self._lib.epa_rollout_collect_device
+        native.check(fn(self._h, int(steps)))
+
+    def rollout_gae_stored(self, gamma: float, lam: float) -> tuple[np.ndarray, np.ndarray]:
+        """`rollout_gae` with the values the attached actor stored."""
+        t, n = self.rollout_horizon, self.num_envs
+        # (gae's checks of gamma and lam; the values are the device's own)
+        _, _, _, _, gamma, lam = native.check_rollout(1, 0, False, 1, values=np.zeros((2, 1), np.float32),
+                                                      gamma=gamma, lam=lam)
+        adv, ret = np.empty((t, n), dtype=np.float32), np.empty((t, n), dtype=np.float32)
+        native.check(self._lib.epa_rollout_gae(self._h, None, gamma, lam, adv.ctypes.data, ret.ctypes.data))
+        return adv, ret
+
     # -- self-play driver (csrc/pgx_selfplay.hip.h) -----------------------------------
     def selfplay_begin(self, net: Any, **options: Any) -> None:
         """Opens the pool's self-play driver (epa_selfplay_begin) with the built-in network `net` as the evaluator;

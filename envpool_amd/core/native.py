@@ -41,6 +41,7 @@ RECORD_SYMMETRIES = 1    # EPA_RECORD_SYMMETRIES: the flag of a recorder that wr
 RECORD_MAX_PLIES = 256   # EPA_RECORD_MAX_PLIES: the largest max_plies of a recorder (0: 128)
 ROLLOUT_MOMENTS = 1      # EPA_ROLLOUT_MOMENTS: the flag of a rollout collector that keeps observation moments
 ROLLOUT_MAX_BYTES = 1 << 31  # EPA_ROLLOUT_MAX_BYTES: the buffers of one rollout collector
+ACTOR_DETERMINISTIC = 1  # EPA_ACTOR_DETERMINISTIC: a rollout actor that takes the mode of its policy
 SOLVE_MAX_DEPTH = 128    # EPA_SOLVE_MAX_DEPTH: the plies of a solver's longest line
 SOLVE_MAX_TABLE_BITS = 16  # EPA_SOLVE_MAX_TABLE_BITS: a lane's transposition table has at most 2^16 entries
 SOLVE_ILLEGAL = -128     # q of an illegal action, and of every action of a row that is not solved
@@ -222,6 +223,15 @@ def lib() -> ctypes.CDLL:
         "epa_rollout_next": (i32, [vp]),
         "epa_rollout_counters": (i32, [vp, P(ctypes.c_int64)]),
         "epa_rollout_end": (i32, [vp]),
+        "epa_actor_begin": (i32, [vp, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, i32, vp, vp]),
+        "epa_actor_shape": (i32, [vp, P(ctypes.c_int64)]),
+        "epa_actor_end": (i32, [vp]),
+        "epa_actor_eval": (i32, [vp, vp, i32, ctypes.c_int64, P(vp), i32, vp, vp, vp]),
+        "epa_actor_eval_device": (i32, [vp, vp, i32, ctypes.c_int64, P(vp), i32, vp, vp, vp]),
+        "epa_actor_view_device": (i32, [vp, P(vp), P(vp)]),
+        "epa_actor_batch": (i32, [vp, vp, vp]),
+        "epa_rollout_collect": (i32, [vp, i32]),
+        "epa_rollout_collect_device": (i32, [vp, i32]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
         "epa_atari_post_create_ex": (i32, [i32] * 8 + [vp, i32, P(vp)]),
         "epa_atari_create": (i32, [P(EpaAtariConfig), P(vp)]),
@@ -273,6 +283,8 @@ EXPORTED_SYMBOLS = [
     "epa_rollout_view_device", "epa_rollout_batch", "epa_rollout_gae", "epa_rollout_gae_device",
     "epa_rollout_episodes", "epa_rollout_episodes_view_device", "epa_rollout_moments", "epa_rollout_next",
     "epa_rollout_counters", "epa_rollout_end",
+    "epa_actor_begin", "epa_actor_shape", "epa_actor_end", "epa_actor_eval", "epa_actor_eval_device",
+    "epa_actor_view_device", "epa_actor_batch", "epa_rollout_collect", "epa_rollout_collect_device",
     "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_atari_post_create",
@@ -379,13 +391,15 @@ def rollout_bytes(num_envs: int, horizon: int, episodes: int, obs_bytes: int, ac
 
 
 def check_rollout(horizon: Any, episodes: Any = 0, moments: Any = False, num_envs: int = 1, obs_bytes: int = 0,
-                  action_bytes: int = 0, values: Any = None, gamma: Any = None, lam: Any = None) -> tuple:
+                  action_bytes: int = 0, values: Any = None, gamma: Any = None, lam: Any = None,
+                  actor: bool = False) -> tuple:
     """A rollout collector's arguments after the checks every layer makes before the native call, with no device:
     ValueError for a horizon that is no integer of at least 1, episodes that is no integer of at least 0, a `moments`
     that is no bool, and buffers above the 2 GiB limit (`num_envs` envs of `obs_bytes` observation and `action_bytes`
     action bytes each).  With `values` (and `gamma`, `lam`) also gae's arguments: values must be a float32 array of
     shape [horizon + 1, num_envs], gamma and lam numbers in [0, 1].  Returns (horizon, episodes, moments), with values
-    (horizon, episodes, moments, values, gamma, lam) -- gamma and lam rounded to float32."""
+    (horizon, episodes, moments, values, gamma, lam) -- gamma and lam rounded to float32.  `actor`: the limit also
+    counts the logp [T, N] and value [T + 1, N] float32 buffers an attached actor adds (csrc/actor.hip.h)."""
     if isinstance(horizon, (bool, np.bool_)) or not isinstance(horizon, (int, np.integer)) or not 1 <= int(horizon) < 2**31:
         raise ValueError(f"rollout: horizon = {horizon!r} must be an integer of at least 1")
     if isinstance(episodes, (bool, np.bool_)) or not isinstance(episodes, (int, np.integer)) \
@@ -395,6 +409,8 @@ def check_rollout(horizon: Any, episodes: Any = 0, moments: Any = False, num_env
         raise ValueError(f"rollout: moments = {moments!r} must be a bool")
     horizon, episodes, moments = int(horizon), int(episodes), bool(moments)
     total = rollout_bytes(int(num_envs), horizon, episodes, int(obs_bytes), int(action_bytes))
+    if actor:
+        total += 4 * horizon * int(num_envs) + 4 * (horizon + 1) * int(num_envs)
     if total > ROLLOUT_MAX_BYTES:
         raise ValueError(f"rollout: {num_envs} envs over a horizon of {horizon} with {episodes} episode rows need "
                          f"{total} bytes, above the limit of 2 GiB")

@@ -429,6 +429,38 @@ void NetBuildImage(const void* blob, size_t bytes, NetImage* out);
 void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, const unsigned char* obs,
                const unsigned char* mask, const unsigned char* status, float* policy, float* value,
                unsigned int* pending, hipStream_t stream);
+// The rollout actor's form (actor.hip.h): features u8 [rows][F] with bytes 0 .. 127, every row evaluated -> the head's
+// int32 p [rows][A + 1], nothing else
+void NetLaunchRaw(const NetImage& im, const char* d_image, int rows, const unsigned char* features, int32_t* head,
+                  hipStream_t stream);
+// The rollout actor's own kernels (actor.hip; actor.hip.h is the contract), one launch each on `s`.  Every pointer is
+// device memory.
+namespace actor {
+struct FeatureKeys;
+}
+struct ActorSampleArgs {
+  int rows;                     // row i: env id_offset + i, or env_id[i]
+  int H, kind;                  // actor::kDiscrete / kBox
+  int deterministic;
+  int value_only;               // only value [rows] is written
+  int id_offset;
+  const int32_t* env_id;        // global ids [rows], or null
+  long long step;               // the collector's step counter: the noise's
+  uint64_t seed;
+  float scale_p, scale_v;
+  const float* sigma;           // box: [H] each
+  const float* low;
+  const float* high;
+  const int32_t* head;          // [rows][H + 1]
+  void* action;                 // int32 [rows], or the action dtype's [rows][H]
+  int action_dtype;
+  float* logp;                  // [rows]
+  float* value;                 // [rows]
+};
+// obs rows -> features u8 [rows][F], 16-byte stores where the output allows
+void ActorLaunchFeatures(const actor::FeatureKeys& keys, const double* lo, const double* scale, int rows,
+                         unsigned char* out, hipStream_t s);
+void ActorLaunchSample(const ActorSampleArgs& a, hipStream_t s);
 // The pair form (pgx_arena.hip.h).  NetPlanLaunch: PgxNetPlan, the stable partition of `rows` <= 2^20 rows by `side` u8
 // [rows] into order i32 [rows] and n0 i32 [1], with `counts` (NetPlanCountBytes(rows) bytes) as its scratch.
 // NetLaunchPair: one pair PgxNetEval, row r by net side[r] through that plan; both nets of one F and A.
@@ -770,6 +802,29 @@ class Pool {
   void RolloutCounters(int64_t out[6]);  // count, finished, dropped, step counter, t, started
   void RolloutEnd();
 
+  // Rollout actor (include/envpool_amd.h: epa_actor_begin; actor.hip.h is the contract): a built-in actor-critic
+  // attached to the open collector, so that RolloutCollect plays whole steps from C++ -- features of slot t, the int8
+  // trunk (PgxNetEval's raw form), the sample, then exactly what RolloutStep enqueues -- with no host wait in between.
+  // ActorBegin checks the blob (ActorParse) and compares it with the pool: F = the obs keys' components, the action
+  // dtype and row with the blob's kind and H, `actions` (the caller's count of discrete actions, or the Box dimension)
+  // with H; a mismatch, or a pool without an open collector, is std::invalid_argument.  low / high: the Box bounds,
+  // [H] each (ignored for a discrete space).  Its memory -- the net image, lo / scale, sigma and the bounds, the
+  // feature rows, the head's rows, logp [T][N] and value [T+1][N] -- is ONE device allocation of its own, counted with
+  // the collector's in the 2 GiB limit, released by ActorEnd, by the next ActorBegin and with the collector.
+  // RolloutCollect: `steps` steps (0: the rest of the horizon), then the value of slot t; device: only enqueues,
+  // otherwise ONE stream synchronisation at the end.  With an actor attached RolloutGae takes values == nullptr for
+  // the stored ones.  ActorEval, a side operation: (action, logp, value) of k rows of caller observations (one array
+  // per obs key) for the listed global env ids at step counter `step`; nothing of the pool changes.
+  void ActorBegin(const void* blob, size_t bytes, uint64_t seed, unsigned flags, int actions, const double* low,
+                  const double* high);
+  void ActorEnd();
+  void ActorShape(int64_t out[4]);  // F, H, kind, flags of the attached actor
+  void ActorEval(bool device, const int32_t* ids, int k, long long step, const void* const* obs, int n_obs,
+                 void* action, void* logp, void* value);
+  void ActorView(void** logp, void** value);  // the device arrays [T][N] and [T+1][N]
+  void ActorBatch(float* logp, float* value);       // the same, whole, copied to the host
+  void RolloutCollect(int steps, bool device);
+
   // Self-play driver (include/envpool_amd.h: epa_selfplay_begin; the PGX board games, pgx_selfplay.hip.h): plays
   // plies of every env of the pool with a Net as the evaluator, through the device forms of the calls above --
   // GumbelBeginCall / GuidedBeginCall, NetRunCall, *ResultCall, RecordAddCall, SendDevice, RecvDevice, RecordFinishCall --
@@ -1077,6 +1132,25 @@ class Pool {
   void RolloutQuiet(const char* what) const;     // throws unless the result queue is empty
   RolloutStepArgs RolloutArgsOf(const Batch& b) const;
   void RolloutMomentsOf(int slot);               // enqueues the moment kernels for one obs slot
+  // the collector's actor
+  struct Actor {
+    bool open{false};
+    DeviceBlock mem;        // the actor's one device allocation, in the order of `off`
+    NetImage image;
+    int F{0}, H{0}, kind{0};
+    unsigned flags{0};
+    uint64_t seed{0};
+    // offsets into mem: the net image, lo, scale, sigma, low, high, the feature rows [N][F], the head's rows
+    // [N][H + 1], logp [T][N], value [T+1][N], the end
+    size_t off[11]{};
+  };
+  Actor actor_;
+  void ActorFree();
+  void ActorRequire(const char* what) const;     // throws without a collector or without an actor
+  int ActorFeatures() const;                      // F of the pool: the components of the collector's obs keys
+  // enqueues features -> trunk -> sample for `rows` rows on stream_: obs key j's rows at src[j]
+  void ActorEnqueue(const char* const* src, int rows, const int32_t* d_env_id, long long step, bool value_only,
+                    unsigned char* features, int32_t* head, void* action, float* logp, float* value);
   // the pool's self-play driver
   struct Selfplay {
     bool open{false};

@@ -114,7 +114,10 @@ struct NetPlan {
 
 // PAIR: nets.n[1] and plan are read, and the wave's rows are its entries of the plan; otherwise rows row0 .. row0 + 63.
 // A row past the wave's share is `rows`, which every `< rows` test below turns away.
-template <bool PAIR>
+// RAW (the rollout actor, actor.hip.h): the input bytes are features 0 .. 127 and not 0 / 1, every row below `rows` is
+// evaluated (mask and status are not read), and what leaves is the head's int32 p, A + 1 words per row, through
+// `policy`; `value` is not written.  The single form only.
+template <bool PAIR, bool RAW = false>
 __global__ __launch_bounds__(kWave) void PgxNetEval(NetPair nets, NetPlan plan, int rows, int mode,
                                                      const unsigned char* __restrict__ obs,
                                                      const unsigned char* __restrict__ mask,
@@ -133,7 +136,12 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetPair nets, NetPlan plan, 
   const int F = net.F, A = net.A, d_tiles = net.D / 32, f_tiles = (F + 31) / 32, a_tiles = (A + 1 + 31) / 32;
   int my_row = row0 + lane;
   if constexpr (PAIR) my_row = lane < wave.count ? plan.order[row0 + lane] : rows;
-  const int my_status = my_row < rows ? (int)status[my_row] : kGuidedIdle;
+  int my_status = kGuidedIdle;
+  if constexpr (RAW) {
+    my_status = my_row < rows ? pgx::kGuidedEvaluate : kGuidedIdle;
+  } else {
+    my_status = my_row < rows ? (int)status[my_row] : kGuidedIdle;
+  }
   // the run loop's word: some row of the call is not idle (an ordinary atomic of one lane per wave)
   const bool wave_pending = __any(my_status != kGuidedIdle) != 0;
   if (wave_pending && lane == 0 && pending != nullptr) atomicOr(pending, 1u);
@@ -164,7 +172,8 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetPair nets, NetPlan plan, 
                 if (k + b < F) word |= (uint32_t)x[k + b] << (8 * b);
               }
             }
-            frag[g] = (int)(word & 0x01010101u);  // (a bool's byte is 0 or 1; anything else counts as its low bit)
+            // (a bool's byte is 0 or 1; anything else counts as its low bit.  RAW: a feature is 0 .. 127)
+            frag[g] = (int)(word & (RAW ? 0x7f7f7f7fu : 0x01010101u));
           }
         }
         tbuf[(kt * 2 + rt) * kWave + lane] = frag;
@@ -201,13 +210,24 @@ __global__ __launch_bounds__(kWave) void PgxNetEval(NetPair nets, NetPlan plan, 
       }
     }
     __syncthreads();
-    if (my_row < rows) {
-      pgx::NetOutputs(rows_io + lane * stride, mask + (size_t)my_row * A, A, net.scale_p, net.scale_v, mode, my_status);
+    if constexpr (!RAW) {
+      if (my_row < rows) {
+        pgx::NetOutputs(rows_io + lane * stride, mask + (size_t)my_row * A, A, net.scale_p, net.scale_v, mode,
+                        my_status);
+      }
     }
   } else {
     for (int a = 0; a <= A; ++a) rows_io[lane * stride + a] = 0;  // no row of the wave is to be evaluated
   }
   __syncthreads();
+  if constexpr (RAW) {
+    const int n_rows = rows - row0 < kRowsPerWave ? rows - row0 : kRowsPerWave;
+    int32_t* head = reinterpret_cast<int32_t*>(policy);
+    for (int i = lane; i < n_rows * (A + 1); i += kWave) {
+      head[(size_t)row0 * (A + 1) + i] = rows_io[(i / (A + 1)) * stride + i % (A + 1)];
+    }
+    return;
+  }
   if (my_row < rows) value[my_row] = pgx::NetBitsFloat(rows_io[lane * stride + A]);
   if constexpr (PAIR) {
     // entry e's A floats go to its row's own place: consecutive lanes, consecutive floats of a run
@@ -348,6 +368,20 @@ void NetLaunch(const NetImage& im, const char* d_image, int rows, int mode, cons
   const int blocks = (rows + kRowsPerWave - 1) / kRowsPerWave;
   hipLaunchKernelGGL(PgxNetEval<false>, dim3(blocks), dim3(kWave), lds, stream, nets, NetPlan{nullptr, nullptr},
                      rows, mode, obs, mask, status, policy, value, pending);
+}
+
+void NetLaunchRaw(const NetImage& im, const char* d_image, int rows, const unsigned char* features, int32_t* head,
+                  hipStream_t stream) {
+  NetPair nets{};
+  nets.n[0] = DevOf(im, d_image);
+  const size_t lds = LdsBytes(im.F, im.A, im.D);
+  if (lds > 48 * 1024) {
+    EPA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&PgxNetEval<false, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  const int blocks = (rows + kRowsPerWave - 1) / kRowsPerWave;
+  hipLaunchKernelGGL((PgxNetEval<false, true>), dim3(blocks), dim3(kWave), lds, stream, nets, NetPlan{nullptr, nullptr},
+                     rows, 0, features, nullptr, nullptr, reinterpret_cast<float*>(head), nullptr, nullptr);
 }
 
 size_t NetPlanCountBytes(size_t rows) { return 4 * ((rows + kPlanRows - 1) / kPlanRows); }

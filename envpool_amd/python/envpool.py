@@ -143,7 +143,9 @@ class Rollout(NamedTuple):
     """`ro.batch()`: the collected steps, time-major, rows in env id order.  `obs` has t + 1 slots -- slot s + 1 is the
     observation step s returned --, an array for a single obs key and a dict by state key name for several; the others
     have t rows.  `mask[s, n]` is False where step s was the auto-reset step after a done: slot s then holds the final
-    observation of the episode before, the action was ignored and the reward is 0."""
+    observation of the episode before, the action was ignored and the reward is 0.  With an actor attached
+    (`ro.attach`) `logp` [t, N] is the log-probability of each collected action and `value` [t + 1, N] the critic's
+    value of every obs slot, both float32; without one they are None."""
 
     obs: Any
     action: np.ndarray
@@ -151,6 +153,8 @@ class Rollout(NamedTuple):
     term: np.ndarray
     trunc: np.ndarray
     mask: np.ndarray
+    logp: Any = None
+    value: Any = None
 
 
 class Episodes(NamedTuple):
@@ -183,6 +187,7 @@ class RolloutCollector:
         self._env, self._pool, self.horizon = env, pool, horizon
         pool.rollout_begin(horizon, episodes, moments)
         self._names = [pool.state_keys[i][0] for i in pool.rollout_obs_keys()]
+        self._actor: Any = None
 
     def _open(self) -> Any:
         if self._pool is None:
@@ -208,14 +213,64 @@ class RolloutCollector:
     def batch(self) -> Rollout:
         b, t = self._open().rollout_batch(), self.t
         obs = {n: b[n][:t + 1] for n in self._names}
+        logp = value = None
+        if self._actor is not None:
+            logp, value = self._open().actor_batch()
+            logp, value = logp[:t], value[:t + 1]
         return Rollout(obs[self._names[0]] if len(obs) == 1 else obs, b["action"][:t], b["reward"][:t],
-                       b["term"][:t].view(np.bool_), b["trunc"][:t].view(np.bool_), b["mask"][:t].view(np.bool_))
+                       b["term"][:t].view(np.bool_), b["trunc"][:t].view(np.bool_), b["mask"][:t].view(np.bool_),
+                       logp, value)
 
-    def gae(self, values: Any, gamma: float = 0.99, lam: float = 0.95) -> tuple[np.ndarray, np.ndarray]:
+    def gae(self, values: Any = None, gamma: float = 0.99, lam: float = 0.95) -> tuple[np.ndarray, np.ndarray]:
         """(advantages, returns) float32 [T, N] of a full horizon from `values` float32 [T + 1, N]: a terminated step
         does not bootstrap, a truncated one bootstraps from values[t + 1] (the final observation's) and ends the
-        recurrence, a masked step has advantage 0."""
+        recurrence, a masked step has advantage 0.  With an actor attached `values` may be omitted: the values the
+        actor stored are used where they lie."""
+        if values is None:
+            if self._actor is None:
+                raise ValueError("rollout gae: values may only be omitted with an actor attached")
+            return self._open().rollout_gae_stored(gamma, lam)
         return self._open().rollout_gae(values, gamma, lam)
+
+    def attach(self, actor: Any, seed: int = 0, deterministic: bool = False) -> None:
+        """Attaches an `envpool_amd.actor.Actor`: `collect` then plays with it, `batch()` has `logp` and `value`, and
+        `gae()` may use the stored values.  A draw depends on (seed, global env id, the collector's step counter,
+        component) only; `deterministic` takes the mode of the policy.  ValueError for an actor of another F, H or
+        kind than the pool's.  A new actor replaces the one before; closing the collector releases it."""
+        from envpool_amd.actor import space_of
+
+        pool = self._open()
+        want = space_of(self._env)
+        if (actor.features, actor.actions, actor.kind) != (want["features"], want["actions"], want["kind"]):
+            raise ValueError(f"actor: an actor of F = {actor.features}, H = {actor.actions}, kind = {actor.kind} for a "
+                             f"pool of F = {want['features']}, H = {want['actions']}, kind = {want['kind']}")
+        pool.actor_begin(actor, seed, deterministic, want["actions"])
+        self._actor = actor
+
+    def collect(self, steps: Any = None) -> None:
+        """Plays `steps` steps (None: the rest of the horizon) with the attached actor, enqueued from C++ with no
+        Python, torch or host wait between the launches, and waits for the last one.  `collect(a)` then `collect(b)`
+        is `collect(a + b)`; ValueError without an actor, before `reset`, and when the horizon is full."""
+        if self._actor is None:
+            raise ValueError("rollout collect: the collector has no actor (attach one)")
+        if steps is not None and (isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer))
+                                  or int(steps) < 1):
+            raise ValueError(f"rollout collect: steps = {steps!r} must be None or an integer of at least 1")
+        self._open().rollout_collect(0 if steps is None else int(steps))
+
+    def actor_eval(self, obs: Any, env_ids: Any = None, step: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(action, logp, value) of the attached actor on caller observations (the array of a single obs key, or a dict
+        by state key name) for `env_ids` (default: the pool's, in order) at the step counter `step` (default: the
+        collector's): what `collect` would compute for these rows.  Nothing of the pool changes."""
+        if self._actor is None:
+            raise ValueError("rollout actor_eval: the collector has no actor (attach one)")
+        pool = self._open()
+        arrays = [obs[n] for n in self._names] if isinstance(obs, dict) else [np.asarray(obs)]
+        if env_ids is None:
+            env_ids = self._env.all_env_ids
+        if step is None:
+            step = self.counters["steps"]
+        return pool.actor_eval(arrays, env_ids, int(step))
 
     def episodes(self) -> Episodes:
         return Episodes(*self._open().rollout_episodes())

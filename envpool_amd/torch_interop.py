@@ -668,3 +668,52 @@ def rollout_moments_device(pool: Any) -> Any:
     ptr, comps = pool.rollout_moments_device()
     _order_both_ways(pool, dev, lambda: None)
     return torch.as_tensor(_DevArray(ptr, (3, comps), np.float64), device=dev)
+
+
+def rollout_collect_device(pool: Any, steps: int = 0) -> None:
+    """`pool.rollout_collect` on the device path: `steps` steps (0: the rest of the horizon) of the attached actor are
+    enqueued behind torch's current stream and nothing waits; the current stream then waits for the pool's stream."""
+    import torch
+
+    _order_both_ways(pool, torch.device("cuda", pool.device), lambda: pool.rollout_collect(steps, wait=False))
+
+
+def actor_view_device(pool: Any) -> tuple[Any, Any]:
+    """(logp float32 [T, N], value float32 [T + 1, N]) of the attached actor as tensors that alias the buffers."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    logp, value = pool.actor_view_device()
+    t, n = pool.rollout_horizon, pool.num_envs
+    _order_both_ways(pool, dev, lambda: None)
+    return (torch.as_tensor(_DevArray(logp, (t, n), np.float32), device=dev),
+            torch.as_tensor(_DevArray(value, (t + 1, n), np.float32), device=dev))
+
+
+def actor_eval_device(pool: Any, obs: Any, env_ids: Any, step: int) -> tuple[Any, Any, Any]:
+    """`pool.actor_eval` on tensors of the pool's device: `obs` one contiguous tensor per obs key (or the tensor, for
+    a single key) of the key's dtype with a row per env id, `env_ids` int32 [k] global ids.  Returns (action, logp,
+    value) tensors; only enqueued, ordered both ways with torch's current stream."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    keys = pool.rollout_obs_keys()
+    k = int(env_ids.numel())
+    if env_ids.dtype != torch.int32 or not env_ids.is_contiguous() or env_ids.device != dev or k < 1:
+        raise ValueError(f"actor_eval_device: env_ids must be a contiguous int32 tensor on {dev}")
+    if len(obs) != len(keys):
+        raise ValueError(f"actor_eval_device: {len(obs)} observation tensors for {len(keys)} obs keys")
+    for i, o in zip(keys, obs):
+        _, dtype, shape = pool.state_keys[i]
+        if o.dtype != _torch_dtype(dtype) or not o.is_contiguous() or o.device != dev \
+                or o.numel() != k * int(np.prod(shape, dtype=np.int64)):
+            raise ValueError(f"actor_eval_device: an observation must be a contiguous {np.dtype(dtype)} tensor of "
+                             f"{(k, *shape)} on {dev}")
+    action = torch.empty((k, *pool.action_shape), dtype=_torch_dtype(pool.action_dtype), device=dev)
+    logp = torch.empty((k,), dtype=torch.float32, device=dev)
+    value = torch.empty((k,), dtype=torch.float32, device=dev)
+    _order_both_ways(pool, dev, lambda: pool.actor_eval_device([o.data_ptr() for o in obs], env_ids.data_ptr(), k,
+                                                               int(step), action.data_ptr(), logp.data_ptr(),
+                                                               value.data_ptr()))
+    return action, logp, value

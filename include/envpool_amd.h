@@ -999,6 +999,43 @@ int epa_rollout_next(epa_pool* pool);
 int epa_rollout_counters(epa_pool* pool, int64_t* out);
 int epa_rollout_end(epa_pool* pool);
 
+/* Rollout actor (csrc/actor.hip.h is the contract; DESIGN.md section 2 "Rollout actor and collect"): a built-in int8
+ * actor-critic attached to the pool's open collector, so that a whole horizon is played from C++ with nothing between
+ * the launches.  The blob: magic "EPAA", version 1, F, H, D, L, kind, scale_p, scale_v, lo[F], scale[F] float64,
+ * sigma[H] float32 (EPA_ACTOR_BOX only), then the layer section of a network blob (epa_net_create).
+ *   epa_actor_begin(blob, bytes, seed, flags, actions, low, high): checks the blob and compares it with the pool -- F =
+ *     the components of the collector's obs keys (at most 512), kind and H with the action row, `actions` (the number
+ *     of discrete actions, or the Box dimension) with H; low / high: the Box bounds, float64 [H] (NULL for a discrete
+ *     space).  EPA_ERR_INVALID on a mismatch and without an open collector.  It adds logp float32 [T][N] and value
+ *     float32 [T+1][N] to the collector, counted in EPA_ROLLOUT_MAX_BYTES.  EPA_ACTOR_DETERMINISTIC: the mode of the
+ *     policy instead of a sample.  One actor per collector; a new one replaces it, and it goes with the collector.
+ *   epa_actor_shape(out[4]): F, H, kind, flags.
+ *   epa_rollout_collect(steps) / _device: `steps` steps (0: the rest of the horizon) of features of slot t, the net, the
+ *     sample and what epa_rollout_step_device enqueues, then the value of slot t; the host form waits for the stream
+ *     once, the device form only enqueues.  EPA_ERR_INVALID before the first reset, with rows pending, when t == T and
+ *     when t + steps > T.
+ *   epa_actor_eval(env_ids, k, step, obs[n_obs], action, logp, value) / _device: the actor on k rows of caller
+ *     observations (one array per obs key, rows of the key's shape) for the listed global env ids at step counter
+ *     `step`: the action rows of the pool's action dtype, logp and value float32 [k].  Nothing of the pool changes.
+ *   epa_actor_view_device(logp, value): the device arrays.  epa_actor_batch(logp, value): copied whole to the host
+ *     (NULL skips one).  epa_rollout_gae with values == NULL takes the stored values.
+ *   epa_actor_end(): releases the actor. */
+#define EPA_ACTOR_DETERMINISTIC 1u
+#define EPA_ACTOR_DISCRETE 0
+#define EPA_ACTOR_BOX 1
+int epa_actor_begin(epa_pool* pool, const void* blob, size_t bytes, uint64_t seed, uint32_t flags, int32_t actions,
+                    const double* low, const double* high);
+int epa_actor_shape(epa_pool* pool, int64_t* out);
+int epa_actor_end(epa_pool* pool);
+int epa_actor_eval(epa_pool* pool, const int32_t* env_ids, int32_t k, int64_t step, const void* const* obs,
+                   int32_t n_obs, void* action, float* logp, float* value);
+int epa_actor_eval_device(epa_pool* pool, const void* d_env_ids, int32_t k, int64_t step, const void* const* d_obs,
+                          int32_t n_obs, void* d_action, void* d_logp, void* d_value);
+int epa_actor_view_device(epa_pool* pool, void** logp, void** value);
+int epa_actor_batch(epa_pool* pool, float* logp, float* value);
+int epa_rollout_collect(epa_pool* pool, int32_t steps);
+int epa_rollout_collect_device(epa_pool* pool, int32_t steps);
+
 /* Self-play driver (no reference analogue; the four PGX board games; csrc/pgx_selfplay.hip.h is the authority): one
  * call plays `plies` plies of EVERY env of a pool against itself with the built-in network as the evaluator, with
  * auto-resets, and -- with `record` -- the finished games land in the pool's open recorder.  Everything is enqueued
