@@ -777,6 +777,10 @@ class _ShardedPools:
     def selfplay_end(self) -> None:
         self._record_all(lambda p: p.selfplay_end())
 
+    def selfplay_noise(self) -> np.ndarray:
+        """The shards' noise rows in env order."""
+        return np.concatenate(self._record_all(lambda p: p.selfplay_noise()), axis=0)
+
     # -- arena: one per shard; the sides take GLOBAL env ids (every shard knows its offset), so the shards play the
     # unsharded pool's match.  selfplay_run and selfplay_end above drive and close it --
     def arena_begin(self, net_a: Any, net_b: Any, **options: Any) -> None:

@@ -1240,9 +1240,10 @@ class DevicePool:
         """Opens the pool's self-play driver (epa_selfplay_begin) with the built-in network `net` as the evaluator;
         `options` are `native.check_selfplay`'s.  A pool has one driver; a new one replaces it.  It needs a pool in
         sync mode with nothing pending in its result queue, and with `record` an open recorder."""
-        o = native.check_selfplay(**options)
+        o, x = native.check_selfplay(**options), native.selfplay_extra_of(options)
         self.guided_shape()
-        native.check(self._lib.epa_selfplay_begin(self._h, net._handle(self.device), ctypes.byref(o)))
+        native.check(self._lib.epa_selfplay_begin_ex(self._h, net._handle(self.device), None, ctypes.byref(o),
+                                                     ctypes.byref(x)))
         self._selfplay_net = net  # (the driver uses the net's device copy: it must live as long)
 
     def selfplay_run(self, plies: int, wait: bool = True) -> None:
@@ -1264,6 +1265,14 @@ class DevicePool:
         """Closes the driver and releases its device memory; ValueError without one.  The recorder stays open."""
         native.check(self._lib.epa_selfplay_end(self._h))
         self._selfplay_net = None
+
+    def selfplay_noise(self) -> np.ndarray:
+        """float32 [num_envs, A]: the host copy of the last ply's noise rows (epa_selfplay_noise) -- the Dirichlet eta
+        of a PUCT driver (zeros without `dirichlet_alpha`, and before the first ply), the Gumbel rows of a Gumbel
+        driver; waits for the device."""
+        out = np.zeros((self.num_envs, self.guided_shape()[3]), dtype=np.float32)
+        native.check(self._lib.epa_selfplay_noise(self._h, ctypes.c_void_p(out.ctypes.data)))
+        return out
 
     # -- arena (csrc/pgx_arena.hip.h) ---------------------------------------------------
     def net_eval_pair(self, net_a: Any, net_b: Any, obs: Any, mask: Any, status: Any, side: Any,
@@ -1297,10 +1306,10 @@ class DevicePool:
         """Opens the pool's driver as an arena (epa_arena_begin): `net_a` moves for seat (e & 1) of the env with global
         id e and `net_b` for the other seat.  `options` are `native.check_arena`'s: `selfplay_begin`'s, with `record`
         False by default.  `selfplay_run` and `selfplay_end` drive and close it."""
-        o = native.check_arena(net_a, net_b, **options)
+        o, x = native.check_arena(net_a, net_b, **options), native.selfplay_extra_of(options)
         self.guided_shape()
-        native.check(self._lib.epa_arena_begin(self._h, net_a._handle(self.device), net_b._handle(self.device),
-                                               ctypes.byref(o)))
+        native.check(self._lib.epa_selfplay_begin_ex(self._h, net_a._handle(self.device), net_b._handle(self.device),
+                                                     ctypes.byref(o), ctypes.byref(x)))
         self._selfplay_net = (net_a, net_b)  # (the driver uses the nets' device copies: they must live as long)
 
     def arena_run(self, plies: int, wait: bool = True) -> None:

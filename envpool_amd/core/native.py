@@ -192,6 +192,8 @@ def lib() -> ctypes.CDLL:
         "epa_selfplay_run_device": (i32, [vp, i32]),
         "epa_selfplay_stats": (i32, [vp, P(ctypes.c_int64)]),
         "epa_selfplay_end": (i32, [vp]),
+        "epa_selfplay_begin_ex": (i32, [vp, vp, vp, P(SelfplayOptions), P(SelfplayExtra)]),
+        "epa_selfplay_noise": (i32, [vp, vp]),
         "epa_net_eval_pair": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         "epa_net_eval_pair_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         "epa_arena_begin": (i32, [vp, vp, vp, P(SelfplayOptions)]),
@@ -287,6 +289,7 @@ EXPORTED_SYMBOLS = [
     "epa_actor_view_device", "epa_actor_batch", "epa_rollout_collect", "epa_rollout_collect_device",
     "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
+    "epa_selfplay_begin_ex", "epa_selfplay_noise",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -659,29 +662,73 @@ class SelfplayOptions(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class SelfplayExtra(ctypes.Structure):
+    """epa_selfplay_extra (include/envpool_amd.h): the PUCT exploration of a driver or an arena."""
+
+    _fields_ = [("dirichlet_alpha", ctypes.c_float), ("dirichlet_eps", ctypes.c_float),
+                ("temperature", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 SELFPLAY_GUMBEL = 0  # EPA_SELFPLAY_GUMBEL / EPA_SELFPLAY_PUCT: the policies of a self-play driver
 SELFPLAY_PUCT = 1
 # the options of `selfplay` that belong to one policy, with the value that means "not given"
 _SELFPLAY_GUMBEL_ONLY = {"max_considered": None, "c_visit": None, "c_scale": None, "batch": 1, "noise": None}
 _SELFPLAY_PUCT_ONLY = {"c_puct": None, "width": 1, "tactics": 0, "tactics_nodes": None, "prove": False,
-                       "sample_plies": 0}
+                       "sample_plies": 0, "dirichlet_alpha": 0.0, "dirichlet_eps": 0.25, "temperature": 1.0}
+DIRICHLET_MAX_ALPHA = 100.0  # csrc/pgx_dirichlet.hip.h: kDirichletMaxAlpha, kTemperatureMin, kTemperatureMax
+TEMPERATURE_RANGE = (0.05, 20.0)
+
+
+def check_selfplay_extra(policy: Any = "puct", dirichlet_alpha: Any = 0.0, dirichlet_eps: Any = 0.25,
+                         temperature: Any = 1.0) -> SelfplayExtra:
+    """The PUCT exploration of a selfplay_begin or arena_begin call as the C struct (epa_selfplay_extra), after the
+    checks every layer makes before the native call.  ValueError for a `dirichlet_alpha` that is not finite or outside
+    0 .. 100, a `dirichlet_eps` outside 0 .. 1, a `temperature` outside 0.05 .. 20 -- as float32, the values the
+    engine sees -- and for any of them other than its default with policy='gumbel'.  Without noise
+    (`dirichlet_alpha == 0`) the struct's eps is 0: {0, 0, 1, 0} is the plain driver."""
+    if policy not in ("gumbel", "puct"):
+        raise ValueError(f"selfplay: policy = {policy!r} must be 'puct' or 'gumbel'")
+    given = dict(dirichlet_alpha=dirichlet_alpha, dirichlet_eps=dirichlet_eps, temperature=temperature)
+    vals = {}
+    for name, value in given.items():
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError(f"selfplay: {name} = {value!r} must be a number")
+        with np.errstate(over="ignore"):
+            vals[name] = float(np.float32(value))
+    if policy == "gumbel":
+        stray = sorted(n for n in given if not vals[n] == float(np.float32(_SELFPLAY_PUCT_ONLY[n])))
+        if stray:
+            raise ValueError(f"selfplay: {stray} are arguments of policy='puct'")
+        return SelfplayExtra(0.0, 0.0, 1.0, 0)
+    a, e, t = vals["dirichlet_alpha"], vals["dirichlet_eps"], vals["temperature"]
+    if not 0.0 <= a <= DIRICHLET_MAX_ALPHA:
+        raise ValueError(f"selfplay: dirichlet_alpha = {dirichlet_alpha} must be finite and in 0 .. 100")
+    if not 0.0 <= e <= 1.0:
+        raise ValueError(f"selfplay: dirichlet_eps = {dirichlet_eps} must be in 0 .. 1")
+    if not float(np.float32(TEMPERATURE_RANGE[0])) <= t <= TEMPERATURE_RANGE[1]:
+        raise ValueError(f"selfplay: temperature = {temperature} must be in 0.05 .. 20")
+    return SelfplayExtra(a, e if a > 0.0 else 0.0, t, 0)
 
 
 def check_selfplay(policy: Any = "gumbel", simulations: Any = 32, max_considered: Any = None, c_visit: Any = None,
                    c_scale: Any = None, batch: Any = 1, c_puct: Any = None, width: Any = 1, tactics: Any = 0,
                    tactics_nodes: Any = None, prove: Any = False, seed: Any = 0, noise: Any = None,
-                   sample_plies: Any = 0, record: Any = True) -> SelfplayOptions:
+                   sample_plies: Any = 0, record: Any = True, dirichlet_alpha: Any = 0.0, dirichlet_eps: Any = 0.25,
+                   temperature: Any = 1.0) -> SelfplayOptions:
     """The options of a selfplay_begin call as the C struct, after the checks every layer makes before the native call.
     ValueError for an unknown policy; for an option of the other policy, worded as `guided_search` words it; for a seed
     outside 0 .. 2^64 - 1, a `noise` or `record` that is no bool, a `sample_plies` that is no integer >= 0; and for the
     option values the policy's own begin refuses (`check_gumbel`, `check_gumbel_batch`, `check_guided`,
     `check_guided_width`, `check_guided_tactics`, `check_guided_prove`).  Defaults are the searches': max_considered 16,
-    c_visit 50, c_scale 0.1, c_puct 1.25, noise on."""
+    c_visit 50, c_scale 0.1, c_puct 1.25, noise on.  `dirichlet_alpha`, `dirichlet_eps` and `temperature` are
+    `check_selfplay_extra`'s (policy='puct'), which makes their struct."""
     given = dict(max_considered=max_considered, c_visit=c_visit, c_scale=c_scale, batch=batch, noise=noise,
                  c_puct=c_puct, width=width, tactics=tactics, tactics_nodes=tactics_nodes, prove=prove,
-                 sample_plies=sample_plies)
+                 sample_plies=sample_plies, dirichlet_alpha=dirichlet_alpha, dirichlet_eps=dirichlet_eps,
+                 temperature=temperature)
     if policy not in ("gumbel", "puct"):
         raise ValueError(f"selfplay: policy = {policy!r} must be 'puct' or 'gumbel'")
+    check_selfplay_extra(policy, dirichlet_alpha, dirichlet_eps, temperature)
     theirs = _SELFPLAY_PUCT_ONLY if policy == "gumbel" else _SELFPLAY_GUMBEL_ONLY
     stray = sorted(name for name, unset in theirs.items() if given[name] is not None and given[name] != unset)
     if stray:
@@ -730,6 +777,12 @@ def check_arena(net_a: Any, net_b: Any, record: Any = False, **options: Any) -> 
         raise ValueError(f"arena: net_a has F = {int(net_a.inputs)}, A = {int(net_a.actions)} and net_b F = "
                          f"{int(net_b.inputs)}, A = {int(net_b.actions)}: the two nets must agree in both")
     return check_selfplay(record=record, **options)
+
+
+def selfplay_extra_of(options: dict) -> SelfplayExtra:
+    """`check_selfplay_extra` of a dict of `check_selfplay`'s options."""
+    return check_selfplay_extra(options.get("policy", "gumbel"), options.get("dirichlet_alpha", 0.0),
+                                options.get("dirichlet_eps", 0.25), options.get("temperature", 1.0))
 
 
 def check_arena_side(side: Any, rows: int) -> np.ndarray:

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <atomic>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -521,14 +522,23 @@ struct SelfplayArgs {
   int arena;                    // tally: 0 / 1, the seven counters of pgx_arena.hip.h
   int slots;                    // arena sides: leaf rows per env
   unsigned char* side;          // arena sides: [k * slots] out
+  // PUCT exploration (pgx_dirichlet.hip.h)
+  float alpha, gamma_d, gamma_c;  // dirichlet: alpha and the host-rounded d and c of its sampler
+  float eps;                      // dirichlet: the mix
+  float temperature;              // move, PUCT: 1 is the plain rule
+  const unsigned char* mask;      // dirichlet: the leaf rows' legal actions [k * slots][A]
+  const unsigned char* status;    // dirichlet: the leaf rows' status [k * slots]
+  float* prior;                   // dirichlet: the evaluator's policy rows [k * slots][A], mixed in place
 };
 
 // What a driver is opened with (include/envpool_amd.h: epa_selfplay_options)
 using SelfplayOptions = epa_selfplay_options;
+using SelfplayExtra = epa_selfplay_extra;  // (epa_selfplay_begin_ex; {0, 0, 1, 0} is the plain driver)
 // The driver's kernels (pgx_selfplay.hip) for PGX game `game` (pgx::kTicTacToe ...), one launch each on `stream`
 void PgxSelfplayLaunchNoise(int game, const SelfplayArgs& a, hipStream_t stream);
 void PgxSelfplayLaunchMove(int game, const SelfplayArgs& a, hipStream_t stream);
 void PgxSelfplayLaunchTally(const SelfplayArgs& a, hipStream_t stream);  // (a.arena: PgxArenaTally)
+void PgxSelfplayLaunchDirichlet(int game, const SelfplayArgs& a, hipStream_t stream);
 
 class Pool {
  public:
@@ -735,7 +745,11 @@ class Pool {
   // one read of the pending word per pair.  Returns the pairs made.
   void NetEvalCall(Net& net, int rows, int mode, const void* obs, const void* mask, const void* status, void* policy,
                    void* value, bool device);
-  int NetRunCall(Net& net, int advances, void* obs, void* mask, void* status, bool device);
+  // `after_first` (the self-play driver's Dirichlet mix): called once, with the lock held and the side operation
+  // entered, behind the call's first evaluation and before its first advance, with the policy rows it may change.
+  using NetRunHook = std::function<void(float* policy)>;
+  int NetRunCall(Net& net, int advances, void* obs, void* mask, void* status, bool device,
+                 const NetRunHook* after_first = nullptr);
   // The pair forms (pgx_arena.hip.h): row r is evaluated by net_a where side[r] == 0 and by net_b where it is 1; both
   // nets pass NetRequire and so agree in F and A.  NetEvalPairCall: PgxNetPlan + one pair PgxNetEval of `rows` <= 2^20
   // caller rows with the caller's side bytes (host form: a byte other than 0 / 1 is refused; staged like
@@ -743,7 +757,8 @@ class Pool {
   // fixed for the call: the plan is made once, and policy / value rows and the plan live in net_a's allocation.
   void NetEvalPairCall(Net& net_a, Net& net_b, int rows, int mode, const void* obs, const void* mask,
                        const void* status, const void* side, void* policy, void* value, bool device);
-  int NetRunPairCall(Net& net_a, Net& net_b, int advances, void* obs, void* mask, void* status, const void* side);
+  int NetRunPairCall(Net& net_a, Net& net_b, int advances, void* obs, void* mask, void* status, const void* side,
+                     const NetRunHook* after_first = nullptr);
 
   // Self-play recorder (include/envpool_amd.h: epa_record_begin; the PGX board games, pgx_record.hip.h): stages every
   // env's positions and policy targets while its game runs and turns a finished game into training samples in a
@@ -828,7 +843,7 @@ class Pool {
   // Self-play driver (include/envpool_amd.h: epa_selfplay_begin; the PGX board games, pgx_selfplay.hip.h): plays
   // plies of every env of the pool with a Net as the evaluator, through the device forms of the calls above --
   // GumbelBeginCall / GuidedBeginCall, NetRunCall, *ResultCall, RecordAddCall, SendDevice, RecvDevice, RecordFinishCall --
-  // and three launches of its own in between.  A pool has at most one driver.  Its memory -- noise, leaf arrays, result
+  // and three launches of its own in between (four with Dirichlet root noise).  A pool has at most one driver.  Its memory -- noise, leaf arrays, result
   // arrays, action row, target rows, counters -- is ONE device allocation of its own with a single owner, released by
   // SelfplayEnd, by the next SelfplayBegin and by ~Pool; it coexists with the session (which the driver opens ply by
   // ply, and whose last one stays open) and the recorder.  SelfplayRun only enqueues (device == false: then waits for
@@ -844,7 +859,13 @@ class Pool {
   virtual void SelfplayMove(const SelfplayArgs& a);
   virtual void SelfplayTally(const SelfplayArgs& a);
   virtual void ArenaSides(const SelfplayArgs& a);
-  void SelfplayBegin(Net& net, const SelfplayOptions& o, Net* net_b = nullptr, const char* what = "selfplay_begin");
+  // PUCT exploration (pgx_dirichlet.hip.h): `extra` (null: {0, 0, 1, 0}, the plain driver) adds Dirichlet root noise,
+  // one launch (SelfplayDirichlet) between the round's first evaluation and its first advance, and a move temperature.
+  // SelfplayNoiseRows: the host copy of the last ply's noise rows [N][A] (eta; a Gumbel driver: its Gumbel rows).
+  virtual void SelfplayDirichlet(const SelfplayArgs& a);
+  void SelfplayBegin(Net& net, const SelfplayOptions& o, Net* net_b = nullptr, const char* what = "selfplay_begin",
+                     const SelfplayExtra* extra = nullptr);
+  void SelfplayNoiseRows(float* out);
   void SelfplayRun(int plies, bool device);
   void SelfplayStats(int64_t out[6]);  // games, wins0, wins1, draws, plies, t
   void ArenaStats(int64_t out[8]);     // games, wins0, wins1, draws, plies, wins_a, wins_b, t: an arena only
@@ -1158,6 +1179,8 @@ class Pool {
     Net* net{nullptr};
     Net* net_b{nullptr};    // an arena: the net of side 1
     SelfplayOptions o{};
+    SelfplayExtra x{0.0f, 0.0f, 1.0f, 0};
+    size_t noise_bytes{0};  // of the noise rows [N][A]
     uint32_t t{0};          // the ply counter
     std::vector<int32_t> ids;  // the pool's global ids in order
     // offsets into mem: noise, obs, mask, status (the leaf arrays, one row per root or slot), visits, vals, result
@@ -1167,7 +1190,7 @@ class Pool {
   };
   Selfplay selfplay_;
   int NetRunImpl(Net& net, Net* net_b, int advances, void* obs, void* mask, void* status, const void* side,
-                 bool device, const char* what);        // NetRunCall and NetRunPairCall
+                 bool device, const char* what, const NetRunHook* after_first);  // NetRunCall and NetRunPairCall
   void SelfplayFree();                                  // (no driver: nothing)
   void SelfplayPly();                                   // one ply, enqueued
   uint64_t family_hash_{0};

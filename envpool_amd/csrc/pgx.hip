@@ -34,7 +34,8 @@
 // tactics (PgxGuidedTactics, a launch behind every advance: a wave per slot solves the slot's new leaf).
 // Self-play recorder: pgx_record.hip.h, finished games as training samples in the recorder's own memory (PgxRecordAdd /
 // PgxRecordPlan / PgxRecordEmit).
-// Self-play driver: pgx_selfplay.hip.h; its three kernels live in pgx_selfplay.hip, PgxPool only forwards the launches.
+// Self-play driver: pgx_selfplay.hip.h and pgx_dirichlet.hip.h; its kernels live in pgx_selfplay.hip, PgxPool only
+// forwards the launches.
 #include <algorithm>
 #include <string>
 
@@ -1881,6 +1882,7 @@ class PgxPool : public Pool {
     PgxSelfplayLaunchMove(G, b, stream_);
   }
   void SelfplayTally(const SelfplayArgs& a) override { PgxSelfplayLaunchTally(a, stream_); }
+  void SelfplayDirichlet(const SelfplayArgs& a) override { PgxSelfplayLaunchDirichlet(G, a, stream_); }
   void ArenaSides(const SelfplayArgs& a) override {
     hipLaunchKernelGGL(PgxArenaSides<G>, dim3((a.k + kBlock - 1) / kBlock), dim3(kBlock), 0, stream_, state_, a);
   }

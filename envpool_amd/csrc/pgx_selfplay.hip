@@ -14,11 +14,21 @@
 //   PgxSelfplayTally  one thread per row, a wave butterfly over the five integers, then lane 0's atomics on the
 //                     int64 counters (a wave that saw no finished game adds nothing).  <true>, an arena's: the seven
 //                     counters of pgx_arena.hip.h, wins_a and wins_b by the parity of the row's global env id.
+// PUCT exploration (pgx_dirichlet.hip.h is the contract):
+//   PgxSelfplayDirichlet  a row belongs to the GROUP of PgxSelfplayMove<PUCT> (LG lanes, E consecutive actions per
+//                     lane).  A lane runs the rejection loop of each of its legal actions -- divergent, but almost
+//                     every action accepts its first attempt --, adds its run in ascending order, and the group's
+//                     __shfl_xor butterfly gives every lane S.  It stores eta to the noise rows and mixes it into the
+//                     policy row of the root's leaf row (slot 0 of a width session) where the root's status is 0.
+//                     Every lane stays active through the shuffles; loads and stores are predicated.
+//   PgxSelfplayMoveTemp   PgxSelfplayMove<PUCT> for a temperature T != 1: vmax by a butterfly, the lanes' q, and the
+//                     sampled move from the scan of q.  The target rows and the greedy move are PgxSelfplayMove's.
 #include <algorithm>
 #include <climits>
 
 #include "engine.h"
 #include "pgx_arena.hip.h"
+#include "pgx_dirichlet.hip.h"
 #include "pgx_env.hip.h"
 #include "pgx_selfplay.hip.h"
 
@@ -117,6 +127,116 @@ __global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayMove(SelfplayArgs a
   }
 }
 
+// Dirichlet root noise of a PUCT driver: eta to the noise rows, mixed into the roots' policy rows in place
+template <int G>
+__global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayDirichlet(SelfplayArgs a) {
+  constexpr int A = pgx::Dims<G>::A;
+  constexpr int LG = SelfplayGroup<G>(), E = (A + LG - 1) / LG;
+  static_assert(LG == pgx::DirichletGroup(A) && E == pgx::DirichletRun(A), "the contract's summation order");
+  const int g = (int)(((long long)blockIdx.x * kSelfplayBlock + threadIdx.x) / LG), j = threadIdx.x & (LG - 1);
+  const bool live = g < a.k;
+  const int row = live ? g : 0;
+  const size_t leaf = (size_t)row * a.slots;  // the root's own leaf row: slot 0
+  const uint64_t key = pgx::SelfplayKey(a.seed, row + a.id_offset, a.t);
+  const pgx::DirichletParams prm{a.alpha, a.gamma_d, a.gamma_c};
+  float gm[E];
+  bool legal[E];
+  float S = 0.0f;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const int act = j * E + i;
+    legal[i] = live && act < A && a.mask[leaf * A + act] != 0;
+    gm[i] = legal[i] ? pgx::DirichletGamma(key, act, prm, nullptr) : 0.0f;
+    S = S + gm[i];
+  }
+#pragma unroll
+  for (int w = LG / 2; w >= 1; w >>= 1) S = S + __shfl_xor(S, w, LG);
+  const bool mix = live && a.status[leaf] == 0;
+  const float om = 1.0f - a.eps;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const int act = j * E + i;
+    if (live && act < A) {
+      const float eta = legal[i] ? pgx::DirichletEta(gm[i], S) : 0.0f;
+      a.gumbel[(size_t)row * A + act] = eta;
+      if (mix && legal[i]) a.prior[leaf * A + act] = pgx::DirichletMix(a.prior[leaf * A + act], eta, om, a.eps);
+    }
+  }
+}
+
+// PgxSelfplayMove<G, PUCT> with a temperature T != 1 (pgx_dirichlet.hip.h: SelfplayPuctMoveTemp)
+template <int G>
+__global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayMoveTemp(SelfplayArgs a) {
+  constexpr int A = pgx::Dims<G>::A;
+  constexpr int LG = SelfplayGroup<G>(), E = (A + LG - 1) / LG;
+  const int g = (int)(((long long)blockIdx.x * kSelfplayBlock + threadIdx.x) / LG), j = threadIdx.x & (LG - 1);
+  const bool live = g < a.k;
+  const int row = live ? g : 0;
+  int v[E];
+  int V = 0, vmax = 0;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const int act = j * E + i;
+    v[i] = (live && act < A) ? a.visits[(size_t)row * A + act] : 0;
+    V += v[i];
+    vmax = std::max(vmax, v[i]);
+  }
+#pragma unroll
+  for (int w = LG / 2; w >= 1; w >>= 1) {
+    V += __shfl_xor(V, w, LG);
+    vmax = std::max(vmax, __shfl_xor(vmax, w, LG));
+  }
+  const bool zero = V == 0 || (live && a.result_action[row] < 0);
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    const int act = j * E + i;
+    if (live && act < A) a.target[(size_t)row * A + act] = zero ? 0.0f : pgx::SelfplayTarget(v[i], V);
+  }
+  // the sampled move: the lowest action whose prefix sum of q exceeds r ...
+  uint32_t q[E];
+  uint32_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    q[i] = pgx::TemperatureWeight(v[i], vmax, a.temperature);
+    mine += q[i];
+  }
+  uint32_t x = mine;  // the group's inclusive scan of the lanes' totals
+#pragma unroll
+  for (int d = 1; d < LG; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d, LG);
+    if (j >= d) x += y;
+  }
+  const uint32_t Q = __shfl(x, LG - 1, LG);
+  const bool sample = live && !zero && a.cur_step[row] < a.sample_plies;
+  const uint32_t r = pgx::SelfplaySampleAt(pgx::SelfplayKey(a.seed, row + a.id_offset, a.t), Q);
+  uint32_t run = x - mine;
+  int sampled = INT_MAX;
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    run += q[i];
+    if (sampled == INT_MAX && run > r) sampled = j * E + i;
+  }
+  // ... and the greedy one (the most visited action, the lowest on ties)
+  int best = v[0], greedy = j * E;
+#pragma unroll
+  for (int i = 1; i < E; ++i) {
+    if (v[i] > best) {
+      best = v[i];
+      greedy = j * E + i;
+    }
+  }
+#pragma unroll
+  for (int w = LG / 2; w >= 1; w >>= 1) {
+    sampled = std::min(sampled, __shfl_xor(sampled, w, LG));
+    const int ob = __shfl_xor(best, w, LG), op = __shfl_xor(greedy, w, LG);
+    if (ob > best || (ob == best && op < greedy)) {
+      best = ob;
+      greedy = op;
+    }
+  }
+  if (live && j == 0) a.action[row] = zero ? 0 : (sample ? sampled : greedy);
+}
+
 // ARENA: the seven counters of pgx_arena.hip.h (PgxArenaTally in the documents)
 template <bool ARENA>
 __global__ __launch_bounds__(kSelfplayBlock) void PgxSelfplayTally(SelfplayArgs a) {
@@ -158,10 +278,19 @@ void LaunchMove(const SelfplayArgs& a, hipStream_t s) {
   if (a.policy == pgx::kSelfplayGumbel) {
     hipLaunchKernelGGL((PgxSelfplayMove<G, pgx::kSelfplayGumbel>), dim3(Blocks((long long)a.k * pgx::Dims<G>::A)),
                        dim3(kSelfplayBlock), 0, s, a);
+  } else if (a.temperature != 1.0f) {
+    hipLaunchKernelGGL(PgxSelfplayMoveTemp<G>, dim3(Blocks((long long)a.k * SelfplayGroup<G>())), dim3(kSelfplayBlock),
+                       0, s, a);
   } else {
     hipLaunchKernelGGL((PgxSelfplayMove<G, pgx::kSelfplayPuct>), dim3(Blocks((long long)a.k * SelfplayGroup<G>())),
                        dim3(kSelfplayBlock), 0, s, a);
   }
+}
+
+template <int G>
+void LaunchDirichlet(const SelfplayArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(PgxSelfplayDirichlet<G>, dim3(Blocks((long long)a.k * SelfplayGroup<G>())), dim3(kSelfplayBlock), 0,
+                     s, a);
 }
 
 }  // namespace
@@ -181,6 +310,15 @@ void PgxSelfplayLaunchMove(int game, const SelfplayArgs& a, hipStream_t stream) 
     case pgx::kConnectFour: return LaunchMove<pgx::kConnectFour>(a, stream);
     case pgx::kHex: return LaunchMove<pgx::kHex>(a, stream);
     default: return LaunchMove<pgx::kOthello>(a, stream);
+  }
+}
+
+void PgxSelfplayLaunchDirichlet(int game, const SelfplayArgs& a, hipStream_t stream) {
+  switch (game) {
+    case pgx::kTicTacToe: return LaunchDirichlet<pgx::kTicTacToe>(a, stream);
+    case pgx::kConnectFour: return LaunchDirichlet<pgx::kConnectFour>(a, stream);
+    case pgx::kHex: return LaunchDirichlet<pgx::kHex>(a, stream);
+    default: return LaunchDirichlet<pgx::kOthello>(a, stream);
   }
 }
 

@@ -340,6 +340,11 @@ class Selfplay:
     def stats(self) -> Stats:
         return Stats(*(int(x) for x in self._open().selfplay_stats()))
 
+    def noise(self) -> np.ndarray:
+        """float32 [num_envs, A]: the last ply's root noise -- the Dirichlet eta rows of a PUCT driver with
+        `dirichlet_alpha` (zeros without it, and before the first ply), the Gumbel rows of a Gumbel driver; waits."""
+        return self._open().selfplay_noise()
+
     def close(self) -> None:
         """Releases the driver's device memory; an open recorder stays open."""
         if self._pool is not None:
@@ -372,8 +377,8 @@ class Arena:
         stats = arena.run(plies=200)       # ArenaStats(games, wins0, wins1, draws, plies, wins_a, wins_b, t)
         arena.close()
 
-    Without root noise (Gumbel: `noise=True`, the default) or `sample_plies` (PUCT), all envs of a pool play one of
-    two games -- the nets are deterministic, and only the seat that moves first differs --, so a match needs one of
+    Without root noise (Gumbel: `noise=True`, the default; PUCT: `dirichlet_alpha` > 0) or `sample_plies` (PUCT), all
+    envs of a pool play one of two games -- the nets are deterministic, and only the seat that moves first differs --, so a match needs one of
     them on.  `run(n, wait=False)` only enqueues and returns None; `stats()` waits.  `run(3)` then `run(2)` is
     `run(5)`."""
 
@@ -953,7 +958,11 @@ class EnvPoolMixin(ABC):
         `c_visit`, `c_scale`, `batch` and `noise` (False: zero root noise) as `gumbel_search` does;
         `policy="puct"` takes `c_puct`, `width`, `tactics`, `tactics_nodes`, `prove` as `guided_search` does and
         `sample_plies`: a game's first plies are sampled from the visit counts, the later ones take the most visited
-        move.  `record` (default True) feeds the pool's open recorder.  The pool must be in sync mode with nothing
+        move.  `policy="puct"` also takes standard AlphaZero exploration: `dirichlet_alpha` > 0 (default 0: none) mixes
+        eta ~ Dir(alpha) over the legal root actions into every root's priors, (1 - `dirichlet_eps`) p +
+        `dirichlet_eps` eta (default 0.25), before the search expands the root; `temperature` T (default 1, 0.05 .. 20)
+        samples the first `sample_plies` plies from visits^(1/T).  The policy target stays visits / sum.
+        `record` (default True) feeds the pool's open recorder.  The pool must be in sync mode with nothing
         pending in its result queue (after `reset()` or `step()`).  A `batch` or `width` session reads one device word
         per advance, as `search.run(net)` does; a plain session has no host wait between plies.  The arguments are
         checked before any native call."""
@@ -985,8 +994,10 @@ class EnvPoolMixin(ABC):
         """Extension (the PGX board games): opens the pool's self-play driver as an arena -- `Arena` -- in which the
         built-in networks `net_a` and `net_b` (`envpool_amd.pgx.net.Net`; the same inputs and actions, any width and
         depth) play each other: `net_a` moves for seat e & 1 of the env with global id e.  The options are those of
-        `selfplay`; `record` (default False) feeds the pool's open recorder.  Without root noise (Gumbel) or
-        `sample_plies` (PUCT), all envs of a pool play one of two games, so a match needs one of them on.  The
+        `selfplay`, `dirichlet_alpha`, `dirichlet_eps` and `temperature` included (the same for both nets);
+        `record` (default False) feeds the pool's open recorder.  Without root noise (Gumbel; PUCT:
+        `dirichlet_alpha`) or `sample_plies` (PUCT), all envs of a pool play one of two games, so a match needs one of
+        them on.  The
         arguments are checked before any native call."""
         options = dict(options, policy=policy, simulations=simulations, seed=seed, record=record)
         native.check_arena(net_a, net_b, **options)

@@ -486,8 +486,9 @@ def selfplay_device(pool: Any, net: Any, plies: int, **options: Any) -> None:
     ordered both ways with torch's current stream like the other device forms: what torch enqueued before (a `Net`'s
     weights do not change, but the recorder's view or the envs may have been touched) is seen by the plies, and torch
     work enqueued afterwards -- reading `recorder_view_device`'s tensors, say -- sees their samples.  With `options`
-    (`native.check_selfplay`'s), or when the pool's driver was not opened with `net`, the driver is opened first;
-    otherwise the open one continues.  `pool.selfplay_stats()` waits and reads the statistics."""
+    (`native.check_selfplay`'s, `dirichlet_alpha`, `dirichlet_eps` and `temperature` of a PUCT driver included), or
+    when the pool's driver was not opened with `net`, the driver is opened first; otherwise the open one continues.
+    `pool.selfplay_stats()` waits and reads the statistics, `pool.selfplay_noise()` the last ply's noise rows."""
     import torch
 
     plies = native.check_selfplay_plies(plies)

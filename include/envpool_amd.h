@@ -1101,6 +1101,34 @@ int epa_selfplay_run_device(epa_pool* pool, int32_t plies);
 int epa_selfplay_stats(epa_pool* pool, int64_t* out);
 int epa_selfplay_end(epa_pool* pool);
 
+/* PUCT exploration of the driver and the arena (csrc/pgx_dirichlet.hip.h is the authority): Dirichlet root noise and a
+ * move temperature, the two pieces of standard AlphaZero self-play the options above lack.
+ *   dirichlet_alpha > 0: every ply draws eta ~ Dir(alpha) over the legal root actions of every env -- one Gamma(alpha)
+ *     variate per (env, action) by a boosted Marsaglia-Tsang sampler on the counter-based uniforms of key(e, t), at the
+ *     indices 0x200 + ((a * 16 + j) * 4 + c), normalised by a float32 sum in one fixed order -- and mixes it into the
+ *     priors of the roots, p' = (1 - eps) p + eps eta, between the round's first evaluation and its first advance
+ *     (PgxSelfplayDirichlet; an arena: after the pair evaluation of the roots), so the tree stores the mixed priors.  A
+ *     root that is over is left alone.  alpha > 0 with eps == 0 draws and mixes nothing in.  alpha == 0: no noise.
+ *   temperature T != 1: while a game's elapsed step < sample_plies the move is sampled from visits^(1/T), as integers
+ *     q[a] = (uint32)(exp_(log_(visits[a] / max visits) / T) * 2^20) through the pick of the plain rule; the policy
+ *     target stays visits / SUM visits.  T == 1 is the plain rule, byte for byte.
+ *   epa_selfplay_begin_ex(pool, net_a, net_b, options, extra): epa_selfplay_begin (net_b NULL) or epa_arena_begin with
+ *     `extra`; those two behave as extra = {0, 0, 1, 0}.
+ *   epa_selfplay_noise(pool, out): the host copy of the last ply's noise rows, float32 [num_envs][A] -- eta of a PUCT
+ *     driver (zeros without alpha, and before the first ply), the Gumbel rows of a Gumbel driver.  Waits for the device.
+ * Errors (before any launch), EPA_ERR_INVALID: dirichlet_alpha not finite or outside 0 .. 100; dirichlet_eps outside
+ *   0 .. 1; temperature outside 0.05 .. 20; reserved != 0; a Gumbel driver with any of the three other than 0 / 0 / 1;
+ *   epa_selfplay_noise without a driver. */
+typedef struct epa_selfplay_extra {
+  float dirichlet_alpha;
+  float dirichlet_eps;
+  float temperature;
+  int32_t reserved; /* 0 */
+} epa_selfplay_extra;
+int epa_selfplay_begin_ex(epa_pool* pool, epa_net* net_a, epa_net* net_b /* NULL: self-play */,
+                          const epa_selfplay_options* options, const epa_selfplay_extra* extra);
+int epa_selfplay_noise(epa_pool* pool, float* out);
+
 /* Arena (no reference analogue; the four PGX board games; csrc/pgx_arena.hip.h is the authority): two networks play
  * each other in one pool, as a mode of the pool's one self-play driver.
  *   Which net moves: net (m ^ e) & 1 for seat m of the env with GLOBAL id e, 0 = net_a, 1 = net_b: net_a holds seat 0

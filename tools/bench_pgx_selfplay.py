@@ -14,7 +14,14 @@ over the repeats of (wall time of `plies` plies, after `warmup` plies, ending in
 is (max - min) / median over the repeats of the same leg.  One JSON line per game and setting.
 
 `--leg kernels` plays a few plies of every setting and nothing else: the program to put behind
-`rocprofv3 --kernel-trace --stats --` for the device time of PgxSelfplayNoise / Move / Tally beside one advance."""
+`rocprofv3 --kernel-trace --stats --` for the device time of PgxSelfplayNoise / Move / Tally beside one advance.
+
+    python tools/bench_pgx_selfplay.py --dirichlet 0.3 [--parent DIR] ...
+
+measures what Dirichlet root noise costs a PUCT ply instead: leg `plain` is the PUCT setting of leg (b) without noise
+(with --parent DIR on the parent's tree), leg `noisy` the same with `dirichlet_alpha` on this tree; same alternation,
+median and spread.  The noise changes the games (without it all envs of a pool play one of two), so the difference is
+the launch AND the other games; `--dirichlet-eps 0` runs the kernel and mixes nothing in, which leaves the launch.  `--leg noisy_kernels --dirichlet 0.3` is the program for rocprofv3 (PgxSelfplayDirichlet)."""
 import argparse
 import json
 import os
@@ -56,6 +63,11 @@ def leg(args):
     for fam in args.games.split(","):
         net = Net.random(SHAPE[fam], ACTIONS[fam], args.hidden, args.blocks, seed=0)
         for kind, s, kw in SETTINGS:
+            if args.leg in ("plain", "noisy", "noisy_kernels"):
+                if kind != "puct":
+                    continue
+                if args.leg != "plain":
+                    kw = dict(kw, dirichlet_alpha=args.dirichlet, dirichlet_eps=args.dirichlet_eps)
             env = envpool.make(f"{fam}-v1", "gymnasium", num_envs=args.k, seed=7)
             rec = env.recorder(capacity=1 << 18)
             env.reset()
@@ -70,7 +82,7 @@ def leg(args):
             else:
                 sp = env.selfplay(net, policy=kind, simulations=s, seed=0, **kw)
                 sp.run(args.warmup)
-                if args.leg == "kernels":
+                if args.leg in ("kernels", "noisy_kernels"):
                     sp.run(4)
                 else:
                     t0 = time.perf_counter()
@@ -95,16 +107,21 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit for leg (a)")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", default=None, choices=["host", "driver", "kernels"])
+    ap.add_argument("--leg", default=None, choices=["host", "driver", "kernels", "plain", "noisy", "noisy_kernels"])
+    ap.add_argument("--dirichlet", type=float, default=0.0, help="alpha: measure the noise's cost per PUCT ply")
+    ap.add_argument("--dirichlet-eps", type=float, default=0.25,
+                    help="0: the kernel runs and mixes nothing in, so both legs play the same games")
     ap.add_argument("--root", default=HERE)
     args = ap.parse_args()
     if args.leg:
         return leg(args)
     common = [sys.executable, os.path.abspath(__file__), "--games", args.games, "--k", str(args.k), "--hidden",
               str(args.hidden), "--blocks", str(args.blocks), "--plies", str(args.plies), "--warmup", str(args.warmup)]
-    runs = {"host": [], "driver": []}
+    first, second = ("plain", "noisy") if args.dirichlet > 0 else ("host", "driver")
+    common += ["--dirichlet", str(args.dirichlet), "--dirichlet-eps", str(args.dirichlet_eps)]
+    runs = {first: [], second: []}
     for _ in range(args.reps):
-        for name, root in (("host", args.parent or HERE), ("driver", HERE)):
+        for name, root in ((first, args.parent or HERE), (second, HERE)):
             p = subprocess.run(common + ["--leg", name, "--root", os.path.abspath(root)], capture_output=True,
                                text=True, timeout=600, cwd=os.path.abspath(root))
             if p.returncode != 0:
@@ -112,7 +129,20 @@ def main():
             line = [x for x in p.stdout.splitlines() if x.startswith("LEG ")][-1]
             runs[name].append(json.loads(line[4:]))
     lines = []
-    for key in [k for k in runs["driver"][0] if not k.endswith("/games")]:
+    if args.dirichlet > 0:
+        for key in [k for k in runs["plain"][0] if not k.endswith("/games")]:
+            noisy = key + f",dirichlet_alpha={args.dirichlet},dirichlet_eps={args.dirichlet_eps}"
+            rec = {"setting": noisy, "k": args.k, "hidden": args.hidden, "blocks": args.blocks, "plies": args.plies,
+                   "reps": args.reps, "plain_tree": "parent" if args.parent else "this"}
+            for name, col, kk in (("plain", "plain_ms_per_ply", key), ("noisy", "noisy_ms_per_ply", noisy)):
+                xs = [r[kk] for r in runs[name]]
+                med = statistics.median(xs)
+                rec[col] = round(med, 4)
+                rec[col.split("_ms")[0] + "_spread"] = round((max(xs) - min(xs)) / med, 3)
+            rec["noisy_less_plain_us"] = round((rec["noisy_ms_per_ply"] - rec["plain_ms_per_ply"]) * 1e3, 1)
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+    for key in [] if args.dirichlet > 0 else [k for k in runs["driver"][0] if not k.endswith("/games")]:
         rec = {"setting": key, "k": args.k, "hidden": args.hidden, "blocks": args.blocks, "plies": args.plies,
                "reps": args.reps, "host_tree": "parent" if args.parent else "this"}
         for name, col in (("host", "a_host_ms_per_ply"), ("driver", "b_driver_ms_per_ply")):
