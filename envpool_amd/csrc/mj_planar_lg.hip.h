@@ -102,6 +102,11 @@ struct Grp {
   // line-search cache per end-sphere slot: (Jn.a, Jx.a), left by the pass over the rows (round 5: the (Jn.s, Jx.s)
   // slots of the exact search went with it, see Solve)
   static constexpr int kCachePerEnd = 2;
+  // KL = 2, 4: one slot record more than end spheres, the SENTINEL (index kEnds) -- what a lane visits once its own
+  // set has run out: D = +0 and finite numbers, its own two cache entries (see RowsPass).  The Hopper's LDS block has
+  // no room for it (its lanes select D = 0 instead).
+  static constexpr bool kSentinel = KL != 1;
+  static constexpr int kRecs = kEnds + (kSentinel ? 1 : 0);
   // local body of slot s (KL = 1, 2: both ends of a body are consecutive slots; KL = 4: one end per body)
   EPA_HD static constexpr int SlotBody(int s) { return KL == 4 ? s : s / 2; }
   // lane coordinate c (0 .. KL-1) -> leg, parity
@@ -175,15 +180,16 @@ inline void BuildTable(const CheetahModel<double>& m, double* tab) {
   }
 }
 
-// LDS slots of a lane, [slot][lane]: 5 per end-sphere slot (cpx cpz aref_n B*mu*vx D), then 2 per
-// end-sphere slot that live for one Newton iteration: (Jn.a, Jx.a) left by the pass over the rows for the
+// LDS slots of a lane, [slot][lane]: 5 per end-sphere record (cpx cpz aref_n B*mu*vx D; Grp::kRecs records: the end
+// spheres and, at 2 / 4 lanes per env, the sentinel), then 2 per
+// record that live for one Newton iteration: (Jn.a, Jx.a) left by the pass over the rows for the
 // line-search evaluation (which builds J . s itself: one evaluation per iteration, see Solve).  Behind the cache the
 // Hopper's three body pairs take kSlotsPerPair each (nx nz cx cz aref D, as in mj_cheetah.hip.h).
 constexpr int kSlotsPerEnd = 5;
 template <int KL>
-constexpr int CacheBase() { return Grp<KL>::kEnds * kSlotsPerEnd; }
+constexpr int CacheBase() { return Grp<KL>::kRecs * kSlotsPerEnd; }
 template <int KL>
-constexpr int PairBase() { return Grp<KL>::kEnds * (kSlotsPerEnd + Grp<KL>::kCachePerEnd); }
+constexpr int PairBase() { return Grp<KL>::kRecs * (kSlotsPerEnd + Grp<KL>::kCachePerEnd); }
 template <int KL>
 constexpr int LdsSlots() { return PairBase<KL>() + (Grp<KL>::kPairs ? kNPair * kSlotsPerPair : 0); }
 
@@ -351,6 +357,16 @@ inline LU<K> PopSlot(LU<K>& rem) {
   }
   return r;
 }
+// the same with slot kEmpty where the set is empty (the sentinel: nothing to mask)
+template <int kEmpty, int K>
+inline LU<K> PopSlotOr(LU<K>& rem) {
+  LU<K> r;
+  for (int i = 0; i < K; ++i) {
+    r.v[i] = rem.v[i] ? (unsigned)__builtin_ctz(rem.v[i]) : (unsigned)kEmpty;
+    rem.v[i] &= rem.v[i] - 1u;
+  }
+  return r;
+}
 template <int KL, int K>
 inline LU<K> SlotBodyOf(const LU<K>& s) {
   LU<K> r;
@@ -363,9 +379,23 @@ inline LB<K> AtLeast(const LU<K>& a, unsigned b) {
   for (int i = 0; i < K; ++i) r.v[i] = a.v[i] >= b;
   return r;
 }
+// bits `bit`, `bit + 1`, `bit + 2` set where w1, w2, w3 != 0: the three rows of one end-sphere visit (see RowsPass)
 template <typename T, int K>
-inline void MaskSetNZAt(LU<K>& m, const LV<T, K>& w, const LU<K>& slot, int base) {  // bit base + 3 slot where w != 0
-  for (int i = 0; i < K; ++i) m.v[i] |= (w.v[i] != T(0) ? 1u : 0u) << (base + 3 * (int)slot.v[i]);
+inline void MaskSetNZ3(LU<K>& m, const LV<T, K>& w1, const LV<T, K>& w2, const LV<T, K>& w3, int bit) {
+  for (int i = 0; i < K; ++i) {
+    m.v[i] |= ((w1.v[i] != T(0) ? 1u : 0u) | (w2.v[i] != T(0) ? 2u : 0u) | (w3.v[i] != T(0) ? 4u : 0u)) << bit;
+  }
+}
+// an exact per-lane counter (the env's Newton trips): n += 1 where `on`; its value as a V
+template <int K>
+inline void CountWhere(LU<K>& n, LB<K> on) {
+  for (int i = 0; i < K; ++i) n.v[i] += on.v[i] ? 1u : 0u;
+}
+template <typename V, int K>
+inline V CountValue(const LU<K>& n) {
+  V r;
+  for (int i = 0; i < K; ++i) r.v[i] = n.v[i];
+  return r;
 }
 template <typename V>
 struct LaneTypes;
@@ -405,17 +435,19 @@ EPA_HD unsigned PopSlot(unsigned& rem) {
   rem &= rem - 1u;
   return s;
 }
+// (the set's bits all lie below kEmpty: with bit kEmpty set the count of trailing zeros needs no select)
+template <int kEmpty>
+EPA_HD unsigned PopSlotOr(unsigned& rem) {
+  const unsigned s = (unsigned)__builtin_ctz(rem | (1u << kEmpty));
+  rem &= rem - 1u;
+  return s;
+}
 template <int KL>
 EPA_HD unsigned SlotBodyOf(unsigned s) { return KL == 4 ? s : s >> 1; }
 EPA_HD bool AtLeast(unsigned a, unsigned b) { return a >= b; }
-EPA_HD void MaskSetNZAt(unsigned& m, double w, unsigned slot, int base) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned hi = (unsigned)__double2hiint(w);  // see MaskSetNZ
-  m |= (hi < 1u ? hi : 1u) << (base + 3 * slot);
-#else
-  m |= (w != 0.0 ? 1u : 0u) << (base + 3 * slot);
-#endif
-}
+EPA_HD void CountWhere(unsigned& n, bool on) { n += on ? 1u : 0u; }
+template <typename V>
+EPA_HD V CountValue(unsigned n) { return (V)n; }
 // bit set where w != 0, for a weight that is either +0.0 or a positive normal number: its high word is
 // then zero / non-zero, and min(1, high word) is the bit -- two integer VALU ops, no compare, no
 // lane-mask logic on the scalar unit (the row weights are already selected by `jar < 0` and carry
@@ -426,6 +458,23 @@ EPA_HD void MaskSetNZ(unsigned& m, double w, int bit) {
   m |= (hi < 1u ? hi : 1u) << bit;
 #else
   m |= (w != 0.0 ? 1u : 0u) << bit;
+#endif
+}
+// The three rows of one end-sphere visit, same predicate: the 3-bit field is built from the three high words, then
+// shifted once -- by a wave-uniform amount (the visit's index, see RowsPass), so the shift is a scalar operand.
+EPA_HD void MaskSetNZ3(unsigned& m, double w1, double w2, double w3, int bit) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // min(1, high word) spelled as the instruction: from `h < 1 ? h : 1` the compiler makes `h != 0`, i.e. a 64-bit
+  // compare into VCC, the wait states behind it and a select -- three issue slots per bit instead of one
+  auto nz = [](double w) {
+    unsigned r;
+    asm("v_min_u32_e32 %0, 1, %1" : "=v"(r) : "v"((unsigned)__double2hiint(w)));
+    return r;
+  };
+  const unsigned f = nz(w1) | (nz(w2) << 1) | (nz(w3) << 2);
+  m |= f << bit;
+#else
+  m |= ((w1 != 0.0 ? 1u : 0u) | (w2 != 0.0 ? 2u : 0u) | (w3 != 0.0 ? 4u : 0u)) << bit;
 #endif
 }
 template <>
@@ -737,6 +786,14 @@ EPA_HD unsigned MakeConstraint(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p
     lim.aref[j] = -V(m.lim_B) * (sgn * v[j + 3]) - V(m.lim_K) * imp * dist;
   });
   unsigned ends = 0;
+  if constexpr (Grp<KL>::kSentinel) {
+    // The sentinel record: contact point (0, 0), aref = 0, D = +0, cache (0, 0).  Nothing else writes its five
+    // numbers; its cache entries are rewritten by the visits themselves, with finite values (below).
+    static_for<0, kSlotsPerEnd>([&](auto kc) { cx.Lds(Grp<KL>::kEnds * kSlotsPerEnd + decltype(kc)::value) = V(0); });
+    static_for<0, Grp<KL>::kCachePerEnd>([&](auto kc) {
+      cx.Lds(CacheBase<KL>() + Grp<KL>::kEnds * Grp<KL>::kCachePerEnd + decltype(kc)::value) = V(0);
+    });
+  }
   static_for<0, Grp<KL>::kEnds>([&](auto sc) {
     constexpr int s = decltype(sc)::value;
     constexpr int b = Grp<KL>::SlotBody(s);
@@ -744,9 +801,13 @@ EPA_HD unsigned MakeConstraint(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p
     const V wx = p.px[b] + p.cs[b] * ex + p.sn[b] * ez;
     const V wz = p.pz[b] - p.sn[b] * ex + p.cs[b] * ez;
     const V dist = wz - er;  // unused slots of a model carry er = -1e30: never touch
-    V D = V(0), an = V(0), ax = V(0);
     const V cpx = wx, cpz = V(0.5) * dist;
     const auto touch = dist < V(m.con_margin);
+    // A slot's numbers are only read by lanes that visit it, i.e. whose own bit is set -- then some lane touches and
+    // the wave is in here: a slot that touches on no lane of the wave is left as it is (rounds 5-9 carried
+    // an = ax = D = 0 on a path of its own that then skipped the stores, one out-of-line block per slot).  Slot 0 is
+    // also what a lane of the Hopper whose set has run out reads (weight 0, but 0 x NaN would poison the sums): always
+    // written there; with two or four lanes per env such a lane reads the sentinel record instead (below).
     if (AnyWave(touch)) {
       ends |= 1u << s;
       MaskSet(own, touch, s);
@@ -769,18 +830,17 @@ EPA_HD unsigned MakeConstraint(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p
       const V mu = MuOf<b, T, V>(m, cx);
       const V num = (V(1) - imp) * diag;  // R = max(mjMINVAL, num / imp)
       const V invR = Sel(num < V(kMinVal) * imp, V(T(1) / kMinVal), imp / num);
-      D = Sel(touch, invR * d2mu, V(0));
-      an = Sel(touch, -V(m.con_B) * vn - V(m.con_K) * imp * r, V(0));
-      ax = Sel(touch, V(m.con_B) * mu * vx, V(0));
-    }
-    // A slot's numbers are only read by lanes that visit it, i.e. whose own bit is set -- then some lane touches and
-    // the wave is in here; slot 0 is also what a lane whose set has run out reads (weight 0): always written.
-    if (s == 0 || (ends & (1u << s)) != 0) {
       cx.Lds(s * kSlotsPerEnd + 0) = cpx;
       cx.Lds(s * kSlotsPerEnd + 1) = cpz;
-      cx.Lds(s * kSlotsPerEnd + 2) = an;
-      cx.Lds(s * kSlotsPerEnd + 3) = ax;
-      cx.Lds(s * kSlotsPerEnd + 4) = D;
+      cx.Lds(s * kSlotsPerEnd + 2) = Sel(touch, -V(m.con_B) * vn - V(m.con_K) * imp * r, V(0));
+      cx.Lds(s * kSlotsPerEnd + 3) = Sel(touch, V(m.con_B) * mu * vx, V(0));
+      cx.Lds(s * kSlotsPerEnd + 4) = Sel(touch, invR * d2mu, V(0));
+    } else if constexpr (s == 0 && !Grp<KL>::kSentinel) {
+      cx.Lds(0) = cpx;
+      cx.Lds(1) = cpz;
+      cx.Lds(2) = V(0);
+      cx.Lds(3) = V(0);
+      cx.Lds(4) = V(0);
     }
   });
   // body-body capsule pairs of the Hopper (mjc_CapsuleCapsule: closest points of the two axis segments,
@@ -949,14 +1009,36 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
   // A guarded do-while, not a while: with the wave-uniform exit test at the top of the loop the compiler kept the 27
   // accumulators in two sets of registers and copied one set into the other at every trip -- 27 v_mov_b64 of the
   // loop's 203 instructions at KL = 2 (round 7).  Same arithmetic, same trips.
+  // The rows of a visit go into the mask at bits 3 + 3 k .. 5 + 3 k for the lane's k-th VISIT, not at the slot's number
+  // (rounds 5-9: bit 3 + 3 slot, a per-lane shift -- three of them and their address arithmetic in every visit).  The
+  // masks are only ever compared for equality within one lane (mask / prev_mask after a full step, mask1 / mask of one
+  // trip) and only for live envs, whose lanes visit the same set -- `own` -- in the same order -- lowest slot first --
+  // in every pass of every trip: "k-th visit" names the same slot each time, the two encodings are a bijection of one
+  // another on what is compared.  k counts the trips of this loop, so the shift is wave-uniform.  At most kEnds visits.
+  static_assert(3 + 3 * Grp<KL>::kEnds <= kPairMaskBit, "visit bits below the pair bits");
   U rem = vis;
+  int vbit = 3;
+  // KL = 2, 4: a lane whose set has run out visits the SENTINEL record (Grp::kSentinel) -- no `has` selects on D and
+  // no lane-masked cache stores.  Why no bit of a live env changes: the sentinel's D is +0, so w1 = w2 = w3 = +0 whatever
+  // the sign of jar.  Every other number of the visit is FINITE -- the sentinel's cpx = cpz = an = ax = 0, the body
+  // frames, the friction read at the sentinel's "body" (kEnds >> 1 resp. kEnds: index kTMu + 4, the first kTDiag entry,
+  // inside the table), qacc -- so each product with a weight is +-0, never NaN, and so is everything added to an
+  // accumulator.  An accumulator starts at +0.0 and only ever receives sums: x + (+-0) = x for x != 0, (+0) + (+-0) = +0
+  // and a sum that cancels gives +0 under round-to-nearest, so it is never -0.0 and adding +-0 leaves its bits alone --
+  // as with slot 0's numbers and a selected D = 0 before.  The cache entries the visit writes are the sentinel's own.
   if (AnyWave(AnySlot(rem))) do {
-    const auto has = AnySlot(rem);
-    const U sl = PopSlot(rem);
+    [[maybe_unused]] const auto has = AnySlot(rem);
+    U sl;
+    if constexpr (Grp<KL>::kSentinel) {
+      sl = PopSlotOr<Grp<KL>::kEnds>(rem);
+    } else {
+      sl = PopSlot(rem);
+    }
     const U body = SlotBodyOf<KL>(sl);
     const V cpx = cx.LdsL(sl, kSlotsPerEnd, 0), cpz = cx.LdsL(sl, kSlotsPerEnd, 1);
     const V an = cx.LdsL(sl, kSlotsPerEnd, 2), ax = cx.LdsL(sl, kSlotsPerEnd, 3);
-    const V D = Sel(has, cx.LdsL(sl, kSlotsPerEnd, 4), V(0));
+    V D = cx.LdsL(sl, kSlotsPerEnd, 4);
+    if constexpr (!Grp<KL>::kSentinel) D = Sel(has, D, V(0));
     const V mu = cx.CL(kTMu, body);  // (the table also carries the torso's)
     // Jacobian columns of the contact point: dofs 0, 1 (slides), 2 (torso hinge), then the leg's hinges up to the body
     V jn[kLV], jx[kLV];
@@ -978,8 +1060,13 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
       jxa += jx[j] * a[j];
     });
     if constexpr (kHess) {  // the per-iteration pass: kept for the line search
-      cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0, jna, has);
-      cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1, jxa, has);
+      if constexpr (Grp<KL>::kSentinel) {  // (every lane: the sentinel has cache entries of its own)
+        cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0, jna, LaneTypes<V>::True());
+        cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1, jxa, LaneTypes<V>::True());
+      } else {
+        cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0, jna, has);
+        cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1, jxa, has);
+      }
     }
     // rows: 2 x (Jn), (Jn - mu Jx), (Jn + mu Jx); D == 0 for lanes not in contact, which zeroes every weight below
     const V jar1 = jna - an;
@@ -988,9 +1075,8 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
     const V w1 = Sel(jar1 < V(0), V(2) * D, V(0));
     const V w2 = Sel(jar2 < V(0), D, V(0));
     const V w3 = Sel(jar3 < V(0), D, V(0));
-    MaskSetNZAt(mask, w1, sl, 3);
-    MaskSetNZAt(mask, w2, sl, 4);
-    MaskSetNZAt(mask, w3, sl, 5);
+    MaskSetNZ3(mask, w1, w2, w3, vbit);
+    vbit += 3;
     const V gn = w1 * jar1 + w2 * jar2 + w3 * jar3;  // coefficient of Jn
     const V gx = mu * (w3 * jar3 - w2 * jar2);      // coefficient of Jx
     const V A = w1 + w2 + w3, Bc = mu * (w3 - w2), C = mu * mu * (w2 + w3);
@@ -1072,18 +1158,31 @@ EPA_HD void LineEval(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
     }
   }
   // the lane's own touching slots, as in RowsPass (and a guarded do-while for the same reason)
+  // (and the same mask bits: 3 + 3 k for the lane's k-th visit)
   U rem = vis;
+  int vbit = 3;
   if (AnyWave(AnySlot(rem))) do {
-    const auto has = AnySlot(rem);
-    const U sl = PopSlot(rem);
+    [[maybe_unused]] const auto has = AnySlot(rem);
+    U sl;
+    if constexpr (Grp<KL>::kSentinel) {
+      sl = PopSlotOr<Grp<KL>::kEnds>(rem);
+    } else {
+      sl = PopSlot(rem);
+    }
     const U body = SlotBodyOf<KL>(sl);
     const V cpx = cx.LdsL(sl, kSlotsPerEnd, 0), cpz = cx.LdsL(sl, kSlotsPerEnd, 1);
     const V an = cx.LdsL(sl, kSlotsPerEnd, 2), ax = cx.LdsL(sl, kSlotsPerEnd, 3);
-    const V D = Sel(has, cx.LdsL(sl, kSlotsPerEnd, 4), V(0));
-    // (RowsPass<true> at the same `a` left them for the slots it visited: a lane whose set has run out reads
-    // slot 0's, which may never have been written -- 0 x NaN would poison the sums)
-    const V jna = Sel(has, cx.LdsL(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0), V(0));
-    const V jxa = Sel(has, cx.LdsL(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1), V(0));
+    V D = cx.LdsL(sl, kSlotsPerEnd, 4);
+    // (RowsPass<true> at the same `a` left them for the slots it visited.  The Hopper: a lane whose set has run out
+    // reads slot 0's, which may never have been written -- 0 x NaN would poison the sums.  With a sentinel such a lane
+    // reads the sentinel's own entries: zeros from MakeConstraint or what its visits of RowsPass<true> left, finite.)
+    V jna = cx.LdsL(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0);
+    V jxa = cx.LdsL(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1);
+    if constexpr (!Grp<KL>::kSentinel) {
+      D = Sel(has, D, V(0));
+      jna = Sel(has, jna, V(0));
+      jxa = Sel(has, jxa, V(0));
+    }
     const V mu = cx.CL(kTMu, body);
     // s . (Jacobian columns of a point on the slot's body): torso dofs, then the hinges up to the body
     V jns = s[1] - (cpx - p.px[0]) * s[2];
@@ -1104,9 +1203,8 @@ EPA_HD void LineEval(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
     const V c3 = Sel(x3 < V(0), D, V(0));
     *d1 += c1 * x1 * jv1 + c2 * x2 * jv2 + c3 * x3 * jv3;
     *d2 += c1 * jv1 * jv1 + c2 * jv2 * jv2 + c3 * jv3 * jv3;
-    MaskSetNZAt(mask, c1, sl, 3);
-    MaskSetNZAt(mask, c2, sl, 4);
-    MaskSetNZAt(mask, c3, sl, 5);
+    MaskSetNZ3(mask, c1, c2, c3, vbit);
+    vbit += 3;
   } while (AnyWave(AnySlot(rem)));
 }
 
@@ -1288,7 +1386,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
   B full_step = LT::False();
   B live = LT::True();
   B at_min = LT::False();  // the env stopped at an exact minimiser (finite termination in the line search)
-  V iter = V(0);
+  U iter = LT::Fill(0u);  // an integer lane counter (exact; rounds 1-9 counted in fp64: two selects and an add per trip)
   for (int it = 0; it < cfg.max_iter; ++it) {
     // A lane visits its own touching slots while its env is still LIVE (after the first trip of a forward pass a
     // third of the envs are left, after the second one in twenty): the envs that have finished keep the gradient of
@@ -1332,7 +1430,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     EPA_LG_TICK(cx, 2);
     if (!AnyWave(live)) break;
     EPA_LG_COUNT(cx, 0);
-    iter += Sel(live, V(1), V(0));
+    CountWhere(iter, live);
     prev_gn2 = gn2;
     prev_mask = mask;
     V s[kLV];
@@ -1426,7 +1524,7 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
       grad[j] = Sel(live, (Ma[j] - qfrc_smooth[j]) + g, grad[j]);
     });
   }
-  return iter;
+  return CountValue<V>(iter);
 }
 
 // mj_forward: qacc at (q, v) under ctrl; `warm` is qacc_warmstart in/out; `p` keeps M for the caller

@@ -112,6 +112,9 @@ def report(label, seq, src, loops):
     # and integration code behind it (the out-of-line blocks below branch back too, but end in front of the integration)
     fl = [r for r in heads.items() if r[0] < ta and tb < r[1] and "Kinematics" in src[r[0]:ta]
           and "integration" in src[tb + 1:r[1] + 1]]
+    if not fl:  # block placement put part of the integration in front of the trip loop (or Kinematics behind it)
+        fl = [r for r in heads.items() if r[0] < ta and tb < r[1] and "Kinematics" in src[r[0]:r[1] + 1]
+              and "integration" in src[r[0]:r[1] + 1]]
     fa, fb = min(fl, key=lambda r: r[1] - r[0])
     print(f"## {label}")
     print(f"forward-pass loop [{fa}, {fb}] {fb - fa + 1} instructions; trip loop [{ta}, {tb}] {tb - ta + 1}")
