@@ -1380,20 +1380,24 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
   const V gfloor2 = gfloor * gfloor;
   V prev_gn2 = V(-1);
   MulArrow<KL>(p.M, qacc, Ma);  // kept current incrementally: Ma += alpha * M s
-  // (the first trip writes every env's gradient: this is for the Sel in it only)
-  static_for<0, kLV>([&](auto ic) { grad[decltype(ic)::value] = V(0); });
   U prev_mask = LT::Fill(~0u);
   B full_step = LT::False();
   B live = LT::True();
   B at_min = LT::False();  // the env stopped at an exact minimiser (finite termination in the line search)
   U iter = LT::Fill(0u);  // an integer lane counter (exact; rounds 1-9 counted in fp64: two selects and an add per trip)
-  for (int it = 0; it < cfg.max_iter; ++it) {
+  // One Newton trip; true once the wave is done.  The FIRST trip of a forward pass (kFirst, it == 0) is code of its
+  // own in front of the loop (round 11): every env is live there, there is no previous trip to compare the active set
+  // and the gradient with (prev_mask = ~0, full_step false, prev_gn2 = -1), and `grad` is written for every env --
+  // what the general trip computes at run time and finds to be all-true or all-false.  The fp64 operations of a live
+  // env, their operands and their order are the general trip's.
+  auto trip = [&](auto first_c, const int it) -> bool {
+    constexpr bool kFirst = decltype(first_c)::value;
     // A lane visits its own touching slots while its env is still LIVE (after the first trip of a forward pass a
     // third of the envs are left, after the second one in twenty): the envs that have finished keep the gradient of
     // the trip they finished in
     // (their qacc and Ma are frozen, so it is the gradient at their result); H, the masks and the line-search
     // sums are only ever used for live envs.
-    const U vis = SlotsWhere(own, it == 0 ? LT::True() : live);
+    const U vis = SlotsWhere(own, kFirst ? LT::True() : live);
     const B live0 = live;
     V H[kLTri], gc[kLV];
     static_for<0, kLTri>([&](auto kc) { H[decltype(kc)::value] = V(0); });
@@ -1419,16 +1423,29 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
         }
       });
     });
-    SetWhere<kLV>(live0, grad, [&](int j) { return (Ma[j] - qfrc_smooth[j]) + gc[j]; });
+    V r0[kLV];  // Ma - qfrc_smooth: a term of the gradient, and phi'(0) = s . r0 of the line search
+    if constexpr (kFirst) {  // (unmasked; the differences are formed once)
+      static_for<0, kLV>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        r0[j] = Ma[j] - qfrc_smooth[j];
+        grad[j] = r0[j] + gc[j];
+      });
+    } else {
+      SetWhere<kLV>(live0, grad, [&](int j) { return (Ma[j] - qfrc_smooth[j]) + gc[j]; });
+    }
     const V gn2 = DotEnv<KL>(grad, grad);
-    const B same = AllEnvOf<KL>(MaskSame(mask, prev_mask));
     // |grad| <= gstop; or finite termination: same active set after a full Newton step; or at the
     // rounding floor and no longer shrinking (x4)
-    const B stop = (gn2 <= gstop2) | (full_step & same) |
-                   ((prev_gn2 >= V(0)) & (gn2 <= gfloor2) & (gn2 >= V(0.0625) * prev_gn2));
-    live = live & !stop;
+    B stop = gn2 <= gstop2;
+    if constexpr (kFirst) {
+      live = !stop;
+    } else {
+      const B same = AllEnvOf<KL>(MaskSame(mask, prev_mask));
+      stop = stop | (full_step & same) | ((prev_gn2 >= V(0)) & (gn2 <= gfloor2) & (gn2 >= V(0.0625) * prev_gn2));
+      live = live & !stop;
+    }
     EPA_LG_TICK(cx, 2);
-    if (!AnyWave(live)) break;
+    if (!AnyWave(live)) return true;
     EPA_LG_COUNT(cx, 0);
     CountWhere(iter, live);
     prev_gn2 = gn2;
@@ -1438,12 +1455,14 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     FactorArrow<KL>(H);
     SolveArrow<KL>(H, s);
     // line search on the convex piecewise-quadratic phi(alpha): one evaluation at the full step (see above)
-    V Ms[kLV], r0[kLV];
+    V Ms[kLV];
     MulArrow<KL>(p.M, s, Ms);
-    static_for<0, kLV>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      r0[i] = Ma[i] - qfrc_smooth[i];
-    });
+    if constexpr (!kFirst) {
+      static_for<0, kLV>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        r0[i] = Ma[i] - qfrc_smooth[i];
+      });
+    }
     const V g1 = DotEnv<KL>(s, r0), g2 = DotEnv<KL>(s, Ms);
     V alpha = V(1), lo = V(0), hi = V(-1);
     full_step = LT::False();
@@ -1499,7 +1518,20 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     SetWhere<kLV>(live, Ma, [&](int i) { return Ma[i] + alpha * Ms[i]; });
     at_min = at_min | exact;
     live = live & !exact;
-    if (!AnyWave(live)) break;
+    return !AnyWave(live);
+  };
+  // The Hopper's kernel (a group of one lane) keeps one body for every trip: it is the largest of the lane-group
+  // kernels, and with a second copy of the trip the part of it that runs every step (6.8k instructions) would pass
+  // the 6k kept for the instruction cache two CUs share.  Its first trip runs the general body, where `live` is still
+  // all-true and the tests against the values set above come out false.
+  constexpr bool kPeelFirst = KL != 1;
+  if (kPeelFirst && cfg.max_iter >= 1) {
+    bool done = trip(std::true_type{}, 0);
+    for (int it = 1; !done && it < cfg.max_iter; ++it) done = trip(std::false_type{}, it);
+  } else {  // (no first trip of its own writes the gradient: this is for the Sels only)
+    static_for<0, kLV>([&](auto ic) { grad[decltype(ic)::value] = V(0); });
+    bool done = false;
+    for (int it = 0; !done && it < cfg.max_iter; ++it) done = trip(std::false_type{}, it);
   }
   // At the minimiser the gradient vanishes (to rounding).  Set for every env that stopped there,
   // whether or not its wave went on iterating for other envs and re-evaluated this env's rows:

@@ -8,7 +8,16 @@ The trip loop is found as the smallest loop (backward-branch range) that holds t
 60 instructions, one of them with an LDS store (RowsPass<true> writes the line-search cache); the innermost loops in it
 are the slot loops.  Segments: `head` = top of the trip up to the RowsPass slot loop (accumulator zeroing, slot set),
 `mid` = between the two slot loops (group sums, stop tests, factor / solve / products with M, line-search set-up),
-`tail` = after the LineEval slot loop (line-search step, bracketing, the qacc / Ma updates, loop control)."""
+`tail` = after the LineEval slot loop (line-search step, bracketing, the qacc / Ma updates, loop control).
+
+The FIRST trip of a forward pass is code of its own in front of the loop (plg::Solve, round 11).  It is found as the
+last two innermost loops before the trip loop that match the trip's RowsPass and LineEval slot loops in length (within
+10 %) and in the LDS store; its `mid` and `tail` (up to the top of the trip loop) are reported next to the later trips'
+and the difference per category is printed.  Its `head` is straight-line code shared with the forward-pass set-up and
+has no boundary in the ISA; the source differs there by one select of the slot set.  Where no such pair is found (the
+parent of round 11; an instantiation with the peel compiled out) the tool says so.
+
+Last, per lane-group instantiation in the file: VGPRs, AGPRs, scratch bytes per lane, LDS bytes per block, code bytes."""
 import collections
 import re
 import sys
@@ -18,7 +27,9 @@ KERNELS = {"HalfCheetah <2,0,1>": "ILi2ELi0ELi1E", "HalfCheetah <4,0,1>": "ILi4E
 MIN_SLOT_LOOP = 60
 
 
-def cat(x):
+def cat(x, ops=""):
+    if x.startswith("s_") and ("saveexec" in x or re.search(r"\bexec(_lo|_hi)?\b", ops)):
+        return "exec-mask"
     if re.match(r"v_(fma|mul|add|fmac|max|min)_f64|v_(rcp|rsq|sqrt|div_scale|div_fmas|div_fixup|trig|fract|floor|ldexp"
                 r"|frexp)\w*f64", x):
         return "fp64 arith"
@@ -101,7 +112,7 @@ def trip_loop(seq, loops):
 
 
 def mix(xs):
-    c = collections.Counter(cat(x.split()[0]) for x in xs)
+    c = collections.Counter(cat(x.split()[0], x.partition(" ")[2]) for x in xs)
     return sum(c.values()), c
 
 
@@ -134,6 +145,49 @@ def report(label, seq, loops):
     for r0, r1 in merge([l for l in heads.items() if any(inside(sl, l) for sl in slots)]):
         n = r1 - r0 + 1 - sum(s1 - s0 + 1 for s0, s1 in slots if r0 <= s0 and s1 <= r1)
         print(f"  of the fixed part, in the line-search loop [{r0}, {r1}] (minus its slot loop): {n}")
+    first_trip(seq, loops, a, slots, dict(zip(names, segs)))
+
+
+def first_trip(seq, loops, a, slots, later):
+    heads = {}
+    for l0, l1 in loops:
+        heads[l0] = max(heads.get(l0, l1), l1)
+    big = [l for l in heads.items() if l[1] - l[0] + 1 >= MIN_SLOT_LOOP]
+    inner = [r for r in merge([l for l in big if not any(inside(o, l) for o in big)]) if r[1] < a]
+    rows = [r for r in inner if any(x.startswith("ds_write") for x in seq[r[0]:r[1] + 1])][-1:]
+    evals = [r for r in inner if rows and r[0] > rows[0][1]]  # (the Hopper's first trip holds two)
+    # the copies match the trip's own slot loops in length within 10 %, and not much more than a trip lies between
+    if not (rows and evals and abs((rows[0][1] - rows[0][0]) - (slots[0][1] - slots[0][0])) * 10 <= slots[0][1] - slots[0][0]
+            and a - rows[0][0] <= 1500):
+        print("  first trip: no code of its own in front of the loop (every trip runs the loop body)")
+        return
+    r0, r1 = rows[0]
+    print(f"  first trip: slot loops " + ", ".join(f"[{x0}, {x1}] {x1 - x0 + 1}" for x0, x1 in rows + evals) +
+          f"; code of its own up to the trip loop: {a - r0} instructions")
+    tail, cur = [], evals[0][1] + 1
+    for e0, e1 in evals[1:] + [(a, a)]:
+        tail += seq[cur:e0]
+        cur = e1 + 1
+    mine = {"mid": seq[r1 + 1:evals[0][0]], "tail": tail}
+    for n, s in mine.items():
+        print(f"  first {n:4s} {fmt(*mix(s))}")
+    # the later trips' tail is `tail` + the segments behind it (the exact-search fallback lies between them)
+    rest = [x for n, s in later.items() if n not in ("head", "mid") for x in s]
+    for n, mine_s, later_s in (("mid", mine["mid"], later["mid"]), ("tail", mine["tail"], rest)):
+        (t1, c1), (t0, c0) = mix(mine_s), mix(later_s)
+        d = {k: c1[k] - c0[k] for k in sorted(set(c0) | set(c1)) if c1[k] != c0[k]}
+        print(f"  first - later, {n}: {t1 - t0:+d} (" + ", ".join(f"{k} {v:+d}" for k, v in d.items()) + ")")
+
+
+def resources(txt):
+    print("## registers, scratch, LDS and code size of the lane-group instantiations (whole kernel: the reset branch's "
+          "mt19937 draws included)")
+    count = {name: len(parse(body)[0]) for name, body in kernels(txt)}
+    for m in re.finditer(r"\n(_Z\S*PlanarLgStepKernel\S+):.*?codeLenInByte = (\d+).*?NumVgprs: (\d+).*?NumAgprs: (\d+)"
+                         r".*?ScratchSize: (\d+).*?LDSByteSize: (\d+)", txt, re.S):
+        k = re.search(r"KernelILi(\d)ELi(\d)ELi(\d)E", m.group(1))
+        print(f"<{k.group(1)},{k.group(2)},{k.group(3)}>  V {m.group(3)}  A {m.group(4)}  scratch {m.group(5)} B/lane  "
+              f"LDS {m.group(6)} B  code {m.group(2)} B, {count[m.group(1)]} instructions")
 
 
 def main():
@@ -143,6 +197,7 @@ def main():
         for name, body in kernels(txt):
             if sub in name:
                 report(label, *parse(body))
+    resources(txt)
 
 
 if __name__ == "__main__":
