@@ -474,6 +474,29 @@ void NetLaunchPair(const NetImage& im_a, const char* d_image_a, const NetImage& 
                    const unsigned char* mask, const unsigned char* status, float* policy, float* value,
                    unsigned int* pending, hipStream_t stream);
 
+// The PGX convolutional network (pgx_conv.hip.h is the contract, pgx_conv.hip the kernel).  ConvImage describes a
+// checked "PGXC" blob in the kernel's layout -- per layer the weights in 1 KiB (output tile, tap, k-step) fragments and
+// the bias padded to whole tiles --, the boards G a block evaluates and the block's dynamic LDS.
+constexpr int kConvImageLayers = 19;  // stem + 2 * 8 blocks + reduce + head
+struct ConvImage {
+  int H{0}, W{0}, C{0}, A{0}, D{0}, L{0}, P{0}, layers{0};
+  float scale_p{0}, scale_v{0};
+  uint32_t w_off[kConvImageLayers]{}, b_off[kConvImageLayers]{};
+  int32_t shift[kConvImageLayers]{};
+  int G{0};
+  size_t lds{0};
+};
+// true for a blob that begins with the magic "PGXC"
+bool ConvIsBlob(const void* blob, size_t bytes);
+// std::invalid_argument with ConvParse's reason for a blob that is no network, or for one whose single board does not
+// fit `lds_limit` bytes of LDS (the device's per-block limit); `bytes_out`: the device image
+void ConvBuildImage(const void* blob, size_t bytes, size_t lds_limit, ConvImage* out, std::vector<char>* bytes_out);
+// One PgxConvEval on `stream` with NetLaunch's arguments.  order != null: the segment `seg` (0: [0, *n0), 1:
+// [*n0, rows)) of the plan, one launch per net of a pair.
+void ConvLaunch(const ConvImage& im, const char* d_image, int rows, int mode, const int32_t* order, const int32_t* n0,
+                int seg, const unsigned char* obs, const unsigned char* mask, const unsigned char* status,
+                float* policy, float* value, unsigned int* pending, hipStream_t stream);
+
 // A network on a device (epa_net_create): it belongs to the device, not to a pool, and owns ONE device allocation --
 // the image, the pending word, the policy / value rows its evaluations inside epa_net_run and the host forms write,
 // and the plan (order, counts, n0) of the pair evaluations it leads as net A, grown to the largest `rows` seen.  Calls on one net are the caller's to serialise, as a pool's session is.
@@ -481,7 +504,11 @@ class Net {
  public:
   Net(int device, const void* blob, size_t bytes);
   int device() const { return device_; }
+  // (of a ConvNet: F = H W C, A and `bytes`, the device image; the layers are conv()'s)
   const NetImage& image() const { return image_; }
+  bool is_conv() const { return conv_.layers != 0; }
+  const ConvImage& conv() const { return conv_; }
+  const char* kind() const { return is_conv() ? "ConvNet" : "Net"; }
   void Reserve(size_t rows);  // (growing waits for the launches that use the old block)
   const char* d_image() const { return mem_.p; }
   unsigned int* pending() const { return reinterpret_cast<unsigned int*>(mem_.p + image_.bytes.size()); }
@@ -494,9 +521,15 @@ class Net {
  private:
   int device_;
   NetImage image_;
+  ConvImage conv_;
   DeviceBlock mem_;
   size_t rows_{0};
 };
+// One evaluation with `net` (net_b == null), or of the pair net / net_b through net's plan (NetPlanLaunch came before):
+// the launches of either kind of network on `stream`.  Both nets of a pair are of one kind (NetRequire).
+void NetEvalLaunch(const Net& net, const Net* net_b, int rows, int mode, const unsigned char* obs,
+                   const unsigned char* mask, const unsigned char* status, float* policy, float* value,
+                   unsigned int* pending, hipStream_t stream);
 
 // One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
 // row i is local env i of the pool, every pointer device memory.

@@ -10,7 +10,10 @@ sessions.
 `search.run(net)` makes the round without Python between its launches; `net.bind(env)` gives a plain callable with the
 `evaluate` signature (numpy in and out, or torch tensors on the pool's device) for every entry point that takes one.
 `Net.module()` is a torch twin that computes the same integers in float64 with straight-through gradients, and
-`Net.from_module` comes back: the format is trainable."""
+`Net.from_module` comes back: the format is trainable.
+
+`ConvNet` (csrc/pgx_conv.hip.h, csrc/pgx_conv.hip) is the second kind, a tower of 3x3 residual convolutions in the same
+arithmetic and with the same surface; it goes wherever a `Net` goes, except into the rollout actor."""
 from __future__ import annotations
 
 import ctypes
@@ -39,12 +42,71 @@ def _check_sizes(f: int, a: int, d: int, blocks: int) -> None:
         raise ValueError(f"net: L = {blocks} must be 0 .. {MAX_BLOCKS}")
 
 
-class Net:
+class _OnDevice:
+    """What both kinds of built-in network share: the device copies of the blob and the `evaluate` callable.  A
+    subclass has `blob()`, `inputs` (F) and `actions` (A) and sets `_handles = {}`."""
+
+    _is_epa_net = True
+
+    # -- the device ----------------------------------------------------------------
+    def _handle(self, device: int) -> Any:
+        """The net on `device` (epa_net_create), uploaded on first use."""
+        h = self._handles.get(int(device))
+        if h is None:
+            blob = self.blob()
+            out = ctypes.c_void_p()
+            native.check(native.lib().epa_net_create(int(device), blob.ctypes.data, blob.nbytes, ctypes.byref(out)))
+            h = self._handles[int(device)] = out
+        return h
+
+    def close(self) -> None:
+        """Releases the device copies (also done when the object goes)."""
+        handles, self._handles = self._handles, {}
+        for h in handles.values():
+            native.lib().epa_net_destroy(h)
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:  # (interpreter shutdown)
+            pass
+
+    def bind(self, env: Any, priors: bool = False) -> Any:
+        """A callable `evaluate(obs, mask, status) -> (policy, values)` on `env` (an env of a PGX family, or its
+        device pool): numpy arrays in and out, or torch tensors on the pool's device (only enqueued, ordered both ways
+        against torch's current stream).  `priors`: the softmax over the legal actions, what a PUCT session takes;
+        otherwise logits, what a Gumbel session takes."""
+        pool = env._guided() if hasattr(env, "_guided") else env
+
+        def evaluate(obs: Any, mask: Any, status: Any) -> tuple[Any, Any]:
+            return self._evaluate(pool, obs, mask, status, priors)
+
+        return evaluate
+
+    def _evaluate(self, pool: Any, obs: Any, mask: Any, status: Any, priors: bool) -> tuple[Any, Any]:
+        if isinstance(obs, np.ndarray):
+            return pool.net_eval(self, obs, mask, status, priors)
+        import torch
+
+        from envpool_amd import torch_interop
+
+        dev = torch.device("cuda", pool.device)
+        rows, a = int(status.numel()), self.actions
+        for name, t, n in (("obs", obs, rows * self.inputs), ("mask", mask, rows * a), ("status", status, rows)):
+            if t.device != dev or not t.is_contiguous() or t.element_size() != 1 or t.numel() != n:
+                raise ValueError(f"net: {name} must be a contiguous one-byte tensor of {n} elements on {dev}")
+        policy = torch.empty((rows, a), dtype=torch.float32, device=dev)
+        value = torch.empty((rows,), dtype=torch.float32, device=dev)
+        torch_interop._order_both_ways(pool, dev, lambda: pool.net_eval_device(
+            self, rows, priors, obs.data_ptr(), mask.data_ptr(), status.data_ptr(), policy.data_ptr(),
+            value.data_ptr()))
+        return policy, value
+
+
+class Net(_OnDevice):
     """`layers`: the 2 * blocks + 2 layers in the blob's order -- trunk, the two of every block, head -- each a tuple
     (weights int8 [N, K], bias int32 [N], shift int); the trunk is [hidden, F], a block's layers [hidden, hidden], the
     head [actions + 1, hidden] with shift 0.  Everything the contract bounds is checked here (ValueError)."""
-
-    _is_epa_net = True
 
     def __init__(self, obs_shape: Sequence[int], actions: int, hidden: int, blocks: int, layers: Sequence[tuple],
                  scale_p: float, scale_v: float):
@@ -154,60 +216,6 @@ class Net:
         spread = 73.0 * np.sqrt(hidden) * 40.0  # about the deviation of the head's integers
         return cls(obs_shape, actions, hidden, blocks, layers, 4.0 / spread, 1.0 / spread)
 
-    # -- the device ----------------------------------------------------------------
-    def _handle(self, device: int) -> Any:
-        """The net on `device` (epa_net_create), uploaded on first use."""
-        h = self._handles.get(int(device))
-        if h is None:
-            blob = self.blob()
-            out = ctypes.c_void_p()
-            native.check(native.lib().epa_net_create(int(device), blob.ctypes.data, blob.nbytes, ctypes.byref(out)))
-            h = self._handles[int(device)] = out
-        return h
-
-    def close(self) -> None:
-        """Releases the device copies (also done when the object goes)."""
-        handles, self._handles = self._handles, {}
-        for h in handles.values():
-            native.lib().epa_net_destroy(h)
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:  # (interpreter shutdown)
-            pass
-
-    def bind(self, env: Any, priors: bool = False) -> Any:
-        """A callable `evaluate(obs, mask, status) -> (policy, values)` on `env` (an env of a PGX family, or its
-        device pool): numpy arrays in and out, or torch tensors on the pool's device (only enqueued, ordered both ways
-        against torch's current stream).  `priors`: the softmax over the legal actions, what a PUCT session takes;
-        otherwise logits, what a Gumbel session takes."""
-        pool = env._guided() if hasattr(env, "_guided") else env
-
-        def evaluate(obs: Any, mask: Any, status: Any) -> tuple[Any, Any]:
-            return self._evaluate(pool, obs, mask, status, priors)
-
-        return evaluate
-
-    def _evaluate(self, pool: Any, obs: Any, mask: Any, status: Any, priors: bool) -> tuple[Any, Any]:
-        if isinstance(obs, np.ndarray):
-            return pool.net_eval(self, obs, mask, status, priors)
-        import torch
-
-        from envpool_amd import torch_interop
-
-        dev = torch.device("cuda", pool.device)
-        rows, a = int(status.numel()), self.actions
-        for name, t, n in (("obs", obs, rows * self.inputs), ("mask", mask, rows * a), ("status", status, rows)):
-            if t.device != dev or not t.is_contiguous() or t.element_size() != 1 or t.numel() != n:
-                raise ValueError(f"net: {name} must be a contiguous one-byte tensor of {n} elements on {dev}")
-        policy = torch.empty((rows, a), dtype=torch.float32, device=dev)
-        value = torch.empty((rows,), dtype=torch.float32, device=dev)
-        torch_interop._order_both_ways(pool, dev, lambda: pool.net_eval_device(
-            self, rows, priors, obs.data_ptr(), mask.data_ptr(), status.data_ptr(), policy.data_ptr(),
-            value.data_ptr()))
-        return policy, value
-
     # -- the torch twin ------------------------------------------------------------
     def module(self) -> Any:
         """A `torch.nn.Module` with this net's numbers as float64 parameters: `forward(x [rows, F]) -> (logits float32
@@ -266,3 +274,217 @@ def _make_module(net: Net) -> Any:
             return logits, value
 
     return NetModule()
+
+
+# -- the convolutional kind (csrc/pgx_conv.hip.h is the contract, csrc/pgx_conv.hip the kernel) ----------------------
+CONV_MAGIC = 0x43584750  # "PGXC"
+CONV_HEADER_BYTES = 48
+CONV_MAX_SQUARES, CONV_MAX_CHANNELS, CONV_MAX_WIDTH, CONV_MAX_PLANES, CONV_MAX_FLAT = 128, 32, 256, 32, 512
+
+
+def _check_conv_sizes(h: int, w: int, c: int, a: int, d: int, blocks: int, planes: int) -> None:
+    if h < 1 or w < 1 or h * w > CONV_MAX_SQUARES:
+        raise ValueError(f"conv: H = {h}, W = {w} must be at least 1 with H W <= {CONV_MAX_SQUARES}")
+    if not 1 <= c <= CONV_MAX_CHANNELS:
+        raise ValueError(f"conv: C = {c} must be 1 .. {CONV_MAX_CHANNELS}")
+    if not 1 <= a <= MAX_ACTIONS:
+        raise ValueError(f"conv: A = {a} must be 1 .. {MAX_ACTIONS}")
+    if not MIN_WIDTH <= d <= CONV_MAX_WIDTH or d % 32:
+        raise ValueError(f"conv: D = {d} must be a multiple of 32 in {MIN_WIDTH} .. {CONV_MAX_WIDTH}")
+    if not 0 <= blocks <= MAX_BLOCKS:
+        raise ValueError(f"conv: L = {blocks} must be 0 .. {MAX_BLOCKS}")
+    if not 1 <= planes <= CONV_MAX_PLANES or h * w * planes > CONV_MAX_FLAT:
+        raise ValueError(f"conv: P = {planes} must be 1 .. {CONV_MAX_PLANES} with H W P <= {CONV_MAX_FLAT}")
+
+
+def _conv_shapes(h: int, w: int, c: int, a: int, d: int, blocks: int, planes: int) -> list:
+    """The weight shapes of the 2 L + 3 layers in the blob's order."""
+    return [(d, 3, 3, c)] + [(d, 3, 3, d)] * (2 * blocks) + [(planes, d), (a + 1, h * w * planes)]
+
+
+class ConvNet(_OnDevice):
+    """The convolutional built-in network: a stem and `blocks` residual blocks of 3x3 convolutions of `channels`
+    channels over the [H, W, C] board with zero padding, a 1x1 reduction to `planes` planes and a dense head over
+    their H W planes bytes.  `layers`: the 2 * blocks + 3 layers in the blob's order -- stem, the two of every block,
+    reduce, head -- each a tuple (weights int8, bias int32 [N], shift int) with the weights [channels, 3, 3, C],
+    [channels, 3, 3, channels], [planes, channels] and [actions + 1, H W planes] (flattened in the order y, x, plane;
+    shift 0).  Accepted wherever a `Net` is, except by the rollout actor; the two nets of a pair are of one kind."""
+
+    def __init__(self, obs_shape: Sequence[int], actions: int, channels: int, blocks: int, planes: int,
+                 layers: Sequence[tuple], scale_p: float, scale_v: float):
+        self.obs_shape = tuple(int(x) for x in obs_shape)
+        if len(self.obs_shape) != 3:
+            raise ValueError(f"conv: obs_shape = {self.obs_shape} must be (H, W, C)")
+        self.inputs = int(np.prod(self.obs_shape))
+        self.actions, self.channels, self.blocks, self.planes = int(actions), int(channels), int(blocks), int(planes)
+        sizes = self.obs_shape + (self.actions, self.channels, self.blocks, self.planes)
+        _check_conv_sizes(*sizes)
+        shapes = _conv_shapes(*sizes)
+        if len(layers) != len(shapes):
+            raise ValueError(f"conv: {len(layers)} layers for L = {self.blocks} (2 L + 3 = {len(shapes)})")
+        self.scale_p, self.scale_v = float(np.float32(scale_p)), float(np.float32(scale_v))
+        for name, s in (("scale_p", self.scale_p), ("scale_v", self.scale_v)):
+            if not 0.0 < s <= 1e20:
+                raise ValueError(f"conv: {name} must be finite, above 0 and at most 1e20")
+        self.layers = []
+        for i, ((w, b, shift), shape) in enumerate(zip(layers, shapes)):
+            head = i == len(shapes) - 1
+            w, b, shift = np.asarray(w), np.asarray(b), int(shift)
+            if w.shape != shape or b.shape != shape[:1]:
+                raise ValueError(f"conv: layer {i}: weights {w.shape} and bias {b.shape} must be {shape} and "
+                                 f"{shape[:1]}")
+            if not 0 <= shift <= (0 if head else MAX_SHIFT):
+                raise ValueError(f"conv: layer {i}: shift = {shift} must be 0 .. {0 if head else MAX_SHIFT}")
+            if np.any(w != np.rint(w)) or np.any(np.abs(w.astype(np.int64)) > 127):
+                bad = "a weight of -128" if np.any(w == -128) else "a weight outside -127 .. 127"
+                raise ValueError(f"conv: layer {i}: {bad} (weights are -127 .. 127)")
+            if np.any(np.abs(b.astype(np.int64)) > MAX_BIAS):
+                raise ValueError(f"conv: layer {i}: a bias of {int(b[np.argmax(np.abs(b.astype(np.int64)))])} is past "
+                                 f"2^30 in magnitude")
+            self.layers.append((np.ascontiguousarray(w, np.int8), np.ascontiguousarray(b, np.int32), shift))
+        self._handles: dict[int, Any] = {}
+
+    # -- the blob ------------------------------------------------------------------
+    def blob(self) -> np.ndarray:
+        """The network as the C ABI takes it (include/envpool_amd.h): uint8, 4-byte aligned."""
+        h, w, c = self.obs_shape
+        parts = [np.array([CONV_MAGIC, VERSION, h, w, c, self.actions, self.channels, self.blocks, self.planes],
+                          "<u4").tobytes(),
+                 np.array([self.scale_p, self.scale_v], "<f4").tobytes(), np.array([0], "<i4").tobytes()]
+        for wt, b, shift in self.layers:
+            raw = wt.tobytes()
+            parts += [raw, b"\0" * (-len(raw) % 4), b.astype("<i4").tobytes(), np.array([shift], "<i4").tobytes()]
+        return np.frombuffer(b"".join(parts), np.uint8).copy()
+
+    @classmethod
+    def from_blob(cls, blob: Any) -> "ConvNet":
+        blob = np.ascontiguousarray(blob, np.uint8)
+        if blob.nbytes < CONV_HEADER_BYTES:
+            raise ValueError(f"conv: a blob of {blob.nbytes} bytes is shorter than a header")
+        magic, version, h, w, c, a, d, blocks, planes = (int(x) for x in blob[:36].view("<i4"))
+        if magic != CONV_MAGIC:
+            raise ValueError("conv: the blob does not begin with the magic PGXC")
+        if version != VERSION:
+            raise ValueError(f"conv: version = {version} must be {VERSION}")
+        _check_conv_sizes(h, w, c, a, d, blocks, planes)
+        scale_p, scale_v = (float(x) for x in blob[36:44].view("<f4"))
+        at, layers = CONV_HEADER_BYTES, []
+        for i, shape in enumerate(_conv_shapes(h, w, c, a, d, blocks, planes)):
+            n, size = shape[0], int(np.prod(shape))
+            need = at + (size + 3) // 4 * 4 + 4 * n + 4
+            if blob.nbytes < need:
+                raise ValueError(f"conv: a blob of {blob.nbytes} bytes ends inside layer {i}")
+            wt = blob[at:at + size].view(np.int8).reshape(shape)
+            at += (size + 3) // 4 * 4
+            b = blob[at:at + 4 * n].view("<i4")
+            at += 4 * n
+            layers.append((wt, b, int(blob[at:at + 4].view("<i4")[0])))
+            at += 4
+        if at != blob.nbytes:
+            raise ValueError(f"conv: a blob of {blob.nbytes} bytes for a network of {at} bytes")
+        return cls((h, w, c), a, d, blocks, planes, layers, scale_p, scale_v)
+
+    def save(self, path: str) -> None:
+        arrays = {"obs_shape": np.array(self.obs_shape, np.int32), "actions": np.int32(self.actions),
+                  "channels": np.int32(self.channels), "blocks": np.int32(self.blocks),
+                  "planes": np.int32(self.planes), "scale": np.array([self.scale_p, self.scale_v], np.float32),
+                  "shift": np.array([s for _, _, s in self.layers], np.int32)}
+        for i, (w, b, _) in enumerate(self.layers):
+            arrays[f"w{i}"], arrays[f"b{i}"] = w, b
+        with open(path, "wb") as f:  # (np.savez would add ".npz" to a bare name)
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path: str) -> "ConvNet":
+        with np.load(path) as z:
+            blocks = int(z["blocks"])
+            layers = [(z[f"w{i}"], z[f"b{i}"], int(z["shift"][i])) for i in range(2 * blocks + 3)]
+            return cls(z["obs_shape"], int(z["actions"]), int(z["channels"]), blocks, int(z["planes"]), layers,
+                       float(z["scale"][0]), float(z["scale"][1]))
+
+    @classmethod
+    def random(cls, obs_shape: Sequence[int], actions: int, channels: int, blocks: int, planes: int, seed: int = 0,
+               shift_delta: int = 0) -> "ConvNet":
+        """A network for tests and smoke runs from numpy's PCG64(seed): weights uniform in -127 .. 127, biases uniform
+        in -1024 .. 1024, drawn layer by layer (weights, then bias), shifts that keep the activations spread over
+        0 .. 127 for inputs of density 1/4 (`shift_delta` is added to every shift)."""
+        rng = np.random.Generator(np.random.PCG64(seed))
+        h, w, c = (int(x) for x in obs_shape)
+        shapes = _conv_shapes(h, w, c, actions, channels, blocks, planes)
+        shifts = ([round(np.log2(73.0 * np.sqrt(9 * c / 4.0) / 32.0))] +
+                  [round(np.log2(73.0 * np.sqrt(9 * channels) * 40.0 / 32.0))] * (2 * blocks) +
+                  [round(np.log2(73.0 * np.sqrt(channels) * 40.0 / 32.0))])
+        layers = []
+        for i, shape in enumerate(shapes):
+            wt = rng.integers(-127, 128, size=shape).astype(np.int8)
+            b = rng.integers(-1024, 1025, size=shape[0]).astype(np.int32)
+            layers.append((wt, b, 0 if i == len(shapes) - 1 else min(MAX_SHIFT, max(0, int(shifts[i]) + shift_delta))))
+        spread = 73.0 * np.sqrt(h * w * planes) * 40.0  # about the deviation of the head's integers
+        return cls((h, w, c), actions, channels, blocks, planes, layers, 4.0 / spread, 1.0 / spread)
+
+    # -- the torch twin ------------------------------------------------------------
+    def module(self) -> Any:
+        """A `torch.nn.Module` with this net's numbers as float64 parameters: `forward(x [rows, H, W, C] or
+        [rows, H W C]) -> (logits float32 [rows, A], value float32 [rows])` with the contract's bits through
+        `conv2d(padding=1)`, `integers(x)` the head's p as float64; rounding passes gradients straight through."""
+        return _make_conv_module(self)
+
+    @classmethod
+    def from_module(cls, m: Any) -> "ConvNet":
+        layers = [(np.clip(np.rint(w.detach().numpy()), -127, 127).astype(np.int8),
+                   np.clip(np.rint(b.detach().numpy()), -MAX_BIAS, MAX_BIAS).astype(np.int32), int(s))
+                  for w, b, s in zip(m.weights, m.biases, m.shifts)]
+        return cls(m.obs_shape, m.actions, m.channels, m.blocks, m.planes, layers, m.scale_p, m.scale_v)
+
+
+def _make_conv_module(net: ConvNet) -> Any:
+    import torch
+
+    class ConvNetModule(torch.nn.Module):
+        def __init__(self) -> None:
+            super().__init__()
+            self.obs_shape, self.actions, self.channels = net.obs_shape, net.actions, net.channels
+            self.blocks, self.planes = net.blocks, net.planes
+            self.scale_p, self.scale_v = net.scale_p, net.scale_v
+            self.shifts = [s for _, _, s in net.layers]
+            self.weights = torch.nn.ParameterList(
+                [torch.nn.Parameter(torch.tensor(w.astype(np.float64))) for w, _, _ in net.layers])
+            self.biases = torch.nn.ParameterList(
+                [torch.nn.Parameter(torch.tensor(b.astype(np.float64))) for _, b, _ in net.layers])
+
+        @staticmethod
+        def _ste(x: Any, q: Any) -> Any:  # the value of q, the gradient of x
+            return x + (q - x).detach()
+
+        def _layer(self, i: int, x: Any) -> Any:
+            """x [rows, K, H, W] (the head: [rows, K]) -> rs(W x + b) before any clamp."""
+            w, b = self.weights[i], self.biases[i]
+            w = self._ste(w, torch.clamp(torch.round(w), -127, 127))
+            b = self._ste(b, torch.round(b))
+            if w.dim() == 4:  # [N, 3, 3, K] as the blob has it
+                z = torch.nn.functional.conv2d(x, w.permute(0, 3, 1, 2), b, padding=1)
+            elif x.dim() == 4:  # the 1x1 reduction
+                z = torch.nn.functional.conv2d(x, w[:, :, None, None], b)
+            else:
+                z = x @ w.t() + b
+            s = self.shifts[i]
+            if s:
+                z = self._ste(z / 2.0 ** s, torch.floor((z + 2.0 ** (s - 1)) / 2.0 ** s))
+            return z
+
+        def integers(self, x: Any) -> Any:
+            x = x.reshape((x.shape[0],) + self.obs_shape).to(torch.float64).permute(0, 3, 1, 2)
+            h = torch.clamp(self._layer(0, x), 0, 127)
+            for l in range(self.blocks):
+                t = torch.clamp(self._layer(1 + 2 * l, h), 0, 127)
+                h = torch.clamp(self._layer(2 + 2 * l, t) + h, 0, 127)
+            g = torch.clamp(self._layer(2 * self.blocks + 1, h), 0, 127)
+            return self._layer(2 * self.blocks + 2, g.permute(0, 2, 3, 1).reshape(g.shape[0], -1))  # (y, x, plane)
+
+        def forward(self, x: Any) -> tuple[Any, Any]:
+            p = self.integers(x).to(torch.float32)
+            logits = p[:, :self.actions] * torch.tensor(self.scale_p, dtype=torch.float32)
+            value = torch.clamp(p[:, self.actions] * torch.tensor(self.scale_v, dtype=torch.float32), -1.0, 1.0)
+            return logits, value
+
+    return ConvNetModule()

@@ -851,6 +851,15 @@ int epa_gumbel_begin_batch_device(epa_pool* pool, const int32_t* env_ids, int32_
  *   layers (trunk, the blocks' two each, head), each int8 [N][K] row-major padded with zeros to a multiple of 4 bytes,
  *   int32 bias [N], int32 shift (the head's is 0).  D a multiple of 32 in 32 .. 512, L 0 .. 8, F 1 .. 512, A 1 .. 127,
  *   scales finite in (0, 1e20].
+ *   The second kind of blob, a convolutional network (csrc/pgx_conv.hip.h is the contract): 48 bytes { uint32 magic
+ *   "PGXC", int32 version = 1, H, W, C, A, D, L, P, float scale_p, scale_v, int32 0 }, then the 2 L + 3 layers (stem
+ *   [D][3][3][C], the blocks' two each [D][3][3][D], reduce [P][D], head [A + 1][H W P]) in the same layer format.  A
+ *   stem and L residual blocks of 3x3 convolutions with zero padding over the [H][W][C] board, a 1x1 reduction to P
+ *   planes and a dense head over their bytes in the order (y, x, plane); the same arithmetic and outputs.  H W <= 128,
+ *   C 1 .. 32, D a multiple of 32 in 32 .. 256, L 0 .. 8, P 1 .. 32 with H W P <= 512, A 1 .. 127.  epa_net_create tells
+ *   the kinds apart by the magic; every call below takes either kind, except that the pool's H, W and C must be the
+ *   net's as well, that the two nets of a pair call are of one kind, and that a rollout actor takes the first kind
+ *   only.  EPA_ERR_INVALID also for a convolutional net whose single board does not fit a block's LDS on the device.
  *   A net is created on a device and belongs to it, not to a pool: any pool of that device whose epa_guided_shape
  *   gives the same F and A can use it.  It owns one device allocation (the weights in the kernel's layout and the
  *   policy / value rows of its own evaluations, grown to the largest row count seen).  Calls that use one net must not
