@@ -168,14 +168,16 @@ class Actor:
         return r.astype(np.uint8)
 
     # -- the torch twin ------------------------------------------------------------
-    def module(self) -> Any:
+    def module(self, kernels: bool = False) -> Any:
         """A `torch.nn.Module` with this actor's numbers: `features(obs)` the contract's bytes as float64 (rounding
         passes gradients straight through), `integers(obs)` the head's p as float64 -- exactly the device's --,
         `forward(obs) -> (logits float32 [rows, H], value float32 [rows])` with the contract's bits, and the
         differentiable `logp(obs, action)`, `entropy(obs)` and `value(obs)` a learner needs.  `obs`: a tensor [rows, ...]
         (several obs keys: concatenated along the flattened last axis in key order).  The trunk is `Net.module()`'s;
-        sigma is a parameter."""
-        return _make_module(self)
+        sigma is a parameter.  `kernels` goes to the trunk (`Net.module(kernels=True)`: the training kernels for obs on
+        a ROCm device); the features stay torch, and obs must not require grad.  `logp_of(logits, action)` is `logp`
+        from the logits of one `forward(obs)`, which then serves the value too: one pass through the trunk per step."""
+        return _make_module(self, bool(kernels))
 
     @classmethod
     def from_module(cls, m: Any) -> "Actor":
@@ -183,7 +185,7 @@ class Actor:
         return cls(Net.from_module(m.net), m.kind, m.lo.cpu().numpy(), m.scale.cpu().numpy(), sigma, m.low, m.high)
 
 
-def _make_module(actor: Actor) -> Any:
+def _make_module(actor: Actor, kernels: bool = False) -> Any:
     import torch
 
     class ActorModule(torch.nn.Module):
@@ -191,7 +193,7 @@ def _make_module(actor: Actor) -> Any:
             super().__init__()
             self.kind, self.actions = actor.kind, actor.actions
             self.low, self.high = actor.low.copy(), actor.high.copy()
-            self.net = actor.net.module()
+            self.net = actor.net.module(kernels=kernels)
             self.register_buffer("lo", torch.tensor(actor.lo))
             self.register_buffer("scale", torch.tensor(actor.scale))
             self.sigma = torch.nn.Parameter(torch.tensor(actor.sigma.astype(np.float32)))
@@ -216,7 +218,11 @@ def _make_module(actor: Actor) -> Any:
 
         def logp(self, obs: Any, action: Any) -> Any:
             """float64 [rows]: the log-probability (Box: the density) of `action` from the float32 logits."""
-            logits = self.forward(obs)[0].to(torch.float64)
+            return self.logp_of(self.forward(obs)[0], action)
+
+        def logp_of(self, logits: Any, action: Any) -> Any:
+            """`logp` from the logits of a `forward(obs)` the caller already has: one pass serves `logp` and value."""
+            logits = logits.to(torch.float64)
             if self.kind == DISCRETE:
                 return torch.log_softmax(logits, dim=1).gather(1, action.reshape(-1, 1).long()).reshape(-1)
             sigma = self.sigma.to(torch.float64)

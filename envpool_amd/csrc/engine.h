@@ -531,6 +531,32 @@ void NetEvalLaunch(const Net& net, const Net* net_b, int rows, int mode, const u
                    const unsigned char* mask, const unsigned char* status, float* policy, float* value,
                    unsigned int* pending, hipStream_t stream);
 
+// The training handle of the built-in dense network (epa_net_train_create; pgx_train.hip.h is the contract,
+// pgx_train.hip the kernels): it belongs to a device and needs no pool.  It owns ONE device allocation, sized at creation
+// for `max_rows` and kept between steps: the weights in the kernels' two layouts, a copy of the input bytes, the saved
+// bytes (2 L + 1) * rows * D, two split dz buffers of rows * D words, the split dp and the slice workspace.  The calls
+// only enqueue on the caller's stream; calls on one handle are the caller's to serialise.
+class NetTrain {
+ public:
+  NetTrain(int device, int F, int A, int D, int L, long long max_rows);
+  ~NetTrain();
+  // d_w[i] int8 [N][K], d_b[i] int32 [N] on the device, shifts[i] on the host, i < 2 L + 2; d_x bytes [rows][F];
+  // d_p int32 [rows][A + 1].  std::invalid_argument before any launch for what the contract refuses.
+  void Forward(hipStream_t stream, int rows, const void* const* d_w, const void* const* d_b, const int32_t* shifts,
+               const void* d_x, void* d_p);
+  // d_dp float32 [rows][A + 1] -> d_dw[i] float32 [N][K], d_db[i] float32 [N], through the last Forward's activations:
+  // std::invalid_argument when there was none or it had other rows.
+  void Backward(hipStream_t stream, int rows, const void* d_dp, void* const* d_dw, void* const* d_db);
+
+ private:
+  struct Layout;
+  int device_, F_, A_, D_, L_, max_rows_;
+  int rows_{0};  // of the last Forward; 0: none
+  int32_t shift_[kNetImageLayers]{};
+  std::unique_ptr<Layout> at_;
+  DeviceBlock mem_;
+};
+
 // One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
 // row i is local env i of the pool, every pointer device memory.
 struct SelfplayArgs {

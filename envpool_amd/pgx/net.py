@@ -10,7 +10,8 @@ sessions.
 `search.run(net)` makes the round without Python between its launches; `net.bind(env)` gives a plain callable with the
 `evaluate` signature (numpy in and out, or torch tensors on the pool's device) for every entry point that takes one.
 `Net.module()` is a torch twin that computes the same integers in float64 with straight-through gradients, and
-`Net.from_module` comes back: the format is trainable.
+`Net.from_module` comes back: the format is trainable.  `Net.module(kernels=True)` trains on the device: the twin's
+forward and backward as two hand-written kernels (pgx/train.py).
 
 `ConvNet` (csrc/pgx_conv.hip.h, csrc/pgx_conv.hip) is the second kind, a tower of 3x3 residual convolutions in the same
 arithmetic and with the same surface; it goes wherever a `Net` goes, except into the rollout actor."""
@@ -217,11 +218,16 @@ class Net(_OnDevice):
         return cls(obs_shape, actions, hidden, blocks, layers, 4.0 / spread, 1.0 / spread)
 
     # -- the torch twin ------------------------------------------------------------
-    def module(self) -> Any:
+    def module(self, kernels: bool = False) -> Any:
         """A `torch.nn.Module` with this net's numbers as float64 parameters: `forward(x [rows, F]) -> (logits float32
         [rows, A], value float32 [rows])` with the contract's bits, `integers(x)` the head's p as float64; rounding
-        passes gradients straight through."""
-        return _make_module(self)
+        passes gradients straight through.
+        `kernels=True`: for x on a ROCm device `integers` and its backward are the training kernels
+        (csrc/pgx_train.hip.h: the same integers, every gradient within 2^-12 per layer of the twin's); x then holds
+        integers 0 .. 127 (anything else is rounded and clamped to them, on either device), must not require grad
+        (ValueError) and has 1 .. 2^20 rows; the parameters are on x's device (ValueError).  On CPU tensors it is the
+        twin's code.  `envpool_amd.pgx.train.release()` frees the device memory the kernels keep between steps."""
+        return _make_module(self, bool(kernels))
 
     @classmethod
     def from_module(cls, m: Any) -> "Net":
@@ -231,12 +237,13 @@ class Net(_OnDevice):
         return cls(m.obs_shape, m.actions, m.hidden, m.blocks, layers, m.scale_p, m.scale_v)
 
 
-def _make_module(net: Net) -> Any:
+def _make_module(net: Net, kernels: bool = False) -> Any:
     import torch
 
     class NetModule(torch.nn.Module):
         def __init__(self) -> None:
             super().__init__()
+            self.kernels = kernels
             self.obs_shape, self.actions, self.hidden, self.blocks = net.obs_shape, net.actions, net.hidden, net.blocks
             self.scale_p, self.scale_v = net.scale_p, net.scale_v
             self.shifts = [s for _, _, s in net.layers]
@@ -260,6 +267,13 @@ def _make_module(net: Net) -> Any:
             return z
 
         def integers(self, x: Any) -> Any:
+            if self.kernels:
+                from envpool_amd.pgx import train
+
+                train.check_input(x)
+                if x.is_cuda:
+                    return train.integers(self, x.reshape(x.shape[0], -1))
+                x = train.input_integers(x)  # (what the kernels read: nothing changes within 0 .. 127)
             x = x.reshape(x.shape[0], -1).to(torch.float64)
             h = torch.clamp(self._layer(0, x), 0, 127)
             for l in range(self.blocks):

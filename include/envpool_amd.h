@@ -895,6 +895,37 @@ int epa_net_run(epa_pool* pool, epa_net* net, int32_t advances, uint8_t* obs, ui
 int epa_net_run_device(epa_pool* pool, epa_net* net, int32_t advances, void* device_obs, void* device_mask,
                        void* device_status, int32_t* made);
 
+/* Built-in network, training (no reference analogue; csrc/pgx_train.hip.h is the authority): the forward and backward
+ * pass of the dense network above on the device, under the straight-through rules of its float64 twin
+ * (`Net.module()`), as the two halves of a torch.autograd.Function.  Loss, optimizer and re-quantising stay the
+ * caller's.  A training handle belongs to a device and needs no pool; it owns one device allocation sized for
+ * `max_rows` (about (2 L + 9) * max_rows * D bytes) that is kept between steps.
+ *   epa_net_train_create(device, F, A, D, L, max_rows, &handle): F 1 .. 512, A 1 .. 127, D a multiple of 32 in 32 ..
+ *     512, L 0 .. 8, max_rows 1 .. 2^20.
+ *   epa_net_train_forward_device(handle, stream, rows, d_w[], d_b[], shifts[], d_x, d_p): d_w[i] and d_b[i], i < 2 L +
+ *     2 in the blob's layer order, are DEVICE arrays int8 [N][K] row-major (-127 .. 127) and int32 [N] (at most 2^30 in
+ *     magnitude) -- the master parameters quantised by the caller on the device; the arrays of pointers and shifts[]
+ *     (0 .. 24, the head's 0) are host memory.  d_x: bytes [rows][F], 0 .. 127.  d_p: int32 [rows][A + 1], the head's
+ *     sums of the contract above.  The weights are repacked on the device in the same call: nothing is uploaded.
+ *   epa_net_train_backward_device(handle, stream, rows, d_dp, d_dw[], d_db[]): d_dp float32 [rows][A + 1] -> d_dw[i]
+ *     float32 [N][K], d_db[i] float32 [N], every layer's gradients through the activations and weights of the last
+ *     forward.  Each is within c = 2^-12 per layer between it and the output of the exact value, relative to the same
+ *     sums over magnitudes (the header derives c).  The input gets no gradient.  The same inputs give the same bits on
+ *     every run: no atomics, partial sums over row slices are added in an order the sizes fix.
+ *   epa_net_train_destroy(handle).
+ *   `stream` is the caller's HIP stream (torch's current one; null: the default stream) of `device`.  The calls only
+ *   enqueue, all launches of a call from one C++ function; calls on one handle must not overlap.
+ *   EPA_ERR_INVALID, before any launch: sizes or rows outside the limits, rows above max_rows, a shift out of range,
+ *   null arguments, a device index out of range; backward without a forward, or with other rows than the last one. */
+typedef struct epa_net_train epa_net_train;
+int epa_net_train_create(int32_t device, int32_t F, int32_t A, int32_t D, int32_t L, int64_t max_rows,
+                         epa_net_train** out);
+int epa_net_train_destroy(epa_net_train* train);
+int epa_net_train_forward_device(epa_net_train* train, void* stream, int32_t rows, const void* const* d_w,
+                                 const void* const* d_b, const int32_t* shifts, const void* d_x, void* d_p);
+int epa_net_train_backward_device(epa_net_train* train, void* stream, int32_t rows, const void* d_dp,
+                                  void* const* d_dw, void* const* d_db);
+
 /* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
  * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
  * targets of the game in progress; when the game ends it writes one sample per staged ply -- or one per ply and board
