@@ -191,6 +191,10 @@ def lib() -> ctypes.CDLL:
         "epa_net_train_destroy": (i32, [vp]),
         "epa_net_train_forward_device": (i32, [vp, vp, i32, P(vp), P(vp), P(i32), vp, vp]),
         "epa_net_train_backward_device": (i32, [vp, vp, i32, vp, P(vp), P(vp)]),
+        "epa_conv_train_create": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_int64, P(vp)]),
+        "epa_conv_train_destroy": (i32, [vp]),
+        "epa_conv_train_forward_device": (i32, [vp, vp, i32, P(vp), P(vp), P(i32), vp, vp]),
+        "epa_conv_train_backward_device": (i32, [vp, vp, i32, vp, P(vp), P(vp)]),
         "epa_selfplay_begin": (i32, [vp, vp, P(SelfplayOptions)]),
         "epa_selfplay_run": (i32, [vp, i32]),
         "epa_selfplay_run_device": (i32, [vp, i32]),
@@ -295,6 +299,8 @@ EXPORTED_SYMBOLS = [
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_selfplay_begin_ex", "epa_selfplay_noise",
     "epa_net_train_create", "epa_net_train_destroy", "epa_net_train_forward_device", "epa_net_train_backward_device",
+    "epa_conv_train_create", "epa_conv_train_destroy", "epa_conv_train_forward_device",
+    "epa_conv_train_backward_device",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",

@@ -557,6 +557,40 @@ class NetTrain {
   DeviceBlock mem_;
 };
 
+// The dense training launches the convolutional handle shares (pgx_train.hip): the split of dp float32 [rows][N] into
+// [rows][n16]; dW = dz^T x and db of a dense layer over `rows` rows (TrainReduce over TrainSlices(rows, N, K), then
+// TrainSum) with dz split [rows][ldn], x bytes [rows][K] and `ws` of TrainMostSlices * N * (K + 1) floats; and the sum
+// of `slices` partial images [N][K + 1] alone.
+void TrainSplitLaunch(const float* dp, int rows, int N, int n16, uint32_t* out, hipStream_t stream);
+void TrainReduceLaunch(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
+                       float* dw, float* db, hipStream_t stream);
+void TrainSumLaunch(const float* ws, int slices, int N, int K, float* dw, float* db, hipStream_t stream);
+
+// The training handle of the convolutional network (epa_conv_train_create; pgx_conv_train.hip.h is the contract,
+// pgx_conv_train.hip the kernels), as NetTrain is the dense one's.  Its ONE device allocation holds the weights in the
+// kernels' layouts, a copy of the input bytes, the saved bytes (2 L + 1) * rows * H W * D and rows * H W * P, two split
+// dz buffers of rows * H W * D words, the split dz of the reduce layer and of the head, and the slice workspace.
+class ConvTrain {
+ public:
+  ConvTrain(int device, int H, int W, int C, int A, int D, int L, int P, long long max_rows);
+  ~ConvTrain();
+  // d_w[i] int8 in the blob's order, d_b[i] int32 [N] on the device, shifts[i] on the host, i < 2 L + 3; d_x bytes
+  // [rows][H W C]; d_p int32 [rows][A + 1].  std::invalid_argument before any launch for what the contract refuses.
+  void Forward(hipStream_t stream, int rows, const void* const* d_w, const void* const* d_b, const int32_t* shifts,
+               const void* d_x, void* d_p);
+  // d_dp float32 [rows][A + 1] -> d_dw[i] float32 in the blob's order, d_db[i] float32 [N], through the last
+  // Forward's activations: std::invalid_argument when there was none or it had other rows.
+  void Backward(hipStream_t stream, int rows, const void* d_dp, void* const* d_dw, void* const* d_db);
+
+ private:
+  struct Layout;
+  int device_, H_, W_, C_, A_, D_, L_, P_, max_rows_;
+  int rows_{0};  // of the last Forward; 0: none
+  int32_t shift_[kConvImageLayers]{};
+  std::unique_ptr<Layout> at_;
+  DeviceBlock mem_;
+};
+
 // One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
 // row i is local env i of the pool, every pointer device memory.
 struct SelfplayArgs {

@@ -444,6 +444,26 @@ size_t Align256(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
 
 // ---------------------------------------------------------------------------
+// the launches the convolutional training handle shares (engine.h)
+// ---------------------------------------------------------------------------
+void TrainSplitLaunch(const float* dp, int rows, int N, int n16, uint32_t* out, hipStream_t stream) {
+  const size_t cells = (size_t)rows * n16;
+  hipLaunchKernelGGL(TrainSplitDp, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, dp, rows, N, n16, out);
+}
+
+void TrainReduceLaunch(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
+                       float* dw, float* db, hipStream_t stream) {
+  const pgx::TrainSlicing s = pgx::TrainSlices(rows, N, K);
+  RedArgs r{rows, N, K, dz, ldn, x, s.slice_rows, ws};
+  hipLaunchKernelGGL(TrainReduce, dim3((K + 63) / 64, (N + 63) / 64, s.slices), dim3(256), 0, stream, r);
+  TrainSumLaunch(ws, s.slices, N, K, dw, db, stream);
+}
+
+void TrainSumLaunch(const float* ws, int slices, int N, int K, float* dw, float* db, hipStream_t stream) {
+  hipLaunchKernelGGL(TrainSum, dim3((N * (K + 1) + 255) / 256), dim3(256), 0, stream, ws, slices, N, K, dw, db);
+}
+
+// ---------------------------------------------------------------------------
 // the handle (engine.h: NetTrain)
 // ---------------------------------------------------------------------------
 struct NetTrain::Layout {
@@ -583,11 +603,8 @@ void NetTrain::Backward(hipStream_t stream, int rows, const void* d_dp, void* co
   // dW and db of layer i from its dz
   auto reduce = [&](int i, const uint32_t* dz, int ldn) {
     const int N = i == layers - 1 ? A_ + 1 : D_, K = i == 0 ? F_ : D_;
-    const pgx::TrainSlicing s = pgx::TrainSlices(rows, N, K);
-    RedArgs r{rows, N, K, dz, ldn, i == 0 ? x : activation(i - 1), s.slice_rows, ws};
-    hipLaunchKernelGGL(TrainReduce, dim3((K + 63) / 64, (N + 63) / 64, s.slices), dim3(256), 0, stream, r);
-    hipLaunchKernelGGL(TrainSum, dim3((N * (K + 1) + 255) / 256), dim3(256), 0, stream, ws, s.slices, N, K,
-                       static_cast<float*>(d_dw[i]), static_cast<float*>(d_db[i]));
+    TrainReduceLaunch(rows, N, K, dz, ldn, i == 0 ? x : activation(i - 1), ws, static_cast<float*>(d_dw[i]),
+                      static_cast<float*>(d_db[i]), stream);
   };
   // the dz of layer i - 1 from the dz of layer i >= 1
   auto below = [&](int i, const uint32_t* dz, int ldn, int width, const uint32_t* res, int res_layer, uint32_t* out) {
@@ -605,9 +622,7 @@ void NetTrain::Backward(hipStream_t stream, int rows, const void* d_dp, void* co
       hipLaunchKernelGGL(TrainBackRow<4>, grid, block, 0, stream, r);
     }
   };
-  const size_t cells = (size_t)rows * n16;
-  hipLaunchKernelGGL(TrainSplitDp, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream,
-                     static_cast<const float*>(d_dp), rows, A_ + 1, n16, dp);
+  TrainSplitLaunch(static_cast<const float*>(d_dp), rows, A_ + 1, n16, dp, stream);
   reduce(layers - 1, dp, n16);
   below(layers - 1, dp, n16, n16, nullptr, 0, buf_a);
   for (int l = L_ - 1; l >= 0; --l) {

@@ -14,7 +14,8 @@ sessions.
 forward and backward as two hand-written kernels (pgx/train.py).
 
 `ConvNet` (csrc/pgx_conv.hip.h, csrc/pgx_conv.hip) is the second kind, a tower of 3x3 residual convolutions in the same
-arithmetic and with the same surface; it goes wherever a `Net` goes, except into the rollout actor."""
+arithmetic and with the same surface, `module(kernels=True)` included (csrc/pgx_conv_train.hip); it goes wherever a
+`Net` goes, except into the rollout actor."""
 from __future__ import annotations
 
 import ctypes
@@ -437,11 +438,19 @@ class ConvNet(_OnDevice):
         return cls((h, w, c), actions, channels, blocks, planes, layers, 4.0 / spread, 1.0 / spread)
 
     # -- the torch twin ------------------------------------------------------------
-    def module(self) -> Any:
+    def module(self, kernels: bool = False) -> Any:
         """A `torch.nn.Module` with this net's numbers as float64 parameters: `forward(x [rows, H, W, C] or
         [rows, H W C]) -> (logits float32 [rows, A], value float32 [rows])` with the contract's bits through
-        `conv2d(padding=1)`, `integers(x)` the head's p as float64; rounding passes gradients straight through."""
-        return _make_conv_module(self)
+        `conv2d(padding=1)`, `integers(x)` the head's p as float64; rounding passes gradients straight through.
+        `kernels=True`, as for a `Net`: for x on a ROCm device `integers` and its backward are the training kernels
+        (csrc/pgx_conv_train.hip.h: the same integers, every gradient within c_conv = 2^-10 per layer of the twin's); x
+        then holds integers 0 .. 127 (anything else is rounded and clamped to them, on either device), must not
+        require grad (ValueError) and has 1 .. 2^22 / (H W) rows; the parameters are on x's device (ValueError).  On CPU
+        tensors it is the twin's code.  The kernels keep, until `envpool_amd.pgx.train.release()`, about
+        rows H W ((2 L + 9) D + 4 P16 + P + C) bytes of device memory at the largest row count seen (at least 4096;
+        P16 = P up to a multiple of 16) and a workspace of max(512 / tiles, rows H W / 8192) images of 4 D (9 D + 1)
+        bytes, tiles = ceil(D / 64)^2."""
+        return _make_conv_module(self, bool(kernels))
 
     @classmethod
     def from_module(cls, m: Any) -> "ConvNet":
@@ -451,12 +460,13 @@ class ConvNet(_OnDevice):
         return cls(m.obs_shape, m.actions, m.channels, m.blocks, m.planes, layers, m.scale_p, m.scale_v)
 
 
-def _make_conv_module(net: ConvNet) -> Any:
+def _make_conv_module(net: ConvNet, kernels: bool = False) -> Any:
     import torch
 
     class ConvNetModule(torch.nn.Module):
         def __init__(self) -> None:
             super().__init__()
+            self.kernels = kernels
             self.obs_shape, self.actions, self.channels = net.obs_shape, net.actions, net.channels
             self.blocks, self.planes = net.blocks, net.planes
             self.scale_p, self.scale_v = net.scale_p, net.scale_v
@@ -487,6 +497,13 @@ def _make_conv_module(net: ConvNet) -> Any:
             return z
 
         def integers(self, x: Any) -> Any:
+            if self.kernels:
+                from envpool_amd.pgx import train
+
+                train.check_input(x, train.conv_max_rows(self.obs_shape[0] * self.obs_shape[1]), "conv")
+                if x.is_cuda:
+                    return train.conv_integers(self, x.reshape(x.shape[0], -1))
+                x = train.input_integers(x)  # (what the kernels read: nothing changes within 0 .. 127)
             x = x.reshape((x.shape[0],) + self.obs_shape).to(torch.float64).permute(0, 3, 1, 2)
             h = torch.clamp(self._layer(0, x), 0, 127)
             for l in range(self.blocks):

@@ -926,6 +926,30 @@ int epa_net_train_forward_device(epa_net_train* train, void* stream, int32_t row
 int epa_net_train_backward_device(epa_net_train* train, void* stream, int32_t rows, const void* d_dp,
                                   void* const* d_dw, void* const* d_db);
 
+/* Convolutional network, training (csrc/pgx_conv_train.hip.h is the authority): the same two halves for the
+ * convolutional network above, under the rules of `ConvNet.module()`.  The calls mirror epa_net_train_*:
+ *   epa_conv_train_create(device, H, W, C, A, D, L, P, max_rows, &handle): the sizes within the convolutional blob's
+ *     limits, max_rows >= 1 with max_rows * H * W <= 2^22; a net one board of which does not fit a block's LDS in the
+ *     kernels is refused.  The handle keeps about max_rows * H W * ((2 L + 9) D + 4 P16 + P + C) bytes (P16 = P up to
+ *     a multiple of 16) and a slice workspace.
+ *   epa_conv_train_forward_device(handle, stream, rows, d_w[], d_b[], shifts[], d_x, d_p): d_w[i], d_b[i], i < 2 L + 3
+ *     in the blob's layer order and layouts ([D][3][3][K], [P][D], [A + 1][H W P]); d_x bytes [rows][H][W][C],
+ *     0 .. 127; d_p int32 [rows][A + 1].
+ *   epa_conv_train_backward_device(handle, stream, rows, d_dp, d_dw[], d_db[]): d_dp float32 [rows][A + 1] -> d_dw[i]
+ *     float32 in the weights' layouts, d_db[i] float32 [N]; each within c_conv = 2^-10 per layer between it and the
+ *     output of the exact value, relative to the same sums over magnitudes.  No atomics: the same inputs give the same
+ *     bits.
+ *   epa_conv_train_destroy(handle).
+ *   Streams, enqueueing and the EPA_ERR_INVALID refusals are those of epa_net_train_*. */
+typedef struct epa_conv_train epa_conv_train;
+int epa_conv_train_create(int32_t device, int32_t H, int32_t W, int32_t C, int32_t A, int32_t D, int32_t L, int32_t P,
+                          int64_t max_rows, epa_conv_train** out);
+int epa_conv_train_destroy(epa_conv_train* train);
+int epa_conv_train_forward_device(epa_conv_train* train, void* stream, int32_t rows, const void* const* d_w,
+                                  const void* const* d_b, const int32_t* shifts, const void* d_x, void* d_p);
+int epa_conv_train_backward_device(epa_conv_train* train, void* stream, int32_t rows, const void* d_dp,
+                                   void* const* d_dw, void* const* d_db);
+
 /* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
  * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
  * targets of the game in progress; when the game ends it writes one sample per staged ply -- or one per ply and board
