@@ -195,6 +195,11 @@ def lib() -> ctypes.CDLL:
         "epa_conv_train_destroy": (i32, [vp]),
         "epa_conv_train_forward_device": (i32, [vp, vp, i32, P(vp), P(vp), P(i32), vp, vp]),
         "epa_conv_train_backward_device": (i32, [vp, vp, i32, vp, P(vp), P(vp)]),
+        "epa_trainer_create": (i32, [i32, vp, ctypes.c_size_t, P(TrainerOptions), ctypes.c_int64, P(vp)]),
+        "epa_trainer_destroy": (i32, [vp]),
+        "epa_trainer_step_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+        "epa_trainer_fit_device": (i32, [vp, vp, P(vp), ctypes.c_int64, i32, i32]),
+        "epa_trainer_read": (i32, [vp, i32, i32, vp]),
         "epa_selfplay_begin": (i32, [vp, vp, P(SelfplayOptions)]),
         "epa_selfplay_run": (i32, [vp, i32]),
         "epa_selfplay_run_device": (i32, [vp, i32]),
@@ -301,6 +306,8 @@ EXPORTED_SYMBOLS = [
     "epa_net_train_create", "epa_net_train_destroy", "epa_net_train_forward_device", "epa_net_train_backward_device",
     "epa_conv_train_create", "epa_conv_train_destroy", "epa_conv_train_forward_device",
     "epa_conv_train_backward_device",
+    "epa_trainer_create", "epa_trainer_destroy", "epa_trainer_step_device", "epa_trainer_fit_device",
+    "epa_trainer_read",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -671,6 +678,15 @@ class SelfplayOptions(ctypes.Structure):
                 ("prove", ctypes.c_int32), ("tactics_nodes", ctypes.c_int64), ("seed", ctypes.c_uint64),
                 ("noise", ctypes.c_int32), ("sample_plies", ctypes.c_int32), ("record", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class TrainerOptions(ctypes.Structure):
+    """epa_trainer_options (include/envpool_amd.h)."""
+
+    _fields_ = [("optimizer", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lr", ctypes.c_double),
+                ("momentum", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("value_weight", ctypes.c_double),
+                ("clip", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
 class SelfplayExtra(ctypes.Structure):

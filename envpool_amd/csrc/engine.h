@@ -591,6 +591,53 @@ class ConvTrain {
   DeviceBlock mem_;
 };
 
+// The trainer of the built-in nets (epa_trainer_create; pgx_trainer.hip.h is the contract, pgx_trainer.hip the
+// kernels): the whole training step on the device.  It owns a NetTrain or a ConvTrain, by the blob's magic, and ONE
+// device allocation: per parameter array the float32 gradient, the float64 master and optimizer state and the
+// quantised array the forward takes (the segments of the contract, each 256-byte aligned and padded with zeros to
+// whole chunks), then dp, p, the gathered inputs, the partials and the ring of statistics rows.  Every call enqueues
+// all its launches on the caller's stream and waits for nothing; calls on one handle are the caller's to serialise.
+struct TrainerOptions {
+  int optimizer;  // pgx::kTrainerSgd / kTrainerAdam
+  double lr, momentum, beta1, beta2, eps, weight_decay, value_weight, clip;
+  uint64_t seed;
+};
+class Trainer {
+ public:
+  // std::invalid_argument for a blob NetParse / ConvParse refuses and for options outside the contract
+  Trainer(int device, const void* blob, size_t bytes, const TrainerOptions& options, long long max_rows);
+  ~Trainer();
+  // one minibatch: obs bytes [rows][F], mask bytes [rows][A], policy float32 [rows][A], value float32 [rows]
+  void Step(hipStream_t stream, int rows, const void* d_obs, const void* d_mask, const void* d_policy,
+            const void* d_value);
+  // `steps` minibatches of `batch` rows gathered from the sample arrays (obs, mask, policy, value) of `count` samples
+  void Fit(hipStream_t stream, const void* const* arrays, long long count, int batch, int steps);
+  // A host wait.  what: 0 masters, 1 first state, 2 second state (float64), 3 quantised (int8 / int32), 4 gradients
+  // (float32) of array `layer` -- weights 0 .. layers - 1, then the biases --; 5 the last dp float32 [rows][A + 1],
+  // 6 the last p int32; 7 the statistics of the last `layer` steps, float64 [layer][4]; 8 int64 [4]: the arrays, the
+  // steps made, the last rows, the elements of array `layer`
+  void Read(int what, int layer, void* out);
+
+ private:
+  struct Layout;
+  void Enqueue(hipStream_t stream, int rows, const unsigned char* obs, const unsigned char* mask, const float* policy,
+               const float* value);
+  int device_, max_rows_;
+  bool conv_{false};
+  int F_{0}, A_{0}, layers_{0};
+  float scale_p_{0}, scale_v_{0};
+  TrainerOptions opt_;
+  int32_t shift_[kConvImageLayers]{};
+  long long steps_{0};
+  int rows_{0};
+  double beta1_pow_{1.0}, beta2_pow_{1.0};
+  hipStream_t last_{nullptr};
+  std::unique_ptr<NetTrain> net_;
+  std::unique_ptr<ConvTrain> cnn_;
+  std::unique_ptr<Layout> at_;
+  DeviceBlock mem_;
+};
+
 // One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
 // row i is local env i of the pool, every pointer device memory.
 struct SelfplayArgs {

@@ -73,6 +73,14 @@ class _OnDevice:
         except Exception:  # (interpreter shutdown)
             pass
 
+    def trainer(self, **options: Any) -> Any:
+        """A `Trainer` of this net (pgx/trainer.py): the whole training step on the device.  `device=0,
+        optimizer="sgd" | "adam", lr=1.0, momentum=0.9, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+        value_weight=1.0, clip=0.0, seed=0, max_rows=4096`."""
+        from envpool_amd.pgx.trainer import Trainer
+
+        return Trainer(self, **options)
+
     def bind(self, env: Any, priors: bool = False) -> Any:
         """A callable `evaluate(obs, mask, status) -> (policy, values)` on `env` (an env of a PGX family, or its
         device pool): numpy arrays in and out, or torch tensors on the pool's device (only enqueued, ordered both ways

@@ -897,8 +897,8 @@ int epa_net_run_device(epa_pool* pool, epa_net* net, int32_t advances, void* dev
 
 /* Built-in network, training (no reference analogue; csrc/pgx_train.hip.h is the authority): the forward and backward
  * pass of the dense network above on the device, under the straight-through rules of its float64 twin
- * (`Net.module()`), as the two halves of a torch.autograd.Function.  Loss, optimizer and re-quantising stay the
- * caller's.  A training handle belongs to a device and needs no pool; it owns one device allocation sized for
+ * (`Net.module()`), as the two halves of a torch.autograd.Function.  Loss, optimizer and re-quantising on the device
+ * are epa_trainer_* below.  A training handle belongs to a device and needs no pool; it owns one device allocation sized for
  * `max_rows` (about (2 L + 9) * max_rows * D bytes) that is kept between steps.
  *   epa_net_train_create(device, F, A, D, L, max_rows, &handle): F 1 .. 512, A 1 .. 127, D a multiple of 32 in 32 ..
  *     512, L 0 .. 8, max_rows 1 .. 2^20.
@@ -949,6 +949,49 @@ int epa_conv_train_forward_device(epa_conv_train* train, void* stream, int32_t r
                                   const void* const* d_b, const int32_t* shifts, const void* d_x, void* d_p);
 int epa_conv_train_backward_device(epa_conv_train* train, void* stream, int32_t rows, const void* d_dp,
                                    void* const* d_dw, void* const* d_db);
+
+/* Trainer of the built-in networks (no reference analogue; csrc/pgx_trainer.hip.h is the authority): the whole
+ * training step of a dense or convolutional network on the device -- minibatch gather, forward, the AlphaZero loss
+ * (cross entropy of the masked softmax against the policy target plus value_weight times the squared value error),
+ * backward, gradient norm and clipping, SGD with momentum or Adam on float64 masters, and the re-quantising of the
+ * masters into the int8 / int32 arrays the next forward reads.  A trainer belongs to a device and needs no pool; it
+ * owns a training handle of the blob's kind and one device allocation sized for `max_rows`.
+ *   epa_trainer_create(device, blob, bytes, options, max_rows, &handle): the blob of epa_net_create (either magic);
+ *     the masters start as its integers, the optimizer state as zeros.
+ *   epa_trainer_step_device(handle, stream, rows, d_obs, d_mask, d_policy, d_value): one step on a minibatch in device
+ *     memory: obs bytes [rows][F], mask bytes [rows][A], policy float32 [rows][A], value float32 [rows].
+ *   epa_trainer_fit_device(handle, stream, arrays, count, batch, steps): `steps` steps of `batch` rows each; row j of
+ *     the handle's step t is sample TrainerIndex(seed, t, j, count) of arrays[0 .. 3] = the obs, mask, policy and
+ *     value sample arrays (a recorder's: epa_record_view_device), `count` their samples.
+ *   epa_trainer_read(handle, what, layer, out): a host wait.  what 0 .. 4: the masters, the first and second optimizer
+ *     state (float64), the quantised array (int8 weights, int32 biases) and the last gradient (float32) of parameter
+ *     array `layer` -- the weights of the layers in the blob's order, then their biases --; 5: the last dp float32
+ *     [rows][A + 1]; 6: the last p int32 [rows][A + 1]; 7: the statistics rows of the last `layer` (at most 4096)
+ *     steps, float64 [layer][4]: policy loss, value loss, gradient norm, rows; 8: int64 [4]: the parameter arrays, the
+ *     steps made, the rows of the last step, the elements of array `layer`.
+ *   epa_trainer_destroy(handle).
+ *   Both step calls only enqueue on `stream` (0: the null stream) and return; calls on one handle are the caller's to
+ *   serialise.  No atomics: the same inputs give the same bits.
+ *   EPA_ERR_INVALID, before any launch: rows or batch outside 1 .. max_rows; count < 1; steps < 1; an unknown
+ *     optimizer; an lr, momentum, beta, eps, weight_decay, value_weight or clip that is negative or not finite; a null
+ *     argument; a blob that is no network; max_rows past the training handle's limit. */
+#define EPA_TRAINER_SGD 0
+#define EPA_TRAINER_ADAM 1
+typedef struct epa_trainer_options {
+  int32_t optimizer;
+  int32_t reserved;  /* 0 */
+  double lr, momentum, beta1, beta2, eps, weight_decay, value_weight, clip;
+  uint64_t seed;
+} epa_trainer_options;
+typedef struct epa_trainer epa_trainer;
+int epa_trainer_create(int32_t device, const void* blob, size_t bytes, const epa_trainer_options* options,
+                       int64_t max_rows, epa_trainer** out);
+int epa_trainer_destroy(epa_trainer* trainer);
+int epa_trainer_step_device(epa_trainer* trainer, void* stream, int32_t rows, const void* d_obs, const void* d_mask,
+                            const void* d_policy, const void* d_value);
+int epa_trainer_fit_device(epa_trainer* trainer, void* stream, const void* const* arrays, int64_t count, int32_t batch,
+                           int32_t steps);
+int epa_trainer_read(epa_trainer* trainer, int32_t what, int32_t layer, void* out);
 
 /* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
  * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
