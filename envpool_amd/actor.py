@@ -179,6 +179,14 @@ class Actor:
         from the logits of one `forward(obs)`, which then serves the value too: one pass through the trunk per step."""
         return _make_module(self, bool(kernels))
 
+    def trainer(self, **options: Any) -> Any:
+        """An `ActorTrainer` of this actor (actor_trainer.py): PPO on the device.  `device=0, optimizer="adam", lr=3e-2,
+        betas=(0.9, 0.999), eps=1e-8, momentum=0.9, weight_decay=0.0, clip_ratio=0.2, value_weight=0.5,
+        entropy_weight=0.0, normalize_adv=True, train_sigma=True, clip=0.5, seed=0, max_rows=4096`."""
+        from envpool_amd.actor_trainer import ActorTrainer
+
+        return ActorTrainer(self, **options)
+
     @classmethod
     def from_module(cls, m: Any) -> "Actor":
         sigma = m.sigma.detach().cpu().numpy().astype(np.float32) if m.kind == BOX else None

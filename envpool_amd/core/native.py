@@ -200,6 +200,11 @@ def lib() -> ctypes.CDLL:
         "epa_trainer_step_device": (i32, [vp, vp, i32, vp, vp, vp, vp]),
         "epa_trainer_fit_device": (i32, [vp, vp, P(vp), ctypes.c_int64, i32, i32]),
         "epa_trainer_read": (i32, [vp, i32, i32, vp]),
+        "epa_ppo_create": (i32, [i32, vp, ctypes.c_size_t, P(PpoOptions), ctypes.c_int64, P(vp)]),
+        "epa_ppo_destroy": (i32, [vp]),
+        "epa_ppo_step_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "epa_ppo_fit_device": (i32, [vp, vp, vp, P(PpoSource), i32, i32, ctypes.c_float, ctypes.c_float]),
+        "epa_ppo_read": (i32, [vp, i32, i32, vp]),
         "epa_selfplay_begin": (i32, [vp, vp, P(SelfplayOptions)]),
         "epa_selfplay_run": (i32, [vp, i32]),
         "epa_selfplay_run_device": (i32, [vp, i32]),
@@ -308,6 +313,7 @@ EXPORTED_SYMBOLS = [
     "epa_conv_train_backward_device",
     "epa_trainer_create", "epa_trainer_destroy", "epa_trainer_step_device", "epa_trainer_fit_device",
     "epa_trainer_read",
+    "epa_ppo_create", "epa_ppo_destroy", "epa_ppo_step_device", "epa_ppo_fit_device", "epa_ppo_read",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",
@@ -687,6 +693,22 @@ class TrainerOptions(ctypes.Structure):
                 ("momentum", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
                 ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("value_weight", ctypes.c_double),
                 ("clip", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+class PpoOptions(ctypes.Structure):
+    """epa_ppo_options (include/envpool_amd.h)."""
+
+    _fields_ = [("base", TrainerOptions), ("clip_ratio", ctypes.c_double), ("entropy_weight", ctypes.c_double),
+                ("normalize_adv", ctypes.c_int32), ("train_sigma", ctypes.c_int32)]
+
+
+class PpoSource(ctypes.Structure):
+    """epa_ppo_source (include/envpool_amd.h): a collector's buffers as a PPO trainer's fit reads them."""
+
+    _fields_ = [("horizon", ctypes.c_int32), ("envs", ctypes.c_int32), ("n_obs", ctypes.c_int32),
+                ("action_dtype", ctypes.c_int32), ("action_elems", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("obs_dtype", ctypes.c_int32 * 8), ("obs_elems", ctypes.c_int32 * 8), ("obs", ctypes.c_void_p * 8),
+                ("action", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("logp", ctypes.c_void_p)]
 
 
 class SelfplayExtra(ctypes.Structure):

@@ -638,6 +638,75 @@ class Trainer {
   DeviceBlock mem_;
 };
 
+// The trainer's launches the PPO trainer shares (pgx_trainer.hip): the norm partials of `chunks` chunks of the flat
+// gradient table, and the update of `chunks` chunks of parameters, the first `weight_chunks` of them weights.
+namespace pgx {
+struct TrainerRule;
+}
+void TrainerNormLaunch(const float* grad, int chunks, double* partial, hipStream_t stream);
+void TrainerUpdateLaunch(const pgx::TrainerRule& rule, int chunks, int weight_chunks, const float* grad, double* master,
+                         double* s1, double* s2, const double* clip_scale, signed char* q_weight, int32_t* q_bias,
+                         hipStream_t stream);
+
+// The PPO trainer of the rollout actor (epa_ppo_create; ppo_trainer.hip.h is the contract, ppo_trainer.hip the
+// kernels): a whole PPO step, or a whole `fit` of a collected horizon, on the device.  It owns a NetTrain for the trunk
+// and ONE device allocation: per parameter array the float32 gradient, the float64 master and optimizer state and the
+// quantised array, the sigma segment of a trained Box head, dp and p, the gathered minibatch, the partials and the ring
+// of statistics rows; adv and ret [T][N] of a horizon are a second block, sized by the first Fit and kept while the
+// shape stays.  Every call enqueues on the caller's stream and waits for nothing; Read is the host wait.
+struct PpoTrainerOptions {
+  TrainerOptions base;
+  double clip_ratio, entropy_weight;
+  int normalize_adv, train_sigma;
+};
+// a collector's buffers as epa_rollout_view_device / epa_actor_view_device give them
+struct PpoSource {
+  int horizon, envs, n_obs;
+  int obs_dtype[rollout::kMaxKeys], obs_elems[rollout::kMaxKeys];
+  const void* obs[rollout::kMaxKeys];
+  int action_dtype, action_elems;
+  const void* action;
+  const unsigned char* mask;
+  const float* logp;
+};
+class PpoTrainer {
+ public:
+  // std::invalid_argument for a blob ActorParse refuses and for options outside the contract
+  PpoTrainer(int device, const void* blob, size_t bytes, const PpoTrainerOptions& options, long long max_rows);
+  ~PpoTrainer();
+  // one minibatch: features bytes [rows][F], action int32 [rows] or float32 [rows][H], logp, adv, ret float32 [rows],
+  // mask bytes [rows] (null: every row counts)
+  void Step(hipStream_t stream, int rows, const void* d_features, const void* d_action, const void* d_logp,
+            const void* d_adv, const void* d_ret, const void* d_mask);
+  // adv and ret [T][N] of a horizon for the collector's GAE launch to fill before Fit (allocated here)
+  void Horizon(const PpoSource& src, int batch, int epochs, float** adv, float** ret);
+  // `epochs` epochs of T N / batch minibatches gathered from the collector's buffers
+  void Fit(hipStream_t stream, const PpoSource& src, int batch, int epochs);
+  // A host wait.  what 0 .. 8 as Trainer::Read, with the sigma segment as array `2 layers` (3: the float32 sigma the
+  // loss reads) and statistics rows of 8 doubles; 9: the gathered minibatch, layer 0 features, 1 action, 2 logp, 3 adv,
+  // 4 ret, 5 mask, 6 the advantage statistics float64 [3] (count, mean, std)
+  void Read(int what, int layer, void* out);
+
+ private:
+  struct Layout;
+  void Enqueue(hipStream_t stream, int rows, const unsigned char* features, const void* action, const float* logp,
+               const float* adv, const float* ret, const unsigned char* mask);
+  int device_, max_rows_;
+  int F_{0}, H_{0}, kind_{0}, layers_{0};
+  bool sigma_{false};
+  float scale_p_{0}, scale_v_{0};
+  PpoTrainerOptions opt_;
+  int32_t shift_[kNetImageLayers]{};
+  long long steps_{0}, epochs_{0};
+  int rows_{0};
+  size_t horizon_rows_{0};
+  double beta1_pow_{1.0}, beta2_pow_{1.0};
+  hipStream_t last_{nullptr};
+  std::unique_ptr<NetTrain> net_;
+  std::unique_ptr<Layout> at_;
+  DeviceBlock mem_, horizon_;
+};
+
 // One launch of a pool's self-play driver (Pool::SelfplayNoise / SelfplayMove / SelfplayTally; pgx_selfplay.hip.h):
 // row i is local env i of the pool, every pointer device memory.
 struct SelfplayArgs {

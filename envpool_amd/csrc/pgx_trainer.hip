@@ -292,6 +292,18 @@ void CheckOption(const char* name, double v) {
 
 }  // namespace
 
+// the launches the PPO trainer shares (engine.h)
+void TrainerNormLaunch(const float* grad, int chunks, double* partial, hipStream_t stream) {
+  hipLaunchKernelGGL(TrainerNorm, dim3(chunks), dim3(256), 0, stream, grad, partial);
+}
+
+void TrainerUpdateLaunch(const pgx::TrainerRule& rule, int chunks, int weight_chunks, const float* grad, double* master,
+                         double* s1, double* s2, const double* clip_scale, signed char* q_weight, int32_t* q_bias,
+                         hipStream_t stream) {
+  const UpdateArgs up{rule, weight_chunks, grad, master, s1, s2, clip_scale, q_weight, q_bias};
+  hipLaunchKernelGGL(TrainerUpdate, dim3(chunks), dim3(256), 0, stream, up);
+}
+
 // ---------------------------------------------------------------------------
 // the handle (engine.h: Trainer)
 // ---------------------------------------------------------------------------

@@ -993,6 +993,55 @@ int epa_trainer_fit_device(epa_trainer* trainer, void* stream, const void* const
                            int32_t steps);
 int epa_trainer_read(epa_trainer* trainer, int32_t what, int32_t layer, void* out);
 
+/* PPO trainer of the rollout actor (no reference analogue; csrc/ppo_trainer.hip.h is the authority): a whole PPO step
+ * of an actor blob (epa_actor_begin's) on the device -- forward, the clipped-surrogate loss of a Discrete or Box head
+ * with value loss and entropy bonus, backward, gradient norm and clipping, SGD with momentum or Adam on float64
+ * masters (the sigma of a Box head among them), re-quantising -- and a whole `fit` of a collected horizon: the
+ * collector's GAE, the advantage statistics, epochs of minibatches sampled without replacement and gathered straight
+ * out of the collector's buffers.  A trainer belongs to a device; it owns a training handle of the trunk, one device
+ * allocation sized for `max_rows`, and adv / ret of the last horizon's shape.
+ *   epa_ppo_create(device, blob, bytes, options, max_rows, &handle): the masters start as the blob's integers and sigma.
+ *   epa_ppo_step_device(handle, stream, rows, d_features, d_action, d_logp, d_adv, d_ret, d_mask): one step on a
+ *     minibatch in device memory: feature bytes [rows][F], action int32 [rows] (discrete) or float32 [rows][H] (box),
+ *     logp, adv, ret float32 [rows], mask bytes [rows] or null (every row counts).  adv is used as given.
+ *   epa_ppo_fit_device(handle, pool, stream, source, epochs, batch, gamma, lam): `pool`'s collector must hold a full
+ *     horizon and an actor; `source` describes its buffers (epa_rollout_view_device, epa_actor_view_device; dtypes as
+ *     EPA_I32 ..) and `stream` is the pool's.  The pool's GAE over the stored values fills the handle's adv / ret; then
+ *     epochs * (T N / batch) steps; position j of the handle's epoch E is row PpoPermute(seed, E, j, T N).
+ *   epa_ppo_read(handle, what, layer, out): a host wait.  what 0 .. 8 as epa_trainer_read, with statistics rows of 8
+ *     doubles (policy loss, value loss, entropy, approximate KL, clip fraction, gradient norm, unmasked rows, rows) and,
+ *     for a Box actor with train_sigma, the sigma segment as one more parameter array behind the biases (what 3: the
+ *     float32 sigma the loss reads); 9: the last gathered minibatch of a fit, layer 0 features, 1 action, 2 logp, 3 adv,
+ *     4 ret, 5 mask, 6 the advantage statistics float64 [3] (count, mean, std).
+ *   epa_ppo_destroy(handle).
+ *   The step calls only enqueue and return; calls on one handle are the caller's to serialise.  No atomics.
+ *   EPA_ERR_INVALID, before any launch: rows outside 1 .. max_rows; batch outside 1 .. min(T N, max_rows); epochs < 1;
+ *     T N >= 2^31; a source of another F, H or kind than the blob's; a collector without an actor or a full horizon;
+ *     options epa_trainer_create refuses, a clip_ratio or entropy_weight that is negative or not finite; a null
+ *     argument; a blob that is no actor; max_rows outside 1 .. 2^22. */
+typedef struct epa_ppo_options {
+  epa_trainer_options base;
+  double clip_ratio, entropy_weight;
+  int32_t normalize_adv, train_sigma;
+} epa_ppo_options;
+typedef struct epa_ppo_source {
+  int32_t horizon, envs, n_obs, action_dtype, action_elems, reserved;
+  int32_t obs_dtype[8], obs_elems[8];
+  const void* obs[8];
+  const void* action;
+  const void* mask;
+  const void* logp;
+} epa_ppo_source;
+typedef struct epa_ppo epa_ppo;
+int epa_ppo_create(int32_t device, const void* blob, size_t bytes, const epa_ppo_options* options, int64_t max_rows,
+                   epa_ppo** out);
+int epa_ppo_destroy(epa_ppo* ppo);
+int epa_ppo_step_device(epa_ppo* ppo, void* stream, int32_t rows, const void* d_features, const void* d_action,
+                        const void* d_logp, const void* d_adv, const void* d_ret, const void* d_mask);
+int epa_ppo_fit_device(epa_ppo* ppo, epa_pool* pool, void* stream, const epa_ppo_source* source, int32_t epochs,
+                       int32_t batch, float gamma, float lam);
+int epa_ppo_read(epa_ppo* ppo, int32_t what, int32_t layer, void* out);
+
 /* Self-play recorder (no reference analogue; the four PGX board games; csrc/pgx_record.hip.h is the authority): a
  * pool's finished games as training samples on the device.  The recorder stages, per env, the positions and policy
  * targets of the game in progress; when the game ends it writes one sample per staged ply -- or one per ply and board
