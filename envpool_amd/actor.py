@@ -13,7 +13,15 @@ The observation is the concatenation, in key order, of the state keys whose name
 512 components; component i becomes the byte clamp(rint((x_i - lo_i) * scale_i), 0, 127).  The trunk is
 `envpool_amd.pgx.net.Net`'s, with H + 1 head rows: H = the number of actions of a Discrete space (a Gumbel-max sample of
 softmax(logits)), or the dimension of a Box space (mu = logits, a fixed sigma per component, the clamped action goes to
-the env and logp is the density of the raw one).  MultiDiscrete and Dict action spaces are refused (ValueError)."""
+the env and logp is the density of the raw one).  MultiDiscrete and Dict action spaces are refused (ValueError).
+
+Legal-action masks and integer-vector actions are kind 2 (MASKED): one categorical over the legal actions, whose flat
+index goes to the env as C <= 4 integer components.
+
+    env = envpool.make("Minesweeper-v0", "gymnasium", num_envs=4096)
+    actor = Actor.random(env, mask=True)      # obs:action_mask [10, 10]; the action is (row, col) = divmod(flat, 10)
+    ro = env.rollout(horizon=32); ro.attach(actor, seed=1); ro.reset(); ro.collect()
+    tr = actor.trainer(); tr.fit(ro, epochs=4, batch=4096)           # the loss runs over the legal actions only"""
 from __future__ import annotations
 
 from typing import Any, Sequence
@@ -25,23 +33,39 @@ from envpool_amd.pgx.net import MAX_INPUTS, Net
 MAGIC = 0x41415045  # "EPAA"
 VERSION = 1
 HEADER_BYTES = 36
-DISCRETE, BOX = 0, 1
+DISCRETE, BOX, MASKED = 0, 1, 2
+MAX_COMPONENTS, MAX_ACTIONS = 4, 127
 
 
-def space_of(env_or_spec: Any) -> dict:
+def _nvec(nvec: Any, actions: int) -> np.ndarray:
+    """int32 [4]: the components' sizes padded with ones; their product must be H."""
+    v = np.asarray([actions] if nvec is None else nvec, np.int64).reshape(-1)
+    if not 1 <= len(v) <= MAX_COMPONENTS or (v < 1).any() or int(np.prod(v)) != actions:
+        raise ValueError(f"actor: nvec = {v.tolist()} must be 1 .. {MAX_COMPONENTS} sizes of at least 1 whose product "
+                         f"is H = {actions}")
+    return np.concatenate([v, np.ones(MAX_COMPONENTS - len(v), np.int64)]).astype(np.int32)
+
+
+def space_of(env_or_spec: Any, mask: Any = None) -> dict:
     """What an actor needs of an env, its spec or a dict with these entries: `features` F, `kind`, `actions` H, the
     Box bounds `low` / `high` (float32 [H], empty for a Discrete space) and the observation bounds `obs_low` /
-    `obs_high` (float64 [F]).  ValueError for F > 512 and for an action space that is neither Discrete nor Box -- no
-    device is needed."""
+    `obs_high` (float64 [F]); kind 2 (MASKED) adds `mask0` (the first mask component, or -1) and `nvec`.  `mask`: None
+    (no mask), True (the one obs key whose name ends in "action_mask") or the key's name.  A Discrete space with a mask,
+    and an integer Box (all lows 0, at most 4 components, at most 127 flat actions) with or without one, are MASKED.
+    ValueError for F > 512, for an action space that is none of these, and for a mask that is missing, not of H
+    components or asked for a float Box -- no device is needed."""
     if isinstance(env_or_spec, dict):
         d = dict(env_or_spec)
+        if mask is not None:
+            raise ValueError("actor: a dict states mask0 itself; mask= needs an env or a spec")
     else:
         spec = getattr(env_or_spec, "spec", env_or_spec)
-        lows, highs = [], []
+        lows, highs, first = [], [], {}
         for key, s in spec.state_array_spec.items():
             if not key.startswith("obs"):
                 continue
             n = int(np.prod([x for x in s.shape if x > 0], dtype=np.int64))  # (a spec writes a scalar per env as [-1])
+            first[key] = (sum(len(x) for x in lows), n)
             lows.append(np.broadcast_to(np.asarray(s.minimum, np.float64).reshape(-1), (n,)) if np.size(s.minimum) in (1, n)
                         else np.full(n, -np.inf))
             highs.append(np.broadcast_to(np.asarray(s.maximum, np.float64).reshape(-1), (n,)) if np.size(s.maximum) in (1, n)
@@ -55,24 +79,50 @@ def space_of(env_or_spec: Any) -> dict:
         elif name == "Box" and np.dtype(space.dtype).kind == "f":
             d.update(kind=BOX, actions=int(np.prod(space.shape, dtype=np.int64)),
                      low=np.asarray(space.low, np.float32).reshape(-1), high=np.asarray(space.high, np.float32).reshape(-1))
+        elif name == "Box" and np.dtype(space.dtype).kind in "iu":
+            high = np.asarray(space.high, np.int64).reshape(-1)
+            if (np.asarray(space.low).reshape(-1) != 0).any() or not 1 <= len(high) <= MAX_COMPONENTS or (high < 0).any() \
+                    or int(np.prod(high + 1)) > MAX_ACTIONS:
+                raise ValueError(f"actor: an integer Box of low {space.low} and high {space.high} is not supported (all "
+                                 f"lows 0, at most {MAX_COMPONENTS} components, at most {MAX_ACTIONS} flat actions)")
+            d.update(kind=MASKED, actions=int(np.prod(high + 1)), mask0=-1, nvec=(high + 1).astype(np.int32),
+                     low=np.zeros(0, np.float32), high=np.zeros(0, np.float32))
         else:
             raise ValueError(f"actor: an action space of {name} is not supported (Discrete or Box)")
+        if mask is not None and mask is not False:
+            names = [k for k in first if k.endswith("action_mask")] if mask is True else [mask]
+            if len(names) != 1 or names[0] not in first:
+                raise ValueError(f"actor: mask = {mask!r} names no obs key, or not exactly one (obs keys: {list(first)})")
+            if d["kind"] == BOX:
+                raise ValueError("actor: a float Box action space takes no mask")
+            at, n = first[names[0]]
+            if n != d["actions"]:
+                raise ValueError(f"actor: the mask {names[0]!r} has {n} components for H = {d['actions']} actions")
+            d.update(kind=MASKED, mask0=at, nvec=d.get("nvec", np.array([d["actions"]], np.int32)))
     if d["features"] > MAX_INPUTS:
         raise ValueError(f"actor: the observation has {d['features']} components; an actor takes at most {MAX_INPUTS}")
-    if d["kind"] not in (DISCRETE, BOX):
-        raise ValueError(f"actor: kind = {d['kind']!r} must be 0 (discrete) or 1 (box)")
+    if d["kind"] not in (DISCRETE, BOX, MASKED):
+        raise ValueError(f"actor: kind = {d['kind']!r} must be 0 (discrete), 1 (box) or 2 (masked)")
     return d
 
 
 class Actor:
     """`net`: the trunk and head, a `pgx.net.Net` of F inputs and H "actions"; `lo`, `scale`: float64 [F]; `sigma`,
-    `low`, `high`: float32 [H] of a Box actor.  Everything the contract bounds is checked here (ValueError)."""
+    `low`, `high`: float32 [H] of a Box actor; `mask0`, `nvec`: the first mask component (-1: none) and the components'
+    sizes of a MASKED actor.  Everything the contract bounds is checked here (ValueError)."""
 
-    def __init__(self, net: Net, kind: int, lo: Any, scale: Any, sigma: Any = None, low: Any = None, high: Any = None):
-        if kind not in (DISCRETE, BOX):
-            raise ValueError(f"actor: kind = {kind!r} must be 0 (discrete) or 1 (box)")
+    def __init__(self, net: Net, kind: int, lo: Any, scale: Any, sigma: Any = None, low: Any = None, high: Any = None,
+                 mask0: int = -1, nvec: Any = None):
+        if kind not in (DISCRETE, BOX, MASKED):
+            raise ValueError(f"actor: kind = {kind!r} must be 0 (discrete), 1 (box) or 2 (masked)")
         self.net, self.kind = net, int(kind)
         self.features, self.actions = net.inputs, net.actions
+        self.mask0, self.nvec = int(mask0), _nvec(nvec, net.actions)           # nvec: padded to 4 with ones
+        self.components = 1 if nvec is None else int(np.size(np.asarray(nvec)))  # C: the entries given
+        if self.kind != MASKED and (self.mask0 != -1 or self.components != 1):
+            raise ValueError("actor: mask0 and nvec belong to a masked actor (kind 2)")
+        if self.mask0 != -1 and not 0 <= self.mask0 <= self.features - self.actions:
+            raise ValueError(f"actor: mask0 = {mask0} must be -1 or 0 .. F - H = {self.features - self.actions}")
         self.lo = np.ascontiguousarray(lo, np.float64).reshape(-1)
         self.scale = np.ascontiguousarray(scale, np.float64).reshape(-1)
         if self.lo.shape != (self.features,) or self.scale.shape != (self.features,):
@@ -100,6 +150,8 @@ class Actor:
                  self.scale.astype("<f8").tobytes()]
         if self.kind == BOX:
             parts.append(self.sigma.astype("<f4").tobytes())
+        if self.kind == MASKED:
+            parts.append(np.array([self.mask0, self.components, *self.nvec], "<i4").tobytes())
         parts.append(n.blob()[32:].tobytes())  # the layer section, exactly as Net writes it
         return np.frombuffer(b"".join(parts), np.uint8).copy()
 
@@ -109,7 +161,8 @@ class Actor:
                   "hidden": np.int32(n.hidden), "blocks": np.int32(n.blocks),
                   "net_scale": np.array([n.scale_p, n.scale_v], np.float32),
                   "shift": np.array([s for _, _, s in n.layers], np.int32), "lo": self.lo, "scale": self.scale,
-                  "sigma": self.sigma, "low": self.low, "high": self.high}
+                  "sigma": self.sigma, "low": self.low, "high": self.high, "mask0": np.int32(self.mask0),
+                  "nvec": self.nvec[:self.components]}
         for i, (w, b, _) in enumerate(n.layers):
             arrays[f"w{i}"], arrays[f"b{i}"] = w, b
         with open(path, "wb") as f:  # (np.savez would add ".npz" to a bare name)
@@ -122,14 +175,17 @@ class Actor:
             layers = [(z[f"w{i}"], z[f"b{i}"], int(z["shift"][i])) for i in range(2 * blocks + 2)]
             net = Net((int(z["features"]),), int(z["actions"]), int(z["hidden"]), blocks, layers,
                       float(z["net_scale"][0]), float(z["net_scale"][1]))
-            return cls(net, int(z["kind"]), z["lo"], z["scale"], z["sigma"], z["low"], z["high"])
+            masked = dict(mask0=int(z["mask0"]), nvec=z["nvec"]) if int(z["kind"]) == MASKED else {}
+            return cls(net, int(z["kind"]), z["lo"], z["scale"], z["sigma"], z["low"], z["high"], **masked)
 
     @classmethod
-    def random(cls, env_or_spec: Any, hidden: int = 64, blocks: int = 1, seed: int = 0, sigma: float = 0.5) -> "Actor":
+    def random(cls, env_or_spec: Any, hidden: int = 64, blocks: int = 1, seed: int = 0, sigma: float = 0.5,
+               mask: Any = None) -> "Actor":
         """An actor for tests and first runs from numpy's PCG64(seed) (`Net.random`'s recipe, shifts for inputs that
         fill 0 .. 127).  lo / scale map an observation component's bounds onto 0 .. 127 where the spec gives finite
-        ones no wider than 1e6, and -8 .. 8 elsewhere; `fit_features` replaces them by measured ones."""
-        d = space_of(env_or_spec)
+        ones no wider than 1e6, and -8 .. 8 elsewhere; `fit_features` replaces them by measured ones.  `mask`: as
+        `space_of`'s."""
+        d = space_of(env_or_spec, mask)
         f, h = int(d["features"]), int(d["actions"])
         # (Net.random sizes the first shift for 0 / 1 inputs of density 1/4; bytes spread over 0 .. 127 are about
         # 2^7 larger)
@@ -142,7 +198,8 @@ class Actor:
         ok = np.isfinite(lo) & np.isfinite(hi) & (span > 0) & (span <= 1e6)
         lo = np.where(ok, lo, -8.0)
         scale = 127.0 / np.where(ok, span, 16.0)
-        return cls(net, d["kind"], lo, scale, np.full(h, sigma, np.float32), d["low"], d["high"])
+        masked = dict(mask0=d.get("mask0", -1), nvec=d.get("nvec")) if d["kind"] == MASKED else {}
+        return cls(net, d["kind"], lo, scale, np.full(h, sigma, np.float32), d["low"], d["high"], **masked)
 
     def fit_features(self, cnt: Any, s1: Any, s2: Any) -> "Actor":
         """lo and scale from a collector's moments (`ro.moments()`): mean +- 4 sigma of every component onto 0 .. 127.
@@ -190,7 +247,9 @@ class Actor:
     @classmethod
     def from_module(cls, m: Any) -> "Actor":
         sigma = m.sigma.detach().cpu().numpy().astype(np.float32) if m.kind == BOX else None
-        return cls(Net.from_module(m.net), m.kind, m.lo.cpu().numpy(), m.scale.cpu().numpy(), sigma, m.low, m.high)
+        masked = dict(mask0=m.mask0, nvec=m.nvec) if m.kind == MASKED else {}
+        return cls(Net.from_module(m.net), m.kind, m.lo.cpu().numpy(), m.scale.cpu().numpy(), sigma, m.low, m.high,
+                   **masked)
 
 
 def _make_module(actor: Actor, kernels: bool = False) -> Any:
@@ -201,6 +260,7 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             super().__init__()
             self.kind, self.actions = actor.kind, actor.actions
             self.low, self.high = actor.low.copy(), actor.high.copy()
+            self.mask0, self.nvec = actor.mask0, actor.nvec[:actor.components].copy()
             self.net = actor.net.module(kernels=kernels)
             self.register_buffer("lo", torch.tensor(actor.lo))
             self.register_buffer("scale", torch.tensor(actor.scale))
@@ -224,12 +284,35 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
         def value(self, obs: Any) -> Any:
             return self.forward(obs)[1]
 
-        def logp(self, obs: Any, action: Any) -> Any:
-            """float64 [rows]: the log-probability (Box: the density) of `action` from the float32 logits."""
-            return self.logp_of(self.forward(obs)[0], action)
+        def legal(self, obs: Any) -> Any:
+            """bool [rows, H] of a MASKED actor: the raw mask components of `obs` that are not 0; every action for a row
+            without any, and for an actor without a mask."""
+            rows = obs.shape[0]
+            if self.mask0 < 0:
+                return torch.ones((rows, self.actions), dtype=torch.bool, device=obs.device)
+            ok = obs.reshape(rows, -1)[:, self.mask0:self.mask0 + self.actions] != 0
+            return ok | ~ok.any(dim=1, keepdim=True)
 
-        def logp_of(self, logits: Any, action: Any) -> Any:
-            """`logp` from the logits of a `forward(obs)` the caller already has: one pass serves `logp` and value."""
+        def _masked(self, logits: Any, legal: Any) -> Any:
+            """log-softmax over the legal actions, float64; -inf at the others."""
+            return torch.log_softmax(logits.to(torch.float64).masked_fill(~legal, -torch.inf), dim=1)
+
+        def logp(self, obs: Any, action: Any) -> Any:
+            """float64 [rows]: the log-probability (Box: the density) of `action` from the float32 logits.  MASKED:
+            `action` is the flat index, or its [rows, C] components."""
+            return self.logp_of(self.forward(obs)[0], action, self.legal(obs) if self.kind == MASKED else None)
+
+        def logp_of(self, logits: Any, action: Any, legal: Any = None) -> Any:
+            """`logp` from the logits of a `forward(obs)` the caller already has: one pass serves `logp` and value.
+            MASKED: `legal` is `self.legal(obs)` (None: every action)."""
+            if self.kind == MASKED:
+                if action.dim() == 2:  # components, most significant first
+                    flat = torch.zeros_like(action[:, 0])
+                    for c, n in enumerate(self.nvec):
+                        flat = flat * int(n) + action[:, c]
+                    action = flat
+                legal = torch.ones_like(logits, dtype=torch.bool) if legal is None else legal
+                return self._masked(logits, legal).gather(1, action.reshape(-1, 1).long()).reshape(-1)
             logits = logits.to(torch.float64)
             if self.kind == DISCRETE:
                 return torch.log_softmax(logits, dim=1).gather(1, action.reshape(-1, 1).long()).reshape(-1)
@@ -239,6 +322,10 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
 
         def entropy(self, obs: Any) -> Any:
             logits = self.forward(obs)[0].to(torch.float64)
+            if self.kind == MASKED:
+                legal = self.legal(obs)
+                lp = self._masked(logits, legal).masked_fill(~legal, 0.0)  # (no -inf reaches a product)
+                return -(lp.exp() * lp * legal).sum(dim=1)
             if self.kind == DISCRETE:
                 lp = torch.log_softmax(logits, dim=1)
                 return -(lp.exp() * lp).sum(dim=1)

@@ -19,14 +19,23 @@ from typing import Any
 
 import numpy as np
 
-from envpool_amd.actor import BOX, Actor
+from envpool_amd.actor import BOX, MASKED, Actor
 from envpool_amd.core import native
 from envpool_amd.pgx.net import Net
 from envpool_amd.pgx.trainer import OPTIMIZERS, STAT_ROWS, _number
 
 MASTER, STATE1, STATE2, QUANTISED, GRADIENT, DP, P, STATS, INFO, BATCH = range(10)  # epa_ppo_read's `what`
-FEATURES, ACTION, LOGP, ADV, RET, MASK, ADV_STATS = range(7)                        # the parts of BATCH
+FEATURES, ACTION, LOGP, ADV, RET, MASK, ADV_STATS, LEGAL = range(8)                 # the parts of BATCH
 DTYPE_CODES = {np.dtype(v): k for k, v in native.DTYPES.items()}
+
+
+def pack_legal(legal: Any, actions: int) -> np.ndarray:
+    """uint32 [rows, 4] of bool [rows, H]: bit j of a row in word j // 32; a row without a legal action is all ones."""
+    legal = np.asarray(legal, np.bool_).reshape(-1, actions)
+    bits = np.zeros((len(legal), 128), np.uint8)
+    bits[:, :actions] = legal
+    bits[~legal.any(axis=1)] = 1
+    return np.packbits(bits, axis=1, bitorder="little").view("<u4").astype(np.uint32)
 
 
 class ActorTrainer:
@@ -80,21 +89,29 @@ class ActorTrainer:
             pass
 
     # -- steps -----------------------------------------------------------------------
-    def step(self, features: Any, action: Any, logp: Any, adv: Any, ret: Any, mask: Any = None) -> None:
+    def step(self, features: Any, action: Any, logp: Any, adv: Any, ret: Any, mask: Any = None, legal: Any = None) -> None:
         """One step on a minibatch the caller has put together: features uint8 [rows, F] (`actor.features_of`), action
-        int32 [rows] (Discrete) or float32 [rows, H] (Box), logp, adv, ret float32 [rows], mask bool [rows] or None --
-        numpy arrays, or torch tensors on the device (then nothing is copied and nothing waits).  `adv` is used as
-        given."""
+        int32 [rows] (Discrete; MASKED: the flat index) or float32 [rows, H] (Box), logp, adv, ret float32 [rows], mask
+        bool [rows] or None -- numpy arrays, or torch tensors on the device (then nothing is copied and nothing waits).
+        `adv` is used as given.  A MASKED actor needs `legal`: the rows' legal words uint32 [rows, 4], or bool [rows, H],
+        which is packed here before it goes to the device (a row without a legal action: every action)."""
         import torch
 
         h = self._open()
         a = self._actor
         dev = torch.device("cuda", self.device)
         box = a.kind == BOX
+        if (a.kind == MASKED) != (legal is not None):
+            raise ValueError("trainer: legal is required for a masked actor (kind 2) and taken by no other")
+        if legal is not None:
+            legal = legal.cpu().numpy() if hasattr(legal, "cpu") else np.asarray(legal)
+            if legal.dtype == np.bool_:
+                legal = pack_legal(legal, a.actions)
+            legal = np.ascontiguousarray(legal, np.uint32).view(np.int32)  # (torch has no uint32 arithmetic; bits only)
         kept = []
         for name, x, dtype in (("features", features, torch.uint8), ("action", action, torch.float32 if box else torch.int32),
                                ("logp", logp, torch.float32), ("adv", adv, torch.float32), ("ret", ret, torch.float32),
-                               ("mask", mask, torch.uint8)):
+                               ("mask", mask, torch.uint8), ("legal", legal, torch.int32)):
             if x is None:
                 kept.append(None)
                 continue
@@ -107,12 +124,14 @@ class ActorTrainer:
             kept.append(x.to(dtype).contiguous())
         rows = int(kept[2].numel())
         for name, x, n in (("features", kept[0], rows * a.features), ("action", kept[1], rows * (a.actions if box else 1)),
-                           ("adv", kept[3], rows), ("ret", kept[4], rows), ("mask", kept[5], rows)):
+                           ("adv", kept[3], rows), ("ret", kept[4], rows), ("mask", kept[5], rows),
+                           ("legal", kept[6], rows * 4)):
             if x is not None and x.numel() != n:
                 raise ValueError(f"trainer: {name} has {x.numel()} elements for {rows} rows ({n})")
         stream = torch.cuda.current_stream(dev).cuda_stream
-        native.check(native.lib().epa_ppo_step_device(h, ctypes.c_void_p(stream), rows,
-                                                      *[x.data_ptr() if x is not None else None for x in kept]))
+        call = native.lib().epa_ppo_step_legal_device if a.kind == MASKED else native.lib().epa_ppo_step_device
+        native.check(call(h, ctypes.c_void_p(stream), rows,
+                          *[x.data_ptr() if x is not None else None for x in kept[:7 if a.kind == MASKED else 6]]))
         self._kept = kept  # (until the next call: the launches read them)
         self._last = 1
 
@@ -167,7 +186,7 @@ class ActorTrainer:
     def read(self, what: int, layer: int = 0) -> np.ndarray:
         """`epa_ppo_read`: as `Trainer.read`, with the sigma segment as parameter array `sigma_layer` (MASTER, STATE1,
         STATE2, GRADIENT; QUANTISED: the float32 sigma the loss reads) and BATCH: part `layer` (FEATURES, ACTION, LOGP,
-        ADV, RET, MASK, ADV_STATS) of the last minibatch a `fit` gathered."""
+        ADV, RET, MASK, ADV_STATS, and LEGAL uint32 [rows, 4] of a MASKED actor) of the last minibatch a `fit` gathered."""
         h = self._open()
         lib = native.lib()
         a = self._actor
@@ -191,8 +210,10 @@ class ActorTrainer:
             shapes = {FEATURES: ((rows, a.features), np.uint8), LOGP: ((rows,), np.float32), ADV: ((rows,), np.float32),
                       ACTION: ((rows, a.actions) if box else (rows,), np.float32 if box else np.int32),
                       RET: ((rows,), np.float32), MASK: ((rows,), np.uint8), ADV_STATS: ((3,), np.float64)}
+            if a.kind == MASKED:
+                shapes[LEGAL] = ((rows, 4), np.uint32)
             if layer not in shapes:
-                raise ValueError(f"trainer: a minibatch has parts 0 .. 6, not {layer}")
+                raise ValueError(f"trainer: a minibatch has parts 0 .. {len(shapes) - 1}, not {layer}")
             out = np.empty(*shapes[layer])
         if out.size:
             native.check(lib.epa_ppo_read(h, int(what), int(layer), out.ctypes.data))
@@ -211,4 +232,5 @@ class ActorTrainer:
         t = a.net
         net = Net(t.obs_shape, t.actions, t.hidden, t.blocks, layers, t.scale_p, t.scale_v)
         sigma = self.read(QUANTISED, self.sigma_layer) if self.sigma_layer is not None else a.sigma
-        return Actor(net, a.kind, a.lo, a.scale, sigma, a.low, a.high)
+        masked = dict(mask0=a.mask0, nvec=a.nvec[:a.components]) if a.kind == MASKED else {}
+        return Actor(net, a.kind, a.lo, a.scale, sigma, a.low, a.high, **masked)

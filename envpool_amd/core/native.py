@@ -203,6 +203,7 @@ def lib() -> ctypes.CDLL:
         "epa_ppo_create": (i32, [i32, vp, ctypes.c_size_t, P(PpoOptions), ctypes.c_int64, P(vp)]),
         "epa_ppo_destroy": (i32, [vp]),
         "epa_ppo_step_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "epa_ppo_step_legal_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
         "epa_ppo_fit_device": (i32, [vp, vp, vp, P(PpoSource), i32, i32, ctypes.c_float, ctypes.c_float]),
         "epa_ppo_read": (i32, [vp, i32, i32, vp]),
         "epa_selfplay_begin": (i32, [vp, vp, P(SelfplayOptions)]),
@@ -313,7 +314,8 @@ EXPORTED_SYMBOLS = [
     "epa_conv_train_backward_device",
     "epa_trainer_create", "epa_trainer_destroy", "epa_trainer_step_device", "epa_trainer_fit_device",
     "epa_trainer_read",
-    "epa_ppo_create", "epa_ppo_destroy", "epa_ppo_step_device", "epa_ppo_fit_device", "epa_ppo_read",
+    "epa_ppo_create", "epa_ppo_destroy", "epa_ppo_step_device", "epa_ppo_step_legal_device", "epa_ppo_fit_device",
+    "epa_ppo_read",
     "epa_atari_post_create",
     "epa_atari_post_create_ex", "epa_atari_create", "epa_atari_num_actions",
     "epa_pool_state_keys", "epa_pool_action_keys",

@@ -32,10 +32,23 @@
 //             max |error| 1.260977683159581e-06 (at the smallest u), max relative error 3.924487003430764e-07; finite and
 //             strictly increasing everywhere.
 //
+//   masked    kind 2: ONE categorical over the H flat actions, restricted to the row's legal set, whose index may go to
+//             the env as C <= 4 integer components.  legal_j = (the RAW observation component mask0 + j, as ActorLoad
+//             gives it) != 0 -- not the feature byte, which lo and scale may move off 0.  With mask0 = -1, or for a row
+//             without any legal component (the slot after a done), every j is legal.  The mask components stay features
+//             like any other.  The set travels as 128 bits per row, bit j in word j / 32 (LegalBit); bits H .. 127 are 0,
+//             except that "every j" is all 128 bits set.  u_j, g_j as for discrete, indexed by j;  top = max of the legal
+//             logits;  S = the legal GumbelExp(l_j - top) in ascending j from 0.0f;  action = the lowest legal j that
+//             maximises l_j + g_j (deterministic: l_j);  logp = (l_a - top) - GumbelLog(S): a row whose set is everything
+//             gives SampleDiscrete's bits.  The env gets the components of the flat index in mixed radix nvec, most
+//             significant first (ActorComponents; C = 2: a / nvec[1], a % nvec[1], row major).
+//
 // THE BLOB (little endian, 4-byte aligned): a 36-byte header -- uint32 magic "EPAA", int32 version 1, int32 F, H, D, L,
-// kind (0 discrete, 1 box), float32 scale_p, scale_v -- then lo[F], scale[F] float64, sigma[H] float32 (box only), then
-// the layer section exactly as a PGXN blob has it behind its header.  ActorParse refuses what NetParse refuses, and a
-// lo, scale or sigma that is not finite, and sigma <= 0.
+// kind (0 discrete, 1 box, 2 masked), float32 scale_p, scale_v -- then lo[F], scale[F] float64, then sigma[H] float32
+// (box only) or int32 mask0, C, nvec[4] (masked only: mask0 = -1 or 0 <= mask0 <= F - H, C = 1 .. 4, every nvec >= 1, the
+// unused ones 1, their product H), then the layer section exactly as a PGXN blob has it behind its header.  ActorParse
+// refuses what NetParse refuses, a lo, scale or sigma that is not finite, sigma <= 0, and a masked section outside the
+// above.
 #ifndef ENVPOOL_AMD_CSRC_ACTOR_HIP_H_
 #define ENVPOOL_AMD_CSRC_ACTOR_HIP_H_
 
@@ -55,7 +68,10 @@ namespace actor {
 constexpr uint32_t kActorMagic = 0x41415045u;  // "EPAA"
 constexpr int kActorVersion = 1;
 constexpr int kActorHeaderBytes = 36;
-constexpr int kDiscrete = 0, kBox = 1;
+constexpr int kDiscrete = 0, kBox = 1, kMasked = 2;
+constexpr int kMaxComponents = 4;               // C of a masked head
+constexpr int kMaskedBytes = 24;                // mask0, C, nvec[4] of its blob
+constexpr int kSampleRows = 32;                 // rows per block of ActorSampleMasked, eight lanes a row
 constexpr uint64_t kActorSalt = 0x41435452ull;  // "ACTR": no stream of the self-play driver's
 constexpr int kFeatureRows = 64;                // rows per block of ActorFeatures
 constexpr int kFeatureBlock = 256;              // its threads
@@ -178,9 +194,80 @@ PGX_HD inline SampleOut SampleBox(const int32_t* p, int H, float scale_p, float 
   return o;
 }
 
+// ---- the masked head ---------------------------------------------------------------------------------------------------
+PGX_HD inline bool LegalBit(const uint32_t* w, int j) { return ((w[j >> 5] >> (j & 31)) & 1u) != 0; }
+// The legal words of one row by the book: its raw mask components at element `first` of `src` (null: no mask).
+PGX_HD inline void LegalOfRow(const char* src, int dtype, size_t first, int H, uint32_t w[4]) {
+  w[0] = w[1] = w[2] = w[3] = 0u;
+  if (src != nullptr) {
+    for (int j = 0; j < H; ++j) {
+      if (ActorLoad(src, dtype, first + (size_t)j) != 0.0) w[j >> 5] |= 1u << (j & 31);
+    }
+  }
+  if ((w[0] | w[1] | w[2] | w[3]) == 0u) w[0] = w[1] = w[2] = w[3] = 0xFFFFFFFFu;
+}
+// flat index <-> the C components the env takes, most significant first
+PGX_HD inline void ActorComponents(int action, const int* nvec, int C, int32_t* out) {
+  for (int c = C - 1; c >= 0; --c) {
+    out[c] = action % nvec[c];
+    action = action / nvec[c];
+  }
+}
+PGX_HD inline int ActorFlat(const int32_t* comp, const int* nvec, int C) {
+  int a = 0;
+  for (int c = 0; c < C; ++c) a = a * nvec[c] + comp[c];
+  return a;
+}
+// One candidate of the running best of a masked row, and the order it is kept in: the larger score, then the lower j.
+struct MaskedBest {
+  float score, logit;
+  int j;  // kNoAction: none yet
+};
+constexpr int kNoAction = 0x7FFFFFFF;
+PGX_HD inline bool MaskedBetter(const MaskedBest& a, const MaskedBest& b) {  // a before b
+  return a.j != kNoAction && (b.j == kNoAction || a.score > b.score || (a.score == b.score && a.j < b.j));
+}
+// One row of a masked head by the book: SampleDiscrete with j running over the legal set.
+PGX_HD inline SampleOut SampleMasked(const int32_t* p, int H, const uint32_t* legal, float scale_p, float scale_v,
+                                     uint64_t key, bool deterministic) {
+  SampleOut o;
+  float top = -FLT_MAX;
+  MaskedBest best{-FLT_MAX, 0.0f, kNoAction};
+  for (int j = 0; j < H; ++j) {
+    if (!LegalBit(legal, j)) continue;
+    const float l = pgx::NetLogit(p[j], scale_p);
+    const MaskedBest c{deterministic ? l : l + pgx::SelfplayNoise(key, j), l, j};
+    top = l > top ? l : top;
+    if (MaskedBetter(c, best)) best = c;
+  }
+  float sum = 0.0f;
+  for (int j = 0; j < H; ++j) {
+    if (LegalBit(legal, j)) sum = sum + pgx::GumbelExp(pgx::NetLogit(p[j], scale_p) - top);
+  }
+  o.action = best.j == kNoAction ? 0 : best.j;
+  o.logp = (best.logit - top) - pgx::GumbelLog(sum);
+  o.value = (float)p[H] * scale_v;
+  return o;
+}
+#if defined(__HIPCC__)
+// The legal words of one row by a whole wave: lanes j and j + 64 load the raw components, two ballots give the words, an
+// empty set becomes all ones.  Every lane returns the row's words.
+__device__ inline uint4 LegalBallot(const char* src, int dtype, size_t first, int H, int lane) {
+  bool b0 = false, b1 = false;
+  if (src != nullptr) {
+    if (lane < H) b0 = ActorLoad(src, dtype, first + (size_t)lane) != 0.0;
+    if (lane + 64 < H) b1 = ActorLoad(src, dtype, first + (size_t)lane + 64) != 0.0;
+  }
+  unsigned long long m0 = __ballot(b0), m1 = __ballot(b1);
+  if ((m0 | m1) == 0ull) m0 = m1 = ~0ull;
+  return make_uint4((unsigned)m0, (unsigned)(m0 >> 32), (unsigned)m1, (unsigned)(m1 >> 32));
+}
+#endif
+
 // ---- the blob ----------------------------------------------------------------------------------------------------------
 struct ActorView {
   int F, H, D, L, kind;
+  int mask0{-1}, C{1}, nvec[kMaxComponents]{1, 1, 1, 1};  // masked
   float scale_p, scale_v;
   std::vector<double> lo, scale;
   std::vector<float> sigma;
@@ -190,6 +277,7 @@ struct ActorView {
 };
 inline size_t ActorBlobBytes(int F, int H, int D, int L, int kind) {
   return (size_t)kActorHeaderBytes + 16 * (size_t)F + (kind == kBox ? 4 * (size_t)H : 0) +
+         (kind == kMasked ? (size_t)kMaskedBytes : 0) +
          (pgx::NetBlobBytes(F, H, D, L) - (size_t)pgx::kNetHeaderBytes);
 }
 inline bool ActorParse(const void* blob, size_t bytes, ActorView* v, char* err, size_t err_bytes) {
@@ -218,15 +306,51 @@ inline bool ActorParse(const void* blob, size_t bytes, ActorView* v, char* err, 
   }
   v->F = head[1], v->H = head[2], v->D = head[3], v->L = head[4], v->kind = head[5];
   v->scale_p = sc[0], v->scale_v = sc[1];
-  if (v->kind != kDiscrete && v->kind != kBox) {
-    std::snprintf(err, err_bytes, "actor: kind = %d must be 0 (discrete) or 1 (box)", v->kind);
+  if (v->kind != kDiscrete && v->kind != kBox && v->kind != kMasked) {
+    std::snprintf(err, err_bytes, "actor: kind = %d must be 0 (discrete), 1 (box) or 2 (masked)", v->kind);
     return false;
   }
   // the trunk's header as NetParse takes it: it checks F, H (its A), D, L, the scales and the size of the layer section
   const size_t front = (size_t)kActorHeaderBytes +
                        ((v->F >= 1 && v->F <= pgx::kNetMaxInputs) ? 16 * (size_t)v->F : 0) +
-                       ((v->kind == kBox && v->H >= 1 && v->H <= pgx::kNetMaxActions) ? 4 * (size_t)v->H : 0);
+                       ((v->kind == kBox && v->H >= 1 && v->H <= pgx::kNetMaxActions) ? 4 * (size_t)v->H : 0) +
+                       (v->kind == kMasked ? (size_t)kMaskedBytes : 0);
   const size_t rest = bytes >= front ? bytes - front : 0;
+  v->mask0 = -1, v->C = 1;
+  for (int c = 0; c < kMaxComponents; ++c) v->nvec[c] = 1;
+  // the masked section, where F places it (an F outside its range is NetParse's to refuse, below)
+  if (v->kind == kMasked && v->F >= 1 && v->F <= pgx::kNetMaxInputs) {
+    if (bytes < front) {
+      std::snprintf(err, err_bytes, "actor: kind 2 (masked): a blob of %zu bytes ends before mask0, C and nvec", bytes);
+      return false;
+    }
+    int32_t m[2 + kMaxComponents];
+    std::memcpy(m, p + kActorHeaderBytes + 16 * (size_t)v->F, sizeof(m));
+    v->mask0 = m[0], v->C = m[1];
+    if (v->C < 1 || v->C > kMaxComponents) {
+      std::snprintf(err, err_bytes, "actor: kind 2 (masked): C = %d components must be 1 .. %d", v->C, kMaxComponents);
+      return false;
+    }
+    long long product = 1;
+    for (int c = 0; c < kMaxComponents; ++c) {
+      v->nvec[c] = m[2 + c];
+      if (m[2 + c] < 1 || (c >= v->C && m[2 + c] != 1) || m[2 + c] > pgx::kNetMaxActions) {
+        std::snprintf(err, err_bytes, "actor: kind 2 (masked): nvec[%d] = %d must be 1 .. %d, and 1 behind the C components",
+                      c, m[2 + c], pgx::kNetMaxActions);
+        return false;
+      }
+      product *= m[2 + c];
+    }
+    if (product != v->H) {
+      std::snprintf(err, err_bytes, "actor: kind 2 (masked): the product of nvec = %lld must be H = %d", product, v->H);
+      return false;
+    }
+    if (v->mask0 != -1 && (v->mask0 < 0 || v->mask0 > v->F - v->H)) {
+      std::snprintf(err, err_bytes, "actor: kind 2 (masked): mask0 = %d must be -1 or 0 .. F - H = %d", v->mask0,
+                    v->F - v->H);
+      return false;
+    }
+  }
   v->net_blob.assign(((size_t)pgx::kNetHeaderBytes + rest + 3) / 4, 0u);
   unsigned char* nb = reinterpret_cast<unsigned char*>(v->net_blob.data());
   const uint32_t net_magic = pgx::kNetMagic;

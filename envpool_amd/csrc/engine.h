@@ -457,7 +457,17 @@ struct ActorSampleArgs {
   int action_dtype;
   float* logp;                  // [rows]
   float* value;                 // [rows]
+  const uint4* legal;           // masked: the rows' legal words (ActorLaunchLegal's)
+  int C, nvec[4];               // masked: the action row is C int32 components of the flat index, in mixed radix nvec
 };
+// the masked head's legal words: row i's H raw mask components begin at element i * elems + first of `src` (null: the
+// actor has no mask and every word is all ones)
+struct ActorLegalArgs {
+  int rows, H, elems, first, dtype;
+  const char* src;
+  uint4* legal;                 // [rows]
+};
+void ActorLaunchLegal(const ActorLegalArgs& a, hipStream_t s);
 // obs rows -> features u8 [rows][F], 16-byte stores where the output allows
 void ActorLaunchFeatures(const actor::FeatureKeys& keys, const double* lo, const double* scale, int rows,
                          unsigned char* out, hipStream_t s);
@@ -676,23 +686,26 @@ class PpoTrainer {
   ~PpoTrainer();
   // one minibatch: features bytes [rows][F], action int32 [rows] or float32 [rows][H], logp, adv, ret float32 [rows],
   // mask bytes [rows] (null: every row counts)
+  // a masked actor (kind 2): action is the flat index, and legal, the rows' 128-bit words uint32 [rows][4] (16-byte
+  // aligned), is required; for every other actor it must be null
   void Step(hipStream_t stream, int rows, const void* d_features, const void* d_action, const void* d_logp,
-            const void* d_adv, const void* d_ret, const void* d_mask);
+            const void* d_adv, const void* d_ret, const void* d_mask, const void* d_legal = nullptr);
   // adv and ret [T][N] of a horizon for the collector's GAE launch to fill before Fit (allocated here)
   void Horizon(const PpoSource& src, int batch, int epochs, float** adv, float** ret);
   // `epochs` epochs of T N / batch minibatches gathered from the collector's buffers
   void Fit(hipStream_t stream, const PpoSource& src, int batch, int epochs);
   // A host wait.  what 0 .. 8 as Trainer::Read, with the sigma segment as array `2 layers` (3: the float32 sigma the
   // loss reads) and statistics rows of 8 doubles; 9: the gathered minibatch, layer 0 features, 1 action, 2 logp, 3 adv,
-  // 4 ret, 5 mask, 6 the advantage statistics float64 [3] (count, mean, std)
+  // 4 ret, 5 mask, 6 the advantage statistics float64 [3] (count, mean, std), 7 the legal words (a masked actor)
   void Read(int what, int layer, void* out);
 
  private:
   struct Layout;
   void Enqueue(hipStream_t stream, int rows, const unsigned char* features, const void* action, const float* logp,
-               const float* adv, const float* ret, const unsigned char* mask);
+               const float* adv, const float* ret, const unsigned char* mask, const void* legal);
   int device_, max_rows_;
   int F_{0}, H_{0}, kind_{0}, layers_{0};
+  int mask0_{-1}, C_{1}, nvec_[4]{1, 1, 1, 1};  // a masked actor's
   bool sigma_{false};
   float scale_p_{0}, scale_v_{0};
   PpoTrainerOptions opt_;
@@ -1371,8 +1384,11 @@ class Pool {
     unsigned flags{0};
     uint64_t seed{0};
     // offsets into mem: the net image, lo, scale, sigma, low, high, the feature rows [N][F], the head's rows
-    // [N][H + 1], logp [T][N], value [T+1][N], the end
-    size_t off[11]{};
+    // [N][H + 1], logp [T][N], value [T+1][N], the current step's legal words [N] (masked), the end
+    size_t off[12]{};
+    // masked: the components of the action row, and where the mask lies: obs key mask_key, from its element mask_first
+    // (mask_key = -1: no mask)
+    int C{1}, nvec[4]{1, 1, 1, 1}, mask_key{-1}, mask_first{0};
   };
   Actor actor_;
   void ActorFree();
@@ -1380,7 +1396,7 @@ class Pool {
   int ActorFeatures() const;                      // F of the pool: the components of the collector's obs keys
   // enqueues features -> trunk -> sample for `rows` rows on stream_: obs key j's rows at src[j]
   void ActorEnqueue(const char* const* src, int rows, const int32_t* d_env_id, long long step, bool value_only,
-                    unsigned char* features, int32_t* head, void* action, float* logp, float* value);
+                    unsigned char* features, int32_t* head, void* legal, void* action, float* logp, float* value);
   // the pool's self-play driver
   struct Selfplay {
     bool open{false};

@@ -11,7 +11,12 @@
 //   index round by a shuffle; the wave then featurises the row's obs keys straight out of slot t of the collector's
 //   buffers into the F contiguous bytes the forward reads, consecutive lanes taking consecutive components, converts
 //   the action row, and lanes 0 .. 3 move logp, the (normalised) advantage, ret and the mask.  No copy of the
-//   observations exists in between.
+//   observations exists in between.  For a masked head the wave also ballots the row's legal word out of slot t of the
+//   mask's obs key (actor.hip.h: LegalBallot; no copy of the mask exists either) and lane 4 folds the stored C
+//   components into the flat index.
+// PpoLoss<masked> is PpoLoss<discrete> with the rows' legal words in LDS beside p: lanes skip illegal j, and the
+//   single-lane walks of S and of the entropy skip them by testing the bit; dp of an illegal j leaves as 0.0f.  Three
+//   instantiations in all.
 // PpoLoss<box>: a block of 256 threads takes kPpoLossRows = 32 rows, eight lanes a row; p, the Box action rows and
 //   the per-row inputs enter LDS as flat 16-byte copies.  The order-free work is spread over a row's eight lanes
 //   (j = lane, lane + 8, ..): logits, their maximum by three xor shuffles, exponentials, q, z, the terms and the
@@ -134,6 +139,11 @@ struct GatherArgs {
   float* out_adv;
   float* out_ret;
   unsigned char* out_mask;
+  // a masked head: the stored action row is C int32 components of the flat index; the mask is slot 0 of its obs key
+  // (null: none), rows of mask_elems elements, from element mask_first on
+  int masked, C, nvec[actor::kMaxComponents], mask_elems, mask_first, mask_dtype;
+  const char* mask_src;
+  uint4* out_legal;
 };
 
 __global__ __launch_bounds__(256) void PpoGather(GatherArgs a) {
@@ -161,6 +171,14 @@ __global__ __launch_bounds__(256) void PpoGather(GatherArgs a) {
       act[c] = a.action_dtype == actor::kF32 ? reinterpret_cast<const float*>(a.action)[at]
                                              : (float)reinterpret_cast<const double*>(a.action)[at];
     }
+  } else if (a.masked) {  // (uniform in the launch: every lane of the wave takes the ballots)
+    const uint4 w = actor::LegalBallot(a.mask_src, a.mask_dtype, idx * (size_t)a.mask_elems + (size_t)a.mask_first,
+                                       a.H, lane);
+    if (lane == 5) a.out_legal[row] = w;
+    if (lane == 4) {
+      static_cast<int32_t*>(a.out_action)[row] =
+          actor::ActorFlat(reinterpret_cast<const int32_t*>(a.action) + idx * (size_t)a.C, a.nvec, a.C);
+    }
   } else if (lane == 4) {
     static_cast<int32_t*>(a.out_action)[row] = reinterpret_cast<const int32_t*>(a.action)[idx];
   }
@@ -186,10 +204,13 @@ struct LossArgs {
   float* dp;
   double* partial;        // [blocks][kPpoPartials]
   double* sigma_partial;  // box with a trained sigma: [blocks][H]; else null
+  const uint4* legal;     // masked: the rows' legal words
 };
 
-template <bool kBox>
+template <int kHead>  // actor::kDiscrete, kBox, kMasked
 __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
+  constexpr bool kBox = kHead == actor::kBox, kMask = kHead == actor::kMasked;
+  __shared__ __attribute__((aligned(16))) uint32_t s_legal[kMask ? kRows : 1][4];  // masked: beside p
   __shared__ __attribute__((aligned(16))) int32_t s_p[kRows * kWide];  // p, then the bits of the logits, then of dp
   __shared__ __attribute__((aligned(16))) float s_x[kRows * kWide];    // discrete: e, then q; box: the action, then z
   __shared__ __attribute__((aligned(16))) float s_t[kRows * kWide];    // the terms of the ordered sum; box: then dsigma
@@ -210,6 +231,7 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
     }
   } else {
     FlatCopy(s_in[0], static_cast<const int32_t*>(a.action) + r0, (size_t)nr * 4, t, 256);
+    if (kMask) FlatCopy(s_legal, a.legal + r0, (size_t)nr * 16, t, 256);
   }
   FlatCopy(s_in[1], a.logp + r0, (size_t)nr * 4, t, 256);
   FlatCopy(s_in[2], a.adv + r0, (size_t)nr * 4, t, 256);
@@ -228,6 +250,8 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
   float* term = s_t + row * H;
   float top = 0.0f, log_s = 0.0f, Hn = 0.0f, lp = 0.0f;
   int action = 0;
+  const uint32_t* legal = s_legal[kMask && row < nr ? row : 0];
+  auto in = [legal](int k) { return !kMask || actor::LegalBit(legal, k); };  // (a masked head: lanes skip illegal k)
 
   if (kBox) {
     if (live) {
@@ -251,7 +275,7 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
       for (int k = l; k < H; k += kGroup) {
         const float logit = pgx::NetLogit(p[k], a.o.scale_p);
         p[k] = pgx::NetFloatBits(logit);
-        top = logit > top ? logit : top;
+        if (in(k)) top = logit > top ? logit : top;
       }
     }
     for (int w = kGroup / 2; w >= 1; w >>= 1) {
@@ -259,19 +283,24 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
       top = other > top ? other : top;
     }
     if (live) {
-      for (int k = l; k < H; k += kGroup) x[k] = pgx::GumbelExp(pgx::NetBitsFloat(p[k]) - top);
+      for (int k = l; k < H; k += kGroup) {
+        if (in(k)) x[k] = pgx::GumbelExp(pgx::NetBitsFloat(p[k]) - top);
+      }
     }
     __syncthreads();
     // the ordered sums, both by lane 0: S, and behind it the entropy over q = e / S
     float sum = 0.0f;
     if (live && l == 0) {
-      for (int k = 0; k < H; ++k) sum = sum + x[k];
+      for (int k = 0; k < H; ++k) {
+        if (in(k)) sum = sum + x[k];
+      }
     }
     const float S = __shfl(sum, base);
     __syncthreads();
     if (live) {
       log_s = pgx::GumbelLog(S);
       for (int k = l; k < H; k += kGroup) {
+        if (!in(k)) continue;
         const float q = x[k] / S;
         x[k] = q;
         term[k] = q * ((pgx::NetBitsFloat(p[k]) - top) - log_s);
@@ -280,7 +309,9 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
     __syncthreads();
     sum = 0.0f;
     if (live && l == 0) {
-      for (int k = 0; k < H; ++k) sum = sum + term[k];
+      for (int k = 0; k < H; ++k) {
+        if (in(k)) sum = sum + term[k];
+      }
       action = s_in[0][row];
       action = action < 0 ? 0 : (action >= H ? H - 1 : action);  // (LDS stays in bounds whatever the caller sent)
       lp = (pgx::NetBitsFloat(p[action]) - top) - log_s;
@@ -299,7 +330,7 @@ __global__ __launch_bounds__(256) void PpoLoss(LossArgs a) {
       if (kBox) {
         if (live) d = ppo::PpoBoxGrad(a.o, g, x[k], s_sigma[k]);
         term[k] = live ? ppo::PpoSigmaGrad(a.o, g, x[k], s_sigma[k]) : 0.0f;
-      } else if (live) {
+      } else if (live && in(k)) {
         d = ppo::PpoDiscreteGrad(a.o, g, k == action, x[k], (pgx::NetBitsFloat(p[k]) - top) - log_s, Hn);
       }
       p[k] = pgx::NetFloatBits(d);
@@ -425,7 +456,7 @@ struct PpoTrainer::Layout {
   size_t count[2 * kNetImageLayers + 1]{}, eoff[2 * kNetImageLayers + 1]{};  // elements and the flat offset of an array
   size_t net_elems{0}, elems{0}, weight_elems{0};                            // of the flat space, all whole chunks
   // byte offsets into the block
-  size_t grad, master, s1, s2, q_weight, q_bias, sigma, lo, scale, dp, p, features, action, logp, adv, ret, mask,
+  size_t grad, master, s1, s2, q_weight, q_bias, sigma, lo, scale, dp, p, features, action, logp, adv, ret, mask, legal,
       loss_partial, sigma_partial, norm_partial, clip, adv_stats, stats, total;
   // and into the horizon's
   size_t h_adv, h_ret, h_partial;
@@ -450,6 +481,8 @@ PpoTrainer::PpoTrainer(int device, const void* blob, size_t bytes, const PpoTrai
   Layout& at = *at_;
   layers_ = v.net.layers(), F_ = v.F, H_ = v.H, kind_ = v.kind, scale_p_ = v.scale_p, scale_v_ = v.scale_v;
   sigma_ = kind_ == actor::kBox && o.train_sigma != 0;
+  mask0_ = v.mask0, C_ = v.C;
+  std::memcpy(nvec_, v.nvec, sizeof(nvec_));
   for (int i = 0; i < layers_; ++i) {
     const pgx::NetLayer& l = v.net.layer[i];
     at.count[i] = (size_t)l.n_out * l.k_in, at.count[layers_ + i] = (size_t)l.n_out;
@@ -480,6 +513,7 @@ PpoTrainer::PpoTrainer(int device, const void* blob, size_t bytes, const PpoTrai
   at.dp = take(rows * H1 * 4), at.p = take(rows * H1 * 4);
   at.features = take(rows * F_), at.action = take(rows * (size_t)H_ * 4);
   at.logp = take(rows * 4), at.adv = take(rows * 4), at.ret = take(rows * 4), at.mask = take(rows);
+  at.legal = take(kind_ == actor::kMasked ? rows * 16 : 0);
   at.loss_partial = take(blocks * ppo::kPpoPartials * 8), at.sigma_partial = take(blocks * (size_t)H_ * 8);
   at.norm_partial = take(E / kChunk * 8), at.clip = take(8), at.adv_stats = take(24);
   at.stats = take((size_t)pgx::kTrainerStatRows * ppo::kPpoStats * 8);
@@ -530,7 +564,8 @@ PpoTrainer::~PpoTrainer() {
 }
 
 void PpoTrainer::Enqueue(hipStream_t stream, int rows, const unsigned char* features, const void* action,
-                         const float* logp, const float* adv, const float* ret, const unsigned char* mask) {
+                         const float* logp, const float* adv, const float* ret, const unsigned char* mask,
+                         const void* legal) {
   const Layout& at = *at_;
   char* m = mem_.p;
   const void* qw[kNetImageLayers];
@@ -558,12 +593,15 @@ void PpoTrainer::Enqueue(hipStream_t stream, int rows, const unsigned char* feat
   const LossArgs loss{rows, H_,
                       ppo::PpoOptionsOf(scale_p_, scale_v_, (float)opt_.clip_ratio, (float)opt_.base.value_weight,
                                         (float)opt_.entropy_weight, rows),
-                      p, action, logp, adv, ret, mask, sigma, dp, loss_partial, sigma_ ? sigma_partial : nullptr};
+                      p, action, logp, adv, ret, mask, sigma, dp, loss_partial, sigma_ ? sigma_partial : nullptr,
+                      static_cast<const uint4*>(legal)};
   OnDevice(device_, [&] {
     if (box) {
-      hipLaunchKernelGGL(PpoLoss<true>, dim3(loss_blocks), dim3(256), 0, stream, loss);
+      hipLaunchKernelGGL(PpoLoss<actor::kBox>, dim3(loss_blocks), dim3(256), 0, stream, loss);
+    } else if (kind_ == actor::kMasked) {
+      hipLaunchKernelGGL(PpoLoss<actor::kMasked>, dim3(loss_blocks), dim3(256), 0, stream, loss);
     } else {
-      hipLaunchKernelGGL(PpoLoss<false>, dim3(loss_blocks), dim3(256), 0, stream, loss);
+      hipLaunchKernelGGL(PpoLoss<actor::kDiscrete>, dim3(loss_blocks), dim3(256), 0, stream, loss);
     }
   });
   net_->Backward(stream, rows, dp, dw, db);
@@ -597,16 +635,24 @@ void PpoTrainer::Enqueue(hipStream_t stream, int rows, const unsigned char* feat
 }
 
 void PpoTrainer::Step(hipStream_t stream, int rows, const void* d_features, const void* d_action, const void* d_logp,
-                      const void* d_adv, const void* d_ret, const void* d_mask) {
+                      const void* d_adv, const void* d_ret, const void* d_mask, const void* d_legal) {
   if (d_features == nullptr || d_action == nullptr || d_logp == nullptr || d_adv == nullptr || d_ret == nullptr) {
     throw std::invalid_argument("ppo_step: null argument");
+  }
+  if ((kind_ == actor::kMasked) != (d_legal != nullptr)) {
+    throw std::invalid_argument("ppo_step: a masked actor (kind 2), and no other, takes the rows' legal words "
+                                "(epa_ppo_step_legal_device)");
+  }
+  if (d_legal != nullptr && reinterpret_cast<uintptr_t>(d_legal) % 16 != 0) {
+    throw std::invalid_argument("ppo_step: the legal words must be 16-byte aligned");
   }
   if (rows < 1 || rows > max_rows_) {
     throw std::invalid_argument("ppo_step: rows = " + std::to_string(rows) + " must be 1 .. " +
                                 std::to_string(max_rows_) + " (the handle's max_rows)");
   }
   Enqueue(stream, rows, static_cast<const unsigned char*>(d_features), d_action, static_cast<const float*>(d_logp),
-          static_cast<const float*>(d_adv), static_cast<const float*>(d_ret), static_cast<const unsigned char*>(d_mask));
+          static_cast<const float*>(d_adv), static_cast<const float*>(d_ret), static_cast<const unsigned char*>(d_mask),
+          d_legal);
 }
 
 void PpoTrainer::Horizon(const PpoSource& src, int batch, int epochs, float** adv, float** ret) {
@@ -632,8 +678,17 @@ void PpoTrainer::Horizon(const PpoSource& src, int batch, int epochs, float** ad
     F += src.obs_elems[j];
   }
   const bool box = kind_ == actor::kBox;
-  const bool fits = box ? (src.action_dtype == actor::kF32 || src.action_dtype == actor::kF64) && src.action_elems == H_
-                        : src.action_dtype == actor::kI32 && src.action_elems == 1;
+  bool fits = box ? (src.action_dtype == actor::kF32 || src.action_dtype == actor::kF64) && src.action_elems == H_
+                  : src.action_dtype == actor::kI32 && src.action_elems == (kind_ == actor::kMasked ? C_ : 1);
+  if (kind_ == actor::kMasked && mask0_ >= 0 && F == F_) {  // the mask lies inside one obs key
+    bool inside = false;
+    int comp = 0;
+    for (int j = 0; j < src.n_obs; ++j) {
+      inside = inside || (mask0_ >= comp && mask0_ + H_ <= comp + src.obs_elems[j]);
+      comp += src.obs_elems[j];
+    }
+    fits = fits && inside;
+  }
   if (F != F_ || !fits) {
     throw std::invalid_argument("ppo_fit: the collector has F = " + std::to_string(F) + " and action rows of " +
                                 std::to_string(src.action_elems) + " of dtype " + std::to_string(src.action_dtype) +
@@ -687,7 +742,18 @@ void PpoTrainer::Fit(hipStream_t stream, const PpoSource& src, int batch, int ep
   for (int j = 0; j < src.n_obs; ++j) {
     g.keys.src[j] = static_cast<const char*>(src.obs[j]);
     g.keys.elems[j] = src.obs_elems[j], g.keys.dtype[j] = src.obs_dtype[j], g.keys.comp0[j] = comp;
+    if (kind_ == actor::kMasked && mask0_ >= comp && mask0_ + H_ <= comp + src.obs_elems[j]) {
+      g.mask_src = g.keys.src[j], g.mask_elems = src.obs_elems[j], g.mask_dtype = src.obs_dtype[j];
+      g.mask_first = mask0_ - comp;
+    }
     comp += src.obs_elems[j];
+  }
+  if (kind_ == actor::kMasked) {
+    if (mask0_ >= 0 && g.mask_src == nullptr) throw std::invalid_argument("ppo_fit: the mask does not lie inside one obs key");
+    if (src.action_elems != C_) throw std::invalid_argument("ppo_fit: the action rows are not the actor's components");
+    g.masked = 1, g.C = C_;
+    std::memcpy(g.nvec, nvec_, sizeof(g.nvec));
+    g.out_legal = reinterpret_cast<uint4*>(m + at.legal);
   }
   g.lo = reinterpret_cast<const double*>(m + at.lo), g.scale = reinterpret_cast<const double*>(m + at.scale);
   g.action = static_cast<const char*>(src.action), g.logp = src.logp, g.adv = adv;
@@ -701,7 +767,7 @@ void PpoTrainer::Fit(hipStream_t stream, const PpoSource& src, int batch, int ep
     for (int s = 0; s < steps; ++s) {
       g.first = (uint32_t)s * (uint32_t)batch;
       OnDevice(device_, [&] { hipLaunchKernelGGL(PpoGather, dim3((batch + 3) / 4), dim3(256), 0, stream, g); });
-      Enqueue(stream, batch, g.out_features, g.out_action, g.out_logp, g.out_adv, g.out_ret, g.out_mask);
+      Enqueue(stream, batch, g.out_features, g.out_action, g.out_logp, g.out_adv, g.out_ret, g.out_mask, g.out_legal);
     }
     ++epochs_;
   }
@@ -741,9 +807,11 @@ void PpoTrainer::Read(int what, int layer, void* out) {
     }
   } else if (what == 9) {
     const size_t action_bytes = kind_ == actor::kBox ? n * (size_t)H_ * 4 : n * 4;
-    const size_t offs[7] = {at.features, at.action, at.logp, at.adv, at.ret, at.mask, at.adv_stats};
-    const size_t sizes[7] = {n * (size_t)F_, action_bytes, 4 * n, 4 * n, 4 * n, n, 24};
-    if (layer < 0 || layer > 6) throw std::invalid_argument("ppo_read: a minibatch has parts 0 .. 6");
+    const size_t offs[8] = {at.features, at.action, at.logp, at.adv, at.ret, at.mask, at.adv_stats, at.legal};
+    const size_t sizes[8] = {n * (size_t)F_, action_bytes, 4 * n, 4 * n, 4 * n, n, 24, 16 * n};
+    if (layer < 0 || layer > (kind_ == actor::kMasked ? 7 : 6)) {
+      throw std::invalid_argument("ppo_read: a minibatch has parts 0 .. 6, and 7 (the legal words) for a masked actor");
+    }
     from = offs[layer], bytes = sizes[layer];
   } else {
     throw std::invalid_argument("ppo_read: what = " + std::to_string(what) + " must be 0 .. 9");

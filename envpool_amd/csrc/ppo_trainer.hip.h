@@ -16,6 +16,10 @@
 //   box       mu_j = l_j;  z_j = (a_j - mu_j) / sigma_j;
 //             logp' = SUM ((-0.5f * z_j) * z_j - GumbelLog(sigma_j)) - 0.9189385f, ascending j from 0.0f
 //             (SampleBoxTerm's term with the given action);  Hn = SUM (0.5f + 0.9189385f) + GumbelLog(sigma_j)
+//   masked    (actor.hip.h kind 2) discrete's formulas with j running over the row's legal set (LegalBit of its 128-bit
+//             word) only: top, e_j, S, q_j, lq_j, Hn and dp_j exist for legal j, the ordered sums skip illegal j, and
+//             dp_j = 0.0f exactly for illegal j.  The action is the flat index (a gather rebuilds it from the stored
+//             components by ActorFlat) and must be legal.  A row whose set is everything is a discrete row, bit for bit.
 //   ratio     d = clamp(logp' - logp, -kPpoLogRatio, kPpoLogRatio);  r = d <= 0 ? GumbelExp(d) : 1.0f / GumbelExp(-d)
 //             (GumbelExp clamps its argument to [-87, 0]);  rc = clamp(r, lo, hi);  policy loss = -min(r adv, rc adv);
 //             active = r adv <= rc adv;  g = active ? -(adv * r) / nf : 0
@@ -66,6 +70,8 @@
 //   dsigma_j of a row: kPpoErr * W (|g| (z_j^2 + 1) + ew) / sigma_j; the sums in double and the final (float) add u.
 //   The value gradient takes five roundings.  Loss terms: policy kPpoErr * W |adv| max(r, rc); value 4 u; Hn kPpoErr *
 //   W (Hn + 1) (box: kPpoErr * SUM 1.42 + |log sigma_j|); (r - 1) - d: kPpoErr * W (r + 1).
+//   masked: every bound above holds with its sums, maxima and M_j taken over the legal set -- the same operations on
+//   fewer terms -- so kPpoErr and the discrete formula carry over unchanged; an illegal j has error 0.
 // `active` and r != rc are not continuous: a row whose exact r lies within 1.9e-5 W of lo or hi may fall either way, and
 // the tests keep their rows away from there.
 #ifndef ENVPOOL_AMD_CSRC_PPO_TRAINER_HIP_H_
@@ -197,29 +203,33 @@ inline void PpoValuePart(const int32_t* p, int H, float ret, const PpoOptions& o
   dp[H] = pgx::TrainerValueGrad(o.value_weight, o.scale_v, v, ret, o.nf);
   stat[1] = pgx::TrainerValueLoss(o.value_weight, v, ret);
 }
+// `legal`: the row's words of a masked head (actor::LegalBit); null: a discrete head, every j.
 inline void PpoDiscreteRow(const int32_t* p, int H, int action, float logp, float adv, float ret, unsigned char mask,
-                           const PpoOptions& o, float* dp, float* stat) {
+                           const PpoOptions& o, float* dp, float* stat, const uint32_t* legal = nullptr) {
   for (int j = 0; j <= H; ++j) dp[j] = 0.0f;
   for (int j = 0; j < 5; ++j) stat[j] = 0.0f;
   if (mask == 0) return;
+  auto in = [legal](int j) { return legal == nullptr || actor::LegalBit(legal, j); };
   float top = -FLT_MAX;
   for (int j = 0; j < H; ++j) {
     const float l = pgx::NetLogit(p[j], o.scale_p);
-    top = l > top ? l : top;
+    if (in(j)) top = l > top ? l : top;
   }
   float S = 0.0f;
-  for (int j = 0; j < H; ++j) S = S + pgx::GumbelExp(pgx::NetLogit(p[j], o.scale_p) - top);
+  for (int j = 0; j < H; ++j) {
+    if (in(j)) S = S + pgx::GumbelExp(pgx::NetLogit(p[j], o.scale_p) - top);
+  }
   const float log_s = pgx::GumbelLog(S);
   float sum = 0.0f;
   for (int j = 0; j < H; ++j) {
     const float x = pgx::NetLogit(p[j], o.scale_p) - top;
-    sum = sum + (pgx::GumbelExp(x) / S) * (x - log_s);
+    if (in(j)) sum = sum + (pgx::GumbelExp(x) / S) * (x - log_s);
   }
   const float Hn = -sum;
   const PpoRatioOut r = PpoRatio((pgx::NetLogit(p[action], o.scale_p) - top) - log_s, logp, adv, o);
   for (int j = 0; j < H; ++j) {
     const float x = pgx::NetLogit(p[j], o.scale_p) - top;
-    dp[j] = PpoDiscreteGrad(o, r.g, j == action, pgx::GumbelExp(x) / S, x - log_s, Hn);
+    if (in(j)) dp[j] = PpoDiscreteGrad(o, r.g, j == action, pgx::GumbelExp(x) / S, x - log_s, Hn);
   }
   stat[0] = r.loss, stat[2] = Hn, stat[3] = r.kl, stat[4] = (float)r.clipped;
   PpoValuePart(p, H, ret, o, dp, stat);

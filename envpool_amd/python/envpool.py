@@ -241,6 +241,9 @@ class RolloutCollector:
 
         pool = self._open()
         want = space_of(self._env)
+        if actor.kind == 2 and want["kind"] != 1:  # a masked actor: a Discrete space, or an integer Box of its nvec
+            nvec = list(want.get("nvec", [want["actions"]]))
+            want = dict(want, kind=2 if nvec == list(actor.nvec[:actor.components]) else want["kind"])
         if (actor.features, actor.actions, actor.kind) != (want["features"], want["actions"], want["kind"]):
             raise ValueError(f"actor: an actor of F = {actor.features}, H = {actor.actions}, kind = {actor.kind} for a "
                              f"pool of F = {want['features']}, H = {want['actions']}, kind = {want['kind']}")

@@ -1004,6 +1004,10 @@ int epa_trainer_read(epa_trainer* trainer, int32_t what, int32_t layer, void* ou
  *   epa_ppo_step_device(handle, stream, rows, d_features, d_action, d_logp, d_adv, d_ret, d_mask): one step on a
  *     minibatch in device memory: feature bytes [rows][F], action int32 [rows] (discrete) or float32 [rows][H] (box),
  *     logp, adv, ret float32 [rows], mask bytes [rows] or null (every row counts).  adv is used as given.
+ *   epa_ppo_step_legal_device(..., d_mask, d_legal): the same for an EPA_ACTOR_MASKED blob, which the call above refuses:
+ *     action int32 [rows] is the flat index, d_legal the rows' legal sets, uint32 [rows][4], 16-byte aligned, bit j of a
+ *     row in word j / 32.  The loss runs over the legal actions only; dp of an illegal one is 0.  epa_ppo_fit_device
+ *     builds both from the collector's buffers itself; epa_ppo_read(9, 7) returns the gathered legal words.
  *   epa_ppo_fit_device(handle, pool, stream, source, epochs, batch, gamma, lam): `pool`'s collector must hold a full
  *     horizon and an actor; `source` describes its buffers (epa_rollout_view_device, epa_actor_view_device; dtypes as
  *     EPA_I32 ..) and `stream` is the pool's.  The pool's GAE over the stored values fills the handle's adv / ret; then
@@ -1038,6 +1042,9 @@ int epa_ppo_create(int32_t device, const void* blob, size_t bytes, const epa_ppo
 int epa_ppo_destroy(epa_ppo* ppo);
 int epa_ppo_step_device(epa_ppo* ppo, void* stream, int32_t rows, const void* d_features, const void* d_action,
                         const void* d_logp, const void* d_adv, const void* d_ret, const void* d_mask);
+int epa_ppo_step_legal_device(epa_ppo* ppo, void* stream, int32_t rows, const void* d_features, const void* d_action,
+                              const void* d_logp, const void* d_adv, const void* d_ret, const void* d_mask,
+                              const void* d_legal);
 int epa_ppo_fit_device(epa_ppo* ppo, epa_pool* pool, void* stream, const epa_ppo_source* source, int32_t epochs,
                        int32_t batch, float gamma, float lam);
 int epa_ppo_read(epa_ppo* ppo, int32_t what, int32_t layer, void* out);
@@ -1158,7 +1165,11 @@ int epa_rollout_end(epa_pool* pool);
 /* Rollout actor (csrc/actor.hip.h is the contract; DESIGN.md section 2 "Rollout actor and collect"): a built-in int8
  * actor-critic attached to the pool's open collector, so that a whole horizon is played from C++ with nothing between
  * the launches.  The blob: magic "EPAA", version 1, F, H, D, L, kind, scale_p, scale_v, lo[F], scale[F] float64,
- * sigma[H] float32 (EPA_ACTOR_BOX only), then the layer section of a network blob (epa_net_create).
+ * sigma[H] float32 (EPA_ACTOR_BOX only) or int32 mask0, C, nvec[4] (EPA_ACTOR_MASKED only), then the layer section of a
+ * network blob (epa_net_create).  EPA_ACTOR_MASKED: one categorical over the H = PROD nvec flat actions restricted to the
+ * row's legal set -- the raw observation components mask0 .. mask0 + H - 1 that are not 0; all of them for mask0 = -1
+ * and for a row without any -- whose index goes to the env as C int32 components in mixed radix, most significant first.
+ * epa_actor_begin then also refuses a mask that does not lie inside one obs key and an action row that is not C int32.
  *   epa_actor_begin(blob, bytes, seed, flags, actions, low, high): checks the blob and compares it with the pool -- F =
  *     the components of the collector's obs keys (at most 512), kind and H with the action row, `actions` (the number
  *     of discrete actions, or the Box dimension) with H; low / high: the Box bounds, float64 [H] (NULL for a discrete
@@ -1179,6 +1190,7 @@ int epa_rollout_end(epa_pool* pool);
 #define EPA_ACTOR_DETERMINISTIC 1u
 #define EPA_ACTOR_DISCRETE 0
 #define EPA_ACTOR_BOX 1
+#define EPA_ACTOR_MASKED 2
 int epa_actor_begin(epa_pool* pool, const void* blob, size_t bytes, uint64_t seed, uint32_t flags, int32_t actions,
                     const double* low, const double* high);
 int epa_actor_shape(epa_pool* pool, int64_t* out);
