@@ -72,6 +72,10 @@
 #ifndef EPA_LG_HOST_ROWS
 #define EPA_LG_HOST_ROWS() ((void)0)
 #endif
+// host tests only (tests/cpu_harness/planar_lg_row_peel_host.cpp): the lanes' active-row masks and parts of H after a trip's pass over the rows
+#ifndef EPA_LG_HOST_MASK
+#define EPA_LG_HOST_MASK(mask, H) ((void)0)
+#endif
 #ifndef EPA_LG_LS_RTOL
 #define EPA_LG_LS_RTOL 1e-10
 #endif
@@ -957,20 +961,32 @@ EPA_HD void ForPairCols(const Pos<V>& p, Cx& cx, F&& f) {
   });
 }
 
+// The entries (i <= k) of the packed Hessian that the first end-sphere visit of RowsPass<.., kPeel> writes, not adds to
+// (the argument is in RowsPass): all but the leg's diagonal, which the limit rows have written, and the couplings of the
+// two slides with the hinges.
+EPA_HD constexpr bool PeelInits(int i, int k) { return !(k >= 3 && i == k) && !(i < 2 && k >= 2); }
+
 // One pass over the lane's constraint rows at acceleration `a`: accumulates THIS LANE's part of
 // J^T f into gc (6) and, if kHess, of J^T D_active J into Hc (21); the lane's active-row mask in
 // `mask`.  The caller sums the torso entries over the group.
 // `vis`: the lane's set of end-sphere slots to visit (its own touching slots, or none if its env has finished);
 // `ends`: the wave-uniform set MakeConstraint returned (only its body-pair bits are used here).
-template <int KL, bool kHess, typename T, typename V, typename Cx, typename U>
+// The caller hands gc and Hc in as +0.0.  kPeel (round 12, with kHess, no body-pair rows): the limit rows and
+// the FIRST end-sphere visit WRITE most of Hc where every other visit adds to it -- see PeelInits below.
+template <int KL, bool kHess, bool kPeel = false, typename T, typename V, typename Cx, typename U>
 EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRows<V>& lim,
                      unsigned ends, const U& vis, const V* a, V* gc, V* Hc, U& mask) {
+  static_assert(!kPeel || (kHess && !Grp<KL>::kPairs), "the pair rows add to Hc in front of the first visit");
   static_for<0, 3>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
     const V jar = lim.sgn[j] * a[j + 3] - lim.aref[j];
     const V w = Sel(jar < V(0), lim.D[j], V(0));  // lim.D == 0 where the limit is not violated
     gc[j + 3] += lim.sgn[j] * w * jar;
-    if constexpr (kHess) Hc[Tri(j + 3, j + 3)] += w;
+    if constexpr (kPeel) {
+      Hc[Tri(j + 3, j + 3)] = w;  // (+0.0) + w has w's bits: w is lim.D > 0 or the +0.0 of the select, never -0.0
+    } else if constexpr (kHess) {
+      Hc[Tri(j + 3, j + 3)] += w;
+    }
     MaskSetNZ(mask, w, j);
   });
   if constexpr (Grp<KL>::kPairs) {  // frictionless body-body rows (Hopper)
@@ -1026,7 +1042,135 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
   // accumulator.  An accumulator starts at +0.0 and only ever receives sums: x + (+-0) = x for x != 0, (+0) + (+-0) = +0
   // and a sum that cancels gives +0 under round-to-nearest, so it is never -0.0 and adding +-0 leaves its bits alone --
   // as with slot 0's numbers and a selected D = 0 before.  The cache entries the visit writes are the sentinel's own.
-  if (AnyWave(AnySlot(rem))) do {
+  //
+  // kPeel (round 12): the FIRST visit is code of its own in front of the loop (`first_c`), and there -- as in the limit
+  // rows above -- the entries of Hc for which PeelInits holds are WRITTEN, a product where the loop has 0 + product:
+  // neither the 27 v_mov_b64 that zeroed the accumulators in front of the loop nor the first add.  When no lane of the
+  // wave has a slot the caller's zeros stay; they are then set on that path only.
+  // Why no bit of a live env changes.  (+0) + x and x differ for x = -0.0 only -- x being the same number in both: on
+  // the device the compiler fuses one product of  ui jn + wi jx  into an FMA, and which one it takes depends on the form
+  // of the code around the sum, so the visit's statements stay letter for letter what they were and the device digests
+  // (tests/test_gpu_planar_lg_*.py) pin the build.  So a written entry can hold -0.0 where the accumulated one holds
+  // +0.0, and nothing else.  That state is kept or cured by every later add, never spread: with c in {x, x} or {-0, +0} and the same t added to both,
+  // t != 0 gives t twice, t = +0 gives +0 twice, t = -0 gives {-0, +0} again; the same holds for the sum of two such
+  // pairs, so for the later visits and for SumEnv / SumPar of the lanes' parts.  The first reader that is not such an
+  // add is the caller's  H = p.M + sum : M + (-0) and M + (+0) differ only where M is -0.0 itself.  Per entry:
+  //   (0,0) (1,1)      Hc receives C = mu^2 (w2 + w3) resp. A = w1 + w2 + w3: sums of weights that are D > 0 or the +0.0
+  //   (0,1)            of a select, and Bc = mu (w3 - w2) with x - x = +0: never -0.0 in the first place;
+  //   (j,k), 2 <= j < k  and (2,2):  M = Dot((1, coz_j, -cox_j), buf_k), a sum that is -0.0 only if each of its three
+  //                    terms is, and the first is buf_k.w = (crb.I + mdz coz_k) - mdx (-cox_k), which is -0.0 only if crb.I
+  //                    is: crb.I >= the body's iyy > 0.  M is not -0.0: WRITTEN;
+  //   (k,k), k >= 3    written by the limit rows (w, never -0.0), every visit adds;
+  //   (0,k) (1,k), k >= 2:  M = (0 buf.w + buf.x) + 0 buf.z resp. (0 buf.w + 0 buf.x) + buf.z.  buf.w of a leg's subtree
+  //                    may be negative and buf.z = m (-cox_k) - mdx is -0.0 whenever the robot's centre of mass and the
+  //                    subtree's both stand exactly over the hinge: a -0.0 in M cannot be excluded for every state a
+  //                    caller may set.  These eight keep the zero start, (+0) + product -- still without the v_mov, the
+  //                    zero is an operand of the first visit's add.
+  // gc keeps the zero start everywhere (its reader is (Ma - qfrc_smooth) + gc, and Ma - qfrc_smooth may be -0.0: a
+  // warm start of -0.0 with no force on a dof); in the first visit its zeros are operands too.
+  // H, like the masks, is only ever used for live envs; -0.0 / +0.0 in a finished env's H reaches nothing.
+  // The loop WITHOUT the peel is kept as it was written, next to the visit as a lambda: with one body for both the
+  // Hopper's kernel and the kernels of four lanes per env came out with the other product of those sums fused -- other
+  // bits (measured: their digests and dumps changed; with this copy their machine code is the parent's, instruction
+  // for instruction).
+  if constexpr (!kPeel) {
+    if (AnyWave(AnySlot(rem))) do {
+      [[maybe_unused]] const auto has = AnySlot(rem);
+      U sl;
+      if constexpr (Grp<KL>::kSentinel) {
+        sl = PopSlotOr<Grp<KL>::kEnds>(rem);
+      } else {
+        sl = PopSlot(rem);
+      }
+      const U body = SlotBodyOf<KL>(sl);
+      const V cpx = cx.LdsL(sl, kSlotsPerEnd, 0), cpz = cx.LdsL(sl, kSlotsPerEnd, 1);
+      const V an = cx.LdsL(sl, kSlotsPerEnd, 2), ax = cx.LdsL(sl, kSlotsPerEnd, 3);
+      V D = cx.LdsL(sl, kSlotsPerEnd, 4);
+      if constexpr (!Grp<KL>::kSentinel) D = Sel(has, D, V(0));
+      const V mu = cx.CL(kTMu, body);  // (the table also carries the torso's)
+      // Jacobian columns of the contact point: dofs 0, 1 (slides), 2 (torso hinge), then the leg's hinges up to the body
+      V jn[kLV], jx[kLV];
+      jn[0] = V(0), jx[0] = V(1);
+      jn[1] = V(1), jx[1] = V(0);
+      jn[2] = -(cpx - p.px[0]), jx[2] = cpz - p.pz[0];
+      static_for<3, kLV>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const auto in = AtLeast(body, (unsigned)(j - 2));
+        jn[j] = Sel(in, -(cpx - p.px[j - 2]), V(0));
+        jx[j] = Sel(in, cpz - p.pz[j - 2], V(0));
+      });
+      // (the two slides' columns are the unit vectors: jn = (0, 1, ...), jx = (1, 0, ...); written out, because
+      // 0 x a[j] is an FMA the compiler must keep)
+      V jna = a[1], jxa = a[0];
+      static_for<2, kLV>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        jna += jn[j] * a[j];
+        jxa += jx[j] * a[j];
+      });
+      if constexpr (kHess) {  // the per-iteration pass: kept for the line search
+        if constexpr (Grp<KL>::kSentinel) {  // (every lane: the sentinel has cache entries of its own)
+          cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0, jna, LaneTypes<V>::True());
+          cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1, jxa, LaneTypes<V>::True());
+        } else {
+          cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 0, jna, has);
+          cx.LdsLStore(sl, Grp<KL>::kCachePerEnd, CacheBase<KL>() + 1, jxa, has);
+        }
+      }
+      // rows: 2 x (Jn), (Jn - mu Jx), (Jn + mu Jx); D == 0 for lanes not in contact, which zeroes every weight below
+      const V jar1 = jna - an;
+      const V jar2 = jna - mu * jxa - (an + ax);
+      const V jar3 = jna + mu * jxa - (an - ax);
+      const V w1 = Sel(jar1 < V(0), V(2) * D, V(0));
+      const V w2 = Sel(jar2 < V(0), D, V(0));
+      const V w3 = Sel(jar3 < V(0), D, V(0));
+      MaskSetNZ3(mask, w1, w2, w3, vbit);
+      vbit += 3;
+      const V gn = w1 * jar1 + w2 * jar2 + w3 * jar3;  // coefficient of Jn
+      const V gx = mu * (w3 * jar3 - w2 * jar2);      // coefficient of Jx
+      const V A = w1 + w2 + w3, Bc = mu * (w3 - w2), C = mu * mu * (w2 + w3);
+      // Unconditional (lanes whose rows are inactive add zeros).  Rounds 3-5 skipped the update when no lane of the wave
+      // had an active row in the visit; the branch made every accumulator -- 6 gradient and 21 Hessian doubles -- a
+      // value with two reaching definitions, and the compiler copied all 27 at the head of the slot loop and back at
+      // its end: 54 v_mov_b64 of the loop's 258 instructions.  HalfCheetah 4.13e8 -> 4.33e8, Walker2d +6 %, Hopper +6 %
+      // (profiles/r6i_lg_rowpass_ab.txt).
+      {
+        static_for<0, kLV>([&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          // dofs 0 and 1 (the slides): jn = 0, jx = 1 and jn = 1, jx = 0
+          if constexpr (i == 0) {
+            gc[0] += gx;
+          } else if constexpr (i == 1) {
+            gc[1] += gn;
+          } else {
+            gc[i] += jn[i] * gn + jx[i] * gx;
+          }
+          if constexpr (kHess) {
+            V ui, wi;
+            if constexpr (i == 0) {
+              ui = Bc, wi = C;
+            } else if constexpr (i == 1) {
+              ui = A, wi = Bc;
+            } else {
+              ui = A * jn[i] + Bc * jx[i], wi = Bc * jn[i] + C * jx[i];
+            }
+            static_for<i, kLV>([&](auto kc) {
+              constexpr int k = decltype(kc)::value;
+              if constexpr (k == 0) {
+                Hc[Tri(i, k)] += wi;
+              } else if constexpr (k == 1) {
+                Hc[Tri(i, k)] += ui;
+              } else {
+                Hc[Tri(i, k)] += ui * jn[k] + wi * jx[k];
+              }
+            });
+          }
+        });
+      }
+    } while (AnyWave(AnySlot(rem)));
+    return;
+  }
+  auto visit = [&](auto first_c) {
+    [[maybe_unused]] constexpr bool kInit = kPeel && decltype(first_c)::value;
     [[maybe_unused]] const auto has = AnySlot(rem);
     U sl;
     if constexpr (Grp<KL>::kSentinel) {
@@ -1107,7 +1251,15 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
           }
           static_for<i, kLV>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            if constexpr (k == 0) {
+            if constexpr (kInit && PeelInits(i, k)) {
+              if constexpr (k == 0) {
+                Hc[Tri(i, k)] = wi;
+              } else if constexpr (k == 1) {
+                Hc[Tri(i, k)] = ui;
+              } else {
+                Hc[Tri(i, k)] = ui * jn[k] + wi * jx[k];
+              }
+            } else if constexpr (k == 0) {
               Hc[Tri(i, k)] += wi;
             } else if constexpr (k == 1) {
               Hc[Tri(i, k)] += ui;
@@ -1118,7 +1270,16 @@ EPA_HD void RowsPass(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const Li
         }
       });
     }
-  } while (AnyWave(AnySlot(rem)));
+  };
+  if constexpr (kPeel) {
+    if (AnyWave(AnySlot(rem))) {
+      visit(std::true_type{});
+      if (!AnyWave(AnySlot(rem))) return;  // (guarded do-while again: see above)
+      do {
+        visit(std::false_type{});
+      } while (AnyWave(AnySlot(rem)));
+    }
+  }
 }
 
 // this lane's part of phi'(alpha), phi''(alpha) from its rows along `s` from `a`, and the lane's active-row mask
@@ -1390,6 +1551,10 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
   // and the gradient with (prev_mask = ~0, full_step false, prev_gn2 = -1), and `grad` is written for every env --
   // what the general trip computes at run time and finds to be all-true or all-false.  The fp64 operations of a live
   // env, their operands and their order are the general trip's.
+  // The pass over the rows writes H at its first visit (round 12, see RowsPass) in both bodies, on groups of two lanes.
+  // Not on the Hopper: its body-pair rows add to H in front of the visits, and its one body has no room for a second
+  // visit.  Not on groups of four lanes: peeled, the compiler fused other products there and the digests changed.
+  constexpr bool kPeelRows = KL == 2;
   auto trip = [&](auto first_c, const int it) -> bool {
     constexpr bool kFirst = decltype(first_c)::value;
     // A lane visits its own touching slots while its env is still LIVE (after the first trip of a forward pass a
@@ -1405,7 +1570,8 @@ EPA_HD V Solve(const CheetahModel<T>& m, Cx& cx, const Pos<V>& p, const LimitRow
     U mask = LT::Fill(0u);
     EPA_LG_TICK(cx, 3);
     EPA_LG_HOST_ROWS();
-    RowsPass<KL, true>(m, cx, p, lim, ends, vis, qacc, gc, H, mask);
+    RowsPass<KL, true, kPeelRows>(m, cx, p, lim, ends, vis, qacc, gc, H, mask);
+    EPA_LG_HOST_MASK(mask, H);
     // group sums: the torso entries collect every lane of the env, the leg entries the leg's lanes
     static_for<0, kLV>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
