@@ -21,7 +21,16 @@ index goes to the env as C <= 4 integer components.
     env = envpool.make("Minesweeper-v0", "gymnasium", num_envs=4096)
     actor = Actor.random(env, mask=True)      # obs:action_mask [10, 10]; the action is (row, col) = divmod(flat, 10)
     ro = env.rollout(horizon=32); ro.attach(actor, seed=1); ro.reset(); ro.collect()
-    tr = actor.trainer(); tr.fit(ro, epochs=4, batch=4096)           # the loss runs over the legal actions only"""
+    tr = actor.trainer(); tr.fit(ro, epochs=4, batch=4096)           # the loss runs over the legal actions only
+
+A MEMORY actor (csrc/actor_memory.hip.h is the contract) is an ordinary one behind a gated recurrent cell in the same
+integer arithmetic, for tasks whose observation does not hold the state: the cell turns the feature row and the env's
+state h, M bytes, into the state h' the trunk reads.  The collector keeps h per env and zeroes it where episodes end.
+
+    actor = Actor.random(env, hidden=64, memory=64)                  # MiniGrid's 7x7 view, a MuJoCo task without velocities
+    ro.attach(actor, seed=1); ro.reset(); ro.collect()
+    h0, h = ro.memory()                                              # the states slot 0 was evaluated with, and now
+    m = actor.module(); out = m.unroll(obs, h0, mask)                # BPTT in torch; Actor.from_module(m) comes back"""
 from __future__ import annotations
 
 from typing import Any, Sequence
@@ -35,6 +44,9 @@ VERSION = 1
 HEADER_BYTES = 36
 DISCRETE, BOX, MASKED = 0, 1, 2
 MAX_COMPONENTS, MAX_ACTIONS = 4, 127
+MEMORY_MAGIC = 0x4D415045  # "EPAM"
+MEMORY_HEADER_BYTES = 24
+MAX_SHIFT, MAX_BIAS = 24, 1 << 30
 
 
 def _nvec(nvec: Any, actions: int) -> np.ndarray:
@@ -109,14 +121,24 @@ def space_of(env_or_spec: Any, mask: Any = None) -> dict:
 class Actor:
     """`net`: the trunk and head, a `pgx.net.Net` of F inputs and H "actions"; `lo`, `scale`: float64 [F]; `sigma`,
     `low`, `high`: float32 [H] of a Box actor; `mask0`, `nvec`: the first mask component (-1: none) and the components'
-    sizes of a MASKED actor.  Everything the contract bounds is checked here (ValueError)."""
+    sizes of a MASKED actor.  `cell`: the two layers of a MEMORY actor's cell, ((Wz, bz, sz), (Wn, bn, sn)) with weights
+    int8 [M, F + M] over [x ; h], biases int32 [M] and shifts 0 .. 24; the net then has M inputs, lo and scale are the
+    F outer features', and `memory` is M (0 without a cell).  Everything the contract bounds is checked here
+    (ValueError)."""
 
     def __init__(self, net: Net, kind: int, lo: Any, scale: Any, sigma: Any = None, low: Any = None, high: Any = None,
-                 mask0: int = -1, nvec: Any = None):
+                 mask0: int = -1, nvec: Any = None, cell: Any = None):
         if kind not in (DISCRETE, BOX, MASKED):
             raise ValueError(f"actor: kind = {kind!r} must be 0 (discrete), 1 (box) or 2 (masked)")
         self.net, self.kind = net, int(kind)
         self.features, self.actions = net.inputs, net.actions
+        self.memory, self.cell = 0, None
+        if cell is not None:
+            self.memory, self.features = net.inputs, int(np.size(lo))
+            self.cell = self._check_cell(cell, self.features, self.memory)
+            if self.kind == MASKED:
+                raise ValueError("actor: a masked actor (kind 2) takes no memory: its mask indexes raw observation "
+                                 "components")
         self.mask0, self.nvec = int(mask0), _nvec(nvec, net.actions)           # nvec: padded to 4 with ones
         self.components = 1 if nvec is None else int(np.size(np.asarray(nvec)))  # C: the entries given
         if self.kind != MASKED and (self.mask0 != -1 or self.components != 1):
@@ -141,10 +163,37 @@ class Actor:
         if box and not (self.low <= self.high).all():
             raise ValueError("actor: low must not exceed high")
 
+    @staticmethod
+    def _check_cell(cell: Any, f: int, m: int) -> tuple:
+        if m % 32 or not 32 <= m <= 512 or not 1 <= f <= MAX_INPUTS:
+            raise ValueError(f"actor: memory = {m} must be a multiple of 32 in 32 .. 512 (F = {f} in 1 .. {MAX_INPUTS})")
+        out = []
+        for name, (w, b, shift) in zip(("Wz", "Wn"), cell):
+            w, b, shift = np.asarray(w), np.asarray(b), int(shift)
+            if w.shape != (m, f + m) or b.shape != (m,):
+                raise ValueError(f"actor: cell layer {name}: weights {w.shape} and bias {b.shape} must be "
+                                 f"({m}, {f + m}) and ({m},)")
+            if np.any(w != np.rint(w)) or np.any(np.abs(w.astype(np.int64)) > 127):
+                raise ValueError(f"actor: cell layer {name}: weights are -127 .. 127")
+            if np.any(np.abs(b.astype(np.int64)) > MAX_BIAS) or not 0 <= shift <= MAX_SHIFT:
+                raise ValueError(f"actor: cell layer {name}: |bias| <= 2^30 and shift 0 .. {MAX_SHIFT}")
+            out.append((np.ascontiguousarray(w, np.int8), np.ascontiguousarray(b, np.int32), shift))
+        return tuple(out)
+
     # -- the blob ------------------------------------------------------------------
     def blob(self) -> np.ndarray:
-        """The actor as the C ABI takes it (include/envpool_amd.h: epa_actor_begin): uint8, 4-byte aligned."""
+        """The actor as the C ABI takes it (include/envpool_amd.h: epa_actor_begin): uint8, 4-byte aligned.  A memory
+        actor: the EPAM wrapper around the inner actor's EPAA blob (F = M, lo 0, scale 1)."""
         n = self.net
+        if self.memory:
+            parts = [np.array([MEMORY_MAGIC, VERSION, self.features, self.memory, 0, 0], "<u4").tobytes(),
+                     self.lo.astype("<f8").tobytes(), self.scale.astype("<f8").tobytes()]
+            for w, b, shift in self.cell:
+                raw = w.tobytes()
+                parts += [raw, b"\0" * (-len(raw) % 4), b.astype("<i4").tobytes(), np.array([shift], "<i4").tobytes()]
+            inner = Actor(n, self.kind, np.zeros(self.memory), np.ones(self.memory), self.sigma, self.low, self.high)
+            parts.append(inner.blob().tobytes())
+            return np.frombuffer(b"".join(parts), np.uint8).copy()
         parts = [np.array([MAGIC, VERSION, self.features, self.actions, n.hidden, n.blocks, self.kind], "<u4").tobytes(),
                  np.array([n.scale_p, n.scale_v], "<f4").tobytes(), self.lo.astype("<f8").tobytes(),
                  self.scale.astype("<f8").tobytes()]
@@ -162,9 +211,11 @@ class Actor:
                   "net_scale": np.array([n.scale_p, n.scale_v], np.float32),
                   "shift": np.array([s for _, _, s in n.layers], np.int32), "lo": self.lo, "scale": self.scale,
                   "sigma": self.sigma, "low": self.low, "high": self.high, "mask0": np.int32(self.mask0),
-                  "nvec": self.nvec[:self.components]}
+                  "nvec": self.nvec[:self.components], "memory": np.int32(self.memory)}
         for i, (w, b, _) in enumerate(n.layers):
             arrays[f"w{i}"], arrays[f"b{i}"] = w, b
+        for name, (w, b, shift) in zip("zn", self.cell or ()):
+            arrays[f"cell_w{name}"], arrays[f"cell_b{name}"], arrays[f"cell_s{name}"] = w, b, np.int32(shift)
         with open(path, "wb") as f:  # (np.savez would add ".npz" to a bare name)
             np.savez(f, **arrays)
 
@@ -173,25 +224,36 @@ class Actor:
         with np.load(path) as z:
             blocks = int(z["blocks"])
             layers = [(z[f"w{i}"], z[f"b{i}"], int(z["shift"][i])) for i in range(2 * blocks + 2)]
-            net = Net((int(z["features"]),), int(z["actions"]), int(z["hidden"]), blocks, layers,
+            memory = int(z["memory"]) if "memory" in z.files else 0
+            net = Net((memory or int(z["features"]),), int(z["actions"]), int(z["hidden"]), blocks, layers,
                       float(z["net_scale"][0]), float(z["net_scale"][1]))
             masked = dict(mask0=int(z["mask0"]), nvec=z["nvec"]) if int(z["kind"]) == MASKED else {}
-            return cls(net, int(z["kind"]), z["lo"], z["scale"], z["sigma"], z["low"], z["high"], **masked)
+            cell = tuple((z[f"cell_w{g}"], z[f"cell_b{g}"], int(z[f"cell_s{g}"])) for g in "zn") if memory else None
+            return cls(net, int(z["kind"]), z["lo"], z["scale"], z["sigma"], z["low"], z["high"], cell=cell, **masked)
 
     @classmethod
     def random(cls, env_or_spec: Any, hidden: int = 64, blocks: int = 1, seed: int = 0, sigma: float = 0.5,
-               mask: Any = None) -> "Actor":
+               mask: Any = None, memory: int = 0) -> "Actor":
         """An actor for tests and first runs from numpy's PCG64(seed) (`Net.random`'s recipe, shifts for inputs that
         fill 0 .. 127).  lo / scale map an observation component's bounds onto 0 .. 127 where the spec gives finite
         ones no wider than 1e6, and -8 .. 8 elsewhere; `fit_features` replaces them by measured ones.  `mask`: as
-        `space_of`'s."""
+        `space_of`'s.  `memory` = M: a memory actor, whose trunk has M inputs behind a random cell (PCG64(seed + 1);
+        shifts that spread the gate and the candidate over their ranges)."""
         d = space_of(env_or_spec, mask)
         f, h = int(d["features"]), int(d["actions"])
+        if isinstance(memory, (bool, np.bool_)) or not isinstance(memory, (int, np.integer)) or memory < 0:
+            raise ValueError(f"actor: memory = {memory!r} must be an integer of at least 0")
+        f_net, cell = int(memory) or f, None
+        if memory:
+            rng = np.random.Generator(np.random.PCG64(seed + 1))
+            shift = min(MAX_SHIFT, int(round(np.log2(73.0 * np.sqrt(f + memory) * 74.0 / 40.0))))
+            cell = tuple((rng.integers(-127, 128, size=(memory, f + memory)).astype(np.int8),
+                          rng.integers(-1024, 1025, size=memory).astype(np.int32), shift) for _ in range(2))
         # (Net.random sizes the first shift for 0 / 1 inputs of density 1/4; bytes spread over 0 .. 127 are about
         # 2^7 larger)
-        net = Net.random((f,), h, hidden, blocks, seed)
+        net = Net.random((f_net,), h, hidden, blocks, seed)
         w, b, s = net.layers[0]
-        net = Net((f,), h, hidden, blocks, [(w, b, min(24, s + 7))] + net.layers[1:], net.scale_p, net.scale_v)
+        net = Net((f_net,), h, hidden, blocks, [(w, b, min(24, s + 7))] + net.layers[1:], net.scale_p, net.scale_v)
         lo, hi = np.asarray(d["obs_low"], np.float64), np.asarray(d["obs_high"], np.float64)
         with np.errstate(invalid="ignore", over="ignore"):
             span = hi - lo
@@ -199,7 +261,7 @@ class Actor:
         lo = np.where(ok, lo, -8.0)
         scale = 127.0 / np.where(ok, span, 16.0)
         masked = dict(mask0=d.get("mask0", -1), nvec=d.get("nvec")) if d["kind"] == MASKED else {}
-        return cls(net, d["kind"], lo, scale, np.full(h, sigma, np.float32), d["low"], d["high"], **masked)
+        return cls(net, d["kind"], lo, scale, np.full(h, sigma, np.float32), d["low"], d["high"], cell=cell, **masked)
 
     def fit_features(self, cnt: Any, s1: Any, s2: Any) -> "Actor":
         """lo and scale from a collector's moments (`ro.moments()`): mean +- 4 sigma of every component onto 0 .. 127.
@@ -233,7 +295,14 @@ class Actor:
         (several obs keys: concatenated along the flattened last axis in key order).  The trunk is `Net.module()`'s;
         sigma is a parameter.  `kernels` goes to the trunk (`Net.module(kernels=True)`: the training kernels for obs on
         a ROCm device); the features stay torch, and obs must not require grad.  `logp_of(logits, action)` is `logp`
-        from the logits of one `forward(obs)`, which then serves the value too: one pass through the trunk per step."""
+        from the logits of one `forward(obs)`, which then serves the value too: one pass through the trunk per step.
+        A MEMORY actor's module adds `cell(features, h) -> h'` (float64, the contract's integers, rounding passes
+        gradients straight through) and `unroll(obs [T, N, ...], h0 [N, M], mask [T, N]) -> (logits [T, N, H], value
+        [T, N], h [N, M])` under the state rule, for BPTT in torch; `integers`, `forward`, `logp`, `entropy` and
+        `value` take the state as `h=` (default: zeros).  It has no training kernels: `kernels=True` is a ValueError."""
+        if self.memory and kernels:
+            raise ValueError("actor: module(kernels=True) is not available for a memory actor: the training kernels "
+                             "have no cell; train by BPTT with module()")
         return _make_module(self, bool(kernels))
 
     def trainer(self, **options: Any) -> Any:
@@ -242,14 +311,22 @@ class Actor:
         entropy_weight=0.0, normalize_adv=True, train_sigma=True, clip=0.5, seed=0, max_rows=4096`."""
         from envpool_amd.actor_trainer import ActorTrainer
 
+        if self.memory:
+            raise ValueError("actor: trainer() is not available for a memory actor: the PPO trainer's kernels have no "
+                             "backward pass through time; train by BPTT with module()")
         return ActorTrainer(self, **options)
 
     @classmethod
     def from_module(cls, m: Any) -> "Actor":
         sigma = m.sigma.detach().cpu().numpy().astype(np.float32) if m.kind == BOX else None
         masked = dict(mask0=m.mask0, nvec=m.nvec) if m.kind == MASKED else {}
+        cell = None
+        if m.memory:
+            cell = tuple((np.clip(np.rint(w.detach().cpu().numpy()), -127, 127).astype(np.int8),
+                          np.clip(np.rint(b.detach().cpu().numpy()), -MAX_BIAS, MAX_BIAS).astype(np.int32), int(s))
+                         for w, b, s in zip(m.cell_weights, m.cell_biases, m.cell_shifts))
         return cls(Net.from_module(m.net), m.kind, m.lo.cpu().numpy(), m.scale.cpu().numpy(), sigma, m.low, m.high,
-                   **masked)
+                   cell=cell, **masked)
 
 
 def _make_module(actor: Actor, kernels: bool = False) -> Any:
@@ -265,6 +342,42 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             self.register_buffer("lo", torch.tensor(actor.lo))
             self.register_buffer("scale", torch.tensor(actor.scale))
             self.sigma = torch.nn.Parameter(torch.tensor(actor.sigma.astype(np.float32)))
+            self.memory = actor.memory
+            if actor.memory:
+                self.cell_shifts = [s for _, _, s in actor.cell]
+                self.cell_weights = torch.nn.ParameterList(
+                    [torch.nn.Parameter(torch.tensor(w.astype(np.float64))) for w, _, _ in actor.cell])
+                self.cell_biases = torch.nn.ParameterList(
+                    [torch.nn.Parameter(torch.tensor(b.astype(np.float64))) for _, b, _ in actor.cell])
+
+        def _cell_layer(self, i: int, v: Any) -> Any:
+            ste = self.net._ste
+            w = ste(self.cell_weights[i], torch.clamp(torch.round(self.cell_weights[i]), -127, 127))
+            b = ste(self.cell_biases[i], torch.round(self.cell_biases[i]))
+            z, s = v @ w.t() + b, self.cell_shifts[i]
+            return ste(z / 2.0 ** s, torch.floor((z + 2.0 ** (s - 1)) / 2.0 ** s)) if s else z
+
+        def cell(self, features: Any, h: Any) -> Any:
+            """h' float64 [rows, M] of the feature rows [rows, F] and the states h [rows, M]: the contract's integers."""
+            h = h.to(torch.float64)
+            v = torch.cat([features.to(torch.float64), h], dim=1)
+            z = torch.clamp(64.0 + self._cell_layer(0, v), 0, 128)
+            n = torch.clamp(self._cell_layer(1, v), 0, 127)
+            y = (z * h + (128.0 - z) * n + 64.0) / 128.0
+            return self.net._ste(y, torch.floor(y))
+
+        def unroll(self, obs: Any, h0: Any, mask: Any) -> tuple[Any, Any, Any]:
+            """(logits float32 [T, N, H], value float32 [T, N], h float64 [N, M]) of obs [T, N, ...] from the states h0
+            under the state rule: slot t is evaluated with the state as it is, and the state is zero after a slot
+            whose mask[t, n] is False."""
+            h, logits, values = h0.to(torch.float64), [], []
+            for t in range(obs.shape[0]):
+                h = self.cell(self.features(obs[t]), h)
+                p = self.net.integers(h).to(torch.float32)
+                logits.append(p[:, :self.actions] * torch.tensor(self.net.scale_p, dtype=torch.float32))
+                values.append(p[:, self.actions] * torch.tensor(self.net.scale_v, dtype=torch.float32))
+                h = h * mask[t].to(torch.float64).reshape(-1, 1)
+            return torch.stack(logits), torch.stack(values), h
 
         def features(self, obs: Any) -> Any:
             x = obs.reshape(obs.shape[0], -1).to(torch.float64)
@@ -272,17 +385,21 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             p = torch.where(torch.isfinite(p), p, torch.zeros_like(p))
             return p + (torch.clamp(torch.round(p), 0, 127) - p).detach()  # (torch.round: half to even)
 
-        def integers(self, obs: Any) -> Any:
-            return self.net.integers(self.features(obs))
+        def integers(self, obs: Any, h: Any = None) -> Any:
+            x = self.features(obs)
+            if self.memory:
+                zeros = torch.zeros((x.shape[0], self.memory), dtype=torch.float64, device=x.device)
+                x = self.cell(x, zeros if h is None else h)
+            return self.net.integers(x)
 
-        def forward(self, obs: Any) -> tuple[Any, Any]:
-            p = self.integers(obs).to(torch.float32)
+        def forward(self, obs: Any, h: Any = None) -> tuple[Any, Any]:
+            p = self.integers(obs, h).to(torch.float32)
             logits = p[:, :self.actions] * torch.tensor(self.net.scale_p, dtype=torch.float32)
             value = p[:, self.actions] * torch.tensor(self.net.scale_v, dtype=torch.float32)
             return logits, value
 
-        def value(self, obs: Any) -> Any:
-            return self.forward(obs)[1]
+        def value(self, obs: Any, h: Any = None) -> Any:
+            return self.forward(obs, h)[1]
 
         def legal(self, obs: Any) -> Any:
             """bool [rows, H] of a MASKED actor: the raw mask components of `obs` that are not 0; every action for a row
@@ -297,10 +414,10 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             """log-softmax over the legal actions, float64; -inf at the others."""
             return torch.log_softmax(logits.to(torch.float64).masked_fill(~legal, -torch.inf), dim=1)
 
-        def logp(self, obs: Any, action: Any) -> Any:
+        def logp(self, obs: Any, action: Any, h: Any = None) -> Any:
             """float64 [rows]: the log-probability (Box: the density) of `action` from the float32 logits.  MASKED:
             `action` is the flat index, or its [rows, C] components."""
-            return self.logp_of(self.forward(obs)[0], action, self.legal(obs) if self.kind == MASKED else None)
+            return self.logp_of(self.forward(obs, h)[0], action, self.legal(obs) if self.kind == MASKED else None)
 
         def logp_of(self, logits: Any, action: Any, legal: Any = None) -> Any:
             """`logp` from the logits of a `forward(obs)` the caller already has: one pass serves `logp` and value.
@@ -320,8 +437,8 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             z = (action.reshape(logits.shape).to(torch.float64) - logits) / sigma
             return (-0.5 * z * z - torch.log(sigma) - 0.9189385).sum(dim=1)
 
-        def entropy(self, obs: Any) -> Any:
-            logits = self.forward(obs)[0].to(torch.float64)
+        def entropy(self, obs: Any, h: Any = None) -> Any:
+            logits = self.forward(obs, h)[0].to(torch.float64)
             if self.kind == MASKED:
                 legal = self.legal(obs)
                 lp = self._masked(logits, legal).masked_fill(~legal, 0.0)  # (no -inf reaches a product)

@@ -726,7 +726,11 @@ class _ShardedPools:
         parts = self._record_all(lambda p: p.rollout_gae_stored(gamma, lam))
         return np.concatenate([a for a, _ in parts], axis=1), np.concatenate([b for _, b in parts], axis=1)
 
-    def actor_eval(self, obs: Any, env_ids: Any, step: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def actor_memory(self) -> tuple[np.ndarray, np.ndarray]:
+        parts = self._record_all(lambda p: p.actor_memory())
+        return np.concatenate([a for a, _ in parts], axis=0), np.concatenate([b for _, b in parts], axis=0)
+
+    def actor_eval(self, obs: Any, env_ids: Any, step: int, memory: Any = None) -> tuple:
         """Every row by the shard that holds its env."""
         obs = [obs] if isinstance(obs, np.ndarray) else [np.asarray(o) for o in obs]
         ids = np.ascontiguousarray(env_ids, np.int32).reshape(-1)
@@ -737,11 +741,17 @@ class _ShardedPools:
         p0 = self.pools[0]
         action = np.empty((len(ids), *p0.action_shape), dtype=p0.action_dtype)
         logp, value = np.empty(len(ids), np.float32), np.empty(len(ids), np.float32)
+        if memory is not None:
+            memory = np.ascontiguousarray(memory, np.uint8)
+            out = np.empty_like(memory)
         for s, p in enumerate(self.pools):
             idx = np.flatnonzero(shard == s)
-            if len(idx):
+            if len(idx) and memory is not None:
+                action[idx], logp[idx], value[idx], out[idx] = p.actor_eval([o[idx] for o in obs], ids[idx], step,
+                                                                            memory[idx])
+            elif len(idx):
                 action[idx], logp[idx], value[idx] = p.actor_eval([o[idx] for o in obs], ids[idx], step)
-        return action, logp, value
+        return (action, logp, value) if memory is None else (action, logp, value, out)
 
     # -- self-play driver: one driver per shard; the keys take global env ids, so the shards play the unsharded pool's
     # games --

@@ -1155,7 +1155,7 @@ class DevicePool:
         if getattr(self, "rollout_horizon", None) is not None:
             obs, act = self.rollout_row_bytes()
             native.check_rollout(self.rollout_horizon, self.rollout_capacity, False, self.num_envs, obs, act,
-                                 actor=True)
+                                 actor=True, memory=getattr(actor, "memory", 0))
         blob = actor.blob()
         low = np.ascontiguousarray(actor.low, np.float64)
         high = np.ascontiguousarray(actor.high, np.float64)
@@ -1173,10 +1173,11 @@ class DevicePool:
     def actor_end(self) -> None:
         native.check(self._lib.epa_actor_end(self._h))
 
-    def actor_eval(self, obs: Any, env_ids: Any, step: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def actor_eval(self, obs: Any, env_ids: Any, step: int, memory: Any = None) -> tuple:
         """(action, logp, value) of the attached actor on caller rows: `obs` one array per obs key (or the array, for a
         single key) with a row per listed global env id, at the collector step counter `step`.  Nothing of the pool
-        changes."""
+        changes.  A memory actor (csrc/actor_memory.hip.h) needs `memory`, the rows' state uint8 [rows, M], and returns
+        (action, logp, value, memory_out)."""
         keys = self.rollout_obs_keys()
         obs = [obs] if isinstance(obs, np.ndarray) else list(obs)
         ids = np.ascontiguousarray(env_ids, np.int32).reshape(-1)
@@ -1192,9 +1193,51 @@ class DevicePool:
         ptrs = (ctypes.c_void_p * len(rows))(*[o.ctypes.data for o in rows])
         action = np.empty((len(ids), *self.action_shape), dtype=self.action_dtype)
         logp, value = np.empty(len(ids), np.float32), np.empty(len(ids), np.float32)
+        if memory is not None:
+            m = self.actor_memory_width()
+            h = np.ascontiguousarray(memory, np.uint8)
+            if m == 0 or h.shape != (len(ids), m):
+                raise ValueError(f"actor eval: memory of shape {h.shape} for {(len(ids), m)}"
+                                 if m else "actor eval: the actor has no memory")
+            out = np.empty_like(h)
+            native.check(self._lib.epa_actor_eval_memory(self._h, ids.ctypes.data, len(ids), int(step), ptrs, len(rows),
+                                                         h.ctypes.data, action.ctypes.data, logp.ctypes.data,
+                                                         value.ctypes.data, out.ctypes.data))
+            return action, logp, value, out
         native.check(self._lib.epa_actor_eval(self._h, ids.ctypes.data, len(ids), int(step), ptrs, len(rows),
                                               action.ctypes.data, logp.ctypes.data, value.ctypes.data))
         return action, logp, value
+
+    def actor_eval_memory_device(self, d_obs: list[int], d_env_ids: int, k: int, step: int, d_memory_in: int,
+                                 d_action: int, d_logp: int, d_value: int, d_memory_out: int) -> None:
+        """`actor_eval` of a memory actor on raw device addresses (the states 16-byte aligned): only enqueued."""
+        ptrs = (ctypes.c_void_p * len(d_obs))(*d_obs)
+        native.check(self._lib.epa_actor_eval_memory_device(
+            self._h, ctypes.c_void_p(d_env_ids), int(k), int(step), ptrs, len(d_obs), ctypes.c_void_p(d_memory_in),
+            ctypes.c_void_p(d_action), ctypes.c_void_p(d_logp), ctypes.c_void_p(d_value), ctypes.c_void_p(d_memory_out)))
+
+    def actor_memory_width(self) -> int:
+        """M of the attached actor: 0 for one without memory."""
+        m = ctypes.c_int32()
+        native.check(self._lib.epa_actor_memory(self._h, ctypes.byref(m), None, None))
+        return int(m.value)
+
+    def actor_memory(self) -> tuple[np.ndarray, np.ndarray]:
+        """(h0, h) uint8 [N, M] of a memory actor, copied to the host: the state slot 0 of the current horizon was
+        evaluated with, and the current one."""
+        m = ctypes.c_int32()
+        native.check(self._lib.epa_actor_memory(self._h, ctypes.byref(m), None, None))
+        if m.value == 0:
+            raise ValueError("actor memory: the actor has no memory")
+        h0, h = np.empty((self.num_envs, m.value), np.uint8), np.empty((self.num_envs, m.value), np.uint8)
+        native.check(self._lib.epa_actor_memory(self._h, ctypes.byref(m), h0.ctypes.data, h.ctypes.data))
+        return h0, h
+
+    def actor_memory_view_device(self) -> tuple[int, int, int]:
+        """(the raw device addresses of h0 and h uint8 [N, M], M)."""
+        h0, h = ctypes.c_void_p(), ctypes.c_void_p()
+        native.check(self._lib.epa_actor_memory_view_device(self._h, ctypes.byref(h0), ctypes.byref(h)))
+        return int(h0.value), int(h.value), self.actor_memory_width()
 
     def actor_eval_device(self, d_obs: list[int], d_env_ids: int, k: int, step: int, d_action: int, d_logp: int,
                           d_value: int) -> None:

@@ -251,6 +251,10 @@ def lib() -> ctypes.CDLL:
         "epa_actor_eval_device": (i32, [vp, vp, i32, ctypes.c_int64, P(vp), i32, vp, vp, vp]),
         "epa_actor_view_device": (i32, [vp, P(vp), P(vp)]),
         "epa_actor_batch": (i32, [vp, vp, vp]),
+        "epa_actor_memory": (i32, [vp, P(i32), vp, vp]),
+        "epa_actor_memory_view_device": (i32, [vp, P(vp), P(vp)]),
+        "epa_actor_eval_memory": (i32, [vp, vp, i32, ctypes.c_int64, P(vp), i32, vp, vp, vp, vp, vp]),
+        "epa_actor_eval_memory_device": (i32, [vp, vp, i32, ctypes.c_int64, P(vp), i32, vp, vp, vp, vp, vp]),
         "epa_rollout_collect": (i32, [vp, i32]),
         "epa_rollout_collect_device": (i32, [vp, i32]),
         "epa_atari_post_create": (i32, [i32] * 8 + [P(vp)]),
@@ -306,6 +310,7 @@ EXPORTED_SYMBOLS = [
     "epa_rollout_counters", "epa_rollout_end",
     "epa_actor_begin", "epa_actor_shape", "epa_actor_end", "epa_actor_eval", "epa_actor_eval_device",
     "epa_actor_view_device", "epa_actor_batch", "epa_rollout_collect", "epa_rollout_collect_device",
+    "epa_actor_memory", "epa_actor_memory_view_device", "epa_actor_eval_memory", "epa_actor_eval_memory_device",
     "epa_selfplay_begin", "epa_selfplay_run", "epa_selfplay_run_device", "epa_selfplay_stats", "epa_selfplay_end",
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_selfplay_begin_ex", "epa_selfplay_noise",
@@ -421,14 +426,15 @@ def rollout_bytes(num_envs: int, horizon: int, episodes: int, obs_bytes: int, ac
 
 def check_rollout(horizon: Any, episodes: Any = 0, moments: Any = False, num_envs: int = 1, obs_bytes: int = 0,
                   action_bytes: int = 0, values: Any = None, gamma: Any = None, lam: Any = None,
-                  actor: bool = False) -> tuple:
+                  actor: bool = False, memory: int = 0) -> tuple:
     """A rollout collector's arguments after the checks every layer makes before the native call, with no device:
     ValueError for a horizon that is no integer of at least 1, episodes that is no integer of at least 0, a `moments`
     that is no bool, and buffers above the 2 GiB limit (`num_envs` envs of `obs_bytes` observation and `action_bytes`
     action bytes each).  With `values` (and `gamma`, `lam`) also gae's arguments: values must be a float32 array of
     shape [horizon + 1, num_envs], gamma and lam numbers in [0, 1].  Returns (horizon, episodes, moments), with values
     (horizon, episodes, moments, values, gamma, lam) -- gamma and lam rounded to float32.  `actor`: the limit also
-    counts the logp [T, N] and value [T + 1, N] float32 buffers an attached actor adds (csrc/actor.hip.h)."""
+    counts the logp [T, N] and value [T + 1, N] float32 buffers an attached actor adds (csrc/actor.hip.h), and the two
+    state arrays uint8 [N, memory] of a memory actor (csrc/actor_memory.hip.h)."""
     if isinstance(horizon, (bool, np.bool_)) or not isinstance(horizon, (int, np.integer)) or not 1 <= int(horizon) < 2**31:
         raise ValueError(f"rollout: horizon = {horizon!r} must be an integer of at least 1")
     if isinstance(episodes, (bool, np.bool_)) or not isinstance(episodes, (int, np.integer)) \
@@ -439,7 +445,7 @@ def check_rollout(horizon: Any, episodes: Any = 0, moments: Any = False, num_env
     horizon, episodes, moments = int(horizon), int(episodes), bool(moments)
     total = rollout_bytes(int(num_envs), horizon, episodes, int(obs_bytes), int(action_bytes))
     if actor:
-        total += 4 * horizon * int(num_envs) + 4 * (horizon + 1) * int(num_envs)
+        total += 4 * horizon * int(num_envs) + 4 * (horizon + 1) * int(num_envs) + 2 * int(num_envs) * int(memory)
     if total > ROLLOUT_MAX_BYTES:
         raise ValueError(f"rollout: {num_envs} envs over a horizon of {horizon} with {episodes} episode rows need "
                          f"{total} bytes, above the limit of 2 GiB")

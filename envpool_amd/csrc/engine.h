@@ -472,6 +472,21 @@ void ActorLaunchLegal(const ActorLegalArgs& a, hipStream_t s);
 void ActorLaunchFeatures(const actor::FeatureKeys& keys, const double* lo, const double* scale, int rows,
                          unsigned char* out, hipStream_t s);
 void ActorLaunchSample(const ActorSampleArgs& a, hipStream_t s);
+// The memory cell of a memory actor (actor_memory.hip; actor_memory.hip.h is the contract): x and the state h of `rows`
+// rows -> h' into `out`, the feature rows the trunk reads next, and into `h_out`
+struct ActorCellArgs {
+  int rows, F, M;
+  int shift_z, shift_n;
+  const char* image;            // the cell's weights as CellImage lays them out
+  const int32_t* bias_z;        // [M] each
+  const int32_t* bias_n;
+  const unsigned char* x;       // [rows][F], ActorLaunchFeatures' (the aligned dwords that cover it are read)
+  const unsigned char* h;       // [rows][M], 16-byte aligned
+  unsigned char* h_out;         // [rows][M], 16-byte aligned; may be h; null: nothing is committed
+  const unsigned char* reset;   // [rows] or null: a row whose byte is not 0 commits zeros
+  unsigned char* out;           // [rows][M], 16-byte aligned
+};
+void ActorLaunchCell(const ActorCellArgs& a, hipStream_t s);
 // The pair form (pgx_arena.hip.h).  NetPlanLaunch: PgxNetPlan, the stable partition of `rows` <= 2^20 rows by `side` u8
 // [rows] into order i32 [rows] and n0 i32 [1], with `counts` (NetPlanCountBytes(rows) bytes) as its scratch.
 // NetLaunchPair: one pair PgxNetEval, row r by net side[r] through that plan; both nets of one F and A.
@@ -1060,6 +1075,17 @@ class Pool {
                  void* action, void* logp, void* value);
   void ActorView(void** logp, void** value);  // the device arrays [T][N] and [T+1][N]
   void ActorBatch(float* logp, float* value);       // the same, whole, copied to the host
+  // A memory actor (actor_memory.hip.h): ActorBegin takes an EPAM blob as well, and the actor's block then also holds
+  // the cell's weights and two state arrays u8 [N][M]: h, the current state, and h0, the state slot 0 of the current
+  // horizon was evaluated with (RolloutNext copies h to h0; RolloutReset and ActorBegin zero both).  ActorShape's M is 0
+  // for an actor without memory.  ActorMemory: the two arrays as device addresses and / or copied to the host (null: not
+  // wanted).  ActorEvalMemory: ActorEval of a memory actor -- memory_in u8 [k][M] is the rows' state, memory_out gets
+  // h' -- which touches no state of the collector; the device form needs both 16-byte aligned.  ActorEval itself
+  // refuses a memory actor, and ActorEvalMemory one without memory.
+  int ActorMemoryWidth();
+  void ActorMemory(void** d_h0, void** d_h, void* h0, void* h);
+  void ActorEvalMemory(bool device, const int32_t* ids, int k, long long step, const void* const* obs, int n_obs,
+                       const void* memory_in, void* action, void* logp, void* value, void* memory_out);
   void RolloutCollect(int steps, bool device);
 
   // Self-play driver (include/envpool_amd.h: epa_selfplay_begin; the PGX board games, pgx_selfplay.hip.h): plays
@@ -1384,8 +1410,10 @@ class Pool {
     unsigned flags{0};
     uint64_t seed{0};
     // offsets into mem: the net image, lo, scale, sigma, low, high, the feature rows [N][F], the head's rows
-    // [N][H + 1], logp [T][N], value [T+1][N], the current step's legal words [N] (masked), the end
-    size_t off[12]{};
+    // [N][H + 1], logp [T][N], value [T+1][N], the current step's legal words [N] (masked), then a memory actor's: the
+    // cell's image, its biases bz and bn, the states h and h0 [N][M], the cell's rows [N][M] the trunk reads, the end
+    size_t off[18]{};
+    int M{0}, shift_z{0}, shift_n{0};  // a memory actor's cell (M = 0: none); F is then the cell's, the trunk's is M
     // masked: the components of the action row, and where the mask lies: obs key mask_key, from its element mask_first
     // (mask_key = -1: no mask)
     int C{1}, nvec[4]{1, 1, 1, 1}, mask_key{-1}, mask_first{0};
@@ -1394,9 +1422,20 @@ class Pool {
   void ActorFree();
   void ActorRequire(const char* what) const;     // throws without a collector or without an actor
   int ActorFeatures() const;                      // F of the pool: the components of the collector's obs keys
-  // enqueues features -> trunk -> sample for `rows` rows on stream_: obs key j's rows at src[j]
+  // where the cell of a memory actor reads and writes for one ActorEnqueue (ActorCellArgs' h, h_out, reset, out)
+  struct ActorCellIo {
+    const unsigned char* h;
+    unsigned char* h_out;
+    const unsigned char* reset;
+    unsigned char* rows;
+  };
+  // enqueues features -> (a memory actor: cell ->) trunk -> sample for `rows` rows on stream_: obs key j's rows at
+  // src[j]; `cell`: null for an actor without memory
   void ActorEnqueue(const char* const* src, int rows, const int32_t* d_env_id, long long step, bool value_only,
-                    unsigned char* features, int32_t* head, void* legal, void* action, float* logp, float* value);
+                    unsigned char* features, int32_t* head, void* legal, void* action, float* logp, float* value,
+                    const ActorCellIo* cell = nullptr);
+  void ActorEvalImpl(bool device, const int32_t* ids, int k, long long step, const void* const* obs, int n_obs,
+                     const void* memory_in, void* action, void* logp, void* value, void* memory_out);
   // the pool's self-play driver
   struct Selfplay {
     bool open{false};

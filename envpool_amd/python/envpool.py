@@ -261,19 +261,34 @@ class RolloutCollector:
             raise ValueError(f"rollout collect: steps = {steps!r} must be None or an integer of at least 1")
         self._open().rollout_collect(0 if steps is None else int(steps))
 
-    def actor_eval(self, obs: Any, env_ids: Any = None, step: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def actor_eval(self, obs: Any, env_ids: Any = None, step: Any = None, memory: Any = None) -> tuple:
         """(action, logp, value) of the attached actor on caller observations (the array of a single obs key, or a dict
         by state key name) for `env_ids` (default: the pool's, in order) at the step counter `step` (default: the
-        collector's): what `collect` would compute for these rows.  Nothing of the pool changes."""
+        collector's): what `collect` would compute for these rows.  Nothing of the pool changes.  A memory actor needs
+        `memory`, the rows' state uint8 [rows, M], and returns (action, logp, value, memory_out); the collector's own
+        states are neither read nor written."""
         if self._actor is None:
             raise ValueError("rollout actor_eval: the collector has no actor (attach one)")
+        if (getattr(self._actor, "memory", 0) != 0) != (memory is not None):
+            raise ValueError("rollout actor_eval: memory= is the state of a memory actor's rows: required with one, "
+                             "refused without")
         pool = self._open()
         arrays = [obs[n] for n in self._names] if isinstance(obs, dict) else [np.asarray(obs)]
         if env_ids is None:
             env_ids = self._env.all_env_ids
         if step is None:
             step = self.counters["steps"]
+        if memory is not None:
+            return pool.actor_eval(arrays, env_ids, int(step), memory)
         return pool.actor_eval(arrays, env_ids, int(step))
+
+    def memory(self) -> tuple[np.ndarray, np.ndarray]:
+        """(h0, h) uint8 [N, M] of an attached memory actor: the state slot 0 of the current horizon was evaluated with
+        (`next()` copies h to h0) and the current state.  A state is zero after `attach`, after `reset()` and after the
+        env's auto-reset step (`mask[t, n]` False)."""
+        if self._actor is None or getattr(self._actor, "memory", 0) == 0:
+            raise ValueError("rollout memory: the collector has no memory actor")
+        return self._open().actor_memory()
 
     def episodes(self) -> Episodes:
         return Episodes(*self._open().rollout_episodes())
@@ -292,7 +307,8 @@ class RolloutCollector:
         return m[0], m[1], m[2]
 
     def next(self) -> None:
-        """Slot t becomes slot 0 and t = 0; flags carried over, episode accumulators, episodes and moments are kept."""
+        """Slot t becomes slot 0 and t = 0; flags carried over, episode accumulators, episodes and moments are kept.  A
+        memory actor's h0 becomes its h."""
         self._open().rollout_next()
 
     def close(self) -> None:

@@ -691,10 +691,24 @@ def actor_view_device(pool: Any) -> tuple[Any, Any]:
             torch.as_tensor(_DevArray(value, (t + 1, n), np.float32), device=dev))
 
 
-def actor_eval_device(pool: Any, obs: Any, env_ids: Any, step: int) -> tuple[Any, Any, Any]:
+def actor_memory_view_device(pool: Any) -> tuple[Any, Any]:
+    """(h0, h) uint8 [N, M] of the attached memory actor as tensors that alias the collector's state arrays: the state
+    slot 0 of the current horizon was evaluated with, and the current one."""
+    import torch
+
+    dev = torch.device("cuda", pool.device)
+    h0, h, m = pool.actor_memory_view_device()
+    _order_both_ways(pool, dev, lambda: None)
+    return (torch.as_tensor(_DevArray(h0, (pool.num_envs, m), np.uint8), device=dev),
+            torch.as_tensor(_DevArray(h, (pool.num_envs, m), np.uint8), device=dev))
+
+
+def actor_eval_device(pool: Any, obs: Any, env_ids: Any, step: int, memory: Any = None) -> tuple:
     """`pool.actor_eval` on tensors of the pool's device: `obs` one contiguous tensor per obs key (or the tensor, for
     a single key) of the key's dtype with a row per env id, `env_ids` int32 [k] global ids.  Returns (action, logp,
-    value) tensors; only enqueued, ordered both ways with torch's current stream."""
+    value) tensors; only enqueued, ordered both ways with torch's current stream.  A memory actor needs `memory`, the
+    rows' state as a contiguous uint8 tensor [k, M] on the device (16-byte aligned, as torch allocates), and returns
+    (action, logp, value, memory_out)."""
     import torch
 
     dev = torch.device("cuda", pool.device)
@@ -714,6 +728,16 @@ def actor_eval_device(pool: Any, obs: Any, env_ids: Any, step: int) -> tuple[Any
     action = torch.empty((k, *pool.action_shape), dtype=_torch_dtype(pool.action_dtype), device=dev)
     logp = torch.empty((k,), dtype=torch.float32, device=dev)
     value = torch.empty((k,), dtype=torch.float32, device=dev)
+    if memory is not None:
+        if memory.dtype != torch.uint8 or not memory.is_contiguous() or memory.device != dev \
+                or tuple(memory.shape) != (k, pool.actor_memory_width()):
+            raise ValueError(f"actor_eval_device: memory must be a contiguous uint8 tensor of "
+                             f"[{k}, {pool.actor_memory_width()}] on {dev}")
+        out = torch.empty_like(memory)
+        _order_both_ways(pool, dev, lambda: pool.actor_eval_memory_device(
+            [o.data_ptr() for o in obs], env_ids.data_ptr(), k, int(step), memory.data_ptr(), action.data_ptr(),
+            logp.data_ptr(), value.data_ptr(), out.data_ptr()))
+        return action, logp, value, out
     _order_both_ways(pool, dev, lambda: pool.actor_eval_device([o.data_ptr() for o in obs], env_ids.data_ptr(), k,
                                                                int(step), action.data_ptr(), logp.data_ptr(),
                                                                value.data_ptr()))

@@ -1186,7 +1186,20 @@ int epa_rollout_end(epa_pool* pool);
  *     `step`: the action rows of the pool's action dtype, logp and value float32 [k].  Nothing of the pool changes.
  *   epa_actor_view_device(logp, value): the device arrays.  epa_actor_batch(logp, value): copied whole to the host
  *     (NULL skips one).  epa_rollout_gae with values == NULL takes the stored values.
- *   epa_actor_end(): releases the actor. */
+ *   epa_actor_end(): releases the actor.
+ * A MEMORY ACTOR (csrc/actor_memory.hip.h is the contract): epa_actor_begin also takes a blob of magic "EPAM" -- version
+ * 1, F, M, two zero words, lo[F], scale[F] float64, the layers Wz and Wn of a gated recurrent cell (int8 [M][F + M]
+ * padded to 4 bytes, bias int32 [M], shift int32 each), then a complete EPAA blob of F = M, kind 0 or 1 -- whose cell
+ * turns the feature row and the env's state h, M bytes, into the state h' the inner actor reads as its features.  The
+ * collector then keeps two arrays u8 [N][M], counted in EPA_ROLLOUT_MAX_BYTES: h, the current state, and h0, the state
+ * slot 0 of the current horizon was evaluated with (epa_rollout_next copies h to h0).  A state is zero after
+ * epa_actor_begin, after epa_rollout_reset and after an env's auto-reset step.
+ *   epa_actor_memory(m, h0, h): *m = M, 0 for an actor without memory; h0 / h (NULL: not wanted) receive the arrays.
+ *   epa_actor_memory_view_device(h0, h): the device arrays.
+ *   epa_actor_eval_memory(env_ids, k, step, obs, n_obs, memory_in, action, logp, value, memory_out) / _device:
+ *     epa_actor_eval for a memory actor, with the rows' state memory_in u8 [k][M] -> memory_out (device: both 16-byte
+ *     aligned).  No state of the collector changes.  epa_actor_eval refuses a memory actor (EPA_ERR_INVALID), and these
+ *     an actor without memory. */
 #define EPA_ACTOR_DETERMINISTIC 1u
 #define EPA_ACTOR_DISCRETE 0
 #define EPA_ACTOR_BOX 1
@@ -1201,6 +1214,14 @@ int epa_actor_eval_device(epa_pool* pool, const void* d_env_ids, int32_t k, int6
                           int32_t n_obs, void* d_action, void* d_logp, void* d_value);
 int epa_actor_view_device(epa_pool* pool, void** logp, void** value);
 int epa_actor_batch(epa_pool* pool, float* logp, float* value);
+int epa_actor_memory(epa_pool* pool, int32_t* m, void* h0, void* h);
+int epa_actor_memory_view_device(epa_pool* pool, void** h0, void** h);
+int epa_actor_eval_memory(epa_pool* pool, const int32_t* env_ids, int32_t k, int64_t step, const void* const* obs,
+                          int32_t n_obs, const void* memory_in, void* action, float* logp, float* value,
+                          void* memory_out);
+int epa_actor_eval_memory_device(epa_pool* pool, const void* d_env_ids, int32_t k, int64_t step,
+                                 const void* const* d_obs, int32_t n_obs, const void* d_memory_in, void* d_action,
+                                 void* d_logp, void* d_value, void* d_memory_out);
 int epa_rollout_collect(epa_pool* pool, int32_t steps);
 int epa_rollout_collect_device(epa_pool* pool, int32_t steps);
 

@@ -10,7 +10,9 @@ and prints one JSON line per env: env-steps/s of both (median of `--repeats` win
 two paths alternating, every window ending in a device synchronise) and their spread.  `--check` compares the device's
 head with the twin's through a deterministic actor, all H + 1 integers of it (see `check`).  `--collect-only` runs the
 collect windows alone: the run to put under a kernel trace for the device time of ActorFeatures, PgxNetEval and
-ActorSample."""
+ActorSample.  `--memory M` attaches a memory actor (csrc/actor_memory.hip.h) of M state bytes to the collect path, which
+then launches ActorMemoryCell between the features and the trunk; the Python loop has no such policy, so it implies
+`--collect-only`."""
 import argparse
 import json
 import os
@@ -29,13 +31,13 @@ from envpool_amd.actor import BOX, Actor  # noqa: E402
 
 
 class Collect:
-    def __init__(self, task, n, horizon, seed, hidden, blocks):
+    def __init__(self, task, n, horizon, seed, hidden, blocks, memory=0):
         self.env = envpool.make(task, "gymnasium", num_envs=n, seed=seed)
         self.pool = self.env.device_pool
         self.dev = torch.device("cuda", self.pool.device)
         self.T = horizon
         self.ro = self.env.rollout(horizon=horizon, episodes=1 << 16)
-        self.actor = Actor.random(self.env, hidden=hidden, blocks=blocks, seed=seed)
+        self.actor = Actor.random(self.env, hidden=hidden, blocks=blocks, seed=seed, memory=memory)
         self.ro.attach(self.actor, seed=seed)
         self.out = (torch.empty((horizon, n), dtype=torch.float32, device=self.dev),
                     torch.empty((horizon, n), dtype=torch.float32, device=self.dev))
@@ -155,12 +157,14 @@ def main():
     ap.add_argument("--tasks", default="CartPole-v1,HalfCheetah-v4")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--collect-only", action="store_true")
+    ap.add_argument("--memory", type=int, default=0, help="M of a memory actor on the collect path (0: none)")
     args = ap.parse_args()
+    args.collect_only = args.collect_only or args.memory != 0
     if not torch.cuda.is_available():
         raise SystemExit("bench_collect: no GPU; there is nothing to measure without one")
     for task in args.tasks.split(","):
         n, T = args.num_envs, args.horizon
-        col = Collect(task, n, T, 1, args.hidden, args.blocks)
+        col = Collect(task, n, T, 1, args.hidden, args.blocks, args.memory)
         dev = col.dev
         base = None if args.collect_only else Loop(task, n, T, 1, args.hidden, args.blocks)
         if args.check:
@@ -180,7 +184,7 @@ def main():
             return {"median": steps / float(np.median(ts)), "min": steps / max(ts), "max": steps / min(ts)}
 
         line = {"task": task, "num_envs": n, "horizon": T, "hidden": args.hidden, "blocks": args.blocks,
-                "unit": "env-steps/s", "collect": rate(tc)}
+                "memory": args.memory, "unit": "env-steps/s", "collect": rate(tc)}
         if base is not None:
             line["loop"] = rate(tb)
             line["collect_over_loop"] = line["collect"]["median"] / line["loop"]["median"]
