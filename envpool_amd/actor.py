@@ -30,7 +30,8 @@ state h, M bytes, into the state h' the trunk reads.  The collector keeps h per 
     actor = Actor.random(env, hidden=64, memory=64)                  # MiniGrid's 7x7 view, a MuJoCo task without velocities
     ro.attach(actor, seed=1); ro.reset(); ro.collect()
     h0, h = ro.memory()                                              # the states slot 0 was evaluated with, and now
-    m = actor.module(); out = m.unroll(obs, h0, mask)                # BPTT in torch; Actor.from_module(m) comes back"""
+    m = actor.module(); out = m.unroll(obs, h0, mask)                # BPTT in torch; Actor.from_module(m) comes back
+    m = m.to("cuda"); out = m.unroll(obs, h0, mask, kernels=True)    # BPTT in the training kernels"""
 from __future__ import annotations
 
 from typing import Any, Sequence
@@ -299,7 +300,8 @@ class Actor:
         A MEMORY actor's module adds `cell(features, h) -> h'` (float64, the contract's integers, rounding passes
         gradients straight through) and `unroll(obs [T, N, ...], h0 [N, M], mask [T, N]) -> (logits [T, N, H], value
         [T, N], h [N, M])` under the state rule, for BPTT in torch; `integers`, `forward`, `logp`, `entropy` and
-        `value` take the state as `h=` (default: zeros).  It has no training kernels: `kernels=True` is a ValueError."""
+        `value` take the state as `h=` (default: zeros).  `module(kernels=True)` is a ValueError for it: its training
+        kernels are a per-call switch, `unroll(obs, h0, mask, kernels=True)` (actor_memory_train.py)."""
         if self.memory and kernels:
             raise ValueError("actor: module(kernels=True) is not available for a memory actor: the training kernels "
                              "have no cell; train by BPTT with module()")
@@ -366,10 +368,31 @@ def _make_module(actor: Actor, kernels: bool = False) -> Any:
             y = (z * h + (128.0 - z) * n + 64.0) / 128.0
             return self.net._ste(y, torch.floor(y))
 
-        def unroll(self, obs: Any, h0: Any, mask: Any) -> tuple[Any, Any, Any]:
+        def unroll(self, obs: Any, h0: Any, mask: Any, kernels: bool = False) -> tuple[Any, Any, Any]:
             """(logits float32 [T, N, H], value float32 [T, N], h float64 [N, M]) of obs [T, N, ...] from the states h0
             under the state rule: slot t is evaluated with the state as it is, and the state is zero after a slot
-            whose mask[t, n] is False."""
+            whose mask[t, n] is False.  `kernels=True`: for obs on a ROCm device the cell's unroll, the trunk and the
+            backward through time are the training kernels (csrc/actor_memory_train.hip.h: the same integers, every
+            gradient within 2.6e-4 per step of depth of this code's); the features stay torch, obs must not require
+            grad, T N is at most 2^20 and the parameters, h0 and mask are on obs's device (ValueError).  On CPU
+            tensors it is this code."""
+            if kernels:
+                from envpool_amd import actor_memory_train
+
+                if obs.requires_grad:
+                    raise ValueError("actor: kernels=True computes no gradient for the observation; obs must not "
+                                     "require grad")
+                if self.cell_weights[0].device != obs.device:
+                    raise ValueError(f"actor: the parameters are on {self.cell_weights[0].device} and obs on "
+                                     f"{obs.device}; move the module to obs's device")
+                if obs.is_cuda:
+                    t, n = int(obs.shape[0]), int(obs.shape[1])
+                    x8 = torch.round(self.features(obs.reshape((t * n,) + tuple(obs.shape[2:]))))
+                    x8 = x8.to(torch.uint8).reshape(t, n, -1)
+                    p, h = actor_memory_train.unroll_integers(self, x8, h0, mask)
+                    p = p.to(torch.float32).reshape(t, n, -1)
+                    return (p[:, :, :self.actions] * torch.tensor(self.net.scale_p, dtype=torch.float32),
+                            p[:, :, self.actions] * torch.tensor(self.net.scale_v, dtype=torch.float32), h)
             h, logits, values = h0.to(torch.float64), [], []
             for t in range(obs.shape[0]):
                 h = self.cell(self.features(obs[t]), h)

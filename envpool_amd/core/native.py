@@ -191,6 +191,11 @@ def lib() -> ctypes.CDLL:
         "epa_net_train_destroy": (i32, [vp]),
         "epa_net_train_forward_device": (i32, [vp, vp, i32, P(vp), P(vp), P(i32), vp, vp]),
         "epa_net_train_backward_device": (i32, [vp, vp, i32, vp, P(vp), P(vp)]),
+        "epa_net_train_input_grad_device": (i32, [vp, vp, i32, vp]),
+        "epa_cell_train_create": (i32, [i32, i32, i32, i32, ctypes.c_int64, P(vp)]),
+        "epa_cell_train_destroy": (i32, [vp]),
+        "epa_cell_train_forward_device": (i32, [vp, vp, i32, i32, P(vp), P(vp), P(i32), vp, vp, vp, vp, vp]),
+        "epa_cell_train_backward_device": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         "epa_conv_train_create": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_int64, P(vp)]),
         "epa_conv_train_destroy": (i32, [vp]),
         "epa_conv_train_forward_device": (i32, [vp, vp, i32, P(vp), P(vp), P(i32), vp, vp]),
@@ -315,6 +320,9 @@ EXPORTED_SYMBOLS = [
     "epa_net_eval_pair", "epa_net_eval_pair_device", "epa_arena_begin", "epa_arena_stats",
     "epa_selfplay_begin_ex", "epa_selfplay_noise",
     "epa_net_train_create", "epa_net_train_destroy", "epa_net_train_forward_device", "epa_net_train_backward_device",
+    "epa_net_train_input_grad_device",
+    "epa_cell_train_create", "epa_cell_train_destroy", "epa_cell_train_forward_device",
+    "epa_cell_train_backward_device",
     "epa_conv_train_create", "epa_conv_train_destroy", "epa_conv_train_forward_device",
     "epa_conv_train_backward_device",
     "epa_trainer_create", "epa_trainer_destroy", "epa_trainer_step_device", "epa_trainer_fit_device",

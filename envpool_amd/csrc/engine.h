@@ -572,11 +572,15 @@ class NetTrain {
   // d_dp float32 [rows][A + 1] -> d_dw[i] float32 [N][K], d_db[i] float32 [N], through the last Forward's activations:
   // std::invalid_argument when there was none or it had other rows.
   void Backward(hipStream_t stream, int rows, const void* d_dp, void* const* d_dw, void* const* d_db);
+  // d_dx float32 [rows][F] = dz W of layer 0, from the split dz the last Backward left: std::invalid_argument when
+  // there was none since the last Forward or it had other rows.
+  void InputGrad(hipStream_t stream, int rows, void* d_dx);
 
  private:
   struct Layout;
   int device_, F_, A_, D_, L_, max_rows_;
   int rows_{0};  // of the last Forward; 0: none
+  int back_rows_{0};  // of the last Backward since; 0: none
   int32_t shift_[kNetImageLayers]{};
   std::unique_ptr<Layout> at_;
   DeviceBlock mem_;
@@ -590,6 +594,38 @@ void TrainSplitLaunch(const float* dp, int rows, int N, int n16, uint32_t* out, 
 void TrainReduceLaunch(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
                        float* dw, float* db, hipStream_t stream);
 void TrainSumLaunch(const float* ws, int slices, int N, int K, float* dw, float* db, hipStream_t stream);
+// TrainReduceLaunch whose dw has rows of `ldw` >= K floats: the K columns of a wider matrix
+void TrainReduceLaunchLd(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
+                         float* dw, int ldw, float* db, hipStream_t stream);
+
+// The training handle of a memory actor's cell (epa_cell_train_create; actor_memory_train.hip.h is the contract,
+// actor_memory_train.hip the kernels), beside the trunk's NetTrain.  Its ONE device allocation, sized at creation for
+// `max_rows` = T N, holds the cell's weights in the kernels' two layouts, copies of x and the mask, the input states and the two
+// saved planes (max_rows * M bytes each), the split da (max_rows * 2 M words) and the slice workspace.  The calls only enqueue on
+// the caller's stream; calls on one handle are the caller's to serialise.
+class CellTrain {
+ public:
+  CellTrain(int device, int F, int M, int kind, long long max_rows);
+  ~CellTrain();
+  // d_w[g] int8 [M][F + M], d_b[g] int32 [M] on the device, shifts[g] on the host, g = 0 the gate's and 1 the
+  // candidate's; d_x bytes [T][N][F], d_h0 bytes [N][M], d_mask bytes [T][N]; d_hp bytes [T][N][M] and d_h bytes
+  // [N][M], both 16-byte aligned.  std::invalid_argument before any launch for what the contract refuses.
+  void Forward(hipStream_t stream, int T, int N, const void* const* d_w, const void* const* d_b, const int32_t* shifts,
+               const void* d_x, const void* d_h0, const void* d_mask, void* d_hp, void* d_h);
+  // d_dhp float32 [T][N][M], d_dh float32 [N][M] or null -> d_dw float32 [2][M][F + M], d_db float32 [2][M], d_dh0
+  // float32 [N][M], through the last Forward (whose x and mask the handle kept): std::invalid_argument when there was
+  // none or it had another T or N.
+  void Backward(hipStream_t stream, int T, int N, const void* d_dhp, const void* d_dh, void* d_dw, void* d_db,
+                void* d_dh0);
+
+ private:
+  struct Layout;
+  int device_, F_, M_, max_rows_;
+  int T_{0}, N_{0};  // of the last Forward; 0: none
+  int32_t shift_[2]{};
+  std::unique_ptr<Layout> at_;
+  DeviceBlock mem_;
+};
 
 // The training handle of the convolutional network (epa_conv_train_create; pgx_conv_train.hip.h is the contract,
 // pgx_conv_train.hip the kernels), as NetTrain is the dense one's.  Its ONE device allocation holds the weights in the

@@ -3,8 +3,9 @@
 //
 // TrainPack, once per forward: the caller's quantised weights, int8 [N][K] row-major on the device, into the two forms
 //   the other kernels read -- the 1 KiB (output tile, k-step) fragments of PgxNetEval with the bias padded to whole
-//   tiles, and for every layer but the trunk the transpose as bf16 [K][N16] (N16 = N up to a multiple of 16, zeros
-//   behind N; an int8 is exact in bf16), in which a B fragment of dx = dz W is one 128-bit load.
+//   tiles, and the transpose as bf16 [K32][N16] (N16 = N up to a multiple of 16, K32 = K up to a multiple of 32, which
+//   only the trunk's F can be short of; zeros behind N and K; an int8 is exact in bf16), in which a B fragment of
+//   dx = dz W is one 128-bit load.
 // TrainForward: PgxNetEval's tiling -- one wave per block and 64 rows as two 32-column tiles, the weights as the A
 //   operand of v_mfma_i32_32x32x32_i8, a lane's packed result the next layer's B fragment, activations in LDS slots only
 //   their lane touches.  After every layer the lane stores its four result words, with bit 7 of a byte set where the
@@ -20,6 +21,8 @@
 //   (reg & 3) + 8 (reg >> 2) + 4 hh in register reg: the epilogue adds the residual branch (the split dz of the
 //   block's second layer times 2^s, read before the same lane overwrites it: the kernel may run in place), applies the
 //   saved mask bit and the 2^-s of the layer below, and stores the split result, 128 bytes of a row per register.
+//   TrainBackRow<T, true> is the same product for layer 0 (NetTrain::InputGrad): the column tiles cover F, and the
+//   epilogue stores the float32 sums of the columns below F as they are.
 // TrainReduce: dW = dz^T x and db.  Grid (K tile of 64, N tile of 64, row slice), four waves, one 32 x 32 tile each.
 //   Both operands need the row as the k index, so 64 rows at a time go through LDS transposed: dz as two bf16 planes
 //   [n][row], x as bf16 [k][row] (a saved byte less its bit 7), rows of 72 elements so that a fragment is one aligned
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void TrainPack(PackArgs a) {
   const int i = blockIdx.y;
   const int N = a.n_out[i], K = a.k_in[i];
   const int n_tiles = (N + 31) / 32, k_tiles = (K + 31) / 32, n16 = (N + 15) / 16 * 16;
-  const int frag_bytes = n_tiles * k_tiles * 1024, bias_words = n_tiles * 32, wt_elems = i == 0 ? 0 : K * n16;
+  const int frag_bytes = n_tiles * k_tiles * 1024, bias_words = n_tiles * 32, wt_elems = 32 * k_tiles * n16;
   const signed char* __restrict__ w = a.w[i];
   for (int q = blockIdx.x * 256 + threadIdx.x; q < frag_bytes + bias_words + wt_elems; q += gridDim.x * 256) {
     if (q < frag_bytes) {
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(256) void TrainPack(PackArgs a) {
       reinterpret_cast<int32_t*>(a.image + a.b_off[i])[n] = n < N ? a.b[i][n] : 0;
     } else {
       const int t = q - frag_bytes - bias_words, k = t / n16, n = t - k * n16;
-      const float v = n < N ? (float)w[(size_t)n * K + k] : 0.0f;
+      const float v = n < N && k < K ? (float)w[(size_t)n * K + k] : 0.0f;
       a.wt[a.wt_off[i] + t] = (uint16_t)((uint32_t)pgx::NetFloatBits(v) >> 16);  // (7 bits: exact)
     }
   }
@@ -266,12 +269,13 @@ struct RowArgs {
   const unsigned char* flags;  // [rows][D]: the saved bytes of the activation below
   float out_scale;         // 2^-s of the layer that made it
   uint32_t* out;           // [rows][D] split
+  float* dx;               // kIn: [rows][D] float32 in place of res, flags and out; D is then any width, wt [D32][n16]
 };
 
-template <int T>
+template <int T, bool kIn>
 __global__ __launch_bounds__(256) void TrainBackRow(RowArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, hh = lane >> 5;
-  const int row0 = (int)blockIdx.x * 64, tiles = a.D / 32;
+  const int row0 = (int)blockIdx.x * 64, tiles = (a.D + 31) / 32;
   v16f acc[T][2];
 #pragma unroll
   for (int t = 0; t < T; ++t) {
@@ -316,6 +320,10 @@ __global__ __launch_bounds__(256) void TrainBackRow(RowArgs a) {
         if (row >= a.rows) continue;
         const size_t at = (size_t)row * a.D + 32 * kt + c;
         float g = acc[t][rt][reg];
+        if constexpr (kIn) {
+          if (32 * kt + c < a.D) a.dx[at] = g;
+          continue;
+        }
         if (a.res != nullptr) g = g + pgx::TrainJoin(a.res[at]) * a.res_scale;
         a.out[at] = pgx::TrainSplit((a.flags[at] & 128) != 0 ? 0.0f : g * a.out_scale);
       }
@@ -426,14 +434,14 @@ __global__ __launch_bounds__(256) void TrainReduce(RedArgs a) {
 }
 
 __global__ __launch_bounds__(256) void TrainSum(const float* __restrict__ ws, int slices, int N, int K,
-                                                 float* __restrict__ dw, float* __restrict__ db) {
+                                                 float* __restrict__ dw, int ldw, float* __restrict__ db) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= N * (K + 1)) return;
   float s = 0.0f;
   for (int i = 0; i < slices; ++i) s = s + ws[(size_t)i * N * (K + 1) + q];
   const int n = q / (K + 1), k = q - n * (K + 1);
   if (k < K) {
-    dw[(size_t)n * K + k] = s;
+    dw[(size_t)n * ldw + k] = s;
   } else {
     db[n] = s;
   }
@@ -453,14 +461,19 @@ void TrainSplitLaunch(const float* dp, int rows, int N, int n16, uint32_t* out, 
 
 void TrainReduceLaunch(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
                        float* dw, float* db, hipStream_t stream) {
+  TrainReduceLaunchLd(rows, N, K, dz, ldn, x, ws, dw, K, db, stream);
+}
+
+void TrainReduceLaunchLd(int rows, int N, int K, const uint32_t* dz, int ldn, const unsigned char* x, float* ws,
+                         float* dw, int ldw, float* db, hipStream_t stream) {
   const pgx::TrainSlicing s = pgx::TrainSlices(rows, N, K);
   RedArgs r{rows, N, K, dz, ldn, x, s.slice_rows, ws};
   hipLaunchKernelGGL(TrainReduce, dim3((K + 63) / 64, (N + 63) / 64, s.slices), dim3(256), 0, stream, r);
-  TrainSumLaunch(ws, s.slices, N, K, dw, db, stream);
+  hipLaunchKernelGGL(TrainSum, dim3((N * (K + 1) + 255) / 256), dim3(256), 0, stream, ws, s.slices, N, K, dw, ldw, db);
 }
 
 void TrainSumLaunch(const float* ws, int slices, int N, int K, float* dw, float* db, hipStream_t stream) {
-  hipLaunchKernelGGL(TrainSum, dim3((N * (K + 1) + 255) / 256), dim3(256), 0, stream, ws, slices, N, K, dw, db);
+  hipLaunchKernelGGL(TrainSum, dim3((N * (K + 1) + 255) / 256), dim3(256), 0, stream, ws, slices, N, K, dw, K, db);
 }
 
 // ---------------------------------------------------------------------------
@@ -488,7 +501,7 @@ NetTrain::NetTrain(int device, int F, int A, int D, int L, long long max_rows)
     const size_t n_tiles = (N + 31) / 32, k_tiles = (K + 31) / 32;
     at_->w_off[i] = (uint32_t)image, image += n_tiles * k_tiles * 1024;
     at_->b_off[i] = (uint32_t)image, image += n_tiles * 32 * 4;
-    at_->wt_off[i] = (uint32_t)wt, wt += i == 0 ? 0 : K * ((N + 15) / 16 * 16);
+    at_->wt_off[i] = (uint32_t)wt, wt += 32 * k_tiles * ((N + 15) / 16 * 16);
     ws = std::max(ws, (size_t)pgx::TrainMostSlices(max_rows_, (int)N, (int)K) * N * (K + 1) * 4);
   }
   const size_t rows = (size_t)max_rows_, n16 = ((size_t)A + 1 + 15) / 16 * 16;
@@ -558,7 +571,7 @@ void NetTrain::Forward(hipStream_t stream, int rows, const void* const* d_w, con
   int before = 0;
   EPA_HIP(hipGetDevice(&before));
   EPA_HIP(hipSetDevice(device_));
-  rows_ = 0;  // (a forward that fails leaves nothing to go back through)
+  rows_ = back_rows_ = 0;  // (a forward that fails leaves nothing to go back through)
   hipLaunchKernelGGL(TrainPack, dim3(64, layers), dim3(256), 0, stream, pack);
   unsigned char* x = reinterpret_cast<unsigned char*>(mem_.p + at_->x);
   const hipError_t copied = hipMemcpyAsync(x, d_x, (size_t)rows * F_, hipMemcpyDeviceToDevice, stream);
@@ -610,16 +623,16 @@ void NetTrain::Backward(hipStream_t stream, int rows, const void* d_dp, void* co
   auto below = [&](int i, const uint32_t* dz, int ldn, int width, const uint32_t* res, int res_layer, uint32_t* out) {
     RowArgs r{rows, D_, dz, ldn, width, wt + at_->wt_off[i], res,
               res != nullptr ? (float)(1 << shift_[res_layer]) : 0.0f, activation(i - 1),
-              1.0f / (float)(1 << shift_[i - 1]), out};
+              1.0f / (float)(1 << shift_[i - 1]), out, nullptr};
     const dim3 grid((rows + 63) / 64), block(256);
     if (D_ <= 128) {
-      hipLaunchKernelGGL(TrainBackRow<1>, grid, block, 0, stream, r);
+      hipLaunchKernelGGL((TrainBackRow<1, false>), grid, block, 0, stream, r);
     } else if (D_ <= 256) {
-      hipLaunchKernelGGL(TrainBackRow<2>, grid, block, 0, stream, r);
+      hipLaunchKernelGGL((TrainBackRow<2, false>), grid, block, 0, stream, r);
     } else if (D_ <= 384) {
-      hipLaunchKernelGGL(TrainBackRow<3>, grid, block, 0, stream, r);
+      hipLaunchKernelGGL((TrainBackRow<3, false>), grid, block, 0, stream, r);
     } else {
-      hipLaunchKernelGGL(TrainBackRow<4>, grid, block, 0, stream, r);
+      hipLaunchKernelGGL((TrainBackRow<4, false>), grid, block, 0, stream, r);
     }
   };
   TrainSplitLaunch(static_cast<const float*>(d_dp), rows, A_ + 1, n16, dp, stream);
@@ -632,6 +645,38 @@ void NetTrain::Backward(hipStream_t stream, int rows, const void* d_dp, void* co
     below(1 + 2 * l, buf_b, D_, D_, buf_a, 2 + 2 * l, buf_a);  // (in place: a lane reads its word, then writes it)
   }
   reduce(0, buf_a, D_);
+  const hipError_t launched = hipGetLastError();
+  (void)hipSetDevice(before);
+  EPA_HIP(launched);
+  back_rows_ = rows;
+}
+
+void NetTrain::InputGrad(hipStream_t stream, int rows, void* d_dx) {
+  if (d_dx == nullptr) throw std::invalid_argument("net_train_input_grad: null argument");
+  if (back_rows_ == 0) {
+    throw std::invalid_argument("net_train_input_grad: no backward has been made since the last forward");
+  }
+  if (rows != back_rows_) {
+    throw std::invalid_argument("net_train_input_grad: rows = " + std::to_string(rows) + ", but the last backward had " +
+                                std::to_string(back_rows_));
+  }
+  int before = 0;
+  EPA_HIP(hipGetDevice(&before));
+  EPA_HIP(hipSetDevice(device_));
+  // (the last Backward left the split dz of layer 0 in the first buffer)
+  RowArgs r{rows, F_, reinterpret_cast<const uint32_t*>(mem_.p + at_->dz_a), D_, D_,
+            reinterpret_cast<const uint16_t*>(mem_.p + at_->wt) + at_->wt_off[0], nullptr, 0.0f, nullptr, 0.0f, nullptr,
+            static_cast<float*>(d_dx)};
+  const dim3 grid((rows + 63) / 64), block(256);
+  if (F_ <= 128) {
+    hipLaunchKernelGGL((TrainBackRow<1, true>), grid, block, 0, stream, r);
+  } else if (F_ <= 256) {
+    hipLaunchKernelGGL((TrainBackRow<2, true>), grid, block, 0, stream, r);
+  } else if (F_ <= 384) {
+    hipLaunchKernelGGL((TrainBackRow<3, true>), grid, block, 0, stream, r);
+  } else {
+    hipLaunchKernelGGL((TrainBackRow<4, true>), grid, block, 0, stream, r);
+  }
   const hipError_t launched = hipGetLastError();
   (void)hipSetDevice(before);
   EPA_HIP(launched);

@@ -925,6 +925,42 @@ int epa_net_train_forward_device(epa_net_train* train, void* stream, int32_t row
                                  const void* const* d_b, const int32_t* shifts, const void* d_x, void* d_p);
 int epa_net_train_backward_device(epa_net_train* train, void* stream, int32_t rows, const void* d_dp,
                                   void* const* d_dw, void* const* d_db);
+/*   epa_net_train_input_grad_device(handle, stream, rows, d_dx): after epa_net_train_backward_device of the same rows,
+ *     d_dx float32 [rows][F] = the gradient of the input bytes, one more product of that backward (within c of the
+ *     exact value per layer passed, 2 L + 2 of them).  EPA_ERR_INVALID without such a backward since the last forward.
+ *     What epa_net_train_backward_device computes is not changed by it. */
+int epa_net_train_input_grad_device(epa_net_train* train, void* stream, int32_t rows, void* d_dx);
+
+/* Rollout actor with memory, training (no reference analogue; csrc/actor_memory_train.hip.h is the authority): the
+ * cell of a memory actor over a whole horizon and its backward pass through time on the device, under the
+ * straight-through rules of the float64 twin (`Actor.module().unroll`), as the two halves of a torch.autograd.Function
+ * around the trunk's epa_net_train_* (whose F is M).  A handle belongs to a device and needs no pool; it owns one device
+ * allocation sized for `max_rows` = T N (about max_rows * (11 M + F) bytes and a slice workspace) kept between steps.
+ *   epa_cell_train_create(device, F, M, kind, max_rows, &handle): F 1 .. 512, M a multiple of 32 in 32 .. 512, kind 0
+ *     or 1 (the inner actor's), max_rows 1 .. 2^20.
+ *   epa_cell_train_forward_device(handle, stream, T, N, d_w[2], d_b[2], shifts[2], d_x, d_h0, d_mask, d_hp, d_h):
+ *     d_w[g] int8 [M][F + M] over [x ; h] (-127 .. 127) and d_b[g] int32 [M] are DEVICE arrays, g = 0 the gate's layer
+ *     and 1 the candidate's; the arrays of pointers and shifts[] (0 .. 24) are host memory.  d_x bytes [T][N][F] and
+ *     d_h0 bytes [N][M], 0 .. 127; d_mask bytes [T][N].  With h_{-1} = h0: d_hp[t] = h'_t = cell(x_t, h_{t-1}), which
+ *     the trunk reads, h_t = mask[t] ? h'_t : 0, and d_h = h_{T-1}; both outputs bytes, 16-byte aligned.  One launch
+ *     runs the whole horizon.
+ *   epa_cell_train_backward_device(handle, stream, T, N, d_dhp, d_dh, d_dw, d_db, d_dh0): d_dhp float32
+ *     [T][N][M] (epa_net_train_input_grad_device's d_dx) and d_dh float32 [N][M] (of d_h; null: zeros) -> d_dw float32
+ *     [2][M][F + M], d_db float32 [2][M] and d_dh0 float32 [N][M], through the last forward, whose x and mask the
+ *     handle kept.  Each is within
+ *     kCellTrainErr = 2.6035e-4 per step of depth 2 L + 3 + T of the exact value, relative to the same sums over
+ *     magnitudes (the header derives both).  x gets no gradient.  No atomics: the same inputs give the same bits.
+ *   epa_cell_train_destroy(handle).
+ *   Streams, enqueueing and the EPA_ERR_INVALID refusals are those of epa_net_train_*; T N above max_rows and a
+ *   backward with another T or N than the last forward are refused too. */
+typedef struct epa_cell_train epa_cell_train;
+int epa_cell_train_create(int32_t device, int32_t F, int32_t M, int32_t kind, int64_t max_rows, epa_cell_train** out);
+int epa_cell_train_destroy(epa_cell_train* train);
+int epa_cell_train_forward_device(epa_cell_train* train, void* stream, int32_t T, int32_t N, const void* const* d_w,
+                                  const void* const* d_b, const int32_t* shifts, const void* d_x, const void* d_h0,
+                                  const void* d_mask, void* d_hp, void* d_h);
+int epa_cell_train_backward_device(epa_cell_train* train, void* stream, int32_t T, int32_t N, const void* d_dhp,
+                                   const void* d_dh, void* d_dw, void* d_db, void* d_dh0);
 
 /* Convolutional network, training (csrc/pgx_conv_train.hip.h is the authority): the same two halves for the
  * convolutional network above, under the rules of `ConvNet.module()`.  The calls mirror epa_net_train_*:
